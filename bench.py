@@ -31,7 +31,14 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with two extra o
                  2500 / 3 TFLOP/s for the split engine (f16 dense MFMA peak over the three products
                  per fp32 multiply), 157.3 TFLOP/s for the fp32 MFMA kernels
   cpu_baseline - the reference's per-packet naive fp32 loop restated on the host cores
-                 (oracle/cpu_baseline.py), timed on a bounded sample (rank 0, N = 1 only)
+                 (oracle/cpu_baseline.py), timed on a bounded sample (rank 0, N = 1 only; --full)
+
+Plain run vs `--full`: a plain run sets up, warms up, times `--steps` steps and prints the line (contract
+keys, config, the rooflines the timed steps' own kernel events give).  `--full` adds every side
+measurement after the timed region - oracle parity check, CPU baseline, fp32 MFMA comparison,
+host-buffer legs, latency, regimes, next rows, practical peak, the other BASELINE configurations in
+fresh processes - and writes the whole object to the detail file.  `--dump-outputs DIR` writes what
+the last timed step handed its caller (DNN and LS estimates, a fixed sample of packets) as .npy files.
 """
 import argparse
 import json
@@ -48,6 +55,24 @@ FP32_MATRIX_PEAK_TFLOPS = 157.3     # MI355X_MICROARCH.md, v_mfma_f32_32x32x2_f3
 HBM_PEAK_GBS = 8000.0
 BF16_MATRIX_PEAK_TFLOPS = 2500.0    # dense, v_mfma_f32_32x32x16_bf16 (the same for v_mfma_f32_32x32x16_f16)
 SPLIT_PRODUCTS = 3                  # f16 MFMAs per fp32-grade multiply on the split engine
+DUMP_BYTES = 64 * 10**6             # --dump-outputs: all files of all ranks together, .npy headers included
+DUMP_SEED = 2025                    # which packets --dump-outputs samples when the batch is larger than DUMP_BYTES
+
+
+def dump_outputs(path, arrays, rank, world):
+    """--dump-outputs: the result planes the last timed step left in `arrays` (name -> DeviceArray [npkt, nr, nt, 234]), i.e. what a
+    caller of the timed path receives, as float32 `path/<name>.npy` (`<name>_rank<r>.npy` when N > 1).  A batch larger than this rank's
+    share of DUMP_BYTES is sampled by whole packets, the same ones for the same arguments (seeded, ascending).  Returns a note for the line."""
+    npkt = next(iter(arrays.values())).shape[0]
+    per_pkt = sum(a.nbytes // max(a.shape[0], 1) for a in arrays.values())
+    k = min(npkt, (DUMP_BYTES // world - 1024 * len(arrays)) // per_pkt)
+    assert k >= 1, 'one packet of the outputs (%d bytes) exceeds the --dump-outputs cap' % per_pkt
+    sel = np.arange(npkt) if k == npkt else np.sort(np.random.default_rng(DUMP_SEED).choice(npkt, k, replace=False))
+    os.makedirs(path, exist_ok=True)
+    suffix = '_rank%d' % rank if world > 1 else ''
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + suffix + '.npy'), np.concatenate([a.download(int(p), 1) for p in sel]))
+    return {'dir': path, 'names': sorted(arrays), 'packets': int(k), 'of': int(npkt), 'sample_seed': DUMP_SEED if k < npkt else None}
 
 
 def spawn_ranks(n):
@@ -134,7 +159,16 @@ def main():
     ap.add_argument('--detail-file', default='', help='where the full detail object goes (default: bench_detail.json beside this script, and gpurun_out/ when that exists)')
     ap.add_argument('--rendezvous-only', action='store_true',
                     help='start the ranks, rendezvous, all-reduce a rank count and print it - no GPU work (checks the launch path on any host)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed region also run every side measurement (parity check, CPU baseline, fp32 MFMA comparison, host-buffer '
+                         'legs, latency, regimes, next rows, practical peak, other configurations) and write the detail file; the --no-* / '
+                         '--check / --host-path flags select among them.  Without it a run only times the steps and prints the line')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='after the timed steps write what the last one computed (DNN and LS estimates, float32) as DIR/<name>.npy: '
+                         'a fixed, seeded sample of packets, at most %d MB in all' % (DUMP_BYTES // 10**6))
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         return spawn_ranks(args.gpus)
@@ -157,7 +191,8 @@ def main():
         if rank == 0:
             print(json.dumps({'rendezvous_only': True, 'n_gpus': n_gpus, 'ranks_seen': int(seen), 'requested': args.gpus,
                               'other_configs_scheduled': [dict(config=n_, flags=' '.join(f_), fits=fit_, per_rank_gb=round(gb_, 1))
-                                                          for n_, _, f_, fit_, gb_ in multi_gpu_legs(args, world)] if world > 1 and (default_headline(args) or args.legs_packets) else [],
+                                                          for n_, _, f_, fit_, gb_ in multi_gpu_legs(args, world)]
+                                             if args.full and world > 1 and (default_headline(args) or args.legs_packets) else [],
                               'packets_per_step': int(pkts), 'scaling': args.scaling, 'backend': backend if world > 1 else None,
                               'ranks_ms': [i['ms_per_step'] for i in infos], 'devices': [i['device'] for i in infos], 'ranks': infos}))
         return
@@ -293,19 +328,23 @@ def main():
         assert pkg.dist.world_size() == world == len(infos), (pkg.dist.world_size(), world, len(infos))
         assert ords == list(range(world)), 'ranks did not land on %d distinct devices: %s' % (world, ords)
 
+    # what the last timed step computed, before anything below runs the path again
+    dumped = dump_outputs(args.dump_outputs, {'dnn_real': d_ore, 'dnn_imag': d_oim, 'ls_real': d_hre, 'ls_imag': d_him} if not args.no_ls else
+                          {'dnn_real': d_ore, 'dnn_imag': d_oim}, rank, world) if args.dump_outputs else None
+
     graph_replays = eng.get_option('graph_replays') if args.graph else 0
-    if args.graph:                                 # kernel breakdown: one eager step with events, outside the timed region
+    if args.graph and args.full:                   # kernel breakdown: one eager step with events, outside the timed region
         eng.set_option('use_graph', 0)
         eng.profile_enable(True)
         eng.profile_reset()
         step()
         eng.synchronize()
-    prof = eng.profile()
+    prof = eng.profile() if args.full or not args.graph else None      # a plain hipGraph run has no kernel events
     eng.profile_enable(False)
     # the same steps once more WITHOUT the per-kernel events (round-3 verdict: the timed region carries them, so headline and
     # breakdown could not be told apart): what the event records between the kernels cost.  Rank-local, after the timed region.
     no_events = None
-    if not args.graph:
+    if not args.graph and args.full:
         step(); step()
         eng.synchronize()
         t1 = time.perf_counter()
@@ -329,7 +368,7 @@ def main():
     # ---- host-buffer (PCIe-inclusive) entry points: measured first, before the CPU legs below start their BLAS / OpenMP thread
     # pools and fragment host memory (measured on one box: 50 ms here, 60 ms behind the oracle check)
     host_path = None
-    if rank == 0 and world == 1 and args.host_path > 0:
+    if args.full and rank == 0 and world == 1 and args.host_path > 0:
         k = min(args.host_path, npkt)
         h_re, h_im = d_re.download(0, k), d_im.download(0, k)
         o_ls = (np.zeros((k, nr, nt, 234), np.float32), np.zeros((k, nr, nt, 234), np.float32))
@@ -471,7 +510,7 @@ def main():
     # (--no-cpu-baseline skips the timing) and compared with what the GPU produced for them (--check 0
     # skips the comparison).  The oracle is the checker / the baseline here, never the thing measured.
     check, cpu_baseline = {}, None
-    if rank == 0 and args.check > 0:               # N > 1: rank 0 checks packets of ITS shard
+    if args.full and rank == 0 and args.check > 0:     # N > 1: rank 0 checks packets of ITS shard
         from oracle import csi_oracle as o
         k = min(args.check, npkt)
         # spread over the batch, first and last included: with the mixed-SNR input (8 blocks of npkt / 8) k = 8 takes one packet
@@ -490,7 +529,7 @@ def main():
             r_ls = o.ls_estimate(ltf, wts['P']['pilot'])
             check['ls_rel_err'] = max(o.row_rel_err(take(d_hre), r_ls.real), o.row_rel_err(take(d_him), r_ls.imag))
         check['packets'] = sel
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import cpu_baseline as cb
         k = min(npkt, 256)
         ltf = (d_re.download(0, k) + 1j * d_im.download(0, k)).astype(np.complex64)
@@ -508,7 +547,7 @@ def main():
 
     # the same steps on the fp32 MFMA kernels, for comparison (outside the headline timed region)
     native = None
-    if split_engine and world == 1:
+    if args.full and split_engine and world == 1:
         eng.set_option('f32_engine', 0)
         step(); eng.synchronize()
         eng.profile_enable(True); eng.profile_reset()
@@ -529,7 +568,7 @@ def main():
 
     # one-packet latency (the reference's literal per-packet call, DNN.py:346), device-resident, outside the timed region
     latency = None
-    if rank == 0 and world == 1 and not args.no_latency:
+    if args.full and rank == 0 and world == 1 and not args.no_latency:
         ts = []
         for i in range(40):
             eng.synchronize()
@@ -546,7 +585,7 @@ def main():
     # N > 1: BASELINE.json's two multi-GPU configurations, by ALL ranks, each as a fresh N-rank job of this script (round-4 verdict,
     # next 4): configs[3] Nt=64 Nr=8 50000 packets sharded, configs[4] Nt=128 Nr=16 100000 packets, one hipGraph per step
     legs = None
-    if world > 1 and (default_headline(args) or args.legs_packets) and not args.no_other_configs and not args.graph and not args.option:
+    if args.full and world > 1 and (default_headline(args) or args.legs_packets) and not args.no_other_configs and not args.graph and not args.option:
         del d_re, d_im, d_ore, d_oim, d_hre, d_him
         try:
             eng.comm_destroy()
@@ -587,32 +626,49 @@ def main():
                     return v.get('hbm_bytes_per_launch')
         return None
 
-    dom = prof['pair_dense_gemm']
-    dom_ms = dom['ms'] / max(dom['launches'], 1)
-    achieved = dom['flops'] / max(dom['ms'], 1e-9) / 1e9          # TFLOP/s
-    if args.dtype == 'bf16':
-        mfma_peak, peak_note = BF16_MATRIX_PEAK_TFLOPS, 'dense bf16 MFMA peak'
-    elif split_engine:
-        mfma_peak = BF16_MATRIX_PEAK_TFLOPS / SPLIT_PRODUCTS
-        peak_note = ('split-f16 engine: dense f16 MFMA peak (2500 TFLOP/s) / 3 MFMA products per fp32-grade multiply; '
-                     'achieved counts each multiply-add of the algorithm once (executed f16 flops are 3x)')
-    else:
-        mfma_peak, peak_note = FP32_MATRIX_PEAK_TFLOPS, 'fp32 MFMA peak (v_mfma_f32_32x32x2_f32)'
-    # the practical ceiling of the dominant kernel, measured here: its MFMA + barrier skeleton on the model's own operand data
-    practical = None
-    if band_kernel and world == 1:
-        try:
-            sk_ms, sk_tf = eng.band_skeleton(npkt * nr * nt, 5)
-            practical = {'skeleton_ms_per_launch': sk_ms, 'skeleton_executed_tflops': sk_tf}
-        except Exception as e:
-            practical = {'error': repr(e)}
-    kernels = {}
-    for name, p in prof.items():
-        if p['launches']:
-            kernels[name] = dict(launches=p['launches'], ms_total=round(p['ms'], 3),
-                                 ms_avg=round(p['ms'] / p['launches'], 4),
-                                 tflops=round(p['flops'] / max(p['ms'], 1e-9) / 1e9, 2),
-                                 algo_gbs=round(p['bytes'] / max(p['ms'], 1e-9) / 1e6, 1))
+    kernels, roofline = {}, None
+    if prof is not None:
+        dom = prof['pair_dense_gemm']
+        dom_ms = dom['ms'] / max(dom['launches'], 1)
+        achieved = dom['flops'] / max(dom['ms'], 1e-9) / 1e9          # TFLOP/s
+        if args.dtype == 'bf16':
+            mfma_peak, peak_note = BF16_MATRIX_PEAK_TFLOPS, 'dense bf16 MFMA peak'
+        elif split_engine:
+            mfma_peak = BF16_MATRIX_PEAK_TFLOPS / SPLIT_PRODUCTS
+            peak_note = ('split-f16 engine: dense f16 MFMA peak (2500 TFLOP/s) / 3 MFMA products per fp32-grade multiply; '
+                         'achieved counts each multiply-add of the algorithm once (executed f16 flops are 3x)')
+        else:
+            mfma_peak, peak_note = FP32_MATRIX_PEAK_TFLOPS, 'fp32 MFMA peak (v_mfma_f32_32x32x2_f32)'
+        # the practical ceiling of the dominant kernel, measured here: its MFMA + barrier skeleton on the model's own operand data
+        practical = None
+        if args.full and band_kernel and world == 1:
+            try:
+                sk_ms, sk_tf = eng.band_skeleton(npkt * nr * nt, 5)
+                practical = {'skeleton_ms_per_launch': sk_ms, 'skeleton_executed_tflops': sk_tf}
+            except Exception as e:
+                practical = {'error': repr(e)}
+        for name, p in prof.items():
+            if p['launches']:
+                kernels[name] = dict(launches=p['launches'], ms_total=round(p['ms'], 3),
+                                     ms_avg=round(p['ms'] / p['launches'], 4),
+                                     tflops=round(p['flops'] / max(p['ms'], 1e-9) / 1e9, 2),
+                                     algo_gbs=round(p['bytes'] / max(p['ms'], 1e-9) / 1e6, 1))
+        roofline = {'bound': 'mfma', 'kernel': 'pair_dense_gemm' + ((' (%s: first per-pair layer + regressor fused, h2 in registers)' % band_name) if band_any else ''), 'achieved': achieved, 'peak': mfma_peak,
+                    'unit': 'TFLOP/s', 'frac': achieved / mfma_peak, 'peak_note': peak_note,
+                    'executed_mfma_tflops': achieved * (SPLIT_PRODUCTS if split_engine else 1),
+                    'vs_fp32_mfma_peak': achieved / FP32_MATRIX_PEAK_TFLOPS if args.dtype == 'f32' else None,
+                    'traffic': (hbm_per_launch((band_name if band_kernel else 'gemm_hs_pp_pair_kernel<2') if split_engine else 'pair_gemm') if args.dtype == 'f32'
+                                else hbm_per_launch(band_name if band_any else 'gemm_bf16_pp_pair_kernel<1')), 'traffic_unit': 'HBM bytes per launch (PMC)',
+                    'traffic_source': traffic.get('_file'), 'profile_files': prof_files or None,
+                    'algorithmic_bytes_per_launch': dom['bytes'] / max(dom['launches'], 1),
+                    'avg_launch_ms': dom_ms, 'flops_per_launch': dom['flops'] / max(dom['launches'], 1),
+                    'practical_peak': (practical['skeleton_executed_tflops'] / SPLIT_PRODUCTS) if practical and 'error' not in practical else None,
+                    'frac_of_practical': (achieved / (practical['skeleton_executed_tflops'] / SPLIT_PRODUCTS)) if practical and 'error' not in practical else None,
+                    'practical_peak_note': ('csi_profile_band_skeleton on this box, this run: the same kernel with everything but its MFMAs, barriers and waits '
+                                            'removed and its operand registers holding the model\'s own split weights (relu-like zeros in the activation fragments), '
+                                            '%.3f ms per launch = %.0f TFLOP/s of executed f16 MFMA; divided by 3 products.  The part runs these kernels at its ~1.4 kW '
+                                            'power limit at 1.8-2.0 GHz, not 2.4 (profiles/r04_power.txt), so the table peak is not reachable on real data'
+                                            % (practical['skeleton_ms_per_launch'], practical['skeleton_executed_tflops'])) if practical and 'error' not in practical else (practical or {}).get('error')}
     out = {
         'metric': 'channel-estimates/sec (Nt=%d,Nr=%d)' % (nt, nr),
         'value': value,
@@ -644,29 +700,16 @@ def main():
                    'world_size_checked': pkg.dist.world_size(), 'weights_via': via,
                    'sharding': ('contiguous packet ranges per rank (%s scaling), weights broadcast once over %s, no collective in the step'
                                 % (args.scaling, 'RCCL' if backend == 'nccl' else backend)) if world > 1 else 'single GPU'},
-        'roofline': {'bound': 'mfma', 'kernel': 'pair_dense_gemm' + ((' (%s: first per-pair layer + regressor fused, h2 in registers)' % band_name) if band_any else ''), 'achieved': achieved, 'peak': mfma_peak,
-                     'unit': 'TFLOP/s', 'frac': achieved / mfma_peak, 'peak_note': peak_note,
-                     'executed_mfma_tflops': achieved * (SPLIT_PRODUCTS if split_engine else 1),
-                     'vs_fp32_mfma_peak': achieved / FP32_MATRIX_PEAK_TFLOPS if args.dtype == 'f32' else None,
-                     'traffic': (hbm_per_launch((band_name if band_kernel else 'gemm_hs_pp_pair_kernel<2') if split_engine else 'pair_gemm') if args.dtype == 'f32'
-                                 else hbm_per_launch(band_name if band_any else 'gemm_bf16_pp_pair_kernel<1')), 'traffic_unit': 'HBM bytes per launch (PMC)',
-                     'traffic_source': traffic.get('_file'), 'profile_files': prof_files or None,
-                     'algorithmic_bytes_per_launch': dom['bytes'] / max(dom['launches'], 1),
-                     'avg_launch_ms': dom_ms, 'flops_per_launch': dom['flops'] / max(dom['launches'], 1),
-                     'practical_peak': (practical['skeleton_executed_tflops'] / SPLIT_PRODUCTS) if practical and 'error' not in practical else None,
-                     'frac_of_practical': (achieved / (practical['skeleton_executed_tflops'] / SPLIT_PRODUCTS)) if practical and 'error' not in practical else None,
-                     'practical_peak_note': ('csi_profile_band_skeleton on this box, this run: the same kernel with everything but its MFMAs, barriers and waits '
-                                             'removed and its operand registers holding the model\'s own split weights (relu-like zeros in the activation fragments), '
-                                             '%.3f ms per launch = %.0f TFLOP/s of executed f16 MFMA; divided by 3 products.  The part runs these kernels at its ~1.4 kW '
-                                             'power limit at 1.8-2.0 GHz, not 2.4 (profiles/r04_power.txt), so the table peak is not reachable on real data'
-                                             % (practical['skeleton_ms_per_launch'], practical['skeleton_executed_tflops'])) if practical and 'error' not in practical else (practical or {}).get('error')},
+        'roofline': roofline,
         'kernels': kernels,
-        'parity_check': check,
-        'latency': latency,
         'ranks_ms': [round(i['ms_per_step'], 4) for i in infos],
         'devices': [i['device'] for i in infos],
         'ranks': infos,
     }
+    if args.full:
+        out['parity_check'], out['latency'] = check, latency
+    if dumped:
+        out['outputs'] = dumped
     if no_events is not None:
         out['timed_region_events'] = {'ms_per_step_with_kernel_events': round(dt_rank / args.steps * 1e3, 4), 'ms_per_step_without': round(no_events, 4),
                                       'note': 'rank 0, the same %d steps again behind the timed region with csi_profile_enable(0): `value` is the run WITH the per-kernel '
@@ -682,7 +725,7 @@ def main():
 
     if cpu_baseline:
         out['cpu_baseline'] = cpu_baseline
-    if world == 1 and not args.no_regimes and args.dtype == 'f32' and not args.graph and not args.option and (nt, nr, tuple(hidden)) == (32, 4, (1024, 1024)):
+    if args.full and world == 1 and not args.no_regimes and args.dtype == 'f32' and not args.graph and not args.option and (nt, nr, tuple(hidden)) == (32, 4, (1024, 1024)):
         try:
             out['regimes'] = regimes(pkg, eng, nt, nr, hidden, d_re, d_im, npkt, ls=not args.no_ls)
             big = [r for r in out['regimes'] if r['packets'] == 500]
@@ -690,7 +733,7 @@ def main():
                 big[0]['rate_vs_headline'] = round(big[0]['pairs_per_s'] / value, 4)
         except Exception as e:                      # side measurements never take the headline down
             out['regimes'] = {'error': repr(e)}
-    if world == 1 and not args.no_next_rows and args.dtype == 'f32' and nt > 0:
+    if args.full and world == 1 and not args.no_next_rows and args.dtype == 'f32' and nt > 0:
         try:
             out['next_rows'] = next_rows(pkg, eng, nt, nr, hidden, wts, d_re, d_im, min(npkt, 1000))
         except Exception as e:                      # side measurements never take the headline down
@@ -698,7 +741,7 @@ def main():
     default_run = default_headline(args)
     if legs is not None:
         out['other_configs'] = legs
-    if world == 1 and default_run and not args.no_other_configs and not args.graph and not args.option:
+    if args.full and world == 1 and default_run and not args.no_other_configs and not args.graph and not args.option:
         del d_re, d_im, d_ore, d_oim, d_hre, d_him
         out['other_configs'] = other_configs()
     # the whole process as rank 0 saw it (imports, input synthesis, warm-up, timed region, side measurements): what a clock around
@@ -707,7 +750,7 @@ def main():
     if args.full_line:
         print(json.dumps(out))
         return
-    detail_file = write_detail(out, args.detail_file)
+    detail_file = write_detail(out, args.detail_file) if args.full else None
     print(compact_line(out, detail_file))
 
 LINE_LIMIT = 4096                     # bytes: the driver's capture lost round 5's 20 KB line (BENCH_r05.parsed = null)
@@ -753,20 +796,22 @@ def compact_line(out, detail_file):
     line['config'] = {'workload': cfg['workload'], 'pairs_per_step': cfg['pairs_per_step'], 'packets_per_s': cfg['packets_per_s'],
                       'ranks': cfg['ranks'], 'weights_via': cfg['weights_via'].split(':')[0].split(' (')[0], 'ls_included': cfg['ls_included'],
                       'launch': 'hipGraph' if out['launch'].startswith('one hipGraph') else 'eager'}
-    line['roofline'] = {k: rf.get(k) for k in ('bound', 'achieved', 'peak', 'unit', 'frac', 'traffic', 'avg_launch_ms', 'flops_per_launch',
-                                               'algorithmic_bytes_per_launch', 'practical_peak', 'frac_of_practical')}
-    line['roofline']['kernel'] = rf['kernel'].split(' (')[-1].split(':')[0] if '(' in rf['kernel'] else rf['kernel']
-    line['roofline']['profile_files'] = sorted((rf.get('profile_files') or {}).values()) or None
+    if rf:                                       # (a plain hipGraph run has no kernel events)
+        line['roofline'] = {k: rf.get(k) for k in ('bound', 'achieved', 'peak', 'unit', 'frac', 'traffic', 'avg_launch_ms', 'flops_per_launch',
+                                                   'algorithmic_bytes_per_launch', 'practical_peak', 'frac_of_practical')}
+        line['roofline']['kernel'] = rf['kernel'].split(' (')[-1].split(':')[0] if '(' in rf['kernel'] else rf['kernel']
+        line['roofline']['profile_files'] = sorted((rf.get('profile_files') or {}).values()) or None
     if out.get('roofline_ls'):
         line['roofline_ls'] = {k: out['roofline_ls'].get(k) for k in ('bound', 'achieved', 'peak', 'unit', 'frac', 'traffic', 'avg_launch_ms')}
     if out.get('cpu_baseline'):
         cb = out['cpu_baseline']
         line['cpu_baseline'] = {k: cb.get(k) for k in ('value', 'unit', 'cores', 'cores_is', 'threads', 'host_cpu_count', 'cpu_model', 'kind', 'sample',
                                                        'dnn_only', 'ls_only', 'dnn_one_large_batch', 'gpu_over_cpu')}
-    pc = dict(out.get('parity_check') or {})
-    if 'packets' in pc:
-        pc['packets'] = len(pc['packets'])
-    line['parity_check'] = pc
+    if 'parity_check' in out:                   # --full
+        pc = dict(out['parity_check'] or {})
+        if 'packets' in pc:
+            pc['packets'] = len(pc['packets'])
+        line['parity_check'] = pc
     if out.get('latency'):
         line['latency_us'] = out['latency']['one_packet_us']
     line['ranks_ms'] = out['ranks_ms']
@@ -816,7 +861,10 @@ def compact_line(out, detail_file):
                 e['ranks_ms'] = c.get('ranks_ms')
             oc.append(e)
         line['other_configs'] = oc
-    line['detail_file'] = detail_file
+    if out.get('outputs'):
+        line['outputs'] = out['outputs']
+    if detail_file:
+        line['detail_file'] = detail_file
     line['bench_wall_s'] = out['bench_wall_s']
     line = _sig(line)
     line['value'], line['ms_per_step'] = out['value'], out['ms_per_step']          # the contract's two numbers keep every digit
@@ -1106,7 +1154,7 @@ def run_multi_gpu_legs(pkg, args, rank, world, local):
         env = dict(os.environ, MASTER_PORT=str(box[0]), CSI_RCCL_ID_TOKEN='leg-%s-%d' % (name, box[0]), CSI_DIST_TIMEOUT_S='180')
         for k in [k for k in env if k.startswith('TORCHELASTIC_')]:      # under torchrun: the child job's rank 0 serves its own store
             env.pop(k)                                                     # (TORCHELASTIC_USE_AGENT_STORE would make it look for the agent's)
-        cmd = [sys.executable, os.path.abspath(__file__), '--gpus', str(world), '--full-line', '--no-other-configs', '--no-cpu-baseline', '--no-latency',
+        cmd = [sys.executable, os.path.abspath(__file__), '--gpus', str(world), '--full', '--full-line', '--no-other-configs', '--no-cpu-baseline', '--no-latency',
                '--host-path', '0', '--check', '4', '--no-next-rows', '--no-regimes', '--weights-via', args.weights_via] + flags
         t0 = time.perf_counter()
         try:
@@ -1152,7 +1200,7 @@ def other_configs():
     import subprocess
     res = []
     for name, what, flags in OTHER_CONFIGS:
-        cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--full-line', '--no-other-configs', '--no-cpu-baseline', '--no-latency',
+        cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--full', '--full-line', '--no-other-configs', '--no-cpu-baseline', '--no-latency',
                '--host-path', '0', '--check', '4', '--no-next-rows'] + flags
         t0 = time.perf_counter()
         try:

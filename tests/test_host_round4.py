@@ -117,7 +117,7 @@ def test_bench_gpus_8_rendezvous_only():
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     # (round 5: no retry here any more - the launcher itself starts the ranks again on a fresh port when the rendezvous fails, and says so)
-    r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '8', '--rendezvous-only'], env=env, cwd=REPO,
+    r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '8', '--rendezvous-only', '--full'], env=env, cwd=REPO,
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=600)
     assert r.returncode == 0, r.stdout[-3000:]
     import json
@@ -125,7 +125,7 @@ def test_bench_gpus_8_rendezvous_only():
     assert out['rendezvous_only'] and out['n_gpus'] == 8 and out['ranks_seen'] == 8 and out['requested'] == 8
     assert [rk['rank'] for rk in out['ranks']] == list(range(8)) and len({rk['pid'] for rk in out['ranks']}) == 8
     assert out['scaling'] == 'weak' and out['packets_per_step'] == 8 * out['ranks'][0]['packets']
-    # round-4 verdict, next 4: an 8-rank run of the driver's command also schedules BASELINE.json's two 8-GPU configurations
+    # round-4 verdict, next 4: an 8-rank --full run of the driver's command also schedules BASELINE.json's two 8-GPU configurations
     legs = {l['config']: l for l in out['other_configs_scheduled']}
     assert set(legs) == {'configs[3]', 'configs[4]'} and all(l['fits'] for l in legs.values())
     assert '--scaling strong --nt 64 --nr 8 --packets 50000 --input white' in legs['configs[3]']['flags']
@@ -509,7 +509,7 @@ def test_bench_script_runs_end_to_end_on_the_mock_runtime(mock_so, tmp_path):
     env = dict(os.environ)
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, '-c', runner, '--packets', '64', '--steps', '2', '--warmup', '1', '--host-path', '64', '--no-other-configs',
+    r = subprocess.run([sys.executable, '-c', runner, '--full', '--packets', '64', '--steps', '2', '--warmup', '1', '--host-path', '64', '--no-other-configs',
                         '--cpu-budget-s', '2', '--detail-file', str(tmp_path / 'bench_detail_mock.json')], stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, timeout=600, env=env, cwd=REPO)
     assert r.returncode == 0, r.stderr[-3000:]
     import json
@@ -548,6 +548,40 @@ def test_bench_script_runs_end_to_end_on_the_mock_runtime(mock_so, tmp_path):
     assert 'dnn_only_pinned_result' in c128 and c128['dnn_only_pinned_result']['direct_downloads'] == 4, c128.keys()
     text = json.dumps(detail)
     assert '_error' not in text and '"error"' not in text, [k for k in ('_error', '"error"') if k in text]
+
+
+def test_plain_bench_run_times_the_steps_and_dumps_the_outputs_on_the_mock_runtime(mock_so, tmp_path):
+    """bench.py without --full: set-up, warm-up, the timed steps and the line - none of the side measurements, no detail file - and
+    --dump-outputs writes the last step's result planes as float32 .npy files under the 64 MB cap (a seeded sample of whole packets
+    when the batch is larger).  Mock runtime: the values mean nothing, the files, shapes and the line's keys do."""
+    runner = ("import sys, runpy; sys.path.insert(0, %r); from dl_channel_estimation_mamimo_amd import _lib; _lib._SO = %r; "
+              "sys.argv = ['bench.py'] + sys.argv[1:]; runpy.run_path(%r, run_name='__main__')") % (REPO, mock_so, os.path.join(REPO, 'bench.py'))
+    env = dict(os.environ)
+    for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
+        env.pop(k, None)
+    dump = tmp_path / 'outputs'
+    nt, nr, npkt = 64, 8, 64                     # 1.9 MB of results per packet: 123 MB in all, over the cap
+    r = subprocess.run([sys.executable, '-c', runner, '--nt', str(nt), '--nr', str(nr), '--packets', str(npkt), '--input', 'white', '--steps', '3',
+                        '--warmup', '1', '--dump-outputs', str(dump)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True,
+                       timeout=600, env=env, cwd=REPO)
+    assert r.returncode == 0, r.stderr[-3000:]
+    import json
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])
+    for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'config', 'roofline'):
+        assert key in line, key
+    assert line['steps'] == 3 and line['warmup'] == 1 and line['value'] > 0 and line['ms_per_step'] > 0
+    for key in ('parity_check', 'cpu_baseline', 'host_path', 'latency_us', 'regimes_us', 'next_rows', 'native_fp32_engine', 'other_configs',
+                'ms_per_step_without_kernel_events', 'detail_file'):
+        assert key not in line, key
+    assert line['roofline']['practical_peak'] is None
+    names = ['dnn_imag', 'dnn_real', 'ls_imag', 'ls_real']
+    assert sorted(os.listdir(dump)) == [n + '.npy' for n in names]
+    note = line['outputs']
+    assert note['names'] == names and note['of'] == npkt and 1 <= note['packets'] < npkt and note['sample_seed'] is not None
+    assert sum(os.path.getsize(dump / (n + '.npy')) for n in names) <= 64 * 10**6
+    for n in names:
+        a = np.load(dump / (n + '.npy'))
+        assert a.dtype == np.float32 and a.shape == (note['packets'], nr, nt, 234), (n, a.dtype, a.shape)
 
 
 def test_no_option_of_the_product_build_selects_the_two_workgroup_ringb_form(mock_so):
@@ -606,7 +640,7 @@ def test_two_rank_bench_runs_the_multi_gpu_legs_on_the_mock_runtime(mock_so, tmp
     # child jobs must not inherit (their rank 0 serves its own store); bench.py's own launcher is covered by the rendezvous-only tests
     port = 29600 + os.getpid() % 300
     r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
-                        '--master-port', str(port), os.path.join(REPO, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--check', '0',
+                        '--master-port', str(port), os.path.join(REPO, 'bench.py'), '--gpus', '2', '--full', '--steps', '2', '--warmup', '1', '--check', '0',
                         '--packets', '64', '--legs-packets', '24,6', '--input', 'white',
                         '--detail-file', str(tmp_path / 'bench_detail_2rank.json')], env=env, cwd=REPO,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, timeout=900)

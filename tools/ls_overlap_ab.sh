@@ -5,7 +5,7 @@ NS=${1:-"0 16 32 64"}
 ROUNDS=${2:-2}
 for r in $(seq 1 $ROUNDS); do
   for n in $NS; do
-    python bench.py --steps 20 --warmup 5 --no-other-configs --host-path 0 --no-cpu-baseline --no-latency --option ls_overlap_cus=$n $EXTRA 2>/dev/null | python -c "
+    python bench.py --full --full-line --steps 20 --warmup 5 --no-other-configs --host-path 0 --no-cpu-baseline --no-latency --option ls_overlap_cus=$n $EXTRA 2>/dev/null | python -c "
 import json,sys
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 k=d.get('kernels',{})
