@@ -43,9 +43,49 @@ def build_parser():
     p.add_argument('--useBN', action='store_true')
     p.add_argument('--dropout', default=0.15, type=float, help='training only; identity at inference')
     p.add_argument('--execTime', action='store_true', help='print per-kernel HIP-event times')
+    p.add_argument('--decimate_max', action='store_true', help='MaxPooling1D (pool 2) on the LTF input before Flatten (DNN.py:30,198-200)')
+    p.add_argument('--decimate_avg', action='store_true', help='AveragePooling1D (pool 2) on the LTF input before Flatten (DNN.py:31,201-203)')
     p.add_argument('--dtype', default='f32', choices=['f32', 'bf16'])
     p.add_argument('--device', default=0, type=int)
     return p
+
+
+def input_pool_from_args(args):
+    """The reference's precedence (DNN.py:198-203, if / elif): --decimate_max wins over --decimate_avg."""
+    return 'max' if args.decimate_max else ('avg' if args.decimate_avg else None)
+
+
+def weight_file_input_pool(path):
+    """The input pooling a weight file states, or None: the pooling layer of a Keras HDF5 file, the 'input_pool' record of a
+    checkpoint --train wrote, the config.json beside a CSIModel.save folder's weights.  A SavedModel directory states nothing."""
+    import json
+    from .engine import input_pool_name
+    from .model import CONFIG_FILE, load_weight_file
+    if path.endswith(('.hdf5', '.h5')):
+        from .keras_files import keras_hdf5_input_pool
+        return keras_hdf5_input_pool(path)
+    if os.path.isdir(path):
+        return None
+    cfg = os.path.join(os.path.dirname(path), CONFIG_FILE)
+    if os.path.basename(os.path.dirname(path)).endswith('_keras_model') and os.path.exists(cfg):
+        with open(cfg) as f:
+            return input_pool_name(json.load(f).get('input_pool'))
+    rec = load_weight_file(path).get('input_pool')
+    return input_pool_name(int(np.asarray(rec).ravel()[0])) if rec is not None else None
+
+
+def resolve_input_pool(args, paths):
+    """--decimate_* if given, else what the weight files state; a flag that contradicts a file is an error."""
+    flag = input_pool_from_args(args)
+    stated = {weight_file_input_pool(p) for p in paths}
+    if len(stated) > 1:
+        print('The real and the imag weights disagree in their input pooling (%s). Aborting...' % sorted(m or 'none' for m in stated))
+        sys.exit(0)
+    found = stated.pop() if stated else None
+    if flag and found and flag != found:
+        print('--decimate_%s given, but the weights are of a model with %s pooling. Aborting...' % (flag, found))
+        sys.exit(0)
+    return flag or found
 
 
 def _find_weights(modeldir, d):
@@ -91,7 +131,9 @@ def train_main(args):
         train_ids, val_ids = train_ids[rank::world], val_ids[rank::world]
         n = int(dist.all_reduce_min(len(train_ids) // args.bs))
         train_ids = train_ids[:n * args.bs]                                       # same number of steps on every rank
-    eng = CsiEngine(nt, nr, hidden=args.nn, n_out=n_out, use_bn=args.useBN, device=(local % dist.local_device_count() if world > 1 else args.device))
+    pool = input_pool_from_args(args)
+    eng = CsiEngine(nt, nr, hidden=args.nn, n_out=n_out, use_bn=args.useBN, device=(local % dist.local_device_count() if world > 1 else args.device),
+                    input_pool=pool)
     eng.set_pilot(np.asarray(data['P'], dtype=np.float64).T)          # the pilot columns of a sample are rows of P (resident dataset)
     dims = ['real'] if args.onlyReal else (['imag'] if args.onlyImag else ['real', 'imag'])
     for d in dims:
@@ -118,10 +160,12 @@ def train_main(args):
                            method=args.method, seed=args.seed, verbose=(rank == 0), data_parallel=(world > 1), resident=data)
         if rank == 0:
             path = os.path.join(args.modeldir or args.workdir, d + '_weights-improvement.safetensors')
-            save_weight_file(path, hist['weights'])
+            # (the checkpoint records the input pooling, so that --test on it needs no --decimate_* flag)
+            rec = {'input_pool': np.array([{'max': 1, 'avg': 2}[pool]], np.float32)} if pool else {}
+            save_weight_file(path, dict(hist['weights'], **rec))
             # ... and the file the reference itself writes here (DNN.py:319 save_weights): a Keras HDF5 checkpoint that
             # keras load_weights (DNN.py:334) takes back, so MI355X-trained weights enter the reference's own pipeline
-            save_weight_file(os.path.join(args.modeldir or args.workdir, d + '_weights-improvement.hdf5'), hist['weights'], component=d)
+            save_weight_file(os.path.join(args.modeldir or args.workdir, d + '_weights-improvement.hdf5'), hist['weights'], component=d, input_pool=pool)
             print('%s model: best val_loss %.6e after %d epochs; weights saved to %s' % (d, hist['best_val_loss'], len(hist['loss']), path))
     return 0
 
@@ -157,12 +201,13 @@ def main(argv=None):
             print('The validation split holds no packet (valTrainRatio %.3g of %d packets). Aborting...' % (args.valTrainRatio, first))
             sys.exit(0)
     nt, nr, npkt = packed['nt'], packed['nr'], packed['npkt']
+    paths = {d: _find_weights(modeldir, d) for d in ('real', 'imag')}
     eng = CsiEngine(nt, nr, hidden=args.nn, n_out=packed['labels'].shape[-1], use_bn=args.useBN,
-                    device=args.device, dtype=args.dtype)
+                    device=args.device, dtype=args.dtype, input_pool=resolve_input_pool(args, paths.values()))
     models = {}
     for d in ('real', 'imag'):
         print('Working on *', d, '* model')
-        models[d] = CSIModel(eng, d).load_weights(load_weight_file(_find_weights(modeldir, d)))
+        models[d] = CSIModel(eng, d).load_weights(load_weight_file(paths[d]))
         models[d].summary()
     eng.set_pilot(packed['pilot'])
     if args.execTime:

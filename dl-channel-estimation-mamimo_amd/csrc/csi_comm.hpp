@@ -89,6 +89,7 @@ struct WireMeta {
     int32_t magic, n_layers;
     // the sender's csi_config, as far as it shapes the buffers: a receiver built for anything else refuses the record
     int32_t cfg_nt, cfg_len_ltf, cfg_n_out, cfg_dtype, cfg_use_bn, cfg_hidden[CSI_MAX_HIDDEN];
+    int32_t input_pool;                                // csi_set_input_pool: the layer-0 input width follows from it
     int32_t loaded[2], has_W0p[2], has_W0rm[2], hs_repr_ok[2];
     double hs_repr_err[2];                             // the sender's load-time measurement behind hs_repr_ok ("hs_weight_err_e12" reads the same on every rank)
     int32_t pilot_ok, p_sylvester, p_pieces;
@@ -104,7 +105,7 @@ struct WBlob {
 };
 
 // every device buffer of a component model that csi_load_weights fills, with the size it allocates (same formulas)
-void model_blobs(const csi_config& cf, Model& m, const WireLayer* wl, const int32_t has_W0p, const int32_t has_W0rm, std::vector<WBlob>& v) {
+void model_blobs(const csi_config& cf, int l0_k, Model& m, const WireLayer* wl, const int32_t has_W0p, const int32_t has_W0rm, std::vector<WBlob>& v) {
     const size_t slack = G_SLACK_FLOATS * sizeof(float);
     for (size_t i = 0; i < m.layers.size(); ++i) {
         Layer& L = m.layers[i];
@@ -122,7 +123,7 @@ void model_blobs(const csi_config& cf, Model& m, const WireLayer* wl, const int3
     }
     const size_t h1 = m.layers.empty() ? 0 : (size_t)m.layers[0].out;
     if (has_W0p) v.push_back({(void**)&m.W0p, (size_t)cf.nt * h1 * 4 + slack});
-    if (has_W0rm) v.push_back({(void**)&m.W0rm, (size_t)cf.len_ltf * h1 * 4 + slack});
+    if (has_W0rm) v.push_back({(void**)&m.W0rm, (size_t)l0_k * h1 * 4 + slack});
 }
 
 int ls_prepare(csi_ctx* c);                     // csi_mamimo.hip
@@ -136,6 +137,7 @@ void wire_fill(const csi_ctx* c, WireMeta& w) {
     w.magic = WIRE_MAGIC;
     w.n_layers = cf.n_hidden + 1;
     w.cfg_nt = cf.nt; w.cfg_len_ltf = cf.len_ltf; w.cfg_n_out = cf.n_out; w.cfg_dtype = cf.dtype; w.cfg_use_bn = cf.use_bn != 0;
+    w.input_pool = c->input_pool;
     for (int i = 0; i < cf.n_hidden; ++i) w.cfg_hidden[i] = cf.hidden[i];
     w.pilot_ok = c->pilot_ok;
     w.p_sylvester = c->p_sylvester;
@@ -168,7 +170,7 @@ void wire_fill(const csi_ctx* c, WireMeta& w) {
 void wire_blobs(csi_ctx* c, const WireMeta& w, std::vector<WBlob>& blobs) {
     const csi_config& cf = c->cfg;
     for (int d = 0; d < 2; ++d)
-        if (w.loaded[d]) model_blobs(cf, c->model[d], w.layer[d], w.has_W0p[d], w.has_W0rm[d], blobs);
+        if (w.loaded[d]) model_blobs(cf, c->l0_k, c->model[d], w.layer[d], w.has_W0p[d], w.has_W0rm[d], blobs);
     if (w.pilot_ok && cf.nt > 0) {
         const size_t ldp = (size_t)(cf.nt + 31) / 32 * 32, slack = G_SLACK_FLOATS * sizeof(float);
         blobs.push_back({(void**)&c->P, (size_t)cf.nt * cf.nt * 4 + slack});
@@ -201,6 +203,9 @@ int wire_receive(csi_ctx* c, const WireMeta& w, std::vector<WBlob>& blobs, const
     if (w.cfg_nt != cf.nt || w.cfg_len_ltf != cf.len_ltf || w.cfg_n_out != cf.n_out || w.cfg_dtype != cf.dtype || w.cfg_use_bn != (cf.use_bn != 0))
         return refuse(fail(c, CSI_ERR_INVALID_ARG, "%s: csi_config differs - sender nt %d len_ltf %d n_out %d dtype %d use_bn %d, here nt %d len_ltf %d n_out %d dtype %d use_bn %d",
                            fn, w.cfg_nt, w.cfg_len_ltf, w.cfg_n_out, w.cfg_dtype, w.cfg_use_bn, cf.nt, cf.len_ltf, cf.n_out, cf.dtype, cf.use_bn != 0));
+    if (w.input_pool != c->input_pool)
+        return refuse(fail(c, CSI_ERR_INVALID_ARG, "%s: input pooling differs - sender %s, here %s (csi_set_input_pool)", fn,
+                           input_pool_name(w.input_pool), input_pool_name(c->input_pool)));
     for (int i = 0; i < cf.n_hidden; ++i)
         if (w.cfg_hidden[i] != cf.hidden[i])
             return refuse(fail(c, CSI_ERR_INVALID_ARG, "%s: hidden layer %d is %d wide on the sender, %d here", fn, i, w.cfg_hidden[i], cf.hidden[i]));

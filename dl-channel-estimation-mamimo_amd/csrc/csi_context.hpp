@@ -20,6 +20,7 @@
 #include "ls_estimate.hip.h"
 #include "lmmse.hip.h"
 #include "metrics.hip.h"
+#include "input_pool.hip.h"
 
 using namespace csi;
 
@@ -42,12 +43,13 @@ enum KernelId {
     K_TRAIN_ELEMWISE,    // BatchNormalization, dropout, loss, Adam of csi_train_step
     K_NMSE,              // per-link NMSE metric
     K_PAIR_DENSE_TAIL,   // the last, partly filled round of band workgroups launched in column splits ("band_tail_split", round 6)
+    K_INPUT_POOL,        // MaxPooling1D / AveragePooling1D of the preambles of a decimated-input model (csi_set_input_pool)
     K_COUNT
 };
 const char* const kKernelNames[K_COUNT] = {
     "layer0_ltf_gemm", "splitk_reduce", "pair_dense_gemm", "dense_hidden_gemm", "regressor_gemm",
     "ls_estimate", "naive_dense0_gemm", "synth_white", "pilot_table", "cast_bf16", "pair_h1_bf16", "lmmse_levinson",
-    "train_gemm", "train_elementwise", "nmse_links", "pair_dense_tail"};
+    "train_gemm", "train_elementwise", "nmse_links", "pair_dense_tail", "input_pool"};
 
 thread_local std::string g_create_error;
 
@@ -123,7 +125,9 @@ struct csi_comm;             // csi_comm.hpp
 
 struct csi_ctx {
     csi_config cfg;
-    int d_in = 0;
+    int d_in = 0;                // layer-0 input width: l0_k + nt
+    int input_pool = 0;          // csi_set_input_pool: POOL_NONE / POOL_MAX / POOL_AVG (input_pool.hip.h)
+    int l0_k = 0;                // LTF inputs of layer 0: len_ltf, or len_ltf / 2 with pooling (the preamble row stride stays len_ltf)
     hipStream_t stream = nullptr;
     std::string err;
     Model model[2];
@@ -342,6 +346,31 @@ struct ProfScope {
         return e;
     }
 };
+
+const char* input_pool_name(int mode) { return mode == POOL_MAX ? "max" : (mode == POOL_AVG ? "avg" : "none"); }
+
+// pooled preambles of a decimated-input model: planes x[p] [rows][len_ltf] -> y[p] [rows][len_ltf / 2], fp32 or bf16 (input_pool.hip.h)
+int launch_input_pool(csi_ctx* c, const float* x0, const float* x1, void* y0, void* y1, int64_t rows, bool to_bf16) {
+    const int planes = x1 ? 2 : 1;
+    PoolArgs a{};
+    a.x[0] = x0; a.x[1] = x1 ? x1 : x0;
+    a.y[0] = y0; a.y[1] = y1 ? y1 : y0;
+    a.nq = (size_t)rows * (size_t)c->cfg.len_ltf / 8;
+    // 8 workgroups of 256 lanes per CU (32 waves), 8 loads of 16 bytes in flight per lane: 256 KiB requested per CU at a time
+    const size_t per_trip = (size_t)IPOOL_THREADS * IPOOL_UNR;
+    const unsigned blocks = (unsigned)std::max<size_t>(1, std::min<size_t>((a.nq + per_trip - 1) / per_trip, (size_t)c->n_cu * 8 / planes));
+    ProfScope ps(c, K_INPUT_POOL, 0.0, (double)planes * rows * c->cfg.len_ltf * (4.0 + (to_bf16 ? 1.0 : 2.0)));
+    const bool mx = c->input_pool == POOL_MAX;
+    if (to_bf16) {
+        if (mx) hipLaunchKernelGGL(input_pool_bf16_kernel<POOL_MAX>, dim3(blocks, planes), dim3(IPOOL_THREADS), 0, c->stream, a);
+        else hipLaunchKernelGGL(input_pool_bf16_kernel<POOL_AVG>, dim3(blocks, planes), dim3(IPOOL_THREADS), 0, c->stream, a);
+    } else {
+        if (mx) hipLaunchKernelGGL(input_pool_kernel<POOL_MAX>, dim3(blocks, planes), dim3(IPOOL_THREADS), 0, c->stream, a);
+        else hipLaunchKernelGGL(input_pool_kernel<POOL_AVG>, dim3(blocks, planes), dim3(IPOOL_THREADS), 0, c->stream, a);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return CSI_OK;
+}
 
 int prof_collect(csi_ctx* c) {
     if (c->spans.empty()) return CSI_OK;

@@ -184,6 +184,11 @@ int bf16_tail(csi_ctx* c, Model& m, const bf16_t* hin, int M, bf16_t* hb0, bf16_
 int predict_plane_bf16(csi_ctx* c, Model& m, const float* d_ltf, int64_t npkt, float* d_out) {
     const csi_config& cf = c->cfg;
     const int nt = cf.nt, nr = cf.nr, h1 = cf.hidden[0], nh = cf.n_hidden;
+    // K0 LTF inputs of layer 0 per preamble: len_ltf, or len_ltf / 2 for a decimated-input model (input_pool.hip.h).  Its pooled
+    // preambles sit in the xb slab - as bf16 where the cast pass ran before (the pooling pass writes them instead), as fp32 for the
+    // routes that read fp32 (chunk * nr * len_ltf bf16 = chunk * nr * len_ltf / 2 fp32: the same bytes)
+    const bool pooled = c->input_pool != POOL_NONE;
+    const int K0 = c->l0_k;
     int maxh = 0;
     for (int i = 1; i < nh; ++i) maxh = std::max(maxh, cf.hidden[i]);
     // per packet: bf16 preamble copy, fp32 layer-0 product, bf16 h1, bf16 ping-pong hidden buffers
@@ -208,30 +213,30 @@ int predict_plane_bf16(csi_ctx* c, Model& m, const float* d_ltf, int64_t npkt, f
         const int64_t np = std::min(chunk, npkt - p0);
         const int M1 = (int)(np * nr), M2 = (int)(np * nr * nt);
         GemmBf16Args g{};
-        g.A = xb; g.lda = cf.len_ltf;
+        g.A = xb; g.lda = K0;
         g.Bt = m.layers[0].Wb; g.ldb = m.layers[0].ldwb;
         g.C = l0_ws; g.ldc = h1;
-        g.M = M1; g.N = h1; g.K = cf.len_ltf;
-        int S = bf16_layer0_splits(M1, h1, cf.len_ltf);
-        g.k_per_split = ((cf.len_ltf + S - 1) / S + B_BK - 1) / B_BK * B_BK;
+        g.M = M1; g.N = h1; g.K = K0;
+        int S = bf16_layer0_splits(M1, h1, K0);
+        g.k_per_split = ((K0 + S - 1) / S + B_BK - 1) / B_BK * B_BK;
         // between the streaming kernel's range and the fused 256 x 256 kernel's (fewer than 256 of its tiles): the 128 x 128 kernel, its K cut
         // into as many ranges as fill the 256 CUs (384 packets at Nt = 64: 96 workgroups over the whole K took 320-360 us per model)
         if (S == 1) {
             const long tiles128 = (long)((M1 + 127) / 128) * ((h1 + 127) / 128);
             int s2 = (int)std::min<long>(BF16_L0_MAX_SPLITS, (256 + tiles128 - 1) / tiles128);
-            while (s2 > 1 && cf.len_ltf / s2 < 1024) --s2;
+            while (s2 > 1 && K0 / s2 < 1024) --s2;
             const long tiles256 = (long)((M1 + PP_BM - 1) / PP_BM) * ((h1 + PP_BN - 1) / PP_BN);
             if (s2 > 1 && tiles256 < 256) {
                 S = s2;
-                g.k_per_split = ((cf.len_ltf + S - 1) / S + B_BK - 1) / B_BK * B_BK;
+                g.k_per_split = ((K0 + S - 1) / S + B_BK - 1) / B_BK * B_BK;
             }
         }
         // round 6: between the streaming kernel's range and 256 tiles of the fused kernel (321 ... 4095 packets at Nt = 64, Nr = 4) layer 0 took a cast pass
         // plus the 128 x 128 kernel (1000 packets: 100-130 us + 450 us per model, 0.15 of the bf16 peak; tools/ls_overlap_trace.sh shows it).  The fused
         // 256 x 256 kernel with its K cut so that tiles x ranges fill the CUs does the same product without the cast pass ("bf16_l0_fused_split" = 0: before)
         int kps_hint = 0;
-        const int stream_splits_hint = bf16_l0_stream_splits(c, M1, h1, cf.len_ltf, &kps_hint);       // (the streaming kernel takes the call: nothing to choose)
-        if (!stream_splits_hint && c->bf16_l0_fused_split && c->bf16_fused_h1 != 0 && c->force_pair_tile == 0 && (cf.len_ltf & 3) == 0) {
+        const int stream_splits_hint = bf16_l0_stream_splits(c, M1, h1, K0, &kps_hint);       // (the streaming kernel takes the call: nothing to choose)
+        if (!stream_splits_hint && c->bf16_l0_fused_split && c->bf16_fused_h1 != 0 && c->force_pair_tile == 0 && (K0 & 3) == 0) {
             const long launched = (long)(((M1 + PP_BM - 1) / PP_BM + 7) / 8 * 8) * ((h1 + PP_BN - 1) / PP_BN);      // as pp_grid launches them
             if (launched < 256) {
                 // K ranges: rounds of 256 workgroups x the k extent of one range, plus the slabs written and read back (a 256 x 256 x k workgroup at the
@@ -240,37 +245,44 @@ int predict_plane_bf16(csi_ctx* c, Model& m, const float* d_ltf, int64_t npkt, f
                 int s3 = 1;
                 double best = 1e30;
                 for (int sx = 1; sx <= BF16_L0_MAX_SPLITS; ++sx) {
-                    const int kps = ((cf.len_ltf + sx - 1) / sx + B_BK - 1) / B_BK * B_BK;
-                    if (sx > 1 && (cf.len_ltf / sx < 1024 || kps / PP_BK < 3)) break;
+                    const int kps = ((K0 + sx - 1) / sx + B_BK - 1) / B_BK * B_BK;
+                    if (sx > 1 && (K0 / sx < 1024 || kps / PP_BK < 3)) break;
                     const double cost = (double)((launched * sx + 255) / 256) * kps * 40e-9 + (sx > 1 ? (double)sx * M1 * h1 * 8.0 / 4e12 : 0.0);
                     if (cost < best) { best = cost; s3 = sx; }
                 }
                 if (launched * s3 >= 128) {
                     ++c->bf16_l0_fused_split_launches;
                     S = s3;
-                    g.k_per_split = ((cf.len_ltf + S - 1) / S + B_BK - 1) / B_BK * B_BK;
+                    g.k_per_split = ((K0 + S - 1) / S + B_BK - 1) / B_BK * B_BK;
                 }
             }
         }
         float* l0 = l0_ws;
         int kps_stream = 0;
-        const int stream_splits = bf16_l0_stream_splits(c, M1, h1, cf.len_ltf, &kps_stream);
+        const int stream_splits = bf16_l0_stream_splits(c, M1, h1, K0, &kps_stream);
         const long l0_tiles = (long)((M1 + PP_BM - 1) / PP_BM) * ((h1 + PP_BN - 1) / PP_BN) * S;
         const long l0_launched = (long)(((M1 + PP_BM - 1) / PP_BM + 7) / 8 * 8) * ((h1 + PP_BN - 1) / PP_BN) * S;
         const bool l0_fused = c->bf16_fused_h1 != 0 && c->force_pair_tile != 128 && (l0_tiles >= 256 || c->force_pair_tile == 256 || (c->bf16_l0_fused_split && l0_launched >= 128)) &&
-                              g.k_per_split / PP_BK >= 3 && (cf.len_ltf & 3) == 0;
+                              g.k_per_split / PP_BK >= 3 && (K0 & 3) == 0;
+        const float* x0 = d_ltf + (size_t)p0 * nr * cf.len_ltf;       // layer-0 LTF input [M1][K0], fp32
+        if (pooled && (stream_splits || l0_fused)) {
+            rc = launch_input_pool(c, x0, nullptr, xb, nullptr, M1, false);
+            if (rc) return rc;
+            x0 = reinterpret_cast<const float*>(xb);
+        }
         if (stream_splits) {
             // small and mid-size calls: the weight-streaming kernel, its k-range slabs in the split-K scratch of the context
             rc = ensure_bytes(c, &c->skbuf, &c->skbuf_bytes, (size_t)(stream_splits + 1) * M1 * h1 * sizeof(float));
             if (rc) return rc;
             l0 = reinterpret_cast<float*>(c->skbuf);
             S = stream_splits;
-            rc = bf16_l0_stream_launch(c, m, d_ltf + (size_t)p0 * nr * cf.len_ltf, cf.len_ltf, M1, h1, cf.len_ltf, kps_stream, stream_splits, l0);
+            rc = bf16_l0_stream_launch(c, m, x0, K0, M1, h1, K0, kps_stream, stream_splits, l0);
         } else if (l0_fused) {
             // the conversion happens inside the GEMM: no separate pass over the preambles
-            rc = launch_layer0_cast_bf16(c, g, d_ltf + (size_t)p0 * nr * cf.len_ltf, cf.len_ltf, S);
+            rc = launch_layer0_cast_bf16(c, g, x0, K0, S);
         } else {
-            rc = cast_bf16(c, d_ltf + (size_t)p0 * nr * cf.len_ltf, xb, (size_t)M1 * cf.len_ltf);
+            // (decimated-input model: the pooling pass writes the bf16 operand in place of the cast pass - same launch count)
+            rc = pooled ? launch_input_pool(c, x0, nullptr, xb, nullptr, M1, true) : cast_bf16(c, x0, xb, (size_t)M1 * cf.len_ltf);
             if (rc) return rc;
             rc = launch_gemm_bf16<EPI_RAW, false>(c, K_LAYER0_LTF, g, S);
         }

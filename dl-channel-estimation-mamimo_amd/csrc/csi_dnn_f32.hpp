@@ -173,6 +173,11 @@ int build_pilot_table(csi_ctx* c, Model& m) {
 int predict_plane(csi_ctx* c, Model& m, const float* d_ltf, int64_t npkt, float* d_out) {
     const csi_config& cf = c->cfg;
     const int nt = cf.nt, nr = cf.nr, h1 = cf.hidden[0], nh = cf.n_hidden;
+    // layer 0 reads K0 LTF inputs per preamble: the preambles themselves, or (decimated-input model) their pooled copy, [chunk][nr][K0] in
+    // the workspace behind the activation buffers (input_pool.hip.h)
+    const bool pooled = c->input_pool != POOL_NONE;
+    const int K0 = c->l0_k;
+    const size_t pool_pkt = pooled ? (size_t)nr * K0 * 4 : 0;
     int maxh = 0;
     for (int i = 1; i < nh; ++i) maxh = std::max(maxh, cf.hidden[i]);
     // Packet chunks: as few as the workspace allows, all of (nearly) the same size so that every
@@ -189,10 +194,10 @@ int predict_plane(csi_ctx* c, Model& m, const float* d_ltf, int64_t npkt, float*
     for (;;) {
         chunk = (npkt + nchunks - 1) / nchunks;
         int kps_tmp;
-        splits_max = choose_splits((int)std::min<int64_t>(chunk * nr, 1 << 30), h1, cf.len_ltf, &kps_tmp);
-        if (hs_ok) splits_max = std::max(splits_max, hs_layer0_splits(c, (int)std::min<int64_t>(chunk * nr, 1 << 30), h1, cf.len_ltf, &kps_tmp));
-        if (hs_ok) splits_max = std::max(splits_max, l0_stream_splits(c, m, (int)std::min<int64_t>(chunk * nr, 1 << 30), h1, cf.len_ltf, &kps_tmp));
-        const size_t need = ((size_t)nr * h1 * 4 * (splits_max > 1 ? splits_max + 1 : 1) + hid_pkt) * (size_t)chunk;
+        splits_max = choose_splits((int)std::min<int64_t>(chunk * nr, 1 << 30), h1, K0, &kps_tmp);
+        if (hs_ok) splits_max = std::max(splits_max, hs_layer0_splits(c, (int)std::min<int64_t>(chunk * nr, 1 << 30), h1, K0, &kps_tmp));
+        if (hs_ok) splits_max = std::max(splits_max, l0_stream_splits(c, m, (int)std::min<int64_t>(chunk * nr, 1 << 30), h1, K0, &kps_tmp));
+        const size_t need = ((size_t)nr * h1 * 4 * (splits_max > 1 ? splits_max + 1 : 1) + hid_pkt + pool_pkt) * (size_t)chunk;
         if ((need <= budget && chunk <= max_rows) || chunk == 1) break;
         nchunks = std::max(nchunks + 1, (int64_t)((double)nchunks * (double)need / (double)budget));
     }
@@ -200,15 +205,15 @@ int predict_plane(csi_ctx* c, Model& m, const float* d_ltf, int64_t npkt, float*
         int kps_tmp;
         const int64_t tail = npkt - (nchunks - 1) * chunk;
         if (tail > 0 && tail != chunk) {
-            splits_max = std::max(splits_max, choose_splits((int)(tail * nr), h1, cf.len_ltf, &kps_tmp));
-            if (hs_ok) splits_max = std::max(splits_max, hs_layer0_splits(c, (int)(tail * nr), h1, cf.len_ltf, &kps_tmp));
-            if (hs_ok) splits_max = std::max(splits_max, l0_stream_splits(c, m, (int)(tail * nr), h1, cf.len_ltf, &kps_tmp));
+            splits_max = std::max(splits_max, choose_splits((int)(tail * nr), h1, K0, &kps_tmp));
+            if (hs_ok) splits_max = std::max(splits_max, hs_layer0_splits(c, (int)(tail * nr), h1, K0, &kps_tmp));
+            if (hs_ok) splits_max = std::max(splits_max, l0_stream_splits(c, m, (int)(tail * nr), h1, K0, &kps_tmp));
         }
     }
     const size_t slab_floats = (size_t)chunk * nr * h1;
     // (+ 16 rows per activation buffer: the blocked hs layout addresses whole 16-row blocks)
     const size_t hid_pad = (size_t)16 * maxh * 4;
-    const size_t per_chunk = slab_floats * 4 * (splits_max > 1 ? splits_max + 1 : 1) + hid_pkt * (size_t)chunk + 2 * hid_pad;
+    const size_t per_chunk = slab_floats * 4 * (splits_max > 1 ? splits_max + 1 : 1) + hid_pkt * (size_t)chunk + 2 * hid_pad + pool_pkt * (size_t)chunk;
     int rc = ensure_bytes(c, &c->ws, &c->ws_bytes, per_chunk);
     if (rc) return rc;
 
@@ -221,20 +226,27 @@ int predict_plane(csi_ctx* c, Model& m, const float* d_ltf, int64_t npkt, float*
         float* hbuf[2];
         hbuf[0] = slabs + slab_floats * (splits_max > 1 ? splits_max + 1 : 1);
         hbuf[1] = hbuf[0] + (size_t)chunk * nr * nt * maxh + hid_pad / 4;
+        const float* x0 = d_ltf + (size_t)p0 * nr * cf.len_ltf;       // layer-0 LTF input [M1][K0]
+        if (pooled) {
+            float* xp = reinterpret_cast<float*>(c->ws + per_chunk - pool_pkt * (size_t)chunk);      // the last part of the chunk's workspace
+            rc = launch_input_pool(c, x0, nullptr, xp, nullptr, M1, false);
+            if (rc) return rc;
+            x0 = xp;
+        }
 
-        // layer 0, LTF part: L0[M1][h1] = ltf[M1][len_ltf] * W0[0:len_ltf, :]
+        // layer 0, LTF part: L0[M1][h1] = ltf[M1][K0] * W0[0:K0, :]
         const float* l0 = nullptr;
         if (M1 <= 8 && m.W0rm && !c->force_pair_tile) {
             // a handful of preambles: stream W0 once (HBM-bound) instead of running a GEMM
-            const int S = (cf.len_ltf + 4 * SK_KS - 1) / (4 * SK_KS);
+            const int S = (K0 + 4 * SK_KS - 1) / (4 * SK_KS);
             rc = ensure_bytes(c, &c->l0skinny, &c->l0skinny_bytes, (size_t)(S + 1) * 8 * h1 * sizeof(float));
             if (rc) return rc;
             float* sl = reinterpret_cast<float*>(c->l0skinny);
             float* sum = sl + (size_t)S * M1 * h1;
             {
-                ProfScope ps(c, K_LAYER0_LTF, 2.0 * M1 * h1 * cf.len_ltf, 4.0 * ((double)cf.len_ltf * h1 + (double)M1 * cf.len_ltf + (double)S * M1 * h1));
+                ProfScope ps(c, K_LAYER0_LTF, 2.0 * M1 * h1 * K0, 4.0 * ((double)K0 * h1 + (double)M1 * K0 + (double)S * M1 * h1));
                 hipLaunchKernelGGL((layer0_skinny_kernel<8>), dim3((unsigned)S, (unsigned)((h1 + 255) / 256)), dim3(256), 0, c->stream,
-                                   d_ltf + (size_t)p0 * nr * cf.len_ltf, cf.len_ltf, M1, m.W0rm, h1, cf.len_ltf, sl);
+                                   x0, K0, M1, m.W0rm, h1, K0, sl);
                 HIP_TRY(c, hipGetLastError());
             }
             {
@@ -247,27 +259,27 @@ int predict_plane(csi_ctx* c, Model& m, const float* d_ltf, int64_t npkt, float*
         }
         int kps = 0;
         // 9 ... 256 preambles: the weight-streaming kernel of the split engine (l0_hs_stream.hip.h), k ranges summed below
-        const int stream_splits = (hs_ok && !l0) ? l0_stream_splits(c, m, M1, h1, cf.len_ltf, &kps) : 0;
+        const int stream_splits = (hs_ok && !l0) ? l0_stream_splits(c, m, M1, h1, K0, &kps) : 0;
         if (stream_splits) {
-            rc = l0_stream_launch(c, m, d_ltf + (size_t)p0 * nr * cf.len_ltf, cf.len_ltf, M1, h1, cf.len_ltf, kps, stream_splits, slabs);
+            rc = l0_stream_launch(c, m, x0, K0, M1, h1, K0, kps, stream_splits, slabs);
             if (rc) return rc;
             l0 = slabs;
         }
-        const int hs_splits = (hs_ok && !l0) ? hs_layer0_splits(c, M1, h1, cf.len_ltf, &kps) : 0;
+        const int hs_splits = (hs_ok && !l0) ? hs_layer0_splits(c, M1, h1, K0, &kps) : 0;
         if (hs_splits) {
-            rc = hs_launch_layer0(c, m, d_ltf + (size_t)p0 * nr * cf.len_ltf, cf.len_ltf, M1, h1, cf.len_ltf, kps, hs_splits, slabs);
+            rc = hs_launch_layer0(c, m, x0, K0, M1, h1, K0, kps, hs_splits, slabs);
             if (rc) return rc;
             l0 = slabs;
         }
-        const int splits = stream_splits ? stream_splits : (hs_splits ? hs_splits : (l0 ? 1 : choose_splits(M1, h1, cf.len_ltf, &kps)));
+        const int splits = stream_splits ? stream_splits : (hs_splits ? hs_splits : (l0 ? 1 : choose_splits(M1, h1, K0, &kps)));
         GemmArgs g{};
-        g.A = d_ltf + (size_t)p0 * nr * cf.len_ltf;
-        g.lda = cf.len_ltf;
+        g.A = x0;
+        g.lda = K0;
         g.Bt = m.layers[0].Wt;
         g.ldb = m.layers[0].ldw;
         g.C = slabs;
         g.ldc = h1;
-        g.M = M1; g.N = h1; g.K = cf.len_ltf;
+        g.M = M1; g.N = h1; g.K = K0;
         g.k_per_split = kps;
         if (!l0) {
             rc = launch_gemm<EPI_RAW>(c, K_LAYER0_LTF, g, splits);

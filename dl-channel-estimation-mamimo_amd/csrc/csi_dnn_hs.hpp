@@ -12,7 +12,7 @@ constexpr int HS_L0_MAX_SPLITS = 8;
 // shapes the kernels can serve: every hidden width a multiple of 16 (hs groups), split weights present
 bool hs_static_ok(const csi_ctx* c, const Model& m) {
     const csi_config& cf = c->cfg;
-    if (c->f32_engine == 0 || cf.dtype != CSI_DTYPE_F32 || cf.nt <= 0 || (cf.len_ltf % HS_G) != 0) return false;
+    if (c->f32_engine == 0 || cf.dtype != CSI_DTYPE_F32 || cf.nt <= 0 || (c->l0_k % HS_G) != 0) return false;
     if (!m.hs_repr_ok) return false;          // split copies of this model's weights are not fp32-grade (csi_load_weights): fp32 MFMA kernels
     for (int i = 0; i < cf.n_hidden; ++i)
         if (cf.hidden[i] % HS_G) return false;

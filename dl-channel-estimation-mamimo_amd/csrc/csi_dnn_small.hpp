@@ -58,7 +58,13 @@ int predict_small(csi_ctx* c, const float* d_ltf_re, const float* d_ltf_im, int6
     for (int i = 1; i < nh; ++i) maxh = std::max(maxh, cf.hidden[i]);
     // scratch: the per-pair layer's input rows of both models, then two ping-pong activation buffers per model
     const size_t h1_floats = (size_t)M2 * h1, act_floats = (size_t)M2 * maxh;
-    int rc = ensure_bytes(c, &c->small_ws, &c->small_ws_bytes, (2 * h1_floats + 4 * act_floats) * sizeof(float));
+    // decimated-input model (input_pool.hip.h): layer 0 walks K0 = len_ltf / 2 pooled inputs.  Up to 8 preambles the weight-streaming
+    // kernel pools inside its loads (same launch count as an unpooled call); the tile kernel beyond reads the pooled preambles of both
+    // planes from the end of the scratch, written by one pooling pass in front of it
+    const bool pooled = c->input_pool != POOL_NONE;
+    const int K0 = c->l0_k;
+    const size_t pool_floats = pooled && M1 > SC_MAX_ROWS0 ? (size_t)M1 * K0 : 0;
+    int rc = ensure_bytes(c, &c->small_ws, &c->small_ws_bytes, (2 * h1_floats + 4 * act_floats + 2 * pool_floats) * sizeof(float));
     if (rc) return rc;
     float* h1buf = reinterpret_cast<float*>(c->small_ws);
     float* act = h1buf + 2 * h1_floats;         // [buffer][model][M2][maxh]
@@ -67,18 +73,26 @@ int predict_small(csi_ctx* c, const float* d_ltf_re, const float* d_ltf_im, int6
         // 9 ... 64 preambles: layer 0 on the 16 x 16 tiles, the per-pair layer's input rows written by its epilogue (EPI_H1)
         SmallGemmArgs g{};
         g.A[0] = d_ltf_re; g.A[1] = d_ltf_im;
+        int lda0 = cf.len_ltf;
+        if (pooled) {
+            float* xp = act + 4 * act_floats;
+            rc = launch_input_pool(c, d_ltf_re, d_ltf_im, xp, xp + pool_floats, M1, false);
+            if (rc) return rc;
+            g.A[0] = xp; g.A[1] = xp + pool_floats;
+            lda0 = K0;
+        }
         for (int d = 0; d < 2; ++d) {
             const Model& m = *md[d];
             const bool fold = m.layers[1].bias_hs != nullptr;
             g.Bt[d] = m.layers[0].Wt; g.T[d] = m.T; g.s0[d] = m.layers[0].scale; g.t0[d] = fold ? c->hs_zero : m.layers[0].shift;
             g.C[d] = h1buf + d * h1_floats;
         }
-        g.M = M1; g.N = h1; g.K = cf.len_ltf; g.lda = cf.len_ltf; g.ldb = md[0]->layers[0].ldw; g.ldc = h1; g.nt = nt;
+        g.M = M1; g.N = h1; g.K = K0; g.lda = lda0; g.ldb = md[0]->layers[0].ldw; g.ldc = h1; g.nt = nt;
         const int tiles_n = (h1 + 15) / 16, tiles_m = (M1 + 15) / 16;
         int rg = 4;
         while (rg > 1 && (long)tiles_n * ((tiles_m + rg - 1) / rg) * 2 < 200) rg >>= 1;
         const dim3 grid((unsigned)tiles_n, (unsigned)((tiles_m + rg - 1) / rg), 2);
-        ProfScope ps(c, K_LAYER0_LTF, 2.0 * 2.0 * M1 * h1 * cf.len_ltf, 2.0 * 4.0 * ((double)cf.len_ltf * h1 + (double)M1 * cf.len_ltf + (double)(nt + M2) * h1));
+        ProfScope ps(c, K_LAYER0_LTF, 2.0 * 2.0 * M1 * h1 * K0, 2.0 * 4.0 * ((double)K0 * h1 + (double)M1 * cf.len_ltf + (double)(nt + M2) * h1));
         if (rg == 4) hipLaunchKernelGGL((small_tile_gemm_kernel<EPI_H1, 4, 4>), grid, dim3(1024), 0, c->stream, g);
         else if (rg == 2) hipLaunchKernelGGL((small_tile_gemm_kernel<EPI_H1, 2, 4>), grid, dim3(1024), 0, c->stream, g);
         else hipLaunchKernelGGL((small_tile_gemm_kernel<EPI_H1, 1, 4>), grid, dim3(1024), 0, c->stream, g);
@@ -93,8 +107,8 @@ int predict_small(csi_ctx* c, const float* d_ltf_re, const float* d_ltf_im, int6
             a.Wt[d] = m.layers[0].Wt; a.T[d] = m.T; a.s0[d] = m.layers[0].scale; a.t0[d] = fold ? c->hs_zero : m.layers[0].shift;
             a.h1out[d] = h1buf + d * h1_floats;
         }
-        a.M = M1; a.K = cf.len_ltf; a.lda = cf.len_ltf; a.ldw = md[0]->layers[0].ldw; a.h1 = h1; a.nt = nt;
-        ProfScope ps(c, K_LAYER0_LTF, 2.0 * 2.0 * M1 * h1 * cf.len_ltf, 2.0 * 4.0 * ((double)cf.len_ltf * h1 + (double)M1 * cf.len_ltf + (double)(nt + M2) * h1));
+        a.M = M1; a.K = K0; a.lda = cf.len_ltf; a.ldw = md[0]->layers[0].ldw; a.h1 = h1; a.nt = nt;
+        ProfScope ps(c, K_LAYER0_LTF, 2.0 * 2.0 * M1 * h1 * K0, 2.0 * 4.0 * ((double)K0 * h1 + (double)M1 * cf.len_ltf + (double)(nt + M2) * h1));
         // 4 columns per workgroup, 2 k steps of 1024 in flight: every shape tried (4 / 8 columns, 2 ... 5 steps) lands at 16.2-17.0 us
         // for the 84 MB of the shipped model = 5.2 TB/s - the memory system's rate, not the kernel's (profiles/r05_small_call_trace.txt)
         const dim3 grid((unsigned)((h1 + 3) / 4), 2);
@@ -106,10 +120,12 @@ int predict_small(csi_ctx* c, const float* d_ltf_re, const float* d_ltf_im, int6
             int nblk = M1, ls_blocks = M1;
             const dim3 fgrid(grid.x + (unsigned)ls_blocks, 2);
             const void* fn = nullptr;
-#define SC_LS(NTV) (M1 > 4 ? (const void*)small_l0_ls_kernel<NTV, 8> : (const void*)small_l0_ls_kernel<NTV, 4>)
-            fn = nt == 16 ? SC_LS(16) : (nt == 32 ? SC_LS(32) : SC_LS(64));
+#define SC_LS(NTV, PV) (M1 > 4 ? (const void*)small_l0_ls_kernel<NTV, 8, PV> : (const void*)small_l0_ls_kernel<NTV, 4, PV>)
+#define SC_LSP(PV) (nt == 16 ? SC_LS(16, PV) : (nt == 32 ? SC_LS(32, PV) : SC_LS(64, PV)))
+            fn = c->input_pool == POOL_MAX ? SC_LSP(POOL_MAX) : (c->input_pool == POOL_AVG ? SC_LSP(POOL_AVG) : SC_LSP(POOL_NONE));
+#undef SC_LSP
 #undef SC_LS
-            static thread_local const void* attr_fn[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+            static thread_local const void* attr_fn[18] = {};
             bool seen = false;
             for (const void* f : attr_fn) seen = seen || f == fn;
             if (!seen) {
@@ -120,6 +136,12 @@ int predict_small(csi_ctx* c, const float* d_ltf_re, const float* d_ltf_im, int6
             HIP_TRY(c, hipLaunchKernel(fn, fgrid, dim3(256), kargs, ls_lds, c->stream));
             c->small_ls_h_re = c->small_ls_h_im = nullptr;      // consumed
             ++c->small_ls_launches;
+        } else if (c->input_pool == POOL_MAX) {
+            if (M1 > 4) hipLaunchKernelGGL((small_l0_gemv_kernel<8, 4, 2, POOL_MAX>), grid, dim3(256), 0, c->stream, a);
+            else hipLaunchKernelGGL((small_l0_gemv_kernel<4, 4, 2, POOL_MAX>), grid, dim3(256), 0, c->stream, a);
+        } else if (c->input_pool == POOL_AVG) {
+            if (M1 > 4) hipLaunchKernelGGL((small_l0_gemv_kernel<8, 4, 2, POOL_AVG>), grid, dim3(256), 0, c->stream, a);
+            else hipLaunchKernelGGL((small_l0_gemv_kernel<4, 4, 2, POOL_AVG>), grid, dim3(256), 0, c->stream, a);
         } else if (M1 > 4) hipLaunchKernelGGL((small_l0_gemv_kernel<8, 4, 2>), grid, dim3(256), 0, c->stream, a);
         else hipLaunchKernelGGL((small_l0_gemv_kernel<4, 4, 2>), grid, dim3(256), 0, c->stream, a);
         HIP_TRY(c, hipGetLastError());

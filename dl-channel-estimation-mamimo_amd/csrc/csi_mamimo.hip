@@ -392,6 +392,27 @@ int csi_abi_version(void) { return CSI_ABI_VERSION; }
 
 const char* csi_last_error(const csi_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
 
+int csi_set_input_pool(csi_ctx* c, int mode) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    if (mode < POOL_NONE || mode > POOL_AVG)
+        return fail(c, CSI_ERR_INVALID_ARG, "csi_set_input_pool: mode %d is none (0), max (1) or avg (2)", mode);
+    if (mode != POOL_NONE && c->cfg.nt == 0)
+        return fail(c, CSI_ERR_INVALID_ARG, "csi_set_input_pool: pooling needs the pilot input (nt > 0); the single-input model has none");
+    for (int d = 0; d < 2; ++d) {
+        if (c->model[d].loaded)
+            return fail(c, CSI_ERR_INVALID_ARG, "csi_set_input_pool: the %s model holds weights; the pooling mode is set before csi_load_weights", d ? "imag" : "real");
+        if (c->trainer[d])
+            return fail(c, CSI_ERR_INVALID_ARG, "csi_set_input_pool: a trainer of the %s model exists; the pooling mode is set before csi_train_begin", d ? "imag" : "real");
+    }
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    drop_graphs(c);
+    c->input_pool = mode;
+    c->l0_k = mode == POOL_NONE ? c->cfg.len_ltf : c->cfg.len_ltf / 2;
+    c->d_in = c->l0_k + c->cfg.nt;
+    return CSI_OK;
+}
+
 int csi_create(const csi_config* cfg, csi_ctx** out) {
     if (!cfg || !out) return fail(nullptr, CSI_ERR_INVALID_ARG, "csi_create: null argument");
     *out = nullptr;
@@ -436,7 +457,8 @@ int csi_create(const csi_config* cfg, csi_ctx** out) {
     c->cfg = *cfg;
     c->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     if (c->cfg.bn_eps <= 0.f) c->cfg.bn_eps = 1e-3f;
-    c->d_in = cfg->len_ltf + cfg->nt;
+    c->l0_k = cfg->len_ltf;
+    c->d_in = c->l0_k + cfg->nt;
     if (const char* e = std::getenv("CSI_FORCE_PAIR_TILE")) c->force_pair_tile = std::atoi(e);
     if (const char* e = std::getenv("CSI_LS_FFT_FIRST_MAX")) c->ls_fft_first_max = std::min(64, std::max(0, std::atoi(e)));
     if (const char* e = std::getenv("CSI_LS_DEBUG")) c->ls_debug = std::atoi(e);
@@ -571,6 +593,11 @@ int csi_load_weights(csi_ctx* c, int model, const csi_tensor* tensors, int n) {
         const csi_tensor* k = find_tensor(tensors, n, base + ".kernel");
         const csi_tensor* b = find_tensor(tensors, n, base + ".bias");
         if (!k || !b || !k->data || !b->data) return fail(c, CSI_ERR_INVALID_ARG, "csi_load_weights: missing %s.kernel/.bias", base.c_str());
+        if (li == 0 && cf.nt > 0 && k->rows != fan_in && k->cols == out)
+            return fail(c, CSI_ERR_INVALID_ARG, "csi_load_weights: %s.kernel is [%lld,%lld], expected [%d,%d] (input pooling %s: %d LTF rows + %d pilot rows)%s",
+                        base.c_str(), (long long)k->rows, (long long)k->cols, fan_in, out, input_pool_name(c->input_pool), c->l0_k, cf.nt,
+                        k->rows == (int64_t)cf.len_ltf / 2 + cf.nt ? " - a decimated model: csi_set_input_pool(max | avg) first" :
+                        (k->rows == (int64_t)cf.len_ltf + cf.nt ? " - a model without pooling: csi_set_input_pool(none)" : ""));
         if (k->rows != fan_in || k->cols != out || b->rows * b->cols != out)
             return fail(c, CSI_ERR_INVALID_ARG, "csi_load_weights: %s.kernel is [%lld,%lld], expected [%d,%d]", base.c_str(),
                         (long long)k->rows, (long long)k->cols, fan_in, out);
@@ -628,7 +655,7 @@ int csi_load_weights(csi_ctx* c, int model, const csi_tensor* tensors, int n) {
             // split-f16 copy for gemm_hs.hip.h: W * 2^wshift (largest magnitude in [2^12, 2^13)) as
             // hi + lo halves in groups of 16 k-columns; layer 0 keeps its LTF columns only (the pilot
             // rows live in the table T)
-            const int kh = (li == 0 && cf.nt > 0) ? cf.len_ltf : fan_in;
+            const int kh = (li == 0 && cf.nt > 0) ? c->l0_k : fan_in;
             // layer 1 (the first per-pair layer; the regressor when there is one hidden layer) on the shared-layer-0
             // path: the pair kernel generates A = relu(L0 + T) without bn0, so bn0's scale multiplies the rows of
             // this copy - (relu(z) sc) W = relu(z) (diag(sc) W) - and bn0's shift sits in bias_hs below
@@ -798,13 +825,13 @@ int csi_load_weights(csi_ctx* c, int model, const csi_tensor* tensors, int n) {
         if (li == 0 && cf.nt > 0) {
             // pilot rows of fc_dense0.kernel, [nt][h1] row-major as stored (bf16 mode: rounded like
             // every other weight, the table itself is evaluated in fp32)
-            std::vector<float> w0p(k->data + (size_t)cf.len_ltf * out, k->data + (size_t)(cf.len_ltf + cf.nt) * out);
+            std::vector<float> w0p(k->data + (size_t)c->l0_k * out, k->data + (size_t)(c->l0_k + cf.nt) * out);
             if (bf16)
                 for (float& v : w0p) { const uint32_t u = (uint32_t)rne(v) << 16; std::memcpy(&v, &u, 4); }
             rc = upload(c, &m.W0p, w0p.data(), w0p.size());
             if (rc) return rc;
             if (!bf16) {
-                rc = upload(c, &m.W0rm, k->data, (size_t)cf.len_ltf * out);
+                rc = upload(c, &m.W0rm, k->data, (size_t)c->l0_k * out);
                 if (rc) return rc;
             }
         }
@@ -1239,6 +1266,7 @@ int csi_get_option(csi_ctx* c, const char* name, int64_t* value) {
     else if (n == "small_ls_fused") *value = c->small_ls_fused;
     else if (n == "small_ls_launches") *value = c->small_ls_launches;
     else if (n == "small_calls") *value = c->small_calls;
+    else if (n == "input_pool") *value = c->input_pool;
     else if (n == "small_rows") *value = c->small_rows;
     else if (n == "small_rows_band") *value = c->small_rows_band;
     else if (n == "f32_engine") *value = c->f32_engine;
@@ -1866,9 +1894,25 @@ int csi_predict_samples(csi_ctx* c, int model, const float* x, int64_t B, float*
     HIP_TRY(c, hipSetDevice(cf.device));
     int maxh = 0;
     for (int i = 0; i < cf.n_hidden; ++i) maxh = std::max(maxh, cf.hidden[i]);
+    // rows arrive raw, [B][len_ltf + nt], as keras' predict receives them; a decimated-input model pools them on the device into the
+    // [B][len_ltf / 2 + nt] rows its layer 0 reads (input_pool_rows_kernel)
+    const bool pooled = c->input_pool != POOL_NONE;
+    const int raw_in = pooled ? cf.len_ltf + cf.nt : c->d_in;
+    auto upload_rows = [&](float* d_raw, float* d_rows, int64_t r0, int64_t nb) -> int {
+        HIP_TRY(c, hipMemcpyAsync(pooled ? d_raw : d_rows, x + (size_t)r0 * raw_in, (size_t)nb * raw_in * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        if (!pooled) return CSI_OK;
+        ProfScope ps(c, K_INPUT_POOL, 0.0, 4.0 * (double)nb * (raw_in + c->d_in));
+        const unsigned blocks = (unsigned)std::min<size_t>(((size_t)nb * c->d_in + 255) / 256, 8192);
+        if (c->input_pool == POOL_MAX)
+            hipLaunchKernelGGL(input_pool_rows_kernel<POOL_MAX>, dim3(blocks), dim3(256), 0, c->stream, d_raw, raw_in, d_rows, c->d_in, (int)nb, c->l0_k, cf.nt);
+        else
+            hipLaunchKernelGGL(input_pool_rows_kernel<POOL_AVG>, dim3(blocks), dim3(256), 0, c->stream, d_raw, raw_in, d_rows, c->d_in, (int)nb, c->l0_k, cf.nt);
+        HIP_TRY(c, hipGetLastError());
+        return CSI_OK;
+    };
     if (cf.dtype == CSI_DTYPE_BF16) {
         const int ldx = (c->d_in + B_BK - 1) / B_BK * B_BK;
-        const size_t per_row_b = (size_t)c->d_in * 4 + (size_t)ldx * 2 + 2 * (size_t)maxh * 2 + (size_t)cf.n_out * 4;
+        const size_t per_row_b = (size_t)c->d_in * 4 + (size_t)ldx * 2 + 2 * (size_t)maxh * 2 + (size_t)cf.n_out * 4 + (pooled ? (size_t)raw_in * 4 : 0);
         int64_t chunk_b = std::min<int64_t>(B, std::max<int64_t>(1, ((int64_t)512 << 20) / (int64_t)per_row_b));
         int rcb = ensure_bytes(c, &c->stage, &c->stage_bytes, per_row_b * (size_t)chunk_b + 1024);
         if (rcb) return rcb;
@@ -1877,10 +1921,12 @@ int csi_predict_samples(csi_ctx* c, int model, const float* x, int64_t B, float*
         float* d_yf = reinterpret_cast<float*>(base);      base += (size_t)chunk_b * cf.n_out * 4;
         bf16_t* d_xb = reinterpret_cast<bf16_t*>(base);    base += (size_t)chunk_b * ldx * 2;
         bf16_t* hb0 = reinterpret_cast<bf16_t*>(base);     base += (size_t)chunk_b * maxh * 2;
-        bf16_t* hb1 = reinterpret_cast<bf16_t*>(base);
+        bf16_t* hb1 = reinterpret_cast<bf16_t*>(base);     base += (size_t)chunk_b * maxh * 2;
+        float* d_raw = reinterpret_cast<float*>(base);     // [chunk_b][raw_in] (pooled models)
         for (int64_t r0 = 0; r0 < B; r0 += chunk_b) {
             const int nb = (int)std::min(chunk_b, B - r0);
-            HIP_TRY(c, hipMemcpyAsync(d_xf, x + (size_t)r0 * c->d_in, (size_t)nb * c->d_in * 4, hipMemcpyHostToDevice, c->stream));
+            rcb = upload_rows(d_raw, d_xf, r0, nb);
+            if (rcb) return rcb;
             {
                 ProfScope ps(c, K_CAST_BF16, 0.0, 6.0 * nb * c->d_in);
                 const unsigned blocks = (unsigned)std::min<size_t>(((size_t)nb * ldx + 255) / 256, 8192);
@@ -1905,7 +1951,7 @@ int csi_predict_samples(csi_ctx* c, int model, const float* x, int64_t B, float*
         }
         return CSI_OK;
     }
-    const size_t per_row = ((size_t)c->d_in + 2 * (size_t)maxh + cf.n_out) * sizeof(float);
+    const size_t per_row = ((size_t)c->d_in + 2 * (size_t)maxh + cf.n_out + (pooled ? (size_t)raw_in : 0)) * sizeof(float);
     int64_t chunk = std::max<int64_t>(1, ((int64_t)512 << 20) / (int64_t)per_row);
     chunk = std::min(chunk, B);
     int rc = ensure_bytes(c, &c->stage, &c->stage_bytes, per_row * (size_t)chunk + G_SLACK_FLOATS * sizeof(float));
@@ -1917,9 +1963,11 @@ int csi_predict_samples(csi_ctx* c, int model, const float* x, int64_t B, float*
     hb[0] = d_x + (size_t)chunk * c->d_in + G_SLACK_FLOATS;
     hb[1] = hb[0] + (size_t)chunk * maxh;
     float* d_y = hb[1] + (size_t)chunk * maxh;
+    float* d_raw = d_y + (size_t)chunk * cf.n_out;       // [chunk][raw_in] (pooled models)
     for (int64_t r0 = 0; r0 < B; r0 += chunk) {
         const int64_t nb = std::min(chunk, B - r0);
-        HIP_TRY(c, hipMemcpyAsync(d_x, x + (size_t)r0 * c->d_in, (size_t)nb * c->d_in * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        rc = upload_rows(d_raw, d_x, r0, nb);
+        if (rc) return rc;
         HIP_TRY(c, hipMemsetAsync(d_x + (size_t)nb * c->d_in, 0, G_SLACK_FLOATS * sizeof(float), c->stream));
         const float* cur = d_x;
         int cur_ld = c->d_in, w = 0;

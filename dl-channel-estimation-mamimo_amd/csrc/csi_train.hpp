@@ -34,6 +34,8 @@ struct csi_trainer {
     int cap = 0, ldb = 0;             // batch capacity of the activation buffers, round32(cap)
     int maxw = 0;                     // widest padded layer output
     int k0 = 0, ldx = 0;              // input width, row pitch of xn
+    int kraw = 0;                     // width of the rows the caller hands over (k0, or len_ltf + nt for a decimated-input model)
+    int last_B = 0;                   // rows of the last staged batch (csi_train_get "input")
     float *x = nullptr, *y = nullptr, *xn = nullptr, *xt = nullptr;
     float *dz = nullptr, *dzt = nullptr, *dh[2] = {nullptr, nullptr};
     float *out = nullptr, *dout = nullptr, *doutt = nullptr, *partial = nullptr, *loss = nullptr;
@@ -96,7 +98,7 @@ int tr_reserve(csi_ctx* c, csi_trainer* t, int B) {
     const int n_out_ld = t->layers.back().ldo;
     int maxw = n_out_ld;
     for (auto& l : t->layers) maxw = std::max(maxw, l.ldo);
-    rc |= tr_alloc(c, t, &t->x, (size_t)cap * t->k0);
+    rc |= tr_alloc(c, t, &t->x, (size_t)cap * t->kraw);
     rc |= tr_alloc(c, t, &t->y, (size_t)cap * t->layers.back().out);
     rc |= tr_alloc(c, t, &t->xn, (size_t)cap * t->ldx);
     rc |= tr_alloc(c, t, &t->xt, (size_t)t->k0 * ldb);
@@ -190,7 +192,7 @@ int tr_adam(csi_ctx* c, csi_trainer* t, float* p, const float* g, float* m, floa
 }
 
 int tr_upload_batch(csi_ctx* c, csi_trainer* t, const float* x, const float* y, int B) {
-    HIP_TRY(c, hipMemcpyAsync(t->x, x, (size_t)B * t->k0 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(t->x, x, (size_t)B * t->kraw * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(t->y, y, (size_t)B * t->layers.back().out * sizeof(float), hipMemcpyHostToDevice, c->stream));
     return CSI_OK;
 }
@@ -222,8 +224,16 @@ int tr_stage(csi_ctx* c, csi_trainer* t, const float* x, const float* y, const i
     if (!ids) {
         rc = tr_upload_batch(c, t, x, y, B);
         if (rc) return rc;
-        hipLaunchKernelGGL(train_input_kernel, dim3((t->k0 + 31) / 32, (B + 31) / 32), dim3(256), 0, c->stream, t->x, t->xn, t->xt, B, t->k0,
-                           t->ldx, t->ldb, n_noisy, noise_std, stream);
+        const dim3 grid((t->k0 + 31) / 32, (B + 31) / 32);
+        if (c->input_pool == POOL_MAX)
+            hipLaunchKernelGGL(train_input_kernel<POOL_MAX>, grid, dim3(256), 0, c->stream, t->x, t->xn, t->xt, B, t->k0, t->ldx, t->ldb, n_noisy, noise_std, stream,
+                               t->kraw, c->l0_k);
+        else if (c->input_pool == POOL_AVG)
+            hipLaunchKernelGGL(train_input_kernel<POOL_AVG>, grid, dim3(256), 0, c->stream, t->x, t->xn, t->xt, B, t->k0, t->ldx, t->ldb, n_noisy, noise_std, stream,
+                               t->kraw, c->l0_k);
+        else
+            hipLaunchKernelGGL(train_input_kernel<POOL_NONE>, grid, dim3(256), 0, c->stream, t->x, t->xn, t->xt, B, t->k0, t->ldx, t->ldb, n_noisy, noise_std, stream,
+                               t->kraw, c->l0_k);
     } else {
         if (!t->ds_table) return fail(c, CSI_ERR_NOT_READY, "no resident dataset: call csi_train_set_dataset first");
         if (B > t->ids_cap) {
@@ -237,10 +247,16 @@ int tr_stage(csi_ctx* c, csi_trainer* t, const float* x, const float* y, const i
         for (int b = 0; b < B; ++b)
             if (ids[b] < 0 || ids[b] >= t->ds_n) return fail(c, CSI_ERR_INVALID_ARG, "sample index %d outside the resident dataset (%lld samples)", ids[b], (long long)t->ds_n);
         HIP_TRY(c, hipMemcpyAsync(t->ids, ids, (size_t)B * sizeof(int), hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(train_gather_kernel, dim3((t->k0 + 31) / 32, (B + 31) / 32), dim3(256), 0, c->stream, t->ds_table, t->ds_row, t->ds_itx,
-                           c->P, t->ds_y, t->ids, t->xn, t->xt, t->y, B, t->k0, n_noisy, cf.nt, t->layers.back().out, t->ldx, t->ldb, noise_std, stream);
+        const dim3 grid((t->k0 + 31) / 32, (B + 31) / 32);
+#define TR_GATHER(PV) hipLaunchKernelGGL(train_gather_kernel<PV>, grid, dim3(256), 0, c->stream, t->ds_table, t->ds_row, t->ds_itx, c->P, t->ds_y, t->ids, \
+                                         t->xn, t->xt, t->y, B, t->k0, n_noisy, cf.nt, t->layers.back().out, t->ldx, t->ldb, noise_std, stream, c->l0_k)
+        if (c->input_pool == POOL_MAX) TR_GATHER(POOL_MAX);
+        else if (c->input_pool == POOL_AVG) TR_GATHER(POOL_AVG);
+        else TR_GATHER(POOL_NONE);
+#undef TR_GATHER
     }
     HIP_TRY(c, hipGetLastError());
+    t->last_B = B;
     return CSI_OK;
 }
 
@@ -391,6 +407,16 @@ bool tr_find(const csi_ctx* c, const csi_trainer* t, std::string name, TrRef* r)
 }
 
 int tr_get(csi_ctx* c, csi_trainer* t, const char* name, float* out, int64_t count) {
+    if (std::string(name) == "input") {
+        // the last staged batch [B][k0] as layer 0 read it (noise added, decimated-input models pooled): a test hook
+        if (count != (int64_t)t->last_B * t->k0)
+            return fail(c, CSI_ERR_INVALID_ARG, "csi_train_get: 'input' has %d x %d elements, buffer holds %lld", t->last_B, t->k0, (long long)count);
+        if (count == 0) return CSI_OK;
+        HIP_TRY(c, hipMemcpy2DAsync(out, (size_t)t->k0 * sizeof(float), t->xn, (size_t)t->ldx * sizeof(float), (size_t)t->k0 * sizeof(float), t->last_B,
+                                    hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return CSI_OK;
+    }
     TrRef r;
     if (!tr_find(c, t, name, &r)) return fail(c, CSI_ERR_INVALID_ARG, "csi_train_get: unknown tensor '%s'", name);
     if (count != (int64_t)r.rows * r.cols)
@@ -424,6 +450,7 @@ int tr_begin(csi_ctx* c, int model, const csi_train_config* tc, const csi_tensor
     t->tc = *tc;
     t->k0 = c->d_in;
     t->ldx = c->d_in;
+    t->kraw = c->input_pool != POOL_NONE ? cf.len_ltf + cf.nt : c->d_in;
     const int nh = cf.n_hidden;
     t->layers.resize(nh + 1);
     int fan_in = c->d_in, maxw = 0;

@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 #include "gemm_f32.hip.h"
 #include "ls_estimate.hip.h"
+#include "input_pool.hip.h"
 
 namespace csi {
 
@@ -43,8 +44,10 @@ struct SmallL0Args {
     int M, K, lda, ldw, h1, nt;
 };
 
-// grid (ceil(h1 / COLS), 2), 256 threads; COLS output columns per workgroup (a multiple of 4), UN k steps of 1024 in flight
-template <int MR, int SC_GEMV_COLS, int UN>
+// grid (ceil(h1 / COLS), 2), 256 threads; COLS output columns per workgroup (a multiple of 4), UN k steps of 1024 in flight.
+// POOL (decimated-input model, input_pool.hip.h): k runs over the pooled inputs (K = len_ltf / 2) and every pooled quad is made from two
+// raw quads of the preamble row (lda = len_ltf) - no separate pooling pass, so a pooled call launches what an unpooled one does
+template <int MR, int SC_GEMV_COLS, int UN, int POOL = POOL_NONE>
 __device__ __forceinline__ void small_l0_gemv_body(const SmallL0Args& a, const int wg_x, const int z) {
     __shared__ float red[4][64][MR * SC_GEMV_COLS + 1];
     __shared__ float part[4][MR * SC_GEMV_COLS];
@@ -76,7 +79,14 @@ __device__ __forceinline__ void small_l0_gemv_body(const SmallL0Args& a, const i
             for (int c = 0; c < SC_GEMV_COLS; ++c) w[u][c] = *reinterpret_cast<const f32x4*>(wrow[c] + kc);      // (non-temporal loads measured 20.1 us against 17.0)
             okfs[u] = okf;
 #pragma unroll
-            for (int m = 0; m < MR; ++m) xv[u][m] = *reinterpret_cast<const f32x4*>(x + (size_t)min(m, a.M - 1) * a.lda + kc);
+            for (int m = 0; m < MR; ++m) {
+                if constexpr (POOL == POOL_NONE) {
+                    xv[u][m] = *reinterpret_cast<const f32x4*>(x + (size_t)min(m, a.M - 1) * a.lda + kc);
+                } else {
+                    const float* xr = x + (size_t)min(m, a.M - 1) * a.lda + 2 * kc;
+                    xv[u][m] = pool_quads<POOL>(*reinterpret_cast<const f32x4*>(xr), *reinterpret_cast<const f32x4*>(xr + 4));
+                }
+            }
         }
         __builtin_amdgcn_sched_barrier(0);      // all UN * (4 + MR) loads are requested before the first fma (the scheduler otherwise sinks each to its use)
 #pragma unroll
@@ -125,22 +135,22 @@ __device__ __forceinline__ void small_l0_gemv_body(const SmallL0Args& a, const i
     }
 }
 
-template <int MR, int SC_GEMV_COLS, int UN>
+template <int MR, int SC_GEMV_COLS, int UN, int POOL = POOL_NONE>
 __global__ __launch_bounds__(256) void small_l0_gemv_kernel(SmallL0Args a) {
-    small_l0_gemv_body<MR, SC_GEMV_COLS, UN>(a, blockIdx.x, blockIdx.y);
+    small_l0_gemv_body<MR, SC_GEMV_COLS, UN, POOL>(a, blockIdx.x, blockIdx.y);
 }
 
 // Round 6: the LS estimate of a one-packet call IN THE SAME LAUNCH as layer 0.  The two are independent (the same preambles feed both,
 // generate_maMIMO_LTF.m:336-349), the LS kernel of such a call is 4 workgroups of latency (8.9 us) and the weight stream leaves the CUs
 // idle enough: workgroups (x < ls_blocks, y = 0) run the Walsh-Hadamard LS body (ls_estimate.hip.h), the others layer 0 of component model y.
 // One launch and one boundary less per call; both bodies are the functions the separate kernels call, so the results are the same bits.
-template <int NT, int MR>
+template <int NT, int MR, int POOL = POOL_NONE>
 __global__ __launch_bounds__(256) void small_l0_ls_kernel(SmallL0Args a, LsArgs la, int nblk, int ls_blocks) {
     if ((int)blockIdx.x < ls_blocks) {
         if (blockIdx.y == 0) ls_fwht2_body<NT, 1, 8, (NT == 64 ? 3 : 1), false, false, true>(la, nblk, blockIdx.x, (unsigned)ls_blocks);
         return;
     }
-    small_l0_gemv_body<MR, 4, 2>(a, (int)blockIdx.x - ls_blocks, blockIdx.y);
+    small_l0_gemv_body<MR, 4, 2, POOL>(a, (int)blockIdx.x - ls_blocks, blockIdx.y);
 }
 
 struct SmallGemmArgs {

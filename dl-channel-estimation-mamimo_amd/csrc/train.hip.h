@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "ls_estimate.hip.h"      // splitmix64
+#include "input_pool.hip.h"       // pool2 (decimated-input models)
 
 namespace csi {
 
@@ -35,10 +36,22 @@ __device__ __forceinline__ float tr_normal(uint64_t stream, uint64_t idx) {
     return sqrtf(-2.0f * logf(u1)) * cosf(6.283185307179586f * u2);
 }
 
+// noisy input sample k of raw row b (x [B][kraw]): noise on the LTF columns (k < n_noisy), drawn with the raw element's counter
+__device__ __forceinline__ float tr_noisy(const float* __restrict__ x, int b, int kraw, int k, int n_noisy, float noise_std, uint64_t stream) {
+    float v = x[(size_t)b * kraw + k];
+    if (k < n_noisy && noise_std != 0.f) v += noise_std * tr_normal(stream, (uint64_t)b * kraw + k);
+    return v;
+}
+
 // xn[b][k] = x[b][k] + noise_std * N(0,1) for k < n_noisy (the LTF columns), copied otherwise;
 // xt[k][b] = xn[b][k] (ldt >= B, padding pre-zeroed).  32x32 tiles through LDS.
+// POOL (decimated-input model, input_pool.hip.h): x holds raw rows [B][kraw = n_noisy + nt]; the staged row is
+// [pool(noisy LTF) (l0k = n_noisy / 2) | pilot columns] - the GaussianNoise layer sits in front of the pooling (DNN.py:191-203), and every raw
+// sample draws its noise with its own counter b * kraw + raw k, so the noise a sample receives does not depend on the mode
+template <int POOL = POOL_NONE>
 __global__ __launch_bounds__(256) void train_input_kernel(const float* __restrict__ x, float* __restrict__ xn, float* __restrict__ xt,
-                                                          int B, int K, int ldx, int ldt, int n_noisy, float noise_std, uint64_t stream) {
+                                                          int B, int K, int ldx, int ldt, int n_noisy, float noise_std, uint64_t stream,
+                                                          int kraw = 0, int l0k = 0) {
     __shared__ float tile[32][33];
     const int k0 = blockIdx.x * 32, b0 = blockIdx.y * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;        // 32 x 8
@@ -46,8 +59,13 @@ __global__ __launch_bounds__(256) void train_input_kernel(const float* __restric
         const int b = b0 + r, k = k0 + tx;
         float v = 0.f;
         if (b < B && k < K) {
-            v = x[(size_t)b * K + k];
-            if (k < n_noisy && noise_std != 0.f) v += noise_std * tr_normal(stream, (uint64_t)b * K + k);
+            if constexpr (POOL == POOL_NONE) {
+                v = x[(size_t)b * K + k];
+                if (k < n_noisy && noise_std != 0.f) v += noise_std * tr_normal(stream, (uint64_t)b * K + k);
+            } else {
+                v = k < l0k ? pool2<POOL>(tr_noisy(x, b, kraw, 2 * k, n_noisy, noise_std, stream), tr_noisy(x, b, kraw, 2 * k + 1, n_noisy, noise_std, stream))
+                            : x[(size_t)b * kraw + n_noisy + (k - l0k)];
+            }
             xn[(size_t)b * ldx + k] = v;
         }
         tile[r][tx] = v;
@@ -63,11 +81,14 @@ __global__ __launch_bounds__(256) void train_input_kernel(const float* __restric
 // lives in HBM - its LTF part is row ltf_row[s] of the preamble table (every rx preamble stored once,
 // create_massiveMIMO_CSIest_dnn_dataset.py:50-63), its pilot part row itx[s] of P
 // (massiveMIMO_dataGenerator.py:309-311).  Also gathers the labels: yb[b] = y[ids[b]].
+// POOL: the staged LTF part is pool(noisy table row) (l0k = len_ltf / 2 columns), the noise drawn with the raw counter b * (len_ltf + nt) + raw k
+template <int POOL = POOL_NONE>
 __global__ __launch_bounds__(256) void train_gather_kernel(const float* __restrict__ table, const int* __restrict__ ltf_row,
                                                            const int* __restrict__ itx, const float* __restrict__ P,
                                                            const float* __restrict__ yall, const int* __restrict__ ids,
                                                            float* __restrict__ xn, float* __restrict__ xt, float* __restrict__ yb, int B, int K,
-                                                           int len_ltf, int nt, int n_out, int ldx, int ldt, float noise_std, uint64_t stream) {
+                                                           int len_ltf, int nt, int n_out, int ldx, int ldt, float noise_std, uint64_t stream,
+                                                           int l0k = 0) {
     __shared__ float tile[32][33];
     const int k0 = blockIdx.x * 32, b0 = blockIdx.y * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
@@ -76,7 +97,20 @@ __global__ __launch_bounds__(256) void train_gather_kernel(const float* __restri
         float v = 0.f;
         if (b < B && k < K) {
             const int s = ids[b];
-            if (k < len_ltf) {
+            if constexpr (POOL != POOL_NONE) {
+                const int kraw = len_ltf + nt;
+                if (k < l0k) {
+                    const float* row = table + (size_t)ltf_row[s] * len_ltf;
+                    float v0 = row[2 * k], v1 = row[2 * k + 1];
+                    if (noise_std != 0.f) {
+                        v0 += noise_std * tr_normal(stream, (uint64_t)b * kraw + 2 * k);
+                        v1 += noise_std * tr_normal(stream, (uint64_t)b * kraw + 2 * k + 1);
+                    }
+                    v = pool2<POOL>(v0, v1);
+                } else {
+                    v = P[(size_t)itx[s] * nt + (k - l0k)];
+                }
+            } else if (k < len_ltf) {
                 v = table[(size_t)ltf_row[s] * len_ltf + k];
                 if (noise_std != 0.f) v += noise_std * tr_normal(stream, (uint64_t)b * K + k);
             } else {

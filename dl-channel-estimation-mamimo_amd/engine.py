@@ -131,19 +131,35 @@ def classify_pilot(P):
     return kind, (a if kind else None), (b if kind else None)
 
 
+INPUT_POOL_MODES = {'max': 1, 'avg': 2}
+
+
+def input_pool_name(mode):
+    """None / 'none' / 0 -> None, 'max' / 1 -> 'max', 'avg' / 2 -> 'avg' (csi_set_input_pool modes)."""
+    if mode is None or mode == 0 or mode == 'none':
+        return None
+    for name, v in INPUT_POOL_MODES.items():
+        if mode == name or mode == v:
+            return name
+    raise CsiError(-1, f"input_pool must be None, 'max' or 'avg', got {mode!r}")
+
+
 class CsiEngine:
     """Owns a ``csi_ctx``.  Shapes follow the reference: nt tx antennas, nr rx antennas,
     len_ltf = 320*nt samples per rx preamble, FC hidden widths ``hidden`` (--nn), n_out outputs
     (massiveMIMO_CSI_prediction_DNN.py:18,227)."""
 
     def __init__(self, nt, nr, hidden=(1024, 1024), n_out=N_DATA, use_bn=True, bn_eps=1e-3,
-                 device=0, workspace_bytes=0, dtype='f32', len_ltf=None):
+                 device=0, workspace_bytes=0, dtype='f32', len_ltf=None, input_pool=None):
         self._lib = _lib.load_library()
         self._ctx = None
         self.nt, self.nr = int(nt), int(nr)
         # nt == 0: single-input model without pilot input (DNN.py:180,234); only predict_samples
         self.len_ltf = SYM_LEN * self.nt if self.nt > 0 else int(len_ltf)
-        self.d_in = self.len_ltf + self.nt
+        self.d_in = self.len_ltf + self.nt          # width of the rows the caller hands over (raw, also for a decimated-input model)
+        # decimated-input model (--decimate_max / --decimate_avg): layer 0 sees len_ltf/2 + nt inputs (csi_set_input_pool)
+        self.input_pool = input_pool_name(input_pool)
+        self.l0_in = (self.len_ltf // 2 if self.input_pool else self.len_ltf) + self.nt
         self.hidden = tuple(int(h) for h in hidden)
         self.n_out = int(n_out)
         self.use_bn = bool(use_bn)
@@ -162,6 +178,8 @@ class CsiEngine:
         if rc != 0:
             raise CsiError(rc, (self._lib.csi_last_error(None) or b'').decode())
         self._ctx = ctx
+        if self.input_pool:
+            self._check(self._lib.csi_set_input_pool(ctx, INPUT_POOL_MODES[self.input_pool]))
         self._arrays = weakref.WeakSet()
         me = weakref.ref(self)                                  # (no engine -> pool -> engine cycle: an engine is freed when its last reference goes)
         self.result_pool = PinnedPool(lambda n: me()._pinned_buffer(n))       # estimate(..., pinned_results=True)
@@ -339,7 +357,7 @@ class CsiEngine:
 
     def _train_shape(self, name):
         base = name[5:] if name.startswith('grad:') else name
-        widths = (self.d_in,) + self.hidden
+        widths = (self.l0_in,) + self.hidden
         if base.startswith('fc_regressor'):
             fan_in, out = self.hidden[-1], self.n_out
         else:
@@ -354,6 +372,13 @@ class CsiEngine:
             raise CsiError(-1, f"train_get: unknown tensor '{name}'")
         out = np.empty(self._train_shape(name), np.float32)
         self._check(self._lib.csi_train_get(self._ctx, int(idx), name.encode(), _fp(out), out.size))
+        return out
+
+    def train_staged_input(self, model, rows):
+        """The last staged batch [rows, l0_in] as layer 0 read it - noise added, a decimated-input model's LTF pooled (test hook)."""
+        idx = {'real': 0, 'imag': 1}.get(model, model)
+        out = np.empty((int(rows), self.l0_in), np.float32)
+        self._check(self._lib.csi_train_get(self._ctx, int(idx), b'input', _fp(out), out.size))
         return out
 
     def train_weights(self, model):

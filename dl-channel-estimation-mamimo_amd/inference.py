@@ -9,14 +9,15 @@ import os
 import sys
 import numpy as np
 
-from .engine import CsiEngine
-from .model import CSIModel, load_weight_file, config_from_weights, WEIGHT_FILE, CONFIG_FILE
+from ._lib import CsiError
+from .engine import CsiEngine, input_pool_name
+from .model import CSIModel, load_weight_file, normalize_keras_names, config_from_weights, WEIGHT_FILE, CONFIG_FILE
 
 
 class CSIPredictor:
 
     def __init__(self, model_path, experiment='RICE_RENEW', verbose=False, device=0, pilot=None,
-                 workspace_bytes=0, nr=None, pinned_results=False):
+                 workspace_bytes=0, nr=None, pinned_results=False, input_pool=None):
         self.path = model_path
         self.experiment = experiment
         self.verbose = verbose
@@ -29,6 +30,8 @@ class CSIPredictor:
         # matlab_maMimo: result arrays over recycled pinned buffers (fresh array objects as ever; the library then downloads
         # straight into them and assembles real + 1j*imag on the device - engine.PinnedPool, csi_estimate_c128)
         self.pinned_results = bool(pinned_results)
+        # decimated-input model (--decimate_max / --decimate_avg): 'max' / 'avg' / 'none'; None = as the model files say
+        self._input_pool_arg = input_pool
         self.model_real, self.model_imag = self.load_model()
 
     # inference.py:14-22
@@ -37,40 +40,57 @@ class CSIPredictor:
         config.json) or the TF SavedModel directory the reference's test run leaves there (DNN.py:411), whose
         ``variables/`` bundle is read directly (keras_files.py).  A SavedModel carries neither the pilot matrix
         (pass ``pilot=`` or call set_pilot) nor the rx-antenna count: packets are independent per rx antenna, so
-        without ``nr=`` any [nPkt, nRx, lenLTF] batch is accepted."""
+        without ``nr=`` any [nPkt, nRx, lenLTF] batch is accepted.
+        The input pooling of a decimated-input model comes from config.json (a missing key: none), from the pooling layer
+        of a whole-model HDF5 file (``<d>_keras_model`` itself or with .h5 / .hdf5) or from ``input_pool=``; a SavedModel
+        directory does not name it, so there only the argument counts.  Sources that disagree raise CsiError."""
+        from .keras_files import read_keras_hdf5_weights, keras_hdf5_input_pool
         dirs = {d: os.path.join(self.path, d + '_keras_model') for d in ('real', 'imag')}
         weights, cfg = {}, None
+        pools = []                                          # (source, mode) of every place that states the mode
+        if self._input_pool_arg is not None:
+            pools.append(('input_pool argument', input_pool_name(self._input_pool_arg)))
         for d, p in dirs.items():
+            h5 = next((q for q in (p, p + '.h5', p + '.hdf5') if os.path.isfile(q)), None)
             if os.path.exists(os.path.join(p, WEIGHT_FILE)):
                 weights[d] = load_weight_file(os.path.join(p, WEIGHT_FILE))
                 with open(os.path.join(p, CONFIG_FILE)) as f:
                     c = json.load(f)
                 cfg = cfg or c
+                pools.append((os.path.join(p, CONFIG_FILE), input_pool_name(c.get('input_pool'))))
+            elif h5 is not None and not os.path.isdir(p):
+                weights[d] = normalize_keras_names(read_keras_hdf5_weights(h5))
+                pools.append((h5, keras_hdf5_input_pool(h5)))
             else:
                 weights[d] = load_weight_file(p)            # SavedModel directory (raises if it is neither)
+        modes = {m for _, m in pools}
+        if len(modes) > 1:
+            raise CsiError(-1, 'input pooling disagrees between its sources: ' + ', '.join(f'{src}: {m or "none"}' for src, m in pools))
+        pool = modes.pop() if modes else None
         if cfg is None:
             w = weights['real']
             d_in = int(w['fc_dense0.kernel'].shape[0])
             two_input = self.experiment == 'matlab_maMimo'
-            if two_input and d_in % 321:
-                print('[CSIPredictor] ERROR: the saved model has %d inputs, not 321*nTx (LTF samples + pilot row).' % d_in)
+            per_tx = 161 if pool else 321                   # LTF samples (pooled: half) + pilot entry per tx antenna
+            if two_input and d_in % per_tx:
+                print('[CSIPredictor] ERROR: the saved model has %d inputs, not %d*nTx (LTF samples + pilot row).' % (d_in, per_tx))
                 sys.exit(-1)
             hidden, i = [], 0
             while f'fc_dense{i}.kernel' in w:
                 hidden.append(int(w[f'fc_dense{i}.kernel'].shape[1]))
                 i += 1
-            cfg = dict(nt=d_in // 321 if two_input else 0, nr=self._nr or 1, len_ltf=d_in, hidden=hidden,
+            cfg = dict(nt=d_in // per_tx if two_input else 0, nr=self._nr or 1, len_ltf=d_in, hidden=hidden,
                        n_out=int(w['fc_regressor.kernel'].shape[1]), use_bn='bn0.gamma' in w, bn_eps=1e-3)
             self._any_nr = two_input and self._nr is None
         nt, nr = int(cfg['nt']), int(cfg.get('nr', 1))
         if nt > 0:
-            shape = config_from_weights(weights['real'], nt)
+            shape = config_from_weights(weights['real'], nt, input_pool=pool)
         else:       # single-input model (DNN.py:180,234): no pilot input
             shape = dict(hidden=list(cfg['hidden']), n_out=int(cfg['n_out']), use_bn=bool(cfg['use_bn']))
         self.engine = CsiEngine(nt, nr, hidden=shape['hidden'], n_out=shape['n_out'], use_bn=shape['use_bn'],
                                 bn_eps=float(cfg.get('bn_eps', 1e-3)), device=self.device,
                                 workspace_bytes=self.workspace_bytes,
-                                len_ltf=int(cfg['len_ltf']) if nt == 0 else None)
+                                len_ltf=int(cfg['len_ltf']) if nt == 0 else None, input_pool=pool if nt > 0 else None)
         models = {}
         for d in ('real', 'imag'):
             models[d] = CSIModel(self.engine, d).load_weights(weights[d])

@@ -389,28 +389,53 @@ def _as_names(v):
     return [bytes(x).decode('utf8') if not isinstance(x, str) else x for x in np.asarray(v).reshape(-1).tolist()]
 
 
+def _keras_hdf5_root(path):
+    root = Hdf5File(path).root
+    if 'layer_names' not in root.attrs and 'model_weights' in root:
+        root = root['model_weights']                                            # model.save('x.h5')
+    return root
+
+
+def _listed(path, attrs, key):
+    """A keras name-list attribute (re-joined from ``key0, key1, ...`` chunks when keras split a long one)."""
+    if key in attrs:
+        return _as_names(attrs[key])
+    out, i = [], 0
+    while f'{key}{i}' in attrs:
+        out += _as_names(attrs[f'{key}{i}'])
+        i += 1
+    if i == 0:
+        raise KerasFileError(f'{path}: no {key!r} attribute - not a keras weights file')
+    return out
+
+
+def keras_hdf5_input_pool(path):
+    """The input pooling of the model a Keras HDF5 weights / whole-model file holds, from its ``layer_names``: 'max' for a
+    ``max_pooling1d[_N]`` layer (--decimate_max, DNN.py:198-200), 'avg' for ``average_pooling1d[_N]`` (--decimate_avg, :201-203),
+    None for neither.  A file of the CONV1D branch (``cnn1d_*`` layers, DNN.py:236-270) is refused: that model is not supported."""
+    import re
+    names = _listed(path, _keras_hdf5_root(path).attrs, 'layer_names')
+    if any(n.startswith('cnn1d') for n in names):
+        raise KerasFileError(f'{path}: a CONV1D model (cnn1d_* layers, DNN.py:236-270) - only the FC models are supported')
+    found = set()
+    for n in names:
+        if re.fullmatch(r'max_pooling1d(?:_\d+)?', n):
+            found.add('max')
+        elif re.fullmatch(r'average_pooling1d(?:_\d+)?', n):
+            found.add('avg')
+    if len(found) > 1:
+        raise KerasFileError(f'{path}: both a max_pooling1d and an average_pooling1d layer')
+    return found.pop() if found else None
+
+
 def read_keras_hdf5_weights(path):
     """{'<layer>/<weight name>': float32 ndarray} of a Keras HDF5 weights / whole-model file, in the order keras
     itself walks them when loading by topology: root attribute ``layer_names``, per layer ``weight_names``
     (attributes split into ``name0, name1, ...`` chunks by keras for very long lists are re-joined)."""
-    f = Hdf5File(path)
-    root = f.root
-    if 'layer_names' not in root.attrs and 'model_weights' in root:
-        root = root['model_weights']                                            # model.save('x.h5')
-
-    def listed(attrs, key):
-        if key in attrs:
-            return _as_names(attrs[key])
-        out, i = [], 0
-        while f'{key}{i}' in attrs:
-            out += _as_names(attrs[f'{key}{i}'])
-            i += 1
-        if i == 0:
-            raise KerasFileError(f'{path}: no {key!r} attribute - not a keras weights file')
-        return out
-
+    root = _keras_hdf5_root(path)
+    listed = lambda attrs, key: _listed(path, attrs, key)
     out = {}
-    for layer in listed(root.attrs, 'layer_names'):
+    for layer in _listed(path, root.attrs, 'layer_names'):
         g = root[layer]
         for wname in listed(g.attrs, 'weight_names'):
             node = g
@@ -832,18 +857,25 @@ def write_keras_hdf5_weights(path, layers, keras_version='2.4.0', backend='tenso
         fh.write(w.finish(root))
 
 
-def keras_layers_from_weights(weights, component='real', dropout=True):
+def keras_layers_from_weights(weights, component='real', dropout=True, input_pool=None):
     """Container-named tensors -> the ``layers`` list of write_keras_hdf5_weights for the reference's model
     (DNN.py:176-234): inputs, flatten, concatenate, then per hidden layer fc_dense<i> / batch_normalization[_k] /
     drop<i> (between hidden layers only, :222), fc_regressor.  BatchNormalization auto-numbers continue from the real to
-    the imag model, which is built second in the same process."""
+    the imag model, which is built second in the same process.  ``input_pool`` 'max' / 'avg' (a decimated-input model,
+    DNN.py:197-205) puts max_pooling1d[_k] / average_pooling1d[_k] between the LTF input and flatten, where keras_hdf5_input_pool
+    finds it again."""
     n_hidden = 0
     while f'fc_dense{n_hidden}.kernel' in weights:
         n_hidden += 1
     use_bn = 'bn0.gamma' in weights
     k = 0 if component == 'real' else 1
     sfx = lambda base, i: base + (f'_{i}' if i else '')
-    out = [(f'input_{1 + 2 * k}', []), (sfx('flatten', k), []), (f'input_{2 + 2 * k}', []), (sfx('concatenate', k), [])]
+    out = [(f'input_{1 + 2 * k}', [])]
+    if input_pool not in (None, 'none'):
+        if input_pool not in ('max', 'avg'):
+            raise KerasFileError(f"input_pool must be None, 'max' or 'avg', got {input_pool!r}")
+        out.append((sfx('max_pooling1d' if input_pool == 'max' else 'average_pooling1d', k), []))
+    out += [(sfx('flatten', k), []), (f'input_{2 + 2 * k}', []), (sfx('concatenate', k), [])]
     f32 = lambda a: np.asarray(a, np.float32)
     for i in range(n_hidden):
         out.append((f'fc_dense{i}', [(f'fc_dense{i}/kernel:0', f32(weights[f'fc_dense{i}.kernel'])), (f'fc_dense{i}/bias:0', f32(weights[f'fc_dense{i}.bias']).ravel())]))

@@ -7,30 +7,32 @@ a ``.safetensors`` (or torch ``.pt``) file holding, per component model d in {re
   fc_dense{i}.kernel [in,out]  fc_dense{i}.bias [out]
   bn{i}.gamma / .beta / .moving_mean / .moving_variance [out]        (when --useBN)
   fc_regressor.kernel [in,n_out]  fc_regressor.bias [n_out]
-plus a ``config.json`` next to it (nt, nr, hidden, n_out, use_bn, bn_eps).  Layer order = the
+plus a ``config.json`` next to it (nt, nr, hidden, n_out, use_bn, bn_eps, input_pool - a missing key means none).  Layer order = the
 keras layer order, which is how the reference matches tensors (load_weights by topology)."""
 import json
 import os
 import numpy as np
 
-from .engine import CsiEngine, N_DATA, SYM_LEN
+from .engine import CsiEngine, N_DATA, SYM_LEN, input_pool_name
 from ._lib import CsiError
 
 WEIGHT_FILE = 'weights.safetensors'
 CONFIG_FILE = 'config.json'
 
 
-def save_weight_file(path, weights, component=None):
+def save_weight_file(path, weights, component=None, input_pool=None):
     """weights: dict name -> float32 ndarray.  Format by extension: .safetensors | .pt | .npz | .hdf5 / .h5 - the
     last is a Keras HDF5 weights file in the layout of the reference's own checkpoints (DNN.py:279-281,319), which
     keras ``load_weights`` reads by topology (keras_files.write_keras_hdf5_weights); ``component`` ('real' / 'imag',
-    default: from the file name) only selects keras' auto-numbering of the layer names."""
+    default: from the file name) only selects keras' auto-numbering of the layer names; ``input_pool`` ('max' / 'avg') writes the
+    pooling layer of a decimated-input model into the HDF5 layer list."""
     tensors = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in weights.items() if isinstance(v, np.ndarray)}
     if path.endswith(('.hdf5', '.h5')):
         from .keras_files import write_keras_hdf5_weights, keras_layers_from_weights
         if component is None:
             component = 'imag' if os.path.basename(path).startswith('imag') else 'real'
-        write_keras_hdf5_weights(path, keras_layers_from_weights({k: v for k, v in tensors.items() if k != 'pilot'}, component))
+        write_keras_hdf5_weights(path, keras_layers_from_weights({k: v for k, v in tensors.items() if k != 'pilot'}, component,
+                                                                 input_pool=input_pool))
         return
     if path.endswith('.npz'):
         np.savez(path, **tensors)
@@ -82,7 +84,8 @@ def load_weight_file(path):
         from .keras_files import read_savedmodel_variables
         return normalize_keras_names(read_savedmodel_variables(path))
     if path.endswith(('.hdf5', '.h5')):
-        from .keras_files import read_keras_hdf5_weights
+        from .keras_files import read_keras_hdf5_weights, keras_hdf5_input_pool
+        keras_hdf5_input_pool(path)             # refuses a CONV1D-branch file with text (the pooling mode itself: keras_hdf5_input_pool)
         return normalize_keras_names(read_keras_hdf5_weights(path))
     if path.endswith('.npz'):
         with np.load(path) as z:
@@ -94,17 +97,27 @@ def load_weight_file(path):
     return {k: np.asarray(v, dtype=np.float32) for k, v in load_file(path).items()}
 
 
-def config_from_weights(weights, nt):
+def config_from_weights(weights, nt, input_pool=None):
     """Derive hidden widths / n_out / use_bn from tensor shapes (the reference derives the model
-    shape from --nn, --useBN and the dataset, massiveMIMO_dataGenerator.py:26-38)."""
+    shape from --nn, --useBN and the dataset, massiveMIMO_dataGenerator.py:26-38).  A decimated-input
+    model (--decimate_max / --decimate_avg: pooled LTF, len_ltf/2 + nt rows in fc_dense0.kernel) is
+    accepted only with its ``input_pool`` ('max' / 'avg')."""
     hidden = []
     i = 0
     while f'fc_dense{i}.kernel' in weights:
         hidden.append(int(weights[f'fc_dense{i}.kernel'].shape[1]))
         i += 1
     d_in = int(weights['fc_dense0.kernel'].shape[0])
-    if d_in != SYM_LEN * nt + nt:
-        raise CsiError(-1, f'fc_dense0.kernel has {d_in} rows, expected {SYM_LEN * nt + nt} for nt={nt}')
+    pool = input_pool_name(input_pool)
+    expect = (SYM_LEN * nt // 2 if pool else SYM_LEN * nt) + nt
+    if d_in != expect:
+        hint = ''
+        if not pool and d_in == SYM_LEN * nt // 2 + nt:
+            hint = ' - decimated model: pass input_pool / --decimate_max / --decimate_avg'
+        elif pool and d_in == SYM_LEN * nt + nt:
+            hint = f' - a model without input pooling, but input_pool={pool!r} was given'
+        raise CsiError(-1, f'fc_dense0.kernel has {d_in} rows, expected {expect} for nt={nt}'
+                           f' (input pooling {pool or "none"}){hint}')
     return dict(hidden=hidden, n_out=int(weights['fc_regressor.kernel'].shape[1]), use_bn='bn0.gamma' in weights)
 
 
@@ -155,13 +168,20 @@ class CSIModel:
         e = self.engine
         with open(os.path.join(model_dir, CONFIG_FILE), 'w') as f:
             json.dump(dict(component=self.d, nt=e.nt, nr=e.nr, len_ltf=e.len_ltf, hidden=list(e.hidden),
-                           n_out=e.n_out, use_bn=e.use_bn, bn_eps=1e-3, datasource='matlab_maMimo'), f, indent=1)
+                           n_out=e.n_out, use_bn=e.use_bn, bn_eps=1e-3, datasource='matlab_maMimo', input_pool=e.input_pool), f, indent=1)
 
     def summary(self, print_fn=print):
         e = self.engine
         print_fn(f'Model: "{self.d}"  (FC regressor, massiveMIMO_CSI_prediction_DNN.py:176-234)')
-        print_fn(f' input_1 (None, {e.len_ltf}, 1)   input_2 (None, {e.nt})   concatenate (None, {e.d_in})')
-        fan, total = e.d_in, 0
+        pool = getattr(e, 'input_pool', None)
+        l0_in = getattr(e, 'l0_in', e.d_in)
+        if pool:
+            layer = 'max_pooling1d (MaxPooling1D)' if pool == 'max' else 'average_pooling1d (AveragePooling1D)'
+            print_fn(f' input_1 (None, {e.len_ltf}, 1)   {layer} (None, {e.len_ltf // 2}, 1)   input_2 (None, {e.nt})'
+                     f'   concatenate (None, {l0_in})')
+        else:
+            print_fn(f' input_1 (None, {e.len_ltf}, 1)   input_2 (None, {e.nt})   concatenate (None, {e.d_in})')
+        fan, total = l0_in, 0
         for i, h in enumerate(e.hidden):
             n = fan * h + h
             total += n

@@ -102,6 +102,14 @@ int  csi_create(const csi_config* cfg, csi_ctx** out);
 void csi_destroy(csi_ctx* ctx);
 const char* csi_last_error(const csi_ctx* ctx);      /* ctx may be NULL: last create error  */
 
+/* Decimated-input models (--decimate_max / --decimate_avg, massiveMIMO_CSI_prediction_DNN.py:30-31,197-205): the LTF passes a
+ * MaxPooling1D() (mode 1) or AveragePooling1D() (mode 2) - pool 2, stride 2, 'valid' - before Flatten + Concatenate, so layer 0 sees
+ * len_ltf/2 + nt inputs: fc_dense0.kernel has len_ltf/2 + nt rows.  0 = none (default).  Every entry point still takes the raw
+ * [..][len_ltf] preambles / [B][len_ltf+nt] rows and pools inside; LS, LMMSE and NMSE read the raw preambles.  Only for nt > 0,
+ * and only while neither component model holds weights and no trainer exists (CSI_ERR_INVALID_ARG with text otherwise).
+ * csi_get_option("input_pool") reads the mode; csi_clone_weights / csi_broadcast_weights refuse contexts of different modes. */
+int  csi_set_input_pool(csi_ctx* ctx, int mode);
+
 /* model: 0 = real, 1 = imag.  Tensors are copied (and re-laid-out) to the device. */
 int  csi_load_weights(csi_ctx* ctx, int model, const csi_tensor* tensors, int n);
 /* P [nt][nt], row j = pilot sequence of tx antenna j = MATLAB P(j,:) = dataset['P'][:, j]. */
@@ -394,7 +402,7 @@ int  csi_broadcast_weights(csi_ctx* ctx, int root);
  * device on dst's stream, hipMemcpyPeer when the contexts live on different GPUs), then rebuilds its pilot tables - a second
  * context (another stream, packet range or GPU of the process) without a second csi_load_weights.  It walks exactly the receiver
  * side of csi_broadcast_weights (same record, same buffer list, same rebuild), which is how a one-GPU box tests that code.
- * The contexts must agree in nt, len_ltf, hidden widths, n_out, use_bn and dtype (nr, device and workspace may differ); a
+ * The contexts must agree in nt, len_ltf, hidden widths, n_out, use_bn, dtype and input pooling (nr, device and workspace may differ); a
  * mismatch is refused with text and leaves `dst` empty (nothing loaded, no pilot).  Synchronous at return. */
 int  csi_clone_weights(csi_ctx* dst, const csi_ctx* src);
 
