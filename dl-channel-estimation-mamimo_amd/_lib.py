@@ -56,6 +56,7 @@ SYMBOLS = {
     'csi_destroy': (None, [_ctx]),
     'csi_last_error': (ctypes.c_char_p, [_ctx]),
     'csi_set_input_pool': (ctypes.c_int, [_ctx, ctypes.c_int]),
+    'csi_set_model_type': (ctypes.c_int, [_ctx, ctypes.c_int]),
     'csi_load_weights': (ctypes.c_int, [_ctx, ctypes.c_int, ctypes.POINTER(CsiTensor), ctypes.c_int]),
     'csi_set_pilot': (ctypes.c_int, [_ctx, _fp]),
     'csi_predict': (ctypes.c_int, [_ctx, _fp, _fp, ctypes.c_int64, _fp, _fp]),

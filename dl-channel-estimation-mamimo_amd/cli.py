@@ -34,7 +34,7 @@ def build_parser():
     p.add_argument('--onlyImag', action='store_true')
     p.add_argument('--init', default='', help='folder with weights to start from (default: Glorot-uniform initialisation)')
     p.add_argument('--seed', default=0, type=int)
-    p.add_argument('--model', default='FC', help='DNN model type; only FC is on this path')
+    p.add_argument('--model', default='FC', help="DNN model type: FC or CONV1D (DNN.py:236-270; --test only)")
     p.add_argument('-x', required=True, help='dataset pickle written by create_massiveMIMO_CSIest_dnn_dataset.py')
     p.add_argument('--datasource', default='matlab_maMimo')
     p.add_argument('-d', '--workdir', default='checkpoint', help='output folder for the per-packet .mat files')
@@ -72,6 +72,54 @@ def weight_file_input_pool(path):
             return input_pool_name(json.load(f).get('input_pool'))
     rec = load_weight_file(path).get('input_pool')
     return input_pool_name(int(np.asarray(rec).ravel()[0])) if rec is not None else None
+
+
+def weight_file_model_type(path):
+    """'CONV1D' when a weight file holds the conv front end (cnn1d_1, DNN.py:238), else 'FC', without loading the weights: the layer
+    names of a Keras HDF5 file, the config.json beside a CSIModel.save folder's weights, the bundle index of a SavedModel, else the
+    tensor names themselves (a .pt checkpoint memory-mapped)."""
+    import json
+    from .engine import model_type_name
+    from .model import CONFIG_FILE, load_weight_file, weights_model_type
+    if path.endswith(('.hdf5', '.h5')):
+        from .keras_files import keras_hdf5_model_type
+        return keras_hdf5_model_type(path)
+    if os.path.isdir(path):
+        from .keras_files import savedmodel_model_type
+        return savedmodel_model_type(path)
+    cfg = os.path.join(os.path.dirname(path), CONFIG_FILE)
+    if os.path.basename(os.path.dirname(path)).endswith('_keras_model') and os.path.exists(cfg):
+        with open(cfg) as f:
+            return model_type_name(json.load(f).get('model'))
+    if path.endswith('.npz'):
+        with np.load(path) as z:
+            return 'CONV1D' if any(k.split('/')[0].split('.')[0] == 'cnn1d_1' for k in z.files) else 'FC'
+    if path.endswith('.safetensors'):
+        from safetensors import safe_open
+        with safe_open(path, framework='numpy') as f:
+            return 'CONV1D' if any(k.startswith('cnn1d_1.') for k in f.keys()) else 'FC'
+    if path.endswith('.pt'):
+        import torch
+        try:
+            keys = list(torch.load(path, map_location='cpu', mmap=True).keys())
+        except (RuntimeError, TypeError):          # (a legacy-format file cannot be memory-mapped)
+            keys = list(load_weight_file(path).keys())
+        return 'CONV1D' if any(k.startswith('cnn1d_1.') for k in keys) else 'FC'
+    return weights_model_type(load_weight_file(path))
+
+
+def resolve_model_type(args, weight_sets):
+    """--model against what the (loaded) weights hold: a contradiction is an error, as for the input pooling."""
+    from .model import weights_model_type
+    stated = {weights_model_type(w) for w in weight_sets}
+    if len(stated) > 1:
+        print('The real and the imag weights disagree in their model type (%s). Aborting...' % sorted(stated))
+        sys.exit(0)
+    found = stated.pop()
+    if found != args.model:
+        print('--model %s given, but the weights are of a %s model. Aborting...' % (args.model, found))
+        sys.exit(0)
+    return found
 
 
 def resolve_input_pool(args, paths):
@@ -172,10 +220,18 @@ def train_main(args):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    if args.model != 'FC' or args.datasource != 'matlab_maMimo':
-        print('Only --model FC --datasource matlab_maMimo is on the MI355X path. Aborting...')
+    if args.model not in ('FC', 'CONV1D') or args.datasource != 'matlab_maMimo':
+        print('Only --model FC / CONV1D --datasource matlab_maMimo is on the MI355X path. Aborting...')
         sys.exit(0)
     modeldir = args.modeldir or args.workdir
+    if args.train and args.model == 'CONV1D':
+        print('--train --model CONV1D: training CONV1D models is not supported on this path (it needs the conv backward pass); '
+              'train them elsewhere and run --test on their weights. Aborting...')
+        sys.exit(0)
+    if args.model == 'CONV1D' and (args.decimate_max or args.decimate_avg):
+        # the reference decimates only in its FC branch (DNN.py:196-205): the flag does not change a CONV1D model
+        print('Note: --decimate_max / --decimate_avg apply to the FC model only (DNN.py:196-205); ignored for --model CONV1D')
+        args.decimate_max = args.decimate_avg = False
     if args.train:
         return train_main(args)
     if not os.path.isdir(args.workdir):
@@ -202,12 +258,15 @@ def main(argv=None):
             sys.exit(0)
     nt, nr, npkt = packed['nt'], packed['nr'], packed['npkt']
     paths = {d: _find_weights(modeldir, d) for d in ('real', 'imag')}
+    weights = {d: load_weight_file(paths[d]) for d in ('real', 'imag')}          # loaded once: the model type is read off them
+    mtype = resolve_model_type(args, weights.values())
     eng = CsiEngine(nt, nr, hidden=args.nn, n_out=packed['labels'].shape[-1], use_bn=args.useBN,
-                    device=args.device, dtype=args.dtype, input_pool=resolve_input_pool(args, paths.values()))
+                    device=args.device, dtype=args.dtype, input_pool=resolve_input_pool(args, paths.values()) if mtype == 'FC' else None,
+                    model=mtype)
     models = {}
     for d in ('real', 'imag'):
         print('Working on *', d, '* model')
-        models[d] = CSIModel(eng, d).load_weights(load_weight_file(paths[d]))
+        models[d] = CSIModel(eng, d).load_weights(weights[d])
         models[d].summary()
     eng.set_pilot(packed['pilot'])
     if args.execTime:

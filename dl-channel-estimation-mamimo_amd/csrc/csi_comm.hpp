@@ -90,13 +90,14 @@ struct WireMeta {
     // the sender's csi_config, as far as it shapes the buffers: a receiver built for anything else refuses the record
     int32_t cfg_nt, cfg_len_ltf, cfg_n_out, cfg_dtype, cfg_use_bn, cfg_hidden[CSI_MAX_HIDDEN];
     int32_t input_pool;                                // csi_set_input_pool: the layer-0 input width follows from it
-    int32_t loaded[2], has_W0p[2], has_W0rm[2], hs_repr_ok[2];
+    int32_t model_type;                                // csi_set_model_type: so does it
+    int32_t loaded[2], has_W0p[2], has_W0rm[2], hs_repr_ok[2], has_conv[2];
     double hs_repr_err[2];                             // the sender's load-time measurement behind hs_repr_ok ("hs_weight_err_e12" reads the same on every rank)
     int32_t pilot_ok, p_sylvester, p_pieces;
     int32_t p_fast_ok, p_perm[2][CSI_WIRE_MAX_NT];     // Hadamard-equivalent pilot: output row / symbol permutation with signs (csi_set_pilot)
     WireLayer layer[2][CSI_MAX_HIDDEN + 1];
 };
-constexpr int32_t WIRE_MAGIC = 0x43534932;      // "CSI2"
+constexpr int32_t WIRE_MAGIC = 0x43534933;      // "CSI3": the record with input_pool, model_type and has_conv (a "CSI2" sender is refused)
 constexpr size_t WIRE_STATUS_OFF = (sizeof(WireMeta) + 63) / 64 * 64;     // the ranks' status word sits behind the record in csi_comm::wire
 
 struct WBlob {
@@ -105,7 +106,8 @@ struct WBlob {
 };
 
 // every device buffer of a component model that csi_load_weights fills, with the size it allocates (same formulas)
-void model_blobs(const csi_config& cf, int l0_k, Model& m, const WireLayer* wl, const int32_t has_W0p, const int32_t has_W0rm, std::vector<WBlob>& v) {
+void model_blobs(const csi_config& cf, int l0_k, Model& m, const WireLayer* wl, const int32_t has_W0p, const int32_t has_W0rm, const int32_t has_conv,
+                 std::vector<WBlob>& v) {
     const size_t slack = G_SLACK_FLOATS * sizeof(float);
     for (size_t i = 0; i < m.layers.size(); ++i) {
         Layer& L = m.layers[i];
@@ -124,6 +126,7 @@ void model_blobs(const csi_config& cf, int l0_k, Model& m, const WireLayer* wl, 
     const size_t h1 = m.layers.empty() ? 0 : (size_t)m.layers[0].out;
     if (has_W0p) v.push_back({(void**)&m.W0p, (size_t)cf.nt * h1 * 4 + slack});
     if (has_W0rm) v.push_back({(void**)&m.W0rm, (size_t)l0_k * h1 * 4 + slack});
+    if (has_conv) v.push_back({(void**)&m.conv, (size_t)CONV_PRM_FLOATS * 4 + slack});
 }
 
 int ls_prepare(csi_ctx* c);                     // csi_mamimo.hip
@@ -138,6 +141,7 @@ void wire_fill(const csi_ctx* c, WireMeta& w) {
     w.n_layers = cf.n_hidden + 1;
     w.cfg_nt = cf.nt; w.cfg_len_ltf = cf.len_ltf; w.cfg_n_out = cf.n_out; w.cfg_dtype = cf.dtype; w.cfg_use_bn = cf.use_bn != 0;
     w.input_pool = c->input_pool;
+    w.model_type = c->model_type;
     for (int i = 0; i < cf.n_hidden; ++i) w.cfg_hidden[i] = cf.hidden[i];
     w.pilot_ok = c->pilot_ok;
     w.p_sylvester = c->p_sylvester;
@@ -154,6 +158,7 @@ void wire_fill(const csi_ctx* c, WireMeta& w) {
         w.hs_repr_err[d] = m.hs_repr_err;
         w.has_W0p[d] = m.W0p != nullptr;
         w.has_W0rm[d] = m.W0rm != nullptr;
+        w.has_conv[d] = m.conv != nullptr;
         for (int i = 0; i <= cf.n_hidden; ++i) {
             const Layer& L = m.layers[i];
             WireLayer& x = w.layer[d][i];
@@ -170,7 +175,7 @@ void wire_fill(const csi_ctx* c, WireMeta& w) {
 void wire_blobs(csi_ctx* c, const WireMeta& w, std::vector<WBlob>& blobs) {
     const csi_config& cf = c->cfg;
     for (int d = 0; d < 2; ++d)
-        if (w.loaded[d]) model_blobs(cf, c->l0_k, c->model[d], w.layer[d], w.has_W0p[d], w.has_W0rm[d], blobs);
+        if (w.loaded[d]) model_blobs(cf, c->l0_k, c->model[d], w.layer[d], w.has_W0p[d], w.has_W0rm[d], w.has_conv[d], blobs);
     if (w.pilot_ok && cf.nt > 0) {
         const size_t ldp = (size_t)(cf.nt + 31) / 32 * 32, slack = G_SLACK_FLOATS * sizeof(float);
         blobs.push_back({(void**)&c->P, (size_t)cf.nt * cf.nt * 4 + slack});
@@ -197,7 +202,7 @@ int wire_receive(csi_ctx* c, const WireMeta& w, std::vector<WBlob>& blobs, const
     const csi_config& cf = c->cfg;
     auto refuse = [&](int code) { wire_drop_receiver(c); return code; };
     if (w.magic != WIRE_MAGIC)
-        return refuse(fail(c, CSI_ERR_INVALID_ARG, "%s: the sender's record is not a CSI2 record (magic %08x): libraries of different versions?", fn, (unsigned)w.magic));
+        return refuse(fail(c, CSI_ERR_INVALID_ARG, "%s: the sender's record is not a CSI3 record (magic %08x): libraries of different versions?", fn, (unsigned)w.magic));
     if (w.n_layers != cf.n_hidden + 1)
         return refuse(fail(c, CSI_ERR_INVALID_ARG, "%s: the sender has %d hidden layers, this context %d", fn, w.n_layers - 1, cf.n_hidden));
     if (w.cfg_nt != cf.nt || w.cfg_len_ltf != cf.len_ltf || w.cfg_n_out != cf.n_out || w.cfg_dtype != cf.dtype || w.cfg_use_bn != (cf.use_bn != 0))
@@ -206,6 +211,9 @@ int wire_receive(csi_ctx* c, const WireMeta& w, std::vector<WBlob>& blobs, const
     if (w.input_pool != c->input_pool)
         return refuse(fail(c, CSI_ERR_INVALID_ARG, "%s: input pooling differs - sender %s, here %s (csi_set_input_pool)", fn,
                            input_pool_name(w.input_pool), input_pool_name(c->input_pool)));
+    if (w.model_type != c->model_type)
+        return refuse(fail(c, CSI_ERR_INVALID_ARG, "%s: model type differs - sender %s, here %s (csi_set_model_type)", fn,
+                           model_type_name(w.model_type), model_type_name(c->model_type)));
     for (int i = 0; i < cf.n_hidden; ++i)
         if (w.cfg_hidden[i] != cf.hidden[i])
             return refuse(fail(c, CSI_ERR_INVALID_ARG, "%s: hidden layer %d is %d wide on the sender, %d here", fn, i, w.cfg_hidden[i], cf.hidden[i]));

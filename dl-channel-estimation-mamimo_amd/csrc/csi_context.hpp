@@ -21,6 +21,7 @@
 #include "lmmse.hip.h"
 #include "metrics.hip.h"
 #include "input_pool.hip.h"
+#include "conv_frontend.hip.h"
 
 using namespace csi;
 
@@ -44,12 +45,13 @@ enum KernelId {
     K_NMSE,              // per-link NMSE metric
     K_PAIR_DENSE_TAIL,   // the last, partly filled round of band workgroups launched in column splits ("band_tail_split", round 6)
     K_INPUT_POOL,        // MaxPooling1D / AveragePooling1D of the preambles of a decimated-input model (csi_set_input_pool)
+    K_CONV_FRONTEND,     // Conv1D + BN + AveragePooling1D front end of a CONV1D model (csi_set_model_type, conv_frontend.hip.h)
     K_COUNT
 };
 const char* const kKernelNames[K_COUNT] = {
     "layer0_ltf_gemm", "splitk_reduce", "pair_dense_gemm", "dense_hidden_gemm", "regressor_gemm",
     "ls_estimate", "naive_dense0_gemm", "synth_white", "pilot_table", "cast_bf16", "pair_h1_bf16", "lmmse_levinson",
-    "train_gemm", "train_elementwise", "nmse_links", "pair_dense_tail", "input_pool"};
+    "train_gemm", "train_elementwise", "nmse_links", "pair_dense_tail", "input_pool", "conv_frontend"};
 
 thread_local std::string g_create_error;
 
@@ -91,6 +93,7 @@ struct Model {
     uint16_t* Wt1 = nullptr;     // bf16 contexts: the pair layer's and the regressor's weights pre-tiled for the register-blocked band kernel
     uint16_t* Wt2 = nullptr;     // (band4_tile_kernel, built on first use from layers[1].Wb / layers[2].Wb_p)
     bool tiled_ok = false;
+    float* conv = nullptr;       // CONV1D models: [CONV_PRM_FLOATS] taps, bias, BN scale, BN shift of the front end (conv_frontend.hip.h)
     float* l0_rowmax = nullptr;  // [4096] row maxima of a mid-size call's preambles (l0_row_max_kernel -> l0_hs_stream_kernel)
     bool loaded = false;
     bool table_ok = false;
@@ -127,7 +130,8 @@ struct csi_ctx {
     csi_config cfg;
     int d_in = 0;                // layer-0 input width: l0_k + nt
     int input_pool = 0;          // csi_set_input_pool: POOL_NONE / POOL_MAX / POOL_AVG (input_pool.hip.h)
-    int l0_k = 0;                // LTF inputs of layer 0: len_ltf, or len_ltf / 2 with pooling (the preamble row stride stays len_ltf)
+    int l0_k = 0;                // LTF inputs of layer 0: len_ltf, len_ltf / 2 with pooling, 64 len_ltf for CONV1D (the preamble row stride stays len_ltf)
+    int model_type = 0;          // csi_set_model_type: CSI_MODEL_FC / CSI_MODEL_CONV1D
     hipStream_t stream = nullptr;
     std::string err;
     Model model[2];
@@ -168,6 +172,7 @@ struct csi_ctx {
     float* small_ls_h_re = nullptr;   // set by csi_estimate_device around its predict call, consumed by predict_small
     float* small_ls_h_im = nullptr;
     int64_t small_ls_launches = 0;
+    int64_t conv_launches = 0;   // "conv_launches": CONV1D front-end passes launched (conv_frontend.hip.h)
     int debug_ls_lds_pad = 0;        // CSI_DEBUG_HOOKS=1 CSI_LS_LDS_PAD=<bytes>: the Walsh-Hadamard LS kernel asks for that much more LDS than it uses
     int debug_bf16_fork_late = 0;    // CSI_DEBUG_HOOKS=1 CSI_BF16_FORK_LATE=1: bf16 contexts fork the second stream of a two-stream call behind the LS kernel (A/B runs)
     int debug_small_tile16 = 0;  // CSI_DEBUG_HOOKS=1 CSI_SMALL_TILE16=1, read once at csi_create (A/B runs)
@@ -372,6 +377,61 @@ int launch_input_pool(csi_ctx* c, const float* x0, const float* x1, void* y0, vo
     return CSI_OK;
 }
 
+// K ranges a CONV1D context's layer 0 may be cut into (K0 = 64 len_ltf: a chunk of ~800 preambles at nn0 = 256 has only a handful of
+// output tiles; FC routes stop at 8 ... 40 ranges, tuned at K ~ 10k)
+constexpr int L0_CONV_MAX_SPLITS = 256;
+
+const char* model_type_name(int t) { return t == CSI_MODEL_CONV1D ? "CONV1D" : "FC"; }
+
+// the layer-0 LTF width from BOTH context settings (csi_set_model_type, csi_set_input_pool - either may be called, with any value, after
+// the other): 64 len_ltf features of the CONV1D front end, len_ltf / 2 pooled samples, or the len_ltf samples themselves
+void set_layer0_width(csi_ctx* c) {
+    const int L = c->cfg.len_ltf;
+    c->l0_k = c->model_type == CSI_MODEL_CONV1D ? 64 * L : (c->input_pool != POOL_NONE ? L / 2 : L);
+    c->d_in = c->l0_k + c->cfg.nt;
+}
+
+// layer 0 of this context reads a feature slab written by a pass in front of it (pooling or the CONV1D front end), not the preambles
+bool l0_features(const csi_ctx* c) { return c->input_pool != POOL_NONE || c->model_type == CSI_MODEL_CONV1D; }
+
+// CONV1D front end: planes x[p] [rows][ldx] raw preambles -> y[p] [rows][ldy] features (K0 = 64 len_ltf of them, then `tail` copied
+// columns), fp32 or bf16; the constants of model md[p] (conv_frontend.hip.h)
+int launch_conv_frontend(csi_ctx* c, const Model* md0, const Model* md1, const float* x0, const float* x1, void* y0, void* y1, int64_t rows,
+                         int ldx, int ldy, int tail, bool to_bf16) {
+    const int planes = x1 ? 2 : 1;
+    ConvArgs a{};
+    a.x[0] = x0; a.x[1] = x1 ? x1 : x0;
+    a.y[0] = y0; a.y[1] = y1 ? y1 : y0;
+    a.prm[0] = md0->conv; a.prm[1] = md1 ? md1->conv : md0->conv;
+    a.rows = rows; a.L = c->cfg.len_ltf; a.ldx = ldx; a.ldy = ldy; a.tail = tail;
+    if (!a.prm[0] || !a.prm[1]) return fail(c, CSI_ERR_NOT_READY, "CONV1D front end: the model holds no cnn1d_1 weights");
+    if (c->model_type != CSI_MODEL_CONV1D || c->l0_k != 64 * c->cfg.len_ltf || (int64_t)ldy < (int64_t)c->l0_k + tail || ldx < c->cfg.len_ltf + tail)
+        return fail(c, CSI_ERR_INVALID_ARG, "CONV1D front end: row pitches %d / %d do not hold %d samples / %d features + %d columns (context layer-0 width %d)",
+                    ldx, ldy, c->cfg.len_ltf, 64 * c->cfg.len_ltf, tail, c->l0_k);
+    const int64_t tiles = rows * ((c->cfg.len_ltf / 2 + CF_TILE - 1) / CF_TILE);
+    // 8 workgroups of 256 lanes per CU (32 waves, 8 KB of tile per workgroup in flight as stores)
+    const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(tiles, (int64_t)c->n_cu * 8 / planes));
+    const double outs = (double)planes * rows * ((double)c->l0_k + tail);
+    ProfScope ps(c, K_CONV_FRONTEND, outs * 20.0, (double)planes * rows * ldx * 4.0 + outs * (to_bf16 ? 2.0 : 4.0));
+    // every lane stores 16 bytes: the callers' slabs start on 16-byte boundaries and ldy is K0 (a multiple of 64) or K0 + nt (nt % 4 == 0)
+    if ((ldy % (to_bf16 ? 8 : 4)) != 0 || (reinterpret_cast<uintptr_t>(a.y[0]) & 15) != 0 || (reinterpret_cast<uintptr_t>(a.y[1]) & 15) != 0)
+        return fail(c, CSI_ERR_INVALID_ARG, "CONV1D front end: feature rows of pitch %d at %p / %p are not 16-byte aligned", ldy, a.y[0], a.y[1]);
+    const dim3 grid(blocks, planes);
+    if (to_bf16) hipLaunchKernelGGL((conv_frontend_kernel<8, true>), grid, dim3(CF_THREADS), 0, c->stream, a);
+    else hipLaunchKernelGGL((conv_frontend_kernel<4, false>), grid, dim3(CF_THREADS), 0, c->stream, a);
+    HIP_TRY(c, hipGetLastError());
+    ++c->conv_launches;
+    return CSI_OK;
+}
+
+// the pass in front of layer 0 of a feature-slab context: pooling (planes 0 and 1 of one call share the pooling mode) or the CONV1D
+// front end (md0 / md1: the models whose constants each plane takes).  rows of len_ltf raw samples -> rows of K0 features
+int launch_l0_features(csi_ctx* c, const Model* md0, const Model* md1, const float* x0, const float* x1, void* y0, void* y1, int64_t rows, bool to_bf16) {
+    if (c->model_type == CSI_MODEL_CONV1D)
+        return launch_conv_frontend(c, md0, md1, x0, x1, y0, y1, rows, c->cfg.len_ltf, c->l0_k, 0, to_bf16);
+    return launch_input_pool(c, x0, x1, y0, y1, rows, to_bf16);
+}
+
 int prof_collect(csi_ctx* c) {
     if (c->spans.empty()) return CSI_OK;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -492,6 +552,8 @@ void free_model(Model& m) {
     m.Wt1 = m.Wt2 = nullptr;
     m.tiled_ok = false;
     if (m.l0_rowmax) hipFree(m.l0_rowmax);
+    if (m.conv) hipFree(m.conv);
+    m.conv = nullptr;
     m.W0p = m.T = m.T_hs = m.T_sw = m.l0_rowmax = nullptr;
     m.T_sw_ok = false;
     m.T_hs_shift = HS_SHIFT_AUTO;

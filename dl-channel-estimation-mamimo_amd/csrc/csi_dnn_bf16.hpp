@@ -187,24 +187,31 @@ int predict_plane_bf16(csi_ctx* c, Model& m, const float* d_ltf, int64_t npkt, f
     // K0 LTF inputs of layer 0 per preamble: len_ltf, or len_ltf / 2 for a decimated-input model (input_pool.hip.h).  Its pooled
     // preambles sit in the xb slab - as bf16 where the cast pass ran before (the pooling pass writes them instead), as fp32 for the
     // routes that read fp32 (chunk * nr * len_ltf bf16 = chunk * nr * len_ltf / 2 fp32: the same bytes)
+    // CONV1D (conv_frontend.hip.h): the front end writes the K0 = 64 len_ltf features per preamble as bf16 into the xb slab, and layer 0 is
+    // always the bf16 MFMA GEMM on them - the weight-streaming kernel and the fused-cast kernel read fp32 operands - its K cut into as many
+    // ranges (up to L0_CONV_MAX_SPLITS) as put 256 of its tiles on the chip, the range slabs in the split-K scratch of the context
     const bool pooled = c->input_pool != POOL_NONE;
+    const bool conv = c->model_type == CSI_MODEL_CONV1D;
     const int K0 = c->l0_k;
+    const int64_t xb_k = conv ? K0 : cf.len_ltf;          // bf16 elements of the xb slab per preamble
     int maxh = 0;
     for (int i = 1; i < nh; ++i) maxh = std::max(maxh, cf.hidden[i]);
     // per packet: bf16 preamble copy, fp32 layer-0 product, bf16 h1, bf16 ping-pong hidden buffers
-    const size_t per_pkt = (size_t)nr * cf.len_ltf * 2 + (size_t)nr * h1 * 4 * (BF16_L0_MAX_SPLITS + 1) + (size_t)nr * nt * h1 * 2 +
+    const size_t per_pkt = (size_t)nr * xb_k * 2 + (size_t)nr * h1 * 4 * (BF16_L0_MAX_SPLITS + 1) + (size_t)nr * nt * h1 * 2 +
                            (size_t)nr * nt * maxh * 2 * (nh >= 3 ? 2 : (nh >= 2 ? 1 : 0));
     // default 8 GiB: a whole config-3 step (5000 packets) in one chunk, so that layer 0 sees M1 = 20000 rows
     // (two component models in flight on two streams hold a workspace each: the cap is shared between them - ADVICE round 5)
-    const size_t budget = (cf.workspace_bytes > 0 ? (size_t)cf.workspace_bytes : ((size_t)8 << 30)) / (size_t)std::max(c->models_in_flight, 1);
+    // CONV1D: 16 GiB, and a chunk's features stay below 2^31 elements (3276 preambles at Nt = 32): W0 traffic / feature traffic = h1 / (2 x preambles)
+    const size_t budget = (cf.workspace_bytes > 0 ? (size_t)cf.workspace_bytes : (conv ? (size_t)16 << 30 : (size_t)8 << 30)) / (size_t)std::max(c->models_in_flight, 1);
     int64_t cap = std::max<int64_t>(1, (int64_t)(budget / per_pkt));
     cap = std::min(cap, (int64_t)0x7fffffff / ((int64_t)nr * nt * 2));
+    if (conv) cap = std::max<int64_t>(1, std::min(cap, (int64_t)0x7fffffff / ((int64_t)nr * K0)));
     const int64_t nchunks = (npkt + cap - 1) / cap;
     const int64_t chunk = (npkt + nchunks - 1) / nchunks;
     int rc = ensure_bytes(c, &c->ws, &c->ws_bytes, per_pkt * (size_t)chunk + 1024);
     if (rc) return rc;
     char* base = c->ws;
-    bf16_t* xb = reinterpret_cast<bf16_t*>(base);             base += (size_t)chunk * nr * cf.len_ltf * 2;
+    bf16_t* xb = reinterpret_cast<bf16_t*>(base);             base += (size_t)chunk * nr * xb_k * 2;
     float* l0_ws = reinterpret_cast<float*>(base);            base += (size_t)chunk * nr * h1 * 4 * (BF16_L0_MAX_SPLITS + 1);
     bf16_t* h1b = reinterpret_cast<bf16_t*>(base);            base += (size_t)chunk * nr * nt * h1 * 2;
     bf16_t* hb0 = reinterpret_cast<bf16_t*>(base);            base += (size_t)chunk * nr * nt * maxh * 2;
@@ -234,9 +241,27 @@ int predict_plane_bf16(csi_ctx* c, Model& m, const float* d_ltf, int64_t npkt, f
         // round 6: between the streaming kernel's range and 256 tiles of the fused kernel (321 ... 4095 packets at Nt = 64, Nr = 4) layer 0 took a cast pass
         // plus the 128 x 128 kernel (1000 packets: 100-130 us + 450 us per model, 0.15 of the bf16 peak; tools/ls_overlap_trace.sh shows it).  The fused
         // 256 x 256 kernel with its K cut so that tiles x ranges fill the CUs does the same product without the cast pass ("bf16_l0_fused_split" = 0: before)
+        float* l0 = l0_ws;
+        if (conv) {
+            const long tiles256 = (long)((M1 + PP_BM - 1) / PP_BM) * ((h1 + PP_BN - 1) / PP_BN);
+            S = (int)std::min<long>(L0_CONV_MAX_SPLITS, (256 + tiles256 - 1) / tiles256);
+            while (S > 1 && K0 / S < 1024) --S;
+            g.k_per_split = ((K0 + S - 1) / S + B_BK - 1) / B_BK * B_BK;
+            S = (K0 + g.k_per_split - 1) / g.k_per_split;
+            if (S > BF16_L0_MAX_SPLITS) {            // (the workspace holds BF16_L0_MAX_SPLITS + 1 slabs per preamble)
+                rc = ensure_bytes(c, &c->skbuf, &c->skbuf_bytes, (size_t)(S + 1) * M1 * h1 * sizeof(float));
+                if (rc) return rc;
+                l0 = reinterpret_cast<float*>(c->skbuf);
+            }
+            g.C = l0;
+            rc = launch_conv_frontend(c, &m, nullptr, d_ltf + (size_t)p0 * nr * cf.len_ltf, nullptr, xb, nullptr, M1, cf.len_ltf, K0, 0, true);
+            if (rc) return rc;
+            rc = launch_gemm_bf16<EPI_RAW, false>(c, K_LAYER0_LTF, g, S);
+            if (rc) return rc;
+        }
         int kps_hint = 0;
-        const int stream_splits_hint = bf16_l0_stream_splits(c, M1, h1, K0, &kps_hint);       // (the streaming kernel takes the call: nothing to choose)
-        if (!stream_splits_hint && c->bf16_l0_fused_split && c->bf16_fused_h1 != 0 && c->force_pair_tile == 0 && (K0 & 3) == 0) {
+        const int stream_splits_hint = conv ? 0 : bf16_l0_stream_splits(c, M1, h1, K0, &kps_hint);       // (the streaming kernel takes the call: nothing to choose)
+        if (!conv && !stream_splits_hint && c->bf16_l0_fused_split && c->bf16_fused_h1 != 0 && c->force_pair_tile == 0 && (K0 & 3) == 0) {
             const long launched = (long)(((M1 + PP_BM - 1) / PP_BM + 7) / 8 * 8) * ((h1 + PP_BN - 1) / PP_BN);      // as pp_grid launches them
             if (launched < 256) {
                 // K ranges: rounds of 256 workgroups x the k extent of one range, plus the slabs written and read back (a 256 x 256 x k workgroup at the
@@ -257,12 +282,11 @@ int predict_plane_bf16(csi_ctx* c, Model& m, const float* d_ltf, int64_t npkt, f
                 }
             }
         }
-        float* l0 = l0_ws;
         int kps_stream = 0;
-        const int stream_splits = bf16_l0_stream_splits(c, M1, h1, K0, &kps_stream);
+        const int stream_splits = conv ? 0 : bf16_l0_stream_splits(c, M1, h1, K0, &kps_stream);
         const long l0_tiles = (long)((M1 + PP_BM - 1) / PP_BM) * ((h1 + PP_BN - 1) / PP_BN) * S;
         const long l0_launched = (long)(((M1 + PP_BM - 1) / PP_BM + 7) / 8 * 8) * ((h1 + PP_BN - 1) / PP_BN) * S;
-        const bool l0_fused = c->bf16_fused_h1 != 0 && c->force_pair_tile != 128 && (l0_tiles >= 256 || c->force_pair_tile == 256 || (c->bf16_l0_fused_split && l0_launched >= 128)) &&
+        const bool l0_fused = !conv && c->bf16_fused_h1 != 0 && c->force_pair_tile != 128 && (l0_tiles >= 256 || c->force_pair_tile == 256 || (c->bf16_l0_fused_split && l0_launched >= 128)) &&
                               g.k_per_split / PP_BK >= 3 && (K0 & 3) == 0;
         const float* x0 = d_ltf + (size_t)p0 * nr * cf.len_ltf;       // layer-0 LTF input [M1][K0], fp32
         if (pooled && (stream_splits || l0_fused)) {
@@ -270,7 +294,9 @@ int predict_plane_bf16(csi_ctx* c, Model& m, const float* d_ltf, int64_t npkt, f
             if (rc) return rc;
             x0 = reinterpret_cast<const float*>(xb);
         }
-        if (stream_splits) {
+        if (conv) {
+            // (front end + GEMM launched above)
+        } else if (stream_splits) {
             // small and mid-size calls: the weight-streaming kernel, its k-range slabs in the split-K scratch of the context
             rc = ensure_bytes(c, &c->skbuf, &c->skbuf_bytes, (size_t)(stream_splits + 1) * M1 * h1 * sizeof(float));
             if (rc) return rc;

@@ -129,13 +129,16 @@ int launch_pair(csi_ctx* c, int kid, GemmArgs g) {
 
 // Split-K factor of layer 0.  The grid should fill whole rounds of the 512 resident workgroups
 // (256 CUs x 2): pick the smallest factor whose last round is >= 90 % full, else the fullest.
-int choose_splits(int M, int N, int K, int* k_per_split) {
+// max_splits: 40 (FC models, tuned at K ~ 10k); CONV1D contexts (K0 = 64 len_ltf) allow up to L0_CONV_MAX_SPLITS so that a chunk's few
+// output tiles still put a few hundred workgroups on the chip
+int choose_splits(int M, int N, int K, int* k_per_split, int max_splits = 40) {
     const long tiles = (long)((M + G_BM - 1) / G_BM) * ((N + G_BN - 1) / G_BN);
     const int ktiles = (K + G_BK - 1) / G_BK;
-    static const int cand[] = {1, 2, 3, 4, 5, 6, 8, 10, 12, 16, 20, 32, 40};
+    static const int cand[] = {1, 2, 3, 4, 5, 6, 8, 10, 12, 16, 20, 32, 40, 48, 64, 80, 96, 128, 160, 192, 256};
     int best = 1;
     double best_eff = -1.0;
     for (int s : cand) {
+        if (s > max_splits) break;
         if (s > 1 && ktiles / s < 8) break;           // keep >= 8 k-tiles (of 32) per block
         const int kps = (ktiles + s - 1) / s;
         const int real = (ktiles + kps - 1) / kps;
@@ -173,11 +176,14 @@ int build_pilot_table(csi_ctx* c, Model& m) {
 int predict_plane(csi_ctx* c, Model& m, const float* d_ltf, int64_t npkt, float* d_out) {
     const csi_config& cf = c->cfg;
     const int nt = cf.nt, nr = cf.nr, h1 = cf.hidden[0], nh = cf.n_hidden;
-    // layer 0 reads K0 LTF inputs per preamble: the preambles themselves, or (decimated-input model) their pooled copy, [chunk][nr][K0] in
-    // the workspace behind the activation buffers (input_pool.hip.h)
-    const bool pooled = c->input_pool != POOL_NONE;
+    // layer 0 reads K0 LTF inputs per preamble: the preambles themselves, or a feature slab [chunk][nr][K0] in the workspace behind the
+    // activation buffers - the pooled preambles of a decimated-input model (input_pool.hip.h) or the CONV1D front end's features
+    // (conv_frontend.hip.h, K0 = 64 len_ltf)
+    const bool feats = l0_features(c);
+    const bool conv = c->model_type == CSI_MODEL_CONV1D;
     const int K0 = c->l0_k;
-    const size_t pool_pkt = pooled ? (size_t)nr * K0 * 4 : 0;
+    const size_t pool_pkt = feats ? (size_t)nr * K0 * 4 : 0;
+    const int max_s = conv ? L0_CONV_MAX_SPLITS : 40;
     int maxh = 0;
     for (int i = 1; i < nh; ++i) maxh = std::max(maxh, cf.hidden[i]);
     // Packet chunks: as few as the workspace allows, all of (nearly) the same size so that every
@@ -186,15 +192,20 @@ int predict_plane(csi_ctx* c, Model& m, const float* d_ltf, int64_t npkt, float*
     // the hidden activations.
     const size_t hid_pkt = (size_t)nr * nt * maxh * 4 * (nh >= 3 ? 2 : (nh >= 2 ? 1 : 0));
     // 4 GiB: a config-2 step is one chunk.  Two component models in flight on two streams hold a workspace each: the cap is shared between them
-    const size_t budget = (cf.workspace_bytes > 0 ? (size_t)cf.workspace_bytes : ((size_t)4 << 30)) / (size_t)std::max(c->models_in_flight, 1);
-    const int64_t max_rows = (int64_t)0x7fffffff / ((int64_t)nr * nt * 2);     // M2 must fit an int
+    // CONV1D: 16 GiB.  A chunk streams the LTF part of W0 once (K0 x h1 x 4 bytes) against 8 K0 bytes of features written and read per
+    // preamble, so W0 traffic / feature traffic = h1 / (2 x preambles per chunk): 8 GiB per model = 3276 preambles at Nt = 32 (0.04 at
+    // h1 = 256, 0.16 at 1024) where 2 GiB would hold 819 (0.16 / 0.63)
+    const size_t dflt = conv ? ((size_t)16 << 30) : ((size_t)4 << 30);
+    const size_t budget = (cf.workspace_bytes > 0 ? (size_t)cf.workspace_bytes : dflt) / (size_t)std::max(c->models_in_flight, 1);
+    int64_t max_rows = (int64_t)0x7fffffff / ((int64_t)nr * nt * 2);     // M2 must fit an int
+    if (feats) max_rows = std::min(max_rows, (int64_t)0x7fffffff / ((int64_t)nr * K0));      // ... and the feature slab's element offsets
     int64_t nchunks = 1, chunk = npkt;
     int splits_max = 1;
     const bool hs_ok = hs_static_ok(c, m);          // split-f16 engine available for this model (csi_dnn_hs.hpp)
     for (;;) {
         chunk = (npkt + nchunks - 1) / nchunks;
         int kps_tmp;
-        splits_max = choose_splits((int)std::min<int64_t>(chunk * nr, 1 << 30), h1, K0, &kps_tmp);
+        splits_max = choose_splits((int)std::min<int64_t>(chunk * nr, 1 << 30), h1, K0, &kps_tmp, max_s);
         if (hs_ok) splits_max = std::max(splits_max, hs_layer0_splits(c, (int)std::min<int64_t>(chunk * nr, 1 << 30), h1, K0, &kps_tmp));
         if (hs_ok) splits_max = std::max(splits_max, l0_stream_splits(c, m, (int)std::min<int64_t>(chunk * nr, 1 << 30), h1, K0, &kps_tmp));
         const size_t need = ((size_t)nr * h1 * 4 * (splits_max > 1 ? splits_max + 1 : 1) + hid_pkt + pool_pkt) * (size_t)chunk;
@@ -205,7 +216,7 @@ int predict_plane(csi_ctx* c, Model& m, const float* d_ltf, int64_t npkt, float*
         int kps_tmp;
         const int64_t tail = npkt - (nchunks - 1) * chunk;
         if (tail > 0 && tail != chunk) {
-            splits_max = std::max(splits_max, choose_splits((int)(tail * nr), h1, K0, &kps_tmp));
+            splits_max = std::max(splits_max, choose_splits((int)(tail * nr), h1, K0, &kps_tmp, max_s));
             if (hs_ok) splits_max = std::max(splits_max, hs_layer0_splits(c, (int)(tail * nr), h1, K0, &kps_tmp));
             if (hs_ok) splits_max = std::max(splits_max, l0_stream_splits(c, m, (int)(tail * nr), h1, K0, &kps_tmp));
         }
@@ -213,7 +224,10 @@ int predict_plane(csi_ctx* c, Model& m, const float* d_ltf, int64_t npkt, float*
     const size_t slab_floats = (size_t)chunk * nr * h1;
     // (+ 16 rows per activation buffer: the blocked hs layout addresses whole 16-row blocks)
     const size_t hid_pad = (size_t)16 * maxh * 4;
-    const size_t per_chunk = slab_floats * 4 * (splits_max > 1 ? splits_max + 1 : 1) + hid_pkt * (size_t)chunk + 2 * hid_pad + pool_pkt * (size_t)chunk;
+    // (the feature slab starts on a 256-byte boundary: the front end stores 16-byte vectors)
+    const size_t ws_rest = slab_floats * 4 * (splits_max > 1 ? splits_max + 1 : 1) + hid_pkt * (size_t)chunk + 2 * hid_pad;
+    const size_t pool_off = feats ? (ws_rest + 255) / 256 * 256 : ws_rest;
+    const size_t per_chunk = pool_off + pool_pkt * (size_t)chunk;
     int rc = ensure_bytes(c, &c->ws, &c->ws_bytes, per_chunk);
     if (rc) return rc;
 
@@ -227,9 +241,9 @@ int predict_plane(csi_ctx* c, Model& m, const float* d_ltf, int64_t npkt, float*
         hbuf[0] = slabs + slab_floats * (splits_max > 1 ? splits_max + 1 : 1);
         hbuf[1] = hbuf[0] + (size_t)chunk * nr * nt * maxh + hid_pad / 4;
         const float* x0 = d_ltf + (size_t)p0 * nr * cf.len_ltf;       // layer-0 LTF input [M1][K0]
-        if (pooled) {
-            float* xp = reinterpret_cast<float*>(c->ws + per_chunk - pool_pkt * (size_t)chunk);      // the last part of the chunk's workspace
-            rc = launch_input_pool(c, x0, nullptr, xp, nullptr, M1, false);
+        if (feats) {
+            float* xp = reinterpret_cast<float*>(c->ws + pool_off);      // the last part of the chunk's workspace
+            rc = launch_l0_features(c, &m, nullptr, x0, nullptr, xp, nullptr, M1, false);
             if (rc) return rc;
             x0 = xp;
         }
@@ -271,7 +285,7 @@ int predict_plane(csi_ctx* c, Model& m, const float* d_ltf, int64_t npkt, float*
             if (rc) return rc;
             l0 = slabs;
         }
-        const int splits = stream_splits ? stream_splits : (hs_splits ? hs_splits : (l0 ? 1 : choose_splits(M1, h1, K0, &kps)));
+        const int splits = stream_splits ? stream_splits : (hs_splits ? hs_splits : (l0 ? 1 : choose_splits(M1, h1, K0, &kps, max_s)));
         GemmArgs g{};
         g.A = x0;
         g.lda = K0;

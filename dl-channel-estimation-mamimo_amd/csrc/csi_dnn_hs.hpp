@@ -37,7 +37,9 @@ int hs_layer0_splits(const csi_ctx* c, int M1, int h1, int K, int* k_per_split) 
     const long tiles = (long)((M1 + PP_BM - 1) / PP_BM + 7) / 8 * 8 * ((h1 + PP_BN - 1) / PP_BN);       // as launched (pp_grid)
     int best = 1;
     double best_eff = 0.0;
-    for (int s = 1; s <= HS_L0_MAX_SPLITS; ++s) {
+    // CONV1D contexts (K0 = 64 len_ltf): up to L0_CONV_MAX_SPLITS ranges, so that a chunk's few output tiles fill the chip
+    const int max_s = c->model_type == CSI_MODEL_CONV1D ? L0_CONV_MAX_SPLITS : HS_L0_MAX_SPLITS;
+    for (int s = 1; s <= max_s; ++s) {
         if (s > 1 && K / s < 512) break;
         const long blocks = tiles * s;
         const double eff = (double)blocks / (double)((blocks + 255) / 256 * 256) - 0.01 * (s - 1);

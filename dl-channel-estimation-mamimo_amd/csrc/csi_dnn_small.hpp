@@ -19,6 +19,8 @@ bool small_call_ok(csi_ctx* c, int64_t npkt) {
     // up to 8 preambles layer 0 is the weight-streaming kernel; up to "small_rows" pair rows (default 1024: 8 packets of the shipped
     // shape) it is the tile kernel with the EPI_H1 epilogue - beyond that the general kernels (from 24 packets the split-f16 engine) win
     if (npkt * cf.nr * cf.nt > c->small_rows || npkt * cf.nr > 64) return false;
+    // CONV1D (K0 = 64 len_ltf): only the weight-streaming gemv (at most 8 preambles) - the 16 x 16 tile kernel walks the whole K per tile
+    if (c->model_type == CSI_MODEL_CONV1D && npkt * cf.nr > SC_MAX_ROWS0) return false;
     for (int d = 0; d < 2; ++d)
         if (!c->model[d].loaded || !c->model[d].table_ok || !c->model[d].layers[0].Wt) return false;
     // where the column-split band kernel serves the model the general path (weight-streaming layer 0 + that kernel) wins from 3 packets of
@@ -41,6 +43,7 @@ bool small_ls_fusable(csi_ctx* c, int64_t npkt) {
     const csi_config& cf = c->cfg;
     const int nt = cf.nt;
     if (!c->small_ls_fused || !(nt == 16 || nt == 32 || nt == 64) || cf.dtype != CSI_DTYPE_F32) return false;
+    if (c->model_type == CSI_MODEL_CONV1D) return false;        // its layer 0 reads the front end's feature slab, not the preambles the LS kernel reads
     size_t lds = 0;
     if (!ls_default_fwht2(c, &lds)) return false;
     // ONLY beside the weight-streaming layer 0 of the one-packet path (plain v_fma_f32, no matrix instructions).  The same arrangement beside the
@@ -61,9 +64,12 @@ int predict_small(csi_ctx* c, const float* d_ltf_re, const float* d_ltf_im, int6
     // decimated-input model (input_pool.hip.h): layer 0 walks K0 = len_ltf / 2 pooled inputs.  Up to 8 preambles the weight-streaming
     // kernel pools inside its loads (same launch count as an unpooled call); the tile kernel beyond reads the pooled preambles of both
     // planes from the end of the scratch, written by one pooling pass in front of it
+    // CONV1D (conv_frontend.hip.h): one front-end launch writes the K0 = 64 len_ltf features of both planes to the same place, and the
+    // gemv reads them (no pooling in its loads)
     const bool pooled = c->input_pool != POOL_NONE;
+    const bool conv = c->model_type == CSI_MODEL_CONV1D;
     const int K0 = c->l0_k;
-    const size_t pool_floats = pooled && M1 > SC_MAX_ROWS0 ? (size_t)M1 * K0 : 0;
+    const size_t pool_floats = (pooled && M1 > SC_MAX_ROWS0) || conv ? ((size_t)M1 * K0 + 63) / 64 * 64 : 0;
     int rc = ensure_bytes(c, &c->small_ws, &c->small_ws_bytes, (2 * h1_floats + 4 * act_floats + 2 * pool_floats) * sizeof(float));
     if (rc) return rc;
     float* h1buf = reinterpret_cast<float*>(c->small_ws);
@@ -100,6 +106,14 @@ int predict_small(csi_ctx* c, const float* d_ltf_re, const float* d_ltf_im, int6
     } else {
         SmallL0Args a{};
         a.x[0] = d_ltf_re; a.x[1] = d_ltf_im;
+        int lda0 = cf.len_ltf;
+        if (conv) {
+            float* xp = act + 4 * act_floats;
+            rc = launch_conv_frontend(c, md[0], md[1], d_ltf_re, d_ltf_im, xp, xp + pool_floats, M1, cf.len_ltf, K0, 0, false);
+            if (rc) return rc;
+            a.x[0] = xp; a.x[1] = xp + pool_floats;
+            lda0 = K0;
+        }
         for (int d = 0; d < 2; ++d) {
             const Model& m = *md[d];
             // BatchNormalization shifts live in the next layer's bias where csi_load_weights folded them (Layer::bias_hs)
@@ -107,7 +121,7 @@ int predict_small(csi_ctx* c, const float* d_ltf_re, const float* d_ltf_im, int6
             a.Wt[d] = m.layers[0].Wt; a.T[d] = m.T; a.s0[d] = m.layers[0].scale; a.t0[d] = fold ? c->hs_zero : m.layers[0].shift;
             a.h1out[d] = h1buf + d * h1_floats;
         }
-        a.M = M1; a.K = K0; a.lda = cf.len_ltf; a.ldw = md[0]->layers[0].ldw; a.h1 = h1; a.nt = nt;
+        a.M = M1; a.K = K0; a.lda = lda0; a.ldw = md[0]->layers[0].ldw; a.h1 = h1; a.nt = nt;
         ProfScope ps(c, K_LAYER0_LTF, 2.0 * 2.0 * M1 * h1 * K0, 2.0 * 4.0 * ((double)K0 * h1 + (double)M1 * cf.len_ltf + (double)(nt + M2) * h1));
         // 4 columns per workgroup, 2 k steps of 1024 in flight: every shape tried (4 / 8 columns, 2 ... 5 steps) lands at 16.2-17.0 us
         // for the 84 MB of the shipped model = 5.2 TB/s - the memory system's rate, not the kernel's (profiles/r05_small_call_trace.txt)

@@ -404,12 +404,45 @@ int csi_set_input_pool(csi_ctx* c, int mode) {
         if (c->trainer[d])
             return fail(c, CSI_ERR_INVALID_ARG, "csi_set_input_pool: a trainer of the %s model exists; the pooling mode is set before csi_train_begin", d ? "imag" : "real");
     }
+    if (mode != POOL_NONE && c->model_type == CSI_MODEL_CONV1D)
+        return fail(c, CSI_ERR_INVALID_ARG, "csi_set_input_pool: a CONV1D model has no input pooling (the reference decimates only in its FC branch); csi_set_model_type(FC) first");
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     drop_graphs(c);
     c->input_pool = mode;
-    c->l0_k = mode == POOL_NONE ? c->cfg.len_ltf : c->cfg.len_ltf / 2;
-    c->d_in = c->l0_k + c->cfg.nt;
+    set_layer0_width(c);
+    return CSI_OK;
+}
+
+int csi_set_model_type(csi_ctx* c, int type) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    if (type != CSI_MODEL_FC && type != CSI_MODEL_CONV1D)
+        return fail(c, CSI_ERR_INVALID_ARG, "csi_set_model_type: type %d is FC (0) or CONV1D (1)", type);
+    if (type != CSI_MODEL_FC && c->cfg.nt == 0)
+        return fail(c, CSI_ERR_INVALID_ARG, "csi_set_model_type: CONV1D needs the pilot input (nt > 0); the single-input model has none");
+    for (int d = 0; d < 2; ++d) {
+        if (c->model[d].loaded)
+            return fail(c, CSI_ERR_INVALID_ARG, "csi_set_model_type: the %s model holds weights; the model type is set before csi_load_weights", d ? "imag" : "real");
+        if (c->trainer[d])
+            return fail(c, CSI_ERR_INVALID_ARG, "csi_set_model_type: a trainer of the %s model exists; the model type is set before csi_train_begin", d ? "imag" : "real");
+    }
+    if (type == CSI_MODEL_CONV1D) {
+        if (c->input_pool != POOL_NONE)
+            return fail(c, CSI_ERR_INVALID_ARG, "csi_set_model_type: CONV1D and input pooling (%s) exclude each other (the reference decimates only in its FC branch); "
+                        "csi_set_input_pool(none) first", input_pool_name(c->input_pool));
+        if (c->cfg.len_ltf % 2 != 0 || c->cfg.len_ltf < 2)
+            return fail(c, CSI_ERR_INVALID_ARG, "csi_set_model_type: CONV1D needs an even len_ltf (AveragePooling1D pairs the samples), got %d", c->cfg.len_ltf);
+        // K0 = 64 len_ltf features per preamble: the layer-0 GEMMs address a 256-row tile of their operands with 32-bit byte offsets
+        // (buffer loads of gemm_hs.hip.h / gemm_bf16.hip.h, 2 halves per split-f16 weight): 256 x 2 x 64 len_ltf x 2 bytes stays below 2^31
+        if (c->cfg.len_ltf > 20480)
+            return fail(c, CSI_ERR_INVALID_ARG, "csi_set_model_type: CONV1D supports len_ltf <= 20480 (nt <= 64 at 320 samples per antenna), got %d: "
+                        "its %lld layer-0 features per preamble would overflow the 32-bit offsets of the layer-0 kernels", c->cfg.len_ltf, 64LL * c->cfg.len_ltf);
+    }
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    drop_graphs(c);
+    c->model_type = type;
+    set_layer0_width(c);
     return CSI_OK;
 }
 
@@ -457,8 +490,7 @@ int csi_create(const csi_config* cfg, csi_ctx** out) {
     c->cfg = *cfg;
     c->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     if (c->cfg.bn_eps <= 0.f) c->cfg.bn_eps = 1e-3f;
-    c->l0_k = cfg->len_ltf;
-    c->d_in = c->l0_k + cfg->nt;
+    set_layer0_width(c);
     if (const char* e = std::getenv("CSI_FORCE_PAIR_TILE")) c->force_pair_tile = std::atoi(e);
     if (const char* e = std::getenv("CSI_LS_FFT_FIRST_MAX")) c->ls_fft_first_max = std::min(64, std::max(0, std::atoi(e)));
     if (const char* e = std::getenv("CSI_LS_DEBUG")) c->ls_debug = std::atoi(e);
@@ -583,6 +615,35 @@ int csi_load_weights(csi_ctx* c, int model, const csi_tensor* tensors, int n) {
     drop_graphs(c);
     free_model(m);
     m.layers.resize(cf.n_hidden + 1);
+    if (c->model_type == CSI_MODEL_CONV1D) {
+        // the front end (conv_frontend.hip.h): cnn1d_1 [7 taps][128 filters] + bias, then its BatchNormalization folded to scale / shift in
+        // double - q = relu(conv) * gamma / sqrt(var + eps) + (beta - mean * gamma / sqrt(var + eps))
+        const char* names[6] = {"cnn1d_1.kernel", "cnn1d_1.bias", "conv_bn.gamma", "conv_bn.beta", "conv_bn.moving_mean", "conv_bn.moving_variance"};
+        const csi_tensor* t[6];
+        for (int i = 0; i < 6; ++i) {
+            t[i] = find_tensor(tensors, n, names[i]);
+            if (!t[i] || !t[i]->data)
+                return fail(c, CSI_ERR_INVALID_ARG, "csi_load_weights: CONV1D model: missing %s (the front end needs cnn1d_1.kernel/.bias and conv_bn.gamma/.beta/.moving_mean/.moving_variance)", names[i]);
+            const int64_t want_rows = i == 0 ? CONV_TAPS : 1;
+            if ((i == 0 && (t[i]->rows != want_rows || t[i]->cols != CONV_FILTERS)) || (i > 0 && t[i]->rows * t[i]->cols != CONV_FILTERS))
+                return fail(c, CSI_ERR_INVALID_ARG, "csi_load_weights: CONV1D model: %s is [%lld,%lld], expected %s", names[i], (long long)t[i]->rows,
+                            (long long)t[i]->cols, i == 0 ? "[7,128] (7 taps x 128 filters)" : "128 values");
+        }
+        std::vector<float> prm(CONV_PRM_FLOATS);
+        for (int i = 0; i < CONV_TAPS * CONV_FILTERS; ++i) prm[i] = t[0]->data[i];
+        for (int ch = 0; ch < CONV_FILTERS; ++ch) {
+            const double sc = (double)t[2]->data[ch] / std::sqrt((double)t[5]->data[ch] + (double)cf.bn_eps);
+            prm[CONV_TAPS * CONV_FILTERS + ch] = t[1]->data[ch];
+            prm[(CONV_TAPS + 1) * CONV_FILTERS + ch] = (float)sc;
+            prm[(CONV_TAPS + 2) * CONV_FILTERS + ch] = (float)((double)t[3]->data[ch] - (double)t[4]->data[ch] * sc);
+        }
+        const int64_t ldw0 = ((int64_t)c->d_in + G_BK - 1) / G_BK * G_BK;
+        if (ldw0 * cf.hidden[0] >= ((int64_t)1 << 31))
+            return fail(c, CSI_ERR_INVALID_ARG, "csi_load_weights: CONV1D model: fc_dense0 holds %lld x %d weights, at or above 2^31 elements (the layer-0 kernels "
+                        "index it with 32-bit element offsets); a narrower hidden[0] or a smaller len_ltf", (long long)ldw0, cf.hidden[0]);
+        int rc = upload(c, &m.conv, prm.data(), prm.size());
+        if (rc) return rc;
+    }
     int fan_in = c->d_in;
     std::vector<float> prev_shift;          // BN shift of the previous layer (split engine: folded into this layer's bias)
     std::vector<float> prev_scale;          // BN scale of the previous layer (split engine, layer 1 only: folded into the split weights)
@@ -594,10 +655,11 @@ int csi_load_weights(csi_ctx* c, int model, const csi_tensor* tensors, int n) {
         const csi_tensor* b = find_tensor(tensors, n, base + ".bias");
         if (!k || !b || !k->data || !b->data) return fail(c, CSI_ERR_INVALID_ARG, "csi_load_weights: missing %s.kernel/.bias", base.c_str());
         if (li == 0 && cf.nt > 0 && k->rows != fan_in && k->cols == out)
-            return fail(c, CSI_ERR_INVALID_ARG, "csi_load_weights: %s.kernel is [%lld,%lld], expected [%d,%d] (input pooling %s: %d LTF rows + %d pilot rows)%s",
-                        base.c_str(), (long long)k->rows, (long long)k->cols, fan_in, out, input_pool_name(c->input_pool), c->l0_k, cf.nt,
+            return fail(c, CSI_ERR_INVALID_ARG, "csi_load_weights: %s.kernel is [%lld,%lld], expected [%d,%d] (%s model, input pooling %s: %d LTF rows + %d pilot rows)%s",
+                        base.c_str(), (long long)k->rows, (long long)k->cols, fan_in, out, model_type_name(c->model_type), input_pool_name(c->input_pool), c->l0_k, cf.nt,
+                        k->rows == (int64_t)64 * cf.len_ltf + cf.nt ? " - a CONV1D model: csi_set_model_type(CONV1D) first" :
                         k->rows == (int64_t)cf.len_ltf / 2 + cf.nt ? " - a decimated model: csi_set_input_pool(max | avg) first" :
-                        (k->rows == (int64_t)cf.len_ltf + cf.nt ? " - a model without pooling: csi_set_input_pool(none)" : ""));
+                        (k->rows == (int64_t)cf.len_ltf + cf.nt ? (c->model_type == CSI_MODEL_CONV1D ? " - an FC model: csi_set_model_type(FC)" : " - a model without pooling: csi_set_input_pool(none)") : ""));
         if (k->rows != fan_in || k->cols != out || b->rows * b->cols != out)
             return fail(c, CSI_ERR_INVALID_ARG, "csi_load_weights: %s.kernel is [%lld,%lld], expected [%d,%d]", base.c_str(),
                         (long long)k->rows, (long long)k->cols, fan_in, out);
@@ -1267,6 +1329,8 @@ int csi_get_option(csi_ctx* c, const char* name, int64_t* value) {
     else if (n == "small_ls_launches") *value = c->small_ls_launches;
     else if (n == "small_calls") *value = c->small_calls;
     else if (n == "input_pool") *value = c->input_pool;
+    else if (n == "model_type") *value = c->model_type;
+    else if (n == "conv_launches") *value = c->conv_launches;
     else if (n == "small_rows") *value = c->small_rows;
     else if (n == "small_rows_band") *value = c->small_rows_band;
     else if (n == "f32_engine") *value = c->f32_engine;
@@ -1496,6 +1560,9 @@ static int trainer_of(csi_ctx* c, int model, const char* fn, csi_trainer** t) {
 int csi_train_begin(csi_ctx* c, int model, const csi_train_config* tc, const csi_tensor* tensors, int n) {
     if (!c) return CSI_ERR_INVALID_ARG;
     if (model < 0 || model > 1 || !tc || n < 0 || (n > 0 && !tensors)) return fail(c, CSI_ERR_INVALID_ARG, "csi_train_begin: bad argument");
+    if (c->model_type == CSI_MODEL_CONV1D)
+        return fail(c, CSI_ERR_INVALID_ARG, "csi_train_begin: training a CONV1D model is not supported (it needs the conv backward pass and BatchNormalization "
+                    "batch statistics over B x len_ltf positions); train the FC models, or train CONV1D models elsewhere and load them");
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     const int rc = tr_begin(c, model, tc, tensors, n);
     if (rc && c->trainer[model]) { tr_free(c->trainer[model]); c->trainer[model] = nullptr; }
@@ -1896,11 +1963,13 @@ int csi_predict_samples(csi_ctx* c, int model, const float* x, int64_t B, float*
     for (int i = 0; i < cf.n_hidden; ++i) maxh = std::max(maxh, cf.hidden[i]);
     // rows arrive raw, [B][len_ltf + nt], as keras' predict receives them; a decimated-input model pools them on the device into the
     // [B][len_ltf / 2 + nt] rows its layer 0 reads (input_pool_rows_kernel)
-    const bool pooled = c->input_pool != POOL_NONE;
+    // (a CONV1D model: its front end turns them into [B][64 len_ltf + nt] rows, the pilot columns copied - conv_frontend.hip.h)
+    const bool pooled = l0_features(c);
     const int raw_in = pooled ? cf.len_ltf + cf.nt : c->d_in;
     auto upload_rows = [&](float* d_raw, float* d_rows, int64_t r0, int64_t nb) -> int {
         HIP_TRY(c, hipMemcpyAsync(pooled ? d_raw : d_rows, x + (size_t)r0 * raw_in, (size_t)nb * raw_in * sizeof(float), hipMemcpyHostToDevice, c->stream));
         if (!pooled) return CSI_OK;
+        if (c->model_type == CSI_MODEL_CONV1D) return launch_conv_frontend(c, &m, nullptr, d_raw, nullptr, d_rows, nullptr, nb, raw_in, c->d_in, cf.nt, false);
         ProfScope ps(c, K_INPUT_POOL, 0.0, 4.0 * (double)nb * (raw_in + c->d_in));
         const unsigned blocks = (unsigned)std::min<size_t>(((size_t)nb * c->d_in + 255) / 256, 8192);
         if (c->input_pool == POOL_MAX)

@@ -144,13 +144,26 @@ def input_pool_name(mode):
     raise CsiError(-1, f"input_pool must be None, 'max' or 'avg', got {mode!r}")
 
 
+MODEL_TYPES = {'FC': 0, 'CONV1D': 1}
+
+
+def model_type_name(model):
+    """None / 'FC' / 0 -> 'FC', 'CONV1D' / 1 -> 'CONV1D' (csi_set_model_type types; --model of the reference)."""
+    if model is None:
+        return 'FC'
+    for name, v in MODEL_TYPES.items():
+        if (isinstance(model, str) and model.upper() == name) or (not isinstance(model, str) and model == v):
+            return name
+    raise CsiError(-1, f"model must be 'FC' or 'CONV1D', got {model!r}")
+
+
 class CsiEngine:
     """Owns a ``csi_ctx``.  Shapes follow the reference: nt tx antennas, nr rx antennas,
     len_ltf = 320*nt samples per rx preamble, FC hidden widths ``hidden`` (--nn), n_out outputs
     (massiveMIMO_CSI_prediction_DNN.py:18,227)."""
 
     def __init__(self, nt, nr, hidden=(1024, 1024), n_out=N_DATA, use_bn=True, bn_eps=1e-3,
-                 device=0, workspace_bytes=0, dtype='f32', len_ltf=None, input_pool=None):
+                 device=0, workspace_bytes=0, dtype='f32', len_ltf=None, input_pool=None, model='FC'):
         self._lib = _lib.load_library()
         self._ctx = None
         self.nt, self.nr = int(nt), int(nr)
@@ -159,7 +172,10 @@ class CsiEngine:
         self.d_in = self.len_ltf + self.nt          # width of the rows the caller hands over (raw, also for a decimated-input model)
         # decimated-input model (--decimate_max / --decimate_avg): layer 0 sees len_ltf/2 + nt inputs (csi_set_input_pool)
         self.input_pool = input_pool_name(input_pool)
-        self.l0_in = (self.len_ltf // 2 if self.input_pool else self.len_ltf) + self.nt
+        # CONV1D model (--model CONV1D): Conv1D(128, 7) + BN + AveragePooling1D + Flatten in front of layer 0, which sees 64 len_ltf + nt
+        # inputs (csi_set_model_type)
+        self.model = model_type_name(model)
+        self.l0_in = (64 * self.len_ltf if self.model == 'CONV1D' else (self.len_ltf // 2 if self.input_pool else self.len_ltf)) + self.nt
         self.hidden = tuple(int(h) for h in hidden)
         self.n_out = int(n_out)
         self.use_bn = bool(use_bn)
@@ -178,8 +194,15 @@ class CsiEngine:
         if rc != 0:
             raise CsiError(rc, (self._lib.csi_last_error(None) or b'').decode())
         self._ctx = ctx
-        if self.input_pool:
-            self._check(self._lib.csi_set_input_pool(ctx, INPUT_POOL_MODES[self.input_pool]))
+        try:
+            if self.input_pool:
+                self._check(self._lib.csi_set_input_pool(ctx, INPUT_POOL_MODES[self.input_pool]))
+            if self.model != 'FC':
+                self._check(self._lib.csi_set_model_type(ctx, MODEL_TYPES[self.model]))
+        except CsiError:
+            self._arrays = weakref.WeakSet()
+            self.close()
+            raise
         self._arrays = weakref.WeakSet()
         me = weakref.ref(self)                                  # (no engine -> pool -> engine cycle: an engine is freed when its last reference goes)
         self.result_pool = PinnedPool(lambda n: me()._pinned_buffer(n))       # estimate(..., pinned_results=True)
@@ -237,6 +260,8 @@ class CsiEngine:
             if not isinstance(val, np.ndarray):
                 continue
             a = _f32c(val)
+            if a.ndim == 3:                   # cnn1d_1.kernel [taps, 1, filters] as keras stores it -> [taps, filters]
+                a = a.reshape(a.shape[0], a.shape[1] * a.shape[2])
             keep.append(a)
             arr[n].name = name.encode()
             arr[n].data = _fp(a)

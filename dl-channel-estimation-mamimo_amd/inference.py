@@ -10,8 +10,8 @@ import sys
 import numpy as np
 
 from ._lib import CsiError
-from .engine import CsiEngine, input_pool_name
-from .model import CSIModel, load_weight_file, normalize_keras_names, config_from_weights, WEIGHT_FILE, CONFIG_FILE
+from .engine import CsiEngine, input_pool_name, model_type_name
+from .model import CSIModel, load_weight_file, normalize_keras_names, config_from_weights, weights_model_type, WEIGHT_FILE, CONFIG_FILE
 
 
 class CSIPredictor:
@@ -43,11 +43,14 @@ class CSIPredictor:
         without ``nr=`` any [nPkt, nRx, lenLTF] batch is accepted.
         The input pooling of a decimated-input model comes from config.json (a missing key: none), from the pooling layer
         of a whole-model HDF5 file (``<d>_keras_model`` itself or with .h5 / .hdf5) or from ``input_pool=``; a SavedModel
-        directory does not name it, so there only the argument counts.  Sources that disagree raise CsiError."""
-        from .keras_files import read_keras_hdf5_weights, keras_hdf5_input_pool
+        directory does not name it, so there only the argument counts.  Sources that disagree raise CsiError.
+        The model type (FC / CONV1D, --model) is what the weights hold (cnn1d_1: CONV1D); a config.json "model" key that says
+        otherwise raises CsiError."""
+        from .keras_files import read_keras_hdf5_weights, keras_hdf5_input_pool, keras_hdf5_model_type
         dirs = {d: os.path.join(self.path, d + '_keras_model') for d in ('real', 'imag')}
         weights, cfg = {}, None
         pools = []                                          # (source, mode) of every place that states the mode
+        types = []                                          # (source, model type)
         if self._input_pool_arg is not None:
             pools.append(('input_pool argument', input_pool_name(self._input_pool_arg)))
         for d, p in dirs.items():
@@ -58,22 +61,34 @@ class CSIPredictor:
                     c = json.load(f)
                 cfg = cfg or c
                 pools.append((os.path.join(p, CONFIG_FILE), input_pool_name(c.get('input_pool'))))
+                types.append((os.path.join(p, CONFIG_FILE), model_type_name(c.get('model'))))
             elif h5 is not None and not os.path.isdir(p):
-                weights[d] = normalize_keras_names(read_keras_hdf5_weights(h5))
-                pools.append((h5, keras_hdf5_input_pool(h5)))
+                if keras_hdf5_model_type(h5) == 'CONV1D':
+                    weights[d] = load_weight_file(h5) if h5.endswith(('.h5', '.hdf5')) else normalize_keras_names(read_keras_hdf5_weights(h5))
+                    types.append((h5, 'CONV1D'))
+                else:
+                    weights[d] = normalize_keras_names(read_keras_hdf5_weights(h5))
+                    pools.append((h5, keras_hdf5_input_pool(h5)))
             else:
                 weights[d] = load_weight_file(p)            # SavedModel directory (raises if it is neither)
+            types.append((f'{d} weights', weights_model_type(weights[d])))
         modes = {m for _, m in pools}
         if len(modes) > 1:
             raise CsiError(-1, 'input pooling disagrees between its sources: ' + ', '.join(f'{src}: {m or "none"}' for src, m in pools))
         pool = modes.pop() if modes else None
+        mtypes = {m for _, m in types}
+        if len(mtypes) > 1:
+            raise CsiError(-1, 'model type disagrees between its sources: ' + ', '.join(f'{src}: {m}' for src, m in types))
+        mtype = mtypes.pop()
+        if mtype == 'CONV1D' and pool:
+            raise CsiError(-1, f'a CONV1D model has no input pooling, but input pooling {pool!r} was stated')
         if cfg is None:
             w = weights['real']
             d_in = int(w['fc_dense0.kernel'].shape[0])
             two_input = self.experiment == 'matlab_maMimo'
-            per_tx = 161 if pool else 321                   # LTF samples (pooled: half) + pilot entry per tx antenna
+            per_tx = 64 * 320 + 1 if mtype == 'CONV1D' else (161 if pool else 321)     # LTF inputs (pooled: half, CONV1D: 64x) + pilot entry per tx antenna
             if two_input and d_in % per_tx:
-                print('[CSIPredictor] ERROR: the saved model has %d inputs, not %d*nTx (LTF samples + pilot row).' % (d_in, per_tx))
+                print('[CSIPredictor] ERROR: the saved model has %d inputs, not %d*nTx (LTF inputs + pilot row).' % (d_in, per_tx))
                 sys.exit(-1)
             hidden, i = [], 0
             while f'fc_dense{i}.kernel' in w:
@@ -84,13 +99,14 @@ class CSIPredictor:
             self._any_nr = two_input and self._nr is None
         nt, nr = int(cfg['nt']), int(cfg.get('nr', 1))
         if nt > 0:
-            shape = config_from_weights(weights['real'], nt, input_pool=pool)
+            shape = config_from_weights(weights['real'], nt, input_pool=pool, model=mtype)
         else:       # single-input model (DNN.py:180,234): no pilot input
             shape = dict(hidden=list(cfg['hidden']), n_out=int(cfg['n_out']), use_bn=bool(cfg['use_bn']))
         self.engine = CsiEngine(nt, nr, hidden=shape['hidden'], n_out=shape['n_out'], use_bn=shape['use_bn'],
                                 bn_eps=float(cfg.get('bn_eps', 1e-3)), device=self.device,
                                 workspace_bytes=self.workspace_bytes,
-                                len_ltf=int(cfg['len_ltf']) if nt == 0 else None, input_pool=pool if nt > 0 else None)
+                                len_ltf=int(cfg['len_ltf']) if nt == 0 else None, input_pool=pool if nt > 0 else None,
+                                model=mtype if nt > 0 else 'FC')
         models = {}
         for d in ('real', 'imag'):
             models[d] = CSIModel(self.engine, d).load_weights(weights[d])

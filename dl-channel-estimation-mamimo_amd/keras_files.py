@@ -428,6 +428,32 @@ def keras_hdf5_input_pool(path):
     return found.pop() if found else None
 
 
+def keras_hdf5_model_type(path):
+    """The --model of the model a Keras HDF5 weights / whole-model file holds, from its ``layer_names``: 'CONV1D' when it has a
+    ``cnn1d_*`` layer (DNN.py:236-270), else 'FC'.  (keras_hdf5_input_pool keeps refusing CONV1D files: their pooling is part of the
+    front end, not an input-pooling mode.)"""
+    names = _listed(path, _keras_hdf5_root(path).attrs, 'layer_names')
+    return 'CONV1D' if any(n.startswith('cnn1d') for n in names) else 'FC'
+
+
+def check_conv1d_weights(weights, where):
+    """The live CONV1D branch (DNN.py:238): cnn1d_1 with 7 taps, 1 input channel, 128 filters and a bias, and the BatchNormalization
+    after it.  Anything else (the commented-out cnn1d_2 / cnn1d_3 of :240-246 included) is refused with text naming CONV1D."""
+    conv = sorted({k.split('.')[0] for k in weights if k.startswith('cnn1d')})
+    if conv != ['cnn1d_1']:
+        raise KerasFileError(f'{where}: CONV1D layers {conv} - only the live branch (one cnn1d_1 layer, DNN.py:238) is supported')
+    k = weights.get('cnn1d_1.kernel')
+    if k is None or tuple(np.shape(k)) != (7, 1, 128):
+        raise KerasFileError(f'{where}: CONV1D cnn1d_1.kernel has shape {None if k is None else tuple(np.shape(k))}, '
+                             f'expected (7, 1, 128) - Conv1D(128, 7) on the [len_ltf, 1] LTF (DNN.py:238)')
+    b = weights.get('cnn1d_1.bias')
+    if b is None or np.size(b) != 128:
+        raise KerasFileError(f'{where}: CONV1D cnn1d_1 has {"no bias" if b is None else "a bias of %d values" % np.size(b)}, expected 128 values')
+    for v in _BN_VARS:
+        if f'conv_bn.{v}' not in weights or np.size(weights[f'conv_bn.{v}']) != 128:
+            raise KerasFileError(f'{where}: CONV1D model without the BatchNormalization of cnn1d_1 ({v} of 128 values missing)')
+
+
 def read_keras_hdf5_weights(path):
     """{'<layer>/<weight name>': float32 ndarray} of a Keras HDF5 weights / whole-model file, in the order keras
     itself walks them when loading by topology: root attribute ``layer_names``, per layer ``weight_names``
@@ -596,9 +622,10 @@ def _unmask_crc(masked):
     return ((rot >> 17) | (rot << 15)) & 0xFFFFFFFF
 
 
-def read_tensor_bundle(prefix, verify_crc=True):
+def read_tensor_bundle(prefix, verify_crc=True, shapes_only=False):
     """{key: ndarray} of the tensor bundle ``<prefix>.index`` + ``<prefix>.data-xxxxx-of-yyyyy`` in key order
-    (keys of object-based checkpoints look like ``layer_with_weights-0/kernel/.ATTRIBUTES/VARIABLE_VALUE``)."""
+    (keys of object-based checkpoints look like ``layer_with_weights-0/kernel/.ATTRIBUTES/VARIABLE_VALUE``).
+    ``shapes_only``: {key: shape tuple} from the index alone, no shard is read."""
     with open(prefix + '.index', 'rb') as fh:
         buf = fh.read()
     if len(buf) < 48 or struct.unpack('<Q', buf[-8:])[0] != _TABLE_MAGIC:
@@ -648,6 +675,9 @@ def read_tensor_bundle(prefix, verify_crc=True):
             continue
         if sliced:
             raise KerasFileError(f'{prefix}.index: tensor {name} is stored in slices (partitioned variable)')
+        if shapes_only:
+            out[name] = tuple(shape)
+            continue
         if shard not in shards:
             if not 0 <= shard < max(num_shards, 1):
                 raise KerasFileError(f'{prefix}.index: tensor {name} sits in shard {shard} of {num_shards}')
@@ -673,6 +703,15 @@ def read_tensor_bundle(prefix, verify_crc=True):
 _BN_VARS = ('gamma', 'beta', 'moving_mean', 'moving_variance')
 
 
+def savedmodel_model_type(model_dir):
+    """'CONV1D' when a SavedModel's checkpoint holds a rank-3 kernel (cnn1d_1, DNN.py:238), else 'FC' - from the bundle index alone."""
+    prefix = os.path.join(model_dir, 'variables', 'variables')
+    if not os.path.exists(prefix + '.index'):
+        raise KerasFileError(f'{model_dir}: no variables/variables.index - not a SavedModel directory')
+    shapes = read_tensor_bundle(prefix, shapes_only=True)
+    return 'CONV1D' if any(k.split('/')[1:2] == ['kernel'] and len(v) == 3 for k, v in shapes.items()) else 'FC'
+
+
 def read_savedmodel_variables(model_dir, verify_crc=True):
     """Weights of a Keras model saved as a TF SavedModel directory (DNN.py:411), as keras-style paths in model
     order.  The object-based checkpoint names the tensors by position - ``layer_with_weights-<i>/<attribute>`` with i
@@ -690,11 +729,17 @@ def read_savedmodel_variables(model_dir, verify_crc=True):
             layers.setdefault(int(parts[0].split('-')[1]), {})[parts[1]] = val
     if not layers:
         raise KerasFileError(f'{model_dir}: no layer_with_weights-* variables in the checkpoint')
-    dense = [i for i in sorted(layers) if 'kernel' in layers[i]]
+    dense = [i for i in sorted(layers) if 'kernel' in layers[i] and np.ndim(layers[i]['kernel']) == 2]
     out, n_dense, n_bn = {}, 0, 0
     for i in sorted(layers):
         lw = layers[i]
-        if 'kernel' in lw:
+        if 'kernel' in lw and np.ndim(lw['kernel']) == 3:
+            # a Conv1D kernel [taps, in, filters]: the CONV1D branch's cnn1d_1 (DNN.py:238); the BatchNormalization after it is the
+            # first batch_normalization, which normalize_keras_names maps to conv_bn
+            out['cnn1d_1/kernel:0'] = np.asarray(lw['kernel'], np.float32)
+            if 'bias' in lw:
+                out['cnn1d_1/bias:0'] = np.asarray(lw['bias'], np.float32)
+        elif 'kernel' in lw:
             name = 'fc_regressor' if i == dense[-1] else f'fc_dense{n_dense}'
             n_dense += 1
             out[f'{name}/kernel:0'] = np.asarray(lw['kernel'], np.float32)
@@ -857,30 +902,44 @@ def write_keras_hdf5_weights(path, layers, keras_version='2.4.0', backend='tenso
         fh.write(w.finish(root))
 
 
-def keras_layers_from_weights(weights, component='real', dropout=True, input_pool=None):
+def keras_layers_from_weights(weights, component='real', dropout=True, input_pool=None, model='FC'):
     """Container-named tensors -> the ``layers`` list of write_keras_hdf5_weights for the reference's model
     (DNN.py:176-234): inputs, flatten, concatenate, then per hidden layer fc_dense<i> / batch_normalization[_k] /
     drop<i> (between hidden layers only, :222), fc_regressor.  BatchNormalization auto-numbers continue from the real to
     the imag model, which is built second in the same process.  ``input_pool`` 'max' / 'avg' (a decimated-input model,
     DNN.py:197-205) puts max_pooling1d[_k] / average_pooling1d[_k] between the LTF input and flatten, where keras_hdf5_input_pool
-    finds it again."""
+    finds it again.  ``model`` 'CONV1D' (DNN.py:236-270) puts cnn1d_1, its batch_normalization[_k] and average_pooling1d[_k] there
+    instead (the weights of the container names cnn1d_1.* / conv_bn.*; the BatchNormalization numbers of the imag model continue
+    behind the real model's 1 + n_hidden), and a drop<i> layer between every two hidden layers (:262-266)."""
+    conv = str(model).upper() == 'CONV1D'
     n_hidden = 0
     while f'fc_dense{n_hidden}.kernel' in weights:
         n_hidden += 1
     use_bn = 'bn0.gamma' in weights
     k = 0 if component == 'real' else 1
     sfx = lambda base, i: base + (f'_{i}' if i else '')
+    f32 = lambda a: np.asarray(a, np.float32)
     out = [(f'input_{1 + 2 * k}', [])]
-    if input_pool not in (None, 'none'):
+    bn0 = k * n_hidden if use_bn else 0          # BatchNormalization numbers: the real model's come first
+    if conv:
+        if input_pool not in (None, 'none'):
+            raise KerasFileError('a CONV1D model has no input pooling (DNN.py decimates only in its FC branch)')
+        n_bn = 1 + (n_hidden if use_bn else 0)
+        bn0 = k * n_bn + 1
+        cb = sfx('batch_normalization', k * n_bn)
+        out += [('cnn1d_1', [('cnn1d_1/kernel:0', f32(weights['cnn1d_1.kernel']).reshape(7, 1, 128)), ('cnn1d_1/bias:0', f32(weights['cnn1d_1.bias']).ravel())]),
+                (cb, [(f'{cb}/{v}:0', f32(weights[f'conv_bn.{v}']).ravel()) for v in _BN_VARS]),
+                (sfx('average_pooling1d', k), [])]
+        dropout = True
+    elif input_pool not in (None, 'none'):
         if input_pool not in ('max', 'avg'):
             raise KerasFileError(f"input_pool must be None, 'max' or 'avg', got {input_pool!r}")
         out.append((sfx('max_pooling1d' if input_pool == 'max' else 'average_pooling1d', k), []))
     out += [(sfx('flatten', k), []), (f'input_{2 + 2 * k}', []), (sfx('concatenate', k), [])]
-    f32 = lambda a: np.asarray(a, np.float32)
     for i in range(n_hidden):
         out.append((f'fc_dense{i}', [(f'fc_dense{i}/kernel:0', f32(weights[f'fc_dense{i}.kernel'])), (f'fc_dense{i}/bias:0', f32(weights[f'fc_dense{i}.bias']).ravel())]))
         if use_bn:
-            bn = sfx('batch_normalization', k * n_hidden + i)
+            bn = sfx('batch_normalization', bn0 + i)
             out.append((bn, [(f'{bn}/{v}:0', f32(weights[f'bn{i}.{v}']).ravel()) for v in _BN_VARS]))
         if dropout and i < n_hidden - 1:
             out.append((f'drop{i}', []))

@@ -110,6 +110,28 @@ const char* csi_last_error(const csi_ctx* ctx);      /* ctx may be NULL: last cr
  * csi_get_option("input_pool") reads the mode; csi_clone_weights / csi_broadcast_weights refuse contexts of different modes. */
 int  csi_set_input_pool(csi_ctx* ctx, int mode);
 
+/* CONV1D models (--model CONV1D, massiveMIMO_CSI_prediction_DNN.py:236-270): type 1 puts a front end in front of layer 0.  The
+ * LTF row x[len_ltf] goes through Conv1D(128, 7, padding='same') + bias, relu, its BatchNormalization (always present, moving
+ * statistics, eps = csi_config.bn_eps), AveragePooling1D() (pool 2, stride 2) and Flatten (channels last), so layer 0 sees
+ * K0 = 64 len_ltf features + nt pilot inputs: fc_dense0.kernel has 64 len_ltf + nt rows.  0 = FC (default).  Extra tensors of
+ * csi_load_weights: "cnn1d_1.kernel" [7 taps][128 filters], "cnn1d_1.bias" [128], "conv_bn.gamma" / ".beta" / ".moving_mean" /
+ * ".moving_variance" [128].  Callers still pass raw preambles / [B][len_ltf+nt] rows; LS, LMMSE and NMSE read the raw preambles.
+ * Preconditions and errors as csi_set_input_pool (nt > 0, no weights, no trainer); CONV1D and input pooling exclude each other,
+ * len_ltf must be even and at most 20480 (nt <= 64 at 320 samples per antenna: the 32-bit byte offsets of the buffer loads in the
+ * layer-0 GEMMs), and 64 len_ltf x hidden[0] must stay below 2^31 elements (csi_load_weights refuses it).  csi_train_begin refuses
+ * CONV1D contexts.  csi_get_option("model_type") reads the type, "conv_launches" counts front-end passes; clone / broadcast refuse
+ * contexts of different types.
+ * Routes (the front end writes the features into the per-chunk workspace; the layer-0 kernels read them with lda = K0):
+ *   fp32, <= 8 rx preambles (one-packet path):  1 front-end launch for both models + the weight-streaming gemv + n_hidden launches;
+ *                                               the LS estimate of csi_estimate_device does NOT ride in the layer-0 launch
+ *   fp32, larger calls, per model and chunk:   1 front-end launch + layer 0 (weight-streaming split-f16 kernel, split-f16 GEMM or
+ *                                               fp32 MFMA GEMM, K cut in up to 256 ranges) + its k-range sum + the FC stack as today
+ *   bf16, per model and chunk:                 1 front-end launch (bf16 features) + the bf16 MFMA GEMM (K cut in up to 256 ranges) +
+ *                                               the FC stack as today (no weight-streaming or fused-cast layer 0) */
+#define CSI_MODEL_FC 0
+#define CSI_MODEL_CONV1D 1
+int  csi_set_model_type(csi_ctx* ctx, int type);
+
 /* model: 0 = real, 1 = imag.  Tensors are copied (and re-laid-out) to the device. */
 int  csi_load_weights(csi_ctx* ctx, int model, const csi_tensor* tensors, int n);
 /* P [nt][nt], row j = pilot sequence of tx antenna j = MATLAB P(j,:) = dataset['P'][:, j]. */
