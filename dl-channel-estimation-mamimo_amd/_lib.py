@@ -69,6 +69,13 @@ SYMBOLS = {
     'csi_estimate_device': (ctypes.c_int, [_ctx, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp]),
     'csi_lmmse_estimate': (ctypes.c_int, [_ctx, _fp, _fp, ctypes.c_int64, _fp, ctypes.c_int, _fp, _fp, _fp]),
     'csi_lmmse_estimate_device': (ctypes.c_int, [_ctx, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_int, _vp, _vp, _vp]),
+    'csi_hybrid_set_dictionary': (ctypes.c_int, [_ctx, _fp, _fp, ctypes.c_int]),
+    'csi_hybrid_weights': (ctypes.c_int, [_ctx, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_vp] * 7),
+    'csi_hybrid_weights_device': (ctypes.c_int, [_ctx, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_vp] * 7),
+    'csi_capture_begin': (ctypes.c_int, [_ctx]),
+    'csi_capture_end': (ctypes.c_int, [_ctx, ctypes.POINTER(ctypes.c_void_p)]),
+    'csi_capture_launch': (ctypes.c_int, [_ctx, _vp]),
+    'csi_capture_free': (None, [_ctx, _vp]),
     'csi_train_begin': (ctypes.c_int, [_ctx, ctypes.c_int, ctypes.POINTER(CsiTrainConfig), ctypes.POINTER(CsiTensor), ctypes.c_int]),
     'csi_train_step': (ctypes.c_int, [_ctx, ctypes.c_int, _fp, _fp, ctypes.c_int64, ctypes.c_float, _fp]),
     'csi_train_backward': (ctypes.c_int, [_ctx, ctypes.c_int, _fp, _fp, ctypes.c_int64, ctypes.c_float, _fp]),

@@ -45,6 +45,10 @@ def build_parser():
     p.add_argument('--execTime', action='store_true', help='print per-kernel HIP-event times')
     p.add_argument('--decimate_max', action='store_true', help='MaxPooling1D (pool 2) on the LTF input before Flatten (DNN.py:30,198-200)')
     p.add_argument('--decimate_avg', action='store_true', help='AveragePooling1D (pool 2) on the LTF input before Flatten (DNN.py:31,201-203)')
+    p.add_argument('--hybridWeights', default=0, type=int, metavar='R',
+                   help='--test: also compute the hybrid beamforming weights of the DNN estimate (omphybweights of BER_test_maMIMO_LTF.m:347-376) '
+                        'against a dictionary of R random rays and write hybrid_weights_<n>.mat per packet')
+    p.add_argument('--numSTS', default=1, type=int, help='--hybridWeights: streams = RF chains (the reference calls omphybweights(h, numSTS, numSTS, At))')
     p.add_argument('--dtype', default='f32', choices=['f32', 'bf16'])
     p.add_argument('--device', default=0, type=int)
     return p
@@ -218,6 +222,24 @@ def train_main(args):
     return 0
 
 
+def export_hybrid_weights(args, eng, h_dnn, h_ls):
+    """--hybridWeights R: the step the reference's evaluation runs on every estimate (BER_test_maMIMO_LTF.m:347-376): a dictionary of R
+    random rays (azimuth +-180, elevation +-90 degrees, :364) on a half-wavelength linear array, weights of the DNN estimate with
+    numSTS streams and RF chains, gain on the LS estimate.  Writes hybrid_dictionary.mat (At, az, el) once and hybrid_weights_<n>.mat
+    per packet (fbb [234][numSTS][numSTS], idx [234][numSTS] zero-based columns of At, n_atoms, gain, mFrf = frf_mean)."""
+    from scipy.io import savemat
+    from . import synth
+    az, el = synth.random_rays(np.random.default_rng(args.seed), args.hybridWeights)
+    At = synth.steering_ula(eng.nt, az, el).astype(np.complex64)
+    eng.set_dictionary(At)
+    w = eng.hybrid_weights(h_dnn, ns=args.numSTS, ntrf=args.numSTS, h_eval=h_ls)
+    savemat(os.path.join(args.workdir, 'hybrid_dictionary.mat'), {'At': At, 'az': az, 'el': el})
+    for n in range(w.fbb.shape[0]):
+        savemat(os.path.join(args.workdir, 'hybrid_weights_%d.mat' % (n + 1)),
+                {'fbb': w.fbb[n], 'idx': w.idx[n], 'n_atoms': w.n_atoms[n], 'gain': w.gain[n], 'mFrf': w.frf_mean[n]})
+    return w.fbb.shape[0]
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.model not in ('FC', 'CONV1D') or args.datasource != 'matlab_maMimo':
@@ -284,6 +306,9 @@ def main(argv=None):
     num = np.linalg.norm((h_ls - lab).reshape(npkt, -1), axis=1)
     print('LS(GPU) vs stored LS labels: max packet rel. error %.3e' % float(np.max(num / np.linalg.norm(lab.reshape(npkt, -1), axis=1))))
     files = ds.export_predictions(args.workdir, packed, out_re, out_im)
+    if args.hybridWeights > 0:
+        n_hyb = export_hybrid_weights(args, eng, out_re + 1j * out_im, h_ls)
+        print('hybrid weights: %d rays, numSTS %d; wrote %d hybrid_weights_<n>.mat files and hybrid_dictionary.mat' % (args.hybridWeights, args.numSTS, n_hyb))
     for d in ('real', 'imag'):
         # DNN.py:411 CSI_predictor.save(<workdir>/<d>_keras_model): the folder inference.CSIPredictor loads
         models[d].save(os.path.join(args.workdir, d + '_keras_model'), pilot=packed['pilot'])

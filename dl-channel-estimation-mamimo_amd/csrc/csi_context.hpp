@@ -19,6 +19,7 @@
 #include "l0_hs_stream.hip.h"
 #include "ls_estimate.hip.h"
 #include "lmmse.hip.h"
+#include "hybrid_weights.hip.h"
 #include "metrics.hip.h"
 #include "input_pool.hip.h"
 #include "conv_frontend.hip.h"
@@ -46,12 +47,17 @@ enum KernelId {
     K_PAIR_DENSE_TAIL,   // the last, partly filled round of band workgroups launched in column splits ("band_tail_split", round 6)
     K_INPUT_POOL,        // MaxPooling1D / AveragePooling1D of the preambles of a decimated-input model (csi_set_input_pool)
     K_CONV_FRONTEND,     // Conv1D + BN + AveragePooling1D front end of a CONV1D model (csi_set_model_type, conv_frontend.hip.h)
+    K_HYB_SVD,           // hybrid weights: dominant right singular vectors per (packet, subcarrier) (hybrid_weights.hip.h)
+    K_HYB_CORR,          // hybrid weights: dictionary correlation + argmax of one matching-pursuit step (fp32 MFMA)
+    K_HYB_SOLVE,         // hybrid weights: Cholesky row, coefficients and residual of one matching-pursuit step
+    K_HYB_FINISH,        // hybrid weights: gain and per-packet mean of the analog part
     K_COUNT
 };
 const char* const kKernelNames[K_COUNT] = {
     "layer0_ltf_gemm", "splitk_reduce", "pair_dense_gemm", "dense_hidden_gemm", "regressor_gemm",
     "ls_estimate", "naive_dense0_gemm", "synth_white", "pilot_table", "cast_bf16", "pair_h1_bf16", "lmmse_levinson",
-    "train_gemm", "train_elementwise", "nmse_links", "pair_dense_tail", "input_pool", "conv_frontend"};
+    "train_gemm", "train_elementwise", "nmse_links", "pair_dense_tail", "input_pool", "conv_frontend",
+    "hybrid_svd", "hybrid_corr_argmax", "hybrid_solve", "hybrid_finish"};
 
 thread_local std::string g_create_error;
 
@@ -172,6 +178,17 @@ struct csi_ctx {
     float* small_ls_h_re = nullptr;   // set by csi_estimate_device around its predict call, consumed by predict_small
     float* small_ls_h_im = nullptr;
     int64_t small_ls_launches = 0;
+    // hybrid beamforming weights (csi_hybrid.hpp): the dictionary [nt][hyb_rp] (rays padded to 32 with zero columns) and the per-item workspace
+    float* hyb_at_re = nullptr;
+    float* hyb_at_im = nullptr;
+    int hyb_rays = 0, hyb_rp = 0;
+    char* hyb_ws = nullptr;
+    size_t hyb_ws_bytes = 0;
+    bool user_capture = false;   // between csi_capture_begin and csi_capture_end (csi_hybrid.hpp): device-pointer calls are recorded, not run
+    bool user_capture_use_graph = false;
+    int64_t user_capture_hs0 = 0;
+    uint64_t graph_epoch = 0;    // bumped by drop_graphs: graphs a caller captured before are stale
+    int64_t hybrid_launches = 0; // "hybrid_launches": kernels launched by csi_hybrid_weights[_device]
     int64_t conv_launches = 0;   // "conv_launches": CONV1D front-end passes launched (conv_frontend.hip.h)
     int debug_ls_lds_pad = 0;        // CSI_DEBUG_HOOKS=1 CSI_LS_LDS_PAD=<bytes>: the Walsh-Hadamard LS kernel asks for that much more LDS than it uses
     int debug_bf16_fork_late = 0;    // CSI_DEBUG_HOOKS=1 CSI_BF16_FORK_LATE=1: bf16 contexts fork the second stream of a two-stream call behind the LS kernel (A/B runs)
@@ -449,6 +466,7 @@ void drop_graphs(csi_ctx* c) {
     for (auto& g : c->graphs)
         if (g.exec) hipGraphExecDestroy(g.exec);
     c->graphs.clear();
+    ++c->graph_epoch;
 }
 
 // the CU-masked side stream of "ls_overlap_cus"

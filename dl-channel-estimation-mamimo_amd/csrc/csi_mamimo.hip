@@ -18,6 +18,7 @@
 #include "csi_train.hpp"
 #include "csi_hostpipe.hpp"
 #include "csi_comm.hpp"
+#include "csi_hybrid.hpp"
 
 namespace {
 
@@ -577,6 +578,8 @@ void csi_destroy(csi_ctx* c) {
     comm_free(c);
     if (c->band_mod) hipModuleUnload(c->band_mod);
     if (c->P) hipFree(c->P);
+    if (c->hyb_at_re) hipFree(c->hyb_at_re);
+    if (c->hyb_ws) hipFree(c->hyb_ws);
     if (c->hs_peak) hipFree(c->hs_peak);
     if (c->hs_zero) hipFree(c->hs_zero);
     if (c->fuse_ws) hipFree(c->fuse_ws);
@@ -1105,7 +1108,7 @@ int csi_estimate_device(csi_ctx* c, const float* d_ltf_re, const float* d_ltf_im
     auto run = [&]() -> int {
         const bool g = c->use_graph;
         c->use_graph = false;                      // the two calls below are the graph's content, not graphs of their own
-        c->in_graph_call = g;
+        c->in_graph_call = g || c->user_capture;
         int r = CSI_OK;
         if (c->ls_overlap_cus > 0) {
             // LS beside the per-pair kernels: parked here, fired by the DNN path behind its first layer-0 kernel on a CU-masked side
@@ -1152,7 +1155,7 @@ int csi_estimate_device(csi_ctx* c, const float* d_ltf_re, const float* d_ltf_im
             c->aux_preforked = false;
         }
         c->use_graph = g;
-        c->in_graph_call = false;
+        c->in_graph_call = c->user_capture;
         return r;
     };
     return graph_or_run(c, GraphEntry{d_ltf_re, d_ltf_im, d_out_re, d_out_im, d_h_re, d_h_im, npkt, 0, nullptr}, run);
@@ -1259,6 +1262,41 @@ int csi_lmmse_estimate(csi_ctx* c, const float* h_re, const float* h_im, int64_t
     return CSI_OK;
 }
 
+// ---------------------------------------------------------------- hybrid beamforming weights (csi_hybrid.hpp, hybrid_weights.hip.h)
+int csi_hybrid_set_dictionary(csi_ctx* c, const float* at_re, const float* at_im, int n_rays) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return hybrid_set_dictionary(c, at_re, at_im, n_rays);
+}
+
+int csi_hybrid_weights_device(csi_ctx* c, const float* d_h_re, const float* d_h_im, const float* d_eval_re, const float* d_eval_im, int64_t npkt,
+                              int ns, int ntrf, float stop_tol, float* d_fbb_re, float* d_fbb_im, int32_t* d_idx, int32_t* d_n_atoms,
+                              float* d_gain, float* d_frf_mean_re, float* d_frf_mean_im) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return hybrid_weights_device(c, d_h_re, d_h_im, d_eval_re, d_eval_im, npkt, ns, ntrf, stop_tol, d_fbb_re, d_fbb_im, d_idx, d_n_atoms, d_gain,
+                                 d_frf_mean_re, d_frf_mean_im);
+}
+
+int csi_hybrid_weights(csi_ctx* c, const float* h_re, const float* h_im, const float* eval_re, const float* eval_im, int64_t npkt, int ns, int ntrf,
+                       float stop_tol, float* fbb_re, float* fbb_im, int32_t* idx, int32_t* n_atoms, float* gain, float* frf_mean_re,
+                       float* frf_mean_im) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return hybrid_weights_host(c, h_re, h_im, eval_re, eval_im, npkt, ns, ntrf, stop_tol, fbb_re, fbb_im, idx, n_atoms, gain, frf_mean_re, frf_mean_im);
+}
+
+int csi_capture_begin(csi_ctx* c) { return c ? capture_begin(c) : CSI_ERR_INVALID_ARG; }
+
+int csi_capture_end(csi_ctx* c, void** graph) { return c ? capture_end(c, graph) : CSI_ERR_INVALID_ARG; }
+
+int csi_capture_launch(csi_ctx* c, void* graph) { return c ? capture_launch(c, graph) : CSI_ERR_INVALID_ARG; }
+
+void csi_capture_free(csi_ctx* c, void* graph) {
+    csi_user_graph* g = static_cast<csi_user_graph*>(graph);
+    if (!g) return;
+    if (c) { hipSetDevice(c->cfg.device); hipStreamSynchronize(c->stream); }
+    if (g->exec) hipGraphExecDestroy(g->exec);
+    delete g;
+}
+
 // ---------------------------------------------------------------- accuracy metric
 int csi_nmse_device(csi_ctx* c, const float* d_ref_re, const float* d_ref_im, const float* d_est_re, const float* d_est_im,
                     int64_t nlinks, int n_bins, float* d_per_link, double* mean_out) {
@@ -1331,6 +1369,7 @@ int csi_get_option(csi_ctx* c, const char* name, int64_t* value) {
     else if (n == "input_pool") *value = c->input_pool;
     else if (n == "model_type") *value = c->model_type;
     else if (n == "conv_launches") *value = c->conv_launches;
+    else if (n == "hybrid_launches") *value = c->hybrid_launches;
     else if (n == "small_rows") *value = c->small_rows;
     else if (n == "small_rows_band") *value = c->small_rows_band;
     else if (n == "f32_engine") *value = c->f32_engine;

@@ -1,5 +1,6 @@
 """CsiEngine: one HIP context (one GPU, one stream) holding the two regressors (real, imag),
 the pilot matrix and the activation workspace.  Thin object wrapper over the C-ABI."""
+import collections
 import ctypes
 import weakref
 
@@ -56,6 +57,38 @@ class DeviceArray:
         if self.ptr and self.engine._ctx:
             self.engine._lib.csi_device_free(self.engine._ctx, self.ptr)
         self.ptr = 0
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+HybridWeights = collections.namedtuple('HybridWeights', 'fbb idx n_atoms gain frf_mean')
+
+
+def frf_from_idx(At, idx):
+    """The analog part of hybrid weights: frf[..., m, :] = At[:, idx[..., m]] ([...][ntrf][Nt], the reference's orientation);
+    rows of slots an early stop left empty (index -1) are zero."""
+    At = np.asarray(At)
+    idx = np.asarray(idx)
+    return np.where(idx[..., None] >= 0, At.T[np.maximum(idx, 0)], 0).astype(At.dtype)
+
+
+class CapturedGraph:
+    """Several device-pointer calls of one engine as one hipGraph (CsiEngine.capture_begin / capture_end)."""
+
+    def __init__(self, engine, handle):
+        self.engine, self.handle = engine, handle
+
+    def launch(self):
+        self.engine._check(self.engine._lib.csi_capture_launch(self.engine._ctx, self.handle))
+
+    def free(self):
+        if self.handle and self.engine._ctx:
+            self.engine._lib.csi_capture_free(self.engine._ctx, self.handle)
+        self.handle = None
 
     def __del__(self):
         try:
@@ -536,6 +569,67 @@ class CsiEngine:
         self._check(self._lib.csi_lmmse_estimate(self._ctx, _fp(re), _fp(im), npkt, _fp(hvec), hvec.shape[1], _fp(snr_db),
                                                  _fp(o_re), _fp(o_im)))
         return o_re + 1j * o_im
+
+    # ------------------------------------------------------------------ hybrid beamforming weights
+    def set_dictionary(self, At):
+        """Dictionary of array responses for hybrid_weights: complex [Nt][rays] (for instance synth.steering_ula), kept on the
+        device; columns are used as given.  A second call replaces it."""
+        At = np.asarray(At)
+        if At.ndim != 2 or At.shape[0] != self.nt:
+            raise CsiError(-1, f'dictionary must be [Nt={self.nt}][rays], got {At.shape}')
+        re, im = _f32c(At.real), _f32c(At.imag)
+        self._check(self._lib.csi_hybrid_set_dictionary(self._ctx, _fp(re), _fp(im), At.shape[1]))
+        self.dictionary = (re + 1j * im).astype(np.complex64)
+
+    def hybrid_weights(self, h, ns=1, ntrf=None, h_eval=None, stop_tol=0.0):
+        """Hybrid beamforming weights (SVD + orthogonal matching pursuit, omphybweights of the reference's
+        BER_test_maMIMO_LTF.m:347-376) of a CSI tensor h complex [npkt,nr,nt,234] against the dictionary of set_dictionary.
+        Returns HybridWeights(fbb complex64 [npkt,234,ns,ntrf], idx int32 [npkt,234,ntrf], n_atoms int32 [npkt,234],
+        gain float32 [npkt,234], frf_mean complex64 [npkt,ntrf,nt]); the analog part is frf_from_idx(At, idx).  gain is
+        |h_eval frf^T fbb^T|_F^2 per subcarrier (h_eval defaults to h); ntrf defaults to ns; stop_tol <= 0 selects 1e-5."""
+        ntrf = int(ns if ntrf is None else ntrf)
+        h = np.asarray(h)
+        re, im = _f32c(h.real), _f32c(h.imag)
+        npkt = re.shape[0] if re.ndim else 0
+        if re.shape != (npkt, self.nr, self.nt, N_DATA):
+            raise CsiError(-1, f'h must be [npkt,{self.nr},{self.nt},{N_DATA}], got {re.shape}')
+        e_re = e_im = None
+        if h_eval is not None:
+            h_eval = np.asarray(h_eval)
+            if h_eval.shape != h.shape:
+                raise CsiError(-1, f'h_eval must have the shape of h {h.shape}, got {h_eval.shape}')
+            e_re, e_im = _f32c(h_eval.real), _f32c(h_eval.imag)
+        shape = (npkt, N_DATA, max(int(ns), 0), max(ntrf, 0))
+        f_re, f_im = np.zeros(shape, np.float32), np.zeros(shape, np.float32)
+        idx = np.full((npkt, N_DATA, max(ntrf, 0)), -1, np.int32)
+        n_atoms = np.zeros((npkt, N_DATA), np.int32)
+        gain = np.zeros((npkt, N_DATA), np.float32)
+        m_re, m_im = np.zeros((npkt, max(ntrf, 0), self.nt), np.float32), np.zeros((npkt, max(ntrf, 0), self.nt), np.float32)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        self._check(self._lib.csi_hybrid_weights(self._ctx, ptr(re), ptr(im), ptr(e_re), ptr(e_im), npkt, int(ns), ntrf, float(stop_tol),
+                                                 ptr(f_re), ptr(f_im), ptr(idx), ptr(n_atoms), ptr(gain), ptr(m_re), ptr(m_im)))
+        return HybridWeights((f_re + 1j * f_im).astype(np.complex64), idx, n_atoms, gain, (m_re + 1j * m_im).astype(np.complex64))
+
+    def hybrid_weights_device(self, d_h_re, d_h_im, npkt, ns, ntrf, d_fbb_re, d_fbb_im, d_idx, d_n_atoms=None, d_gain=None,
+                              d_frf_mean_re=None, d_frf_mean_im=None, d_eval_re=None, d_eval_im=None, stop_tol=0.0):
+        """Asynchronous, on the engine's stream, over DeviceArrays: the CSI planes predict_device / ls_estimate_device /
+        estimate_device wrote, unchanged.  d_idx [npkt,234,ntrf] and d_n_atoms [npkt,234] hold int32 in DeviceArrays of the
+        same element size: read them with ``download().view(np.int32)``.  The optional arrays may be None."""
+        ptr = lambda a: None if a is None else a.ptr
+        self._check(self._lib.csi_hybrid_weights_device(self._ctx, d_h_re.ptr, d_h_im.ptr, ptr(d_eval_re), ptr(d_eval_im), int(npkt), int(ns), int(ntrf),
+                                                        float(stop_tol), d_fbb_re.ptr, d_fbb_im.ptr, d_idx.ptr, ptr(d_n_atoms), ptr(d_gain),
+                                                        ptr(d_frf_mean_re), ptr(d_frf_mean_im)))
+
+    def capture_begin(self):
+        """Record the device-pointer calls that follow (estimate_device, hybrid_weights_device, ...) into one hipGraph instead of
+        running them.  Run the same calls once eagerly first, so that every buffer has its size.  Always close with capture_end."""
+        self._check(self._lib.csi_capture_begin(self._ctx))
+
+    def capture_end(self):
+        """Close the capture; returns a CapturedGraph whose launch() replays the recorded calls on the engine's stream."""
+        g = ctypes.c_void_p()
+        self._check(self._lib.csi_capture_end(self._ctx, ctypes.byref(g)))
+        return CapturedGraph(self, g.value)
 
     def predict_samples(self, model, x):
         """Literal Model.predict of one component: x [B, len_ltf+nt] -> float32 [B, n_out]."""

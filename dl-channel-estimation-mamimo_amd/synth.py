@@ -137,3 +137,24 @@ def mixed_snr_batch(seed, nr, P, per_level=500, levels=SNR_LEVELS_DB, block=250,
                 yield j[0], j[2], f.result()
         for j, f in pending:
             yield j[0], j[2], f.result()
+
+
+def steering_ula(nt, az_deg, el_deg=0.0, spacing=0.5):
+    """Array responses of a uniform linear array of nt elements along the y axis, spacing in wavelengths:
+    a_n = exp(2 pi i y_n cos(el) sin(az)), y_n = (n - (nt - 1) / 2) * spacing.  az_deg / el_deg broadcast against each
+    other; returns complex128 [nt][rays], the dictionary layout of CsiEngine.set_dictionary.  The sign and the axis
+    convention of the toolbox's steervec (which the reference calls) cannot be pinned without MATLAB and may differ
+    from this one by a conjugation or a mirror of the azimuth; nothing in the library depends on it, since the
+    dictionary is an input."""
+    az, el = np.broadcast_arrays(np.deg2rad(np.asarray(az_deg, np.float64)), np.deg2rad(np.asarray(el_deg, np.float64)))
+    y = (np.arange(nt, dtype=np.float64) - (nt - 1) / 2.0) * spacing
+    u = (np.cos(el) * np.sin(az)).reshape(-1)
+    return np.exp(2j * np.pi * y[:, None] * u[None, :])
+
+
+def random_rays(rng, n):
+    """n ray directions as BER_test_maMIMO_LTF.m:364 draws them: azimuth uniform in +-180 degrees, elevation uniform
+    in +-90 degrees.  Returns (az_deg [n], el_deg [n])."""
+    az = rng.uniform(-180.0, 180.0, n)
+    el = rng.uniform(-90.0, 90.0, n)
+    return az, el

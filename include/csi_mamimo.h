@@ -21,6 +21,7 @@
  *                                                                   csi_ls_estimate[_device]
  *   LMMSE_ce per link   helperMIMOChannelEstimate.m:37-39, LMMSE_ce.m  csi_lmmse_estimate[_device]
  *   NMSE_subk           BER_test_maMIMO_LTF.m:675-686                csi_nmse[_device]
+ *   omphybweights       BER_test_maMIMO_LTF.m:347-376                csi_hybrid_weights[_device]
  *   --execTime profiler loop                       DNN.py:441-475   csi_profile_*
  *   Model.fit step (noise, BN, dropout, Adam)       DNN.py:272-316   csi_train_*
  *
@@ -199,6 +200,43 @@ int  csi_lmmse_estimate(csi_ctx* ctx, const float* h_re, const float* h_im, int6
                         const float* snr_db, float* out_re, float* out_im);
 int  csi_lmmse_estimate_device(csi_ctx* ctx, const float* d_h_re, const float* d_h_im, int64_t npkt, const float* d_hvec,
                                int L, const float* d_snr_db, float* d_out_re, float* d_out_im);
+
+/* Hybrid beamforming weights from a CSI tensor (BER_test_maMIMO_LTF.m:347-376, generate_maMIMO_LTF.m:414-425: the toolbox's
+ * SVD + orthogonal-matching-pursuit split of the optimal precoder into an analog and a digital part).  One item = one
+ * (packet p, subcarrier k) with H[i][j] = csi[p][i][j][k] (Nr x Nt):
+ *   Fopt = right singular vectors of H for its ns largest singular values;
+ *   for m = 1 .. ntrf, Res = Fopt at the start: k_m = argmax_k sum_s |At[:,k]^H Res[:,s]|^2 (lowest k on a tie),
+ *     C = (A^H A)^-1 A^H Fopt over the chosen columns A, T = Fopt - A C, e = |T|_F, Res = T / e; stop when e <= stop_tol;
+ *   Fbb = sqrt(ns) C / |A C|_F.
+ * Outputs in the reference's orientation: fbb [npkt][234][ns][ntrf] (re / im planes), idx int32 [npkt][234][ntrf] (the analog part
+ * is frf[m][:] = At[:, idx[m]] and is not written out), n_atoms int32 [npkt][234], gain [npkt][234] = |H_eval frf^T fbb^T|_F^2
+ * with H_eval = the eval planes (same shape as h) or h itself when they are NULL, frf_mean [npkt][ntrf][Nt] = mean of frf over a
+ * packet's subcarriers.  Slots behind an early stop hold index -1 and zero coefficients (and add nothing to frf_mean).
+ * stop_tol <= 0 selects 1e-5.  eval, n_atoms, gain and frf_mean may be NULL.
+ * csi_hybrid_set_dictionary: host planes [Nt][n_rays], n_rays <= 4096, kept on the context; columns are used as given (no
+ * normalisation); a second call replaces the dictionary.
+ * csi_hybrid_weights_device: asynchronous on the context's stream, inputs are the planes csi_predict_device /
+ * csi_ls_estimate_device / csi_lmmse_estimate_device write; large calls run in packet chunks against the context's
+ * workspace_bytes (default 1 GiB for this stage).  Refused with text: no dictionary, Nr > Nt, Nr > 16, ns outside
+ * 1 .. min(Nr, ntrf), ntrf outside 1 .. min(Nt, n_rays, 16), bf16 contexts, null required pointers.
+ * "hybrid_launches" (csi_get_option) counts the kernels launched. */
+int  csi_hybrid_set_dictionary(csi_ctx* ctx, const float* at_re, const float* at_im, int n_rays);
+int  csi_hybrid_weights_device(csi_ctx* ctx, const float* d_h_re, const float* d_h_im, const float* d_eval_re, const float* d_eval_im,
+                               int64_t npkt, int ns, int ntrf, float stop_tol, float* d_fbb_re, float* d_fbb_im, int32_t* d_idx,
+                               int32_t* d_n_atoms, float* d_gain, float* d_frf_mean_re, float* d_frf_mean_im);
+int  csi_hybrid_weights(csi_ctx* ctx, const float* h_re, const float* h_im, const float* eval_re, const float* eval_im, int64_t npkt,
+                        int ns, int ntrf, float stop_tol, float* fbb_re, float* fbb_im, int32_t* idx, int32_t* n_atoms, float* gain,
+                        float* frf_mean_re, float* frf_mean_im);
+
+/* Several device-pointer calls as ONE hipGraph (for instance csi_estimate_device followed by csi_hybrid_weights_device):
+ * between csi_capture_begin and csi_capture_end the device-pointer calls on this context are recorded on its stream instead of
+ * run.  Run the same calls once eagerly first: a call that has to grow a buffer fails inside a capture.  csi_capture_end hands back
+ * the graph (also after a failed call: the capture must be closed); csi_capture_launch replays it on the context's stream and
+ * refuses a graph that a later reallocation, weight / pilot / dictionary load or option change made stale. */
+int  csi_capture_begin(csi_ctx* ctx);
+int  csi_capture_end(csi_ctx* ctx, void** graph);
+int  csi_capture_launch(csi_ctx* ctx, void* graph);
+void csi_capture_free(csi_ctx* ctx, void* graph);
 
 /* Accuracy metric of the reference's evaluation, NMSE_subk (BER_test_maMIMO_LTF.m:675-686): per link
  * ||ref - est||^2 / ||ref||^2 over the n_bins bins, mean over the nlinks links ([link][n_bins] planes, e.g.
