@@ -142,6 +142,7 @@ struct csi_ctx {
     std::string err;
     Model model[2];
     csi_trainer* trainer[2] = {nullptr, nullptr};   // on-box fine-tuning state per component model
+    int train_rank = 0;                             // "train_rank": rank of this process in a data-parallel fit; keys the trainers' noise / dropout streams (csi_train.hpp tr_stream)
     csi_hostpipe* hostpipe = nullptr;               // streams / pinned slots / host threads of the host-buffer entry points
     csi_comm* comm = nullptr;                       // RCCL communicator of csi_comm_init (weight broadcast)
     int host_threads = 0;                           // "host_threads" option: threads of the user <-> pinned copies (0 = automatic)

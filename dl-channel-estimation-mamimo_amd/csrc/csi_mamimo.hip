@@ -1412,6 +1412,7 @@ int csi_get_option(csi_ctx* c, const char* name, int64_t* value) {
     else if (n == "hp_weave_us") *value = c->hostpipe ? c->hostpipe->us_weave : 0;
     else if (n == "hp_total_us") *value = c->hostpipe ? c->hostpipe->us_total : 0;
     else if (n == "hp_chunk_packets") *value = c->hp_chunk_packets;
+    else if (n == "train_rank") *value = c->train_rank;
     else if (n == "hp_side_threads") *value = c->hp_side_threads;
     else if (n == "hp_device_weave") *value = c->hp_device_weave;
     else if (n == "hp_direct_out_calls") *value = c->hp_direct_out_calls;
@@ -1565,6 +1566,9 @@ int csi_set_option(csi_ctx* c, const char* name, int64_t value) {
     } else if (n == "hp_chunk_packets") {
         if (value < 0 || value > (1 << 20)) return fail(c, CSI_ERR_INVALID_ARG, "hp_chunk_packets must be 0 (automatic) .. 2^20");
         c->hp_chunk_packets = (int)value;
+    } else if (n == "train_rank") {
+        if (value < 0 || value >= (1 << 20)) return fail(c, CSI_ERR_INVALID_ARG, "train_rank must be 0 .. 2^20 - 1");
+        c->train_rank = (int)value;
     } else if (n == "ls_fast_perm") {
         c->ls_fast_perm = value != 0;
         drop_graphs(c);

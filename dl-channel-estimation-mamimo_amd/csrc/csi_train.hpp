@@ -81,8 +81,16 @@ int tr_transpose(csi_ctx* c, const float* src, float* dst, int R, int C, int lds
     return CSI_OK;
 }
 
-uint64_t tr_stream(const csi_trainer* t, int tag) {
-    uint64_t x = t->tc.seed + 0x9E3779B97F4A7C15ull * (uint64_t)(t->step * 64 + tag + 1);
+// Key of one random stream: (seed, step, tag) -> 64 bits; the kernels hash it with the element index (tr_uniform / tr_normal).
+// Tags: hidden layer li = its dropout mask, 40 + li = the Glorot kernel of layer li (step 0), 60 = the input noise.
+// The rank of a data-parallel fit ("train_rank" option) enters the noise and dropout streams only: every rank then draws its own
+// noise and masks for its shard - as GaussianNoise / Dropout draw every element of the global batch independently - while the
+// initialisation stream stays the same on all ranks (they must start from identical weights).  Rank 0 adds nothing, so a
+// single process has the streams it always had.
+constexpr int TR_TAG_GLOROT = 40, TR_TAG_NOISE = 60;
+uint64_t tr_stream(const csi_ctx* c, const csi_trainer* t, int tag) {
+    const uint64_t rank = tag >= TR_TAG_GLOROT && tag < TR_TAG_NOISE ? 0 : (uint64_t)c->train_rank;
+    uint64_t x = t->tc.seed + 0x9E3779B97F4A7C15ull * (uint64_t)(t->step * 64 + tag + 1) + 0xD6E8FEB86659FD93ull * rank;
     x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
     x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
     return x ^ (x >> 31);
@@ -147,7 +155,7 @@ int tr_forward(csi_ctx* c, csi_trainer* t, int B, bool training) {
             const float p = li < nh - 1 ? t->tc.dropout : 0.f;
             ProfScope ps(c, K_TRAIN_ELEMWISE, 8.0 * B * l.out, 12.0 * B * l.out);
             hipLaunchKernelGGL(bn_dropout_forward_kernel, dim3((l.out + TRC - 1) / TRC), dim3(TRC, TRC), 0, c->stream, l.a, l.h, B, l.out, l.ldo,
-                               cf.use_bn, l.gamma, l.beta, l.mmean, l.mvar, l.mu, l.istd, cf.bn_eps, t->tc.bn_momentum, p, tr_stream(t, li));
+                               cf.use_bn, l.gamma, l.beta, l.mmean, l.mvar, l.mu, l.istd, cf.bn_eps, t->tc.bn_momentum, p, tr_stream(c, t, li));
             HIP_TRY(c, hipGetLastError());
         } else {
             if (cf.use_bn) {
@@ -265,7 +273,7 @@ int tr_backward(csi_ctx* c, csi_trainer* t, const float* x, const float* y, cons
     const csi_config& cf = c->cfg;
     const int nh = cf.n_hidden;
     t->step += 1;
-    int rc = tr_stage(c, t, x, y, ids, B, noise_std, tr_stream(t, 60));
+    int rc = tr_stage(c, t, x, y, ids, B, noise_std, tr_stream(c, t, 60));
     if (rc) return rc;
     rc = tr_forward(c, t, B, true);
     if (rc) return rc;
@@ -291,7 +299,7 @@ int tr_backward(csi_ctx* c, csi_trainer* t, const float* x, const float* y, cons
         {
             ProfScope ps(c, K_TRAIN_ELEMWISE, 12.0 * B * l.out, 20.0 * B * l.out);
             hipLaunchKernelGGL(bn_dropout_backward_kernel, dim3((l.out + TRC - 1) / TRC), dim3(TRC, TRC), 0, c->stream, t->dh[cur], l.a, t->dz, t->dzt, B,
-                               l.out, l.ldo, t->ldb, cf.use_bn, l.gamma, l.mu, l.istd, l.ggamma, l.gbeta, l.gb, p, tr_stream(t, li));
+                               l.out, l.ldo, t->ldb, cf.use_bn, l.gamma, l.mu, l.istd, l.ggamma, l.gbeta, l.gb, p, tr_stream(c, t, li));
             HIP_TRY(c, hipGetLastError());
         }
         const float* in_t = li == 0 ? t->xt : t->layers[li - 1].ht;
@@ -525,7 +533,7 @@ int tr_begin(csi_ctx* c, int model, const csi_train_config* tc, const csi_tensor
             hipFree(stage);
             if (rc) return fail(c, rc, "csi_train_begin: upload of %s failed", base.c_str());
         } else {
-            hipLaunchKernelGGL(glorot_kernel, dim3(1024), dim3(256), 0, c->stream, l.Wt, l.out, l.in, l.ldw, tr_stream(t, 40 + li));
+            hipLaunchKernelGGL(glorot_kernel, dim3(1024), dim3(256), 0, c->stream, l.Wt, l.out, l.in, l.ldw, tr_stream(c, t, 40 + li));
             HIP_TRY(c, hipGetLastError());
         }
         if (li < nh && cf.use_bn) {

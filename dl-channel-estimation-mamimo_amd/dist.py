@@ -168,6 +168,11 @@ def world_size():
     return dist.get_world_size() if dist.is_initialized() else 1
 
 
+def rank():
+    import torch.distributed as dist
+    return dist.get_rank() if dist.is_initialized() else 0
+
+
 def barrier():
     import torch.distributed as dist
     if dist.is_initialized() and dist.get_world_size() > 1:

@@ -69,13 +69,18 @@ def fit(engine, model, train_gen, val_gen, epochs=500, lr=1e-4, dropout=0.15, we
     data_parallel (torch.distributed initialised, one process per GPU, every rank calling fit with its
     own shard of batches and the same seed / initial weights): each step is backward -> one flat
     gradient all-reduce (RCCL) -> Adam, so all ranks hold identical parameters; the validation loss is
-    averaged over the ranks; BatchNormalization running statistics are averaged at the end.
+    averaged over the ranks; BatchNormalization running statistics are averaged at the end.  The engine's
+    'train_rank' option is set from the process group: the noise and dropout streams are keyed by
+    (seed, step, rank), so the rows of the global batch draw independent noise and masks, while the Glorot
+    initialisation depends on the seed alone and is the same on every rank.
 
     resident = the dataset dict (dataset.load_dataset): the training set is uploaded once
     (csi_train_set_dataset, engine.set_pilot must have been called) and every step sends only the batch's
     sample indices (``gen.batch_ids(b)``, dataset.SampleGenerator) - no per-step batch assembly or upload."""
     rng = np.random.default_rng(seed)
     min_lr = lr * 0.01 if min_lr is None else min_lr
+    if data_parallel:
+        engine.set_option('train_rank', dist.rank())      # own noise / dropout streams per rank, same initialisation stream
     engine.train_begin(model, weights=weights, lr=lr, dropout=dropout, seed=seed)
     if resident is not None:
         from . import dataset as _ds

@@ -411,6 +411,9 @@ int  csi_synchronize(csi_ctx* ctx);
  *                         caller's enqueue loop; 0: inline on the calling thread, in turn (A/B runs)
  *   "hp_chunk_packets" packets per pipeline slot of csi_estimate_c128 (0 = automatic)
  *   "hp_device_weave"  1 (default): csi_estimate_c128 with pinned result arrays assembles the complex64 values on the device
+ *   "train_rank"       0 (default) .. 2^20 - 1: rank of this process in a data-parallel fit.  The trainers fold it into the noise and
+ *                         dropout streams (not into the Glorot initialisation), so every rank draws its own noise and masks for its
+ *                         shard of the global batch; rank 0 has the streams of a single process.  Takes effect at the next step.
  *   "ls_debug"         development switches of the LS kernels (tools/ls_race_*.py); write-only, 0 in production */
 int  csi_set_option(csi_ctx* ctx, const char* name, int64_t value);
 /* Current value of an option, or of the read-only values: "hs_launches" (split-engine GEMMs launched), "hs_range_fallbacks"

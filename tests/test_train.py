@@ -1,8 +1,14 @@
 """On-box fine-tuning: csi_train_* against the oracle's fp64 restatement of the
 keras training step, the python fit loop (EarlyStopping / ReduceLROnPlateau / AWGN schedule), and a
 small end-to-end learning problem.  GPU tests call through the C-ABI."""
+import os
+import sys
+
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import train_streams      # noqa: E402  (host replay of the trainer's random streams)
 
 
 def _problem(oracle, rng, nt, hidden, B, n_out=234, use_bn=True):
@@ -160,7 +166,8 @@ def test_train_trajectory_follows_oracle(pkg, oracle):
 def test_train_noise_and_dropout_statistics(pkg, oracle):
     """AWGN only on the LTF columns with the requested stddev; dropout keeps ~(1-p) of the units and
     the same mask is used forward and backward (gradient of dropped units is exactly zero);
-    steps are reproducible for equal seeds."""
+    steps are reproducible for equal seeds.  Noise and masks are held against the host replay of the counter-based streams
+    (tests/train_streams.py); tests/test_train_streams.py has the full stochastic step against the fp64 oracle."""
     rng = np.random.default_rng(9)
     nt, hidden, B = 4, (96, 64), 256
     w, x, y = _problem(oracle, rng, nt, hidden, B)
@@ -175,13 +182,47 @@ def test_train_noise_and_dropout_statistics(pkg, oracle):
             assert not dead.any()                                   # a unit is dropped per sample, not per batch
         e.train_end('imag', commit=False)
     assert losses[0] == losses[1]
-    # noise: zero weights except a probe that copies inputs is awkward; use the loss instead: with all
-    # pilot-column weights and LTF-column weights known, E[loss] rises with noise_std
+    # the loss moves with the noise ...
     e = pkg.CsiEngine(nt, 2, hidden=hidden)
     e.train_begin('real', weights=w, lr=1e-9, dropout=0.0, seed=3)
     l0 = np.mean([e.train_step('real', x, y, noise_std=0.0) for _ in range(2)])
     l1 = np.mean([e.train_step('real', x, y, noise_std=3.0) for _ in range(2)])
     assert np.isfinite(l0) and np.isfinite(l1) and abs(l1 - l0) > 1e-4 * l0
+    # ... which sits on the LTF columns only and has the requested stddev: what layer 0 read in the last step (step 4 of this
+    # trainer) minus the rows is 3 x the replayed N(0,1) stream (tests/train_streams.py; its distribution is checked on the
+    # host and the device's draws against it element by element in tests/test_train_streams.py)
+    staged = e.train_staged_input('real', B).astype(np.float64)
+    L = 320 * nt
+    np.testing.assert_array_equal(staged[:, L:], x[:, L:])
+    added = staged[:, :L] - x[:, :L]
+    z_ref, radius = train_streams.input_noise(3, 4, B, 321 * nt, L, with_radius=True)
+    z_ref = z_ref[:, :L]
+    # 3 x the bound on the device's normal (16 ulp-units of the radius, derived in test_train_streams._noise_bound) + an ulp each for
+    # the product and the sum
+    tol = (3.0 * 16.0 * 2.0 ** -24 * np.maximum(radius[:, :L], 2.0 ** -10) + np.spacing(np.abs(staged[:, :L]).astype(np.float32))
+           + np.spacing(np.abs(3.0 * z_ref).astype(np.float32)))
+    assert np.all(np.abs(added - 3.0 * z_ref) <= tol)
+    n = added.size
+    assert abs(added.mean() / 3.0) * np.sqrt(n) < 4.0 and abs(np.mean((added / 3.0) ** 2) - 1.0) / np.sqrt(2.0 / n) < 4.0
+    e.train_end('real', commit=False)
+    # dropout, per sample: a batch of two rows without BatchNormalization.  The replayed mask says which units of layer 0 are
+    # dropped in both rows (about a quarter at p = 0.5): exactly those (and units whose relu is off in every row where they
+    # are kept) have an exactly zero row in grad:fc_dense1.kernel (forward mask) AND an exactly zero column in
+    # grad:fc_dense0.kernel / entry in grad:fc_dense0.bias (the backward pass recomputes the same mask)
+    wn = {k: v for k, v in w.items() if not k.startswith('bn') or k == 'bn_eps'}
+    e = pkg.CsiEngine(nt, 2, hidden=hidden, use_bn=False)
+    e.train_begin('real', weights=wn, lr=1e-4, dropout=0.5, seed=77)
+    e.train_step('real', x[:2], y[:2], noise_std=0.0)
+    keep = train_streams.dropout_masks(77, 1, 2, hidden, 0.5)[0]            # [2, 96]
+    assert abs(keep.mean() - 0.5) < 4.0 * np.sqrt(0.25 / keep.size)
+    a0 = x[:2].astype(np.float64) @ wn['fc_dense0.kernel'].astype(np.float64) + wn['fc_dense0.bias']
+    on = keep & (a0 > 1e-3)                                                # kept and relu clearly on
+    off = ~(keep & (a0 > -1e-3))                                           # dropped, or relu clearly off
+    g1, g0, gb0 = (e.train_get('real', 'grad:' + k) for k in ('fc_dense1.kernel', 'fc_dense0.kernel', 'fc_dense0.bias'))
+    dead, alive = off.all(axis=0), on.any(axis=0)
+    assert dead.sum() >= 10 and alive.sum() >= 10 and (~keep).all(axis=0).sum() >= 10
+    assert np.all(g1[dead] == 0.0) and np.all(g0[:, dead] == 0.0) and np.all(gb0[dead] == 0.0)
+    assert np.all(np.any(g1[alive] != 0.0, axis=1)) and np.all(np.any(g0[:, alive] != 0.0, axis=0)) and np.all(gb0[alive] != 0.0)
     e.train_end('real', commit=False)
 
 
