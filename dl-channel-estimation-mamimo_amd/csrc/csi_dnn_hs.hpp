@@ -184,7 +184,19 @@ int hs_launch_layer0(csi_ctx* c, const Model& m, const float* x, int ldx, int M1
         HIP_TRY(c, hipGetLastError());
         return CSI_OK;
     }
-    if (c->hs_vm_cast == 2) return go(gemm_hs_pp_pair_kernel<EPI_RAW, false, true, 0, false, 2>, &c->hs_lds_attr[5]);
+    if (c->hs_vm_cast == 2) {
+        // "hs_l0_mfma" = 16: the 16x16x32 main loop walks PAIRS of sub-tiles - every k range must hold an even number of them
+        bool even = c->hs_l0_mfma == 16 && kps % (2 * HS_G) == 0;
+        if (even) {
+            const int klast = K - (splits - 1) * kps;
+            even = klast > 0 && ((klast + HS_G - 1) / HS_G) % 2 == 0;
+        }
+        if (even) {
+            ++c->hs_l0_mfma16_launches;
+            return go(gemm_hs_pp_pair_kernel<EPI_RAW, false, true, 0, false, 2, 16>, &c->hs_lds_attr[20]);
+        }
+        return go(gemm_hs_pp_pair_kernel<EPI_RAW, false, true, 0, false, 2>, &c->hs_lds_attr[5]);
+    }
     if (c->hs_vm_cast == 1) return go(gemm_hs_pp_pair_kernel<EPI_RAW, false, true, 0, false, 1>, &c->hs_lds_attr[6]);
     return go(gemm_hs_pp_pair_kernel<EPI_RAW, false, true>, &c->hs_lds_attr[0]);
 }

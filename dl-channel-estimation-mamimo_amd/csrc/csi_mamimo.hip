@@ -1422,6 +1422,8 @@ int csi_get_option(csi_ctx* c, const char* name, int64_t* value) {
     else if (n == "ls_pilot_fast") *value = !c->p_fast_ok ? 0 : (c->p_fast_identity ? 1 : 2);     // read-only: 0 generic P, 1 Sylvester Hadamard, 2 a signed permutation of it
     else if (n == "hs_vm_cast") *value = c->hs_vm_cast;
     else if (n == "hs_vm_pair") *value = c->hs_vm_pair;
+    else if (n == "hs_l0_mfma") *value = c->hs_l0_mfma;
+    else if (n == "hs_l0_mfma16_launches") *value = c->hs_l0_mfma16_launches;    // read-only: layer-0 launches of the 16x16x32 form
     else if (n == "graph_replays") *value = c->graph_replays;                // read-only counters
     else if (n == "hs_launches") *value = c->hs_launches;
     else if (n == "hs_range_fallbacks") *value = c->hs_range_fallbacks;
@@ -1546,6 +1548,10 @@ int csi_set_option(csi_ctx* c, const char* name, int64_t value) {
         if (value < 0 || value > 3) return fail(c, CSI_ERR_INVALID_ARG, "%s must be 0 ... 3", name);
         drop_graphs(c);
         (n == "hs_vm_cast" ? c->hs_vm_cast : c->hs_vm_pair) = (int)value;
+    } else if (n == "hs_l0_mfma") {
+        if (value != 32 && value != 16) return fail(c, CSI_ERR_INVALID_ARG, "hs_l0_mfma must be 32 or 16");
+        drop_graphs(c);
+        c->hs_l0_mfma = (int)value;
     } else if (n == "ls_overlap_cus" || n == "ls_overlap_stride") {
         if (value < 0 || value > 255) return fail(c, CSI_ERR_INVALID_ARG, "%s must be 0 (LS in front of the DNN kernels on one stream) .. 255", name);
 #ifndef CSI_LS_RACE_VARIANTS

@@ -662,6 +662,228 @@ __device__ __forceinline__ void hs_fused_regressor(f32x16 (&acc)[4][2], const Ge
 }
 
 // ---------------------------------------------------------------------------------------------
+// Layer 0 (CAST mode) on v_mfma_f32_16x16x32_f16: the same three products per 16 k-columns, the same A conversion, LDS
+// image, B-side LDS-DMA and matrix-pipe cycles per flop as the 32x32x16 form below, at less energy per flop - under load
+// the part holds a higher clock on this shape (tools/mfma_shape_probe.hip, profiles/mfma_shape_probe.txt).
+//   * Sub-tiles are consumed in PAIRS.  An instruction takes 32 k; fragment X = the hi planes of sub-tiles 2p and 2p+1,
+//     Y = their lo planes, each ONE ds_read_b128 per 16-row tile: lane l reads row l & 15, its k-octet q = l >> 4 comes
+//     from ring slot (q & 1), 16-byte chunk q >> 1 of the plane (conflict-free with the image's XOR swizzle; taking
+//     q = 0, 1 from one slot is 2-way conflicted).  Products per tile: X_a Y_b, X_a X_b, Y_a X_b (A and B share the k order).
+//   * Registers (256 per lane at 8 waves): 128 accumulators (8 x 4 tiles of f32x4), X_b / Y_b of the wave's four column
+//     tiles held for the pair (32), the A tiles streamed (X_a, Y_a of two tiles in flight: 16), the 16 fp32 A values of
+//     the next pair but one in flight from HBM (16).
+//   * Ring: four slots = two pairs, pair p in slots 2 (p & 1), + 1.  The groups (waves 0-3 / 4-7) alternate one LOAD
+//     segment L(p) (convert pair p + 1, request the values of pair p + 2) with one 96-MFMA segment M(p), group 1 one
+//     segment behind, a workgroup barrier between segments: tick 2p = L0(p) | M1(p-1), tick 2p+1 = M0(p) | L1(p).
+//     A rows are written and read by the same group (a wave converts 32 rows of its group's 128): written in L(p), first
+//     read by the prefetch that ends M(p), old contents (pair p - 1) last read in M(p - 1).  The B rows of a pair are read
+//     ONCE, by the prefetch that ends M(p - 1) (ticks 2p-1 and 2p), and stay in registers: B(p + 2) may overwrite B(p)
+//     from tick 2p+1 on and must be visible at the barrier that ends tick 2p+2.  Group 0 issues its pieces at the head
+//     of M0(p) and waits for them at the end of L0(p + 1); group 1 issues them at the head of L1(p) and waits at the end
+//     of M1(p).  Every wave's queue then reads (old to young) values(p+1) x4, B(p+2) x4 where it waits for the values, and
+//     B x4, values x4 where it waits for the pieces: vmcnt(4) at both places, in every trip (see the clamped pair
+//     index in front of the prologue).
+__device__ __forceinline__ void hs_cast_mfma16_body(const GemmHsArgs& g, const PairSrc& ps, const float in_scale, float* lds) {
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave >> 2, wn = wave & 3;
+
+    int tm, tn;
+    hs_tile_of_block(g, tm, tn);
+    if (tm * PP_BM >= g.M) return;
+    const int m0 = tm * PP_BM, n0 = tn * PP_BN;
+    const int kbeg = blockIdx.z * g.k_per_split;
+    const int kend = min(g.K, kbeg + g.k_per_split);
+    const int np = (kend - kbeg + HS_G - 1) / HS_G / 2;        // pairs of sub-tiles (the launcher checks that none is left over)
+
+    float a_scale = in_scale, acc_scale = g.acc_scale;           // automatic input scale: as in the 32x32x16 form
+    if (g.dyn_max) {
+        const unsigned bits = __builtin_amdgcn_readfirstlane(*g.dyn_max);
+        const int e = (int)((bits >> 23) & 0xffu) - 126;
+        const int n = bits == 0 ? 0 : max(-100, min(100, 14 - e));
+        a_scale = __builtin_bit_cast(float, (unsigned)(n + 127) << 23);
+        acc_scale = __builtin_bit_cast(float, (unsigned)(max(-126, min(126, -n - g.wshift)) + 127) << 23);
+    }
+
+    // ---- B side: pieces 2w, 2w+1 of the 16 B pieces of a sub-tile
+    const uint16_t* bsrc[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const int row = 16 * (2 * wave + u) + (lane >> 2);
+        const int clog = (lane & 3) ^ ((row >> 2) & 3);
+        bsrc[u] = g.Bt + (size_t)n0 * g.ldb + 2 * kbeg + (size_t)min(row, g.N - 1 - n0) * g.ldb + clog * 8;
+    }
+    const uint32_t lds_off = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) float*)lds);
+    auto issue_bs = [&](int psrc, int pslot) {      // both sub-tiles of pair psrc -> slots 2 (pslot & 1), + 1
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+                pp_gdma16(bsrc[u] + (2 * psrc + t) * 32, lds_off + (uint32_t)((2 * (pslot & 1) + t) * PP_SUBF + (PP_BM / 16 + 2 * wave + u) * 256) * 4u);
+    };
+    // ---- A side: the lane -> (row, k half) map and the bank-conflict-free chunk places of the 32x32x16 form
+    const int ridx = lane >> 1, kh = lane & 1;
+    const int arow = 32 * wave + ((ridx & 1) | ((ridx & 2) << 2) | ((ridx & 4) >> 1) | ((ridx & 8) >> 1) | (ridx & 16));
+    const int aswz = (arow >> 2) & 3;
+    const int a_hi_off = arow * PP_ROWF + ((kh ^ aswz) << 2);
+    const int a_lo_off = arow * PP_ROWF + (((2 + kh) ^ aswz) << 2);
+    const float* lrow = ps.L0 + (size_t)min(m0 + arow, g.M - 1) * ps.ldl + kbeg + 8 * kh;
+    f32x4 av[4];                                    // [sub-tile of the pair][half of the lane's 8 values]
+    float apk = 0.f;
+    auto load_vals = [&](int p) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int h = 0; h < 2; ++h) av[2 * t + h] = pp_gload16(lrow + (2 * p + t) * HS_G + 4 * h);
+    };
+    auto convert = [&](int p) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            float* st = lds + (2 * (p & 1) + t) * PP_SUBF;
+            const f32x4 v0 = av[2 * t] * a_scale, v1 = av[2 * t + 1] * a_scale;
+            uint4 oh, ol;
+            oh.x = hs_hi_pair(v0[0], v0[1]);
+            oh.y = hs_hi_pair(v0[2], v0[3]);
+            oh.z = hs_hi_pair(v1[0], v1[1]);
+            oh.w = hs_hi_pair(v1[2], v1[3]);
+            *reinterpret_cast<uint4*>(st + a_hi_off) = oh;
+            ol.x = hs_lo_pair(v0[0], v0[1], oh.x);
+            ol.y = hs_lo_pair(v0[2], v0[3], oh.y);
+            ol.z = hs_lo_pair(v1[0], v1[1], oh.z);
+            ol.w = hs_lo_pair(v1[2], v1[3], oh.w);
+            *reinterpret_cast<uint4*>(st + a_lo_off) = ol;
+            apk = hs_absmax(hs_absmax(hs_absmax(hs_absmax(apk, v0[0], v0[1]), v0[2], v0[3]), v1[0], v1[1]), v1[2], v1[3]);
+        }
+    };
+
+    // ---- fragments: plane 0 = X (hi), 1 = Y (lo)
+    const int r16 = lane & 15, q = lane >> 4;
+    int fo[2];
+#pragma unroll
+    for (int pl = 0; pl < 2; ++pl) fo[pl] = (q & 1) * PP_SUBF + r16 * PP_ROWF + (((2 * pl + (q >> 1)) ^ ((r16 >> 2) & 3)) << 2);
+    const int abase = wm * 128 * PP_ROWF;
+    const int bbase = (PP_BM + wn * 64) * PP_ROWF;
+    auto rd = [&](const float* tile, int pl) { return __builtin_bit_cast(f16x8, *reinterpret_cast<const f32x4*>(tile + fo[pl])); };
+
+    f32x4 acc[8][4];
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f16x8 xb[4], yb[4], xa[2], ya[2];
+
+    // Beyond the last pair the loop keeps its pattern with the pair index clamped (pc): it requests, converts and prefetches
+    // the last pair once or twice more into slots nothing reads any more.  Every wave then issues the same operations in
+    // every trip, so the counted waits hold from the first trip to the last, and the registers of the values in flight
+    // have ONE definition in the loop (with conditional requests hipcc copies them at the loop's end - while the loads
+    // are still in flight).
+    if (np <= 0) return;
+    auto pc = [&](int p) { return min(p, np - 1); };
+    // ---- prologue: B pair 0 landed, A pair 0 converted; in flight: the values of pair 1, then B pair 1
+    issue_bs(0, 0);
+    load_vals(0);
+    pp_wait_vm_dep<0>(av[0], av[1], av[2], av[3]);
+    convert(0);
+    load_vals(pc(1));
+    issue_bs(pc(1), 1);
+    pp_wait_lgkm();
+    pp_barrier();
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        xb[j] = rd(lds + bbase + j * 16 * PP_ROWF, 0);
+        yb[j] = rd(lds + bbase + j * 16 * PP_ROWF, 1);
+    }
+    xa[0] = rd(lds + abase, 0);
+    ya[0] = rd(lds + abase, 1);
+    pp_wait_lgkm();
+    if (wm == 1) {                      // group 1 runs one segment behind; its pieces of B(1) are due at the end of tick 0
+        pp_wait_vm0();
+        pp_barrier();
+    }
+
+#pragma clang loop unroll(disable)
+    for (int p = 0; p < np; ++p) {
+        // ---- L(p)
+        if (wm == 1) issue_bs(pc(p + 2), p + 2);
+        pp_wait_vm_dep<4>(av[0], av[1], av[2], av[3]);              // values(p + 1); younger: four B pieces
+        convert(p + 1);
+        load_vals(pc(p + 2));
+        if (wm == 0) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");     // B(p + 1); the four requests above stay in flight
+        pp_wait_lgkm();
+        __builtin_amdgcn_sched_barrier(0);
+        pp_barrier();
+        // ---- M(p)
+        if (wm == 0) issue_bs(pc(p + 2), p + 2);
+        const float* ac = lds + 2 * (p & 1) * PP_SUBF + abase;
+        const float* an = lds + 2 * ((p + 1) & 1) * PP_SUBF + abase;
+        const float* bn = lds + 2 * ((p + 1) & 1) * PP_SUBF + bbase;
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int i = 0; i < 7; ++i) {
+            const int cur = i & 1;
+            xa[cur ^ 1] = rd(ac + (i + 1) * 16 * PP_ROWF, 0);
+            ya[cur ^ 1] = rd(ac + (i + 1) * 16 * PP_ROWF, 1);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xa[cur], yb[j], acc[i][j], 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xa[cur], xb[j], acc[i][j], 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ya[cur], xb[j], acc[i][j], 0, 0, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, 12, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        // last tile: the products on X_b first, so that the next pair's fragments are requested under the remaining MFMAs
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[7][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xa[1], xb[j], acc[7][j], 0, 0, 0);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[7][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ya[1], xb[j], acc[7][j], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) xb[j] = rd(bn + j * 16 * PP_ROWF, 0);
+        xa[0] = rd(an, 0);
+        ya[0] = rd(an, 1);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[7][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xa[1], yb[j], acc[7][j], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) yb[j] = rd(bn + j * 16 * PP_ROWF, 1);
+        __builtin_amdgcn_s_setprio(0);
+        if (wm == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");     // B(p + 2), issued in L(p); younger: the four value requests
+        pp_wait_lgkm();
+        __builtin_amdgcn_sched_barrier(0);
+        if (!(wm == 1 && p == np - 1)) pp_barrier();
+    }
+    pp_wait_vm0();
+    hs_report_peak(g.peak, apk, true);
+
+    // ---- EPI_RAW from the 16x16 C/D layout: lane = column l & 15, registers = rows 4 (l >> 4) .. + 3 (64-byte row pieces)
+    const bool full_rows = (m0 + PP_BM) <= g.M;
+    const int wrow = m0 + wm * 128 + 4 * q;
+    float* cz = reinterpret_cast<float*>(g.C) + (size_t)blockIdx.z * g.M * g.ldc;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int col = n0 + wn * 64 + j * 16 + r16;
+        if (col >= g.N) continue;
+        float* cf = cz + (size_t)wrow * g.ldc + col;
+        if (full_rows) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) cf[(size_t)(i * 16 + e) * g.ldc] = acc[i][j][e] * acc_scale;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 8; ++i)
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (wrow + i * 16 + e < g.M) cf[(size_t)(i * 16 + e) * g.ldc] = acc[i][j][e] * acc_scale;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // A operand produced in the kernel (PairSrc as in gemm_bf16.hip.h):
 //   pair mode:  A[(pr,t)][k] = split( relu( in_scale * L0[pr][k] + Ts[t][k] ) ),   Ts = in_scale * T (a pre-scaled
 //               copy of the pilot table, in_scale a power of two): one fma and one max per value.  Neither half of
@@ -697,8 +919,16 @@ __device__ __forceinline__ void hs_fused_regressor(f32x16 (&acc)[4][2], const Ge
 // conversion's ds_writes and the A-side values are awaited with a counted vmcnt that names their registers; 2 also requests
 // the A-side values one sub-tile earlier (two register sets), which is what the fp32 rows of layer 0 need - they come
 // from HBM, and two segments of look-ahead are shorter than that latency.
-template <int EPI, bool OUT_HS, bool CAST = false, int DBG = 0, bool FUSE = false, int VM = 0>
+// MFMA: 32 = v_mfma_f32_32x32x16_f16 (everything above), 16 = the 16x16x32 main loop of hs_cast_mfma16_body (layer 0 only: the fused
+// regressor and the hs epilogue depend on the 32x32 accumulator layout)
+template <int EPI, bool OUT_HS, bool CAST = false, int DBG = 0, bool FUSE = false, int VM = 0, int MFMA = 32>
 __global__ __launch_bounds__(PP_THREADS, 1) void gemm_hs_pp_pair_kernel(const GemmHsArgs g, const PairSrc ps, const float in_scale, const PairRegArgs rg) {
+    static_assert(MFMA == 32 || (MFMA == 16 && CAST && !FUSE && EPI == EPI_RAW && !OUT_HS && VM == 2 && DBG == 0), "16x16x32 form: layer 0 only");
+    if constexpr (MFMA == 16) {
+        extern __shared__ __attribute__((aligned(16))) float lds16[];      // 4 * PP_SUBF ring
+        hs_cast_mfma16_body(g, ps, in_scale, lds16);
+        return;
+    }
     // VM 3: VM 2 with ONE load segment and ONE 24-MFMA segment per sub-tile instead of three of each (two barriers per
     // sub-tile and wave instead of six: an 8-MFMA segment is 256 cycles of the matrix pipe, and the skew of a barrier is
     // a fair fraction of that).  The load segment then overlaps the partner group's whole previous MFMA segment, so the

@@ -401,6 +401,12 @@ int  csi_synchronize(csi_ctx* ctx);
  *                         with one drain per sub-tile, 1 hand-counted waits, 2 + one more sub-tile of look-ahead (default for
  *                         layer 0), 3 + one load and one 24-MFMA segment per sub-tile (default for the pair layer); same
  *                         results bit for bit, for A/B runs (tools/vm_ab.sh)
+ *   "hs_l0_mfma"       MFMA shape of the split-f16 layer-0 kernel's main loop: 32 = v_mfma_f32_32x32x16_f16, three products per
+ *                         sub-tile of 16 k-columns; 16 (default) = v_mfma_f32_16x16x32_f16 on pairs of sub-tiles (same terms and matrix-pipe
+ *                         cycles, the part holds a higher clock on it: profiles/mfma_shape_probe.txt, profiles/l0_mfma16_ab.txt).
+ *                         16 is taken with "hs_vm_cast" = 2 when every k range of the launch holds an even number of sub-tiles
+ *                         (every FC model), anything else runs the 32 form.  Same terms, the fp32 sums associate differently
+ *                         (parts in 1e-7).  Read-only: "hs_l0_mfma16_launches" counts the launches of the 16 form.
  *   "ls_fast_perm"     1 (default): a pilot matrix that is a signed row / column permutation of the Sylvester Hadamard matrix
  *                         takes the Walsh-Hadamard LS kernel through permutation tables; 0: the generic kernels (A/B runs)
  *   "ls_overlap_cus", "ls_overlap_stride"  csi_estimate_device: run the LS kernel on a side stream masked to this many CUs beside
