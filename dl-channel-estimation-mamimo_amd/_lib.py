@@ -100,6 +100,8 @@ SYMBOLS = {
     'csi_memcpy_h2d': (ctypes.c_int, [_ctx, _vp, _vp, ctypes.c_int64]),
     'csi_memcpy_d2h': (ctypes.c_int, [_ctx, _vp, _vp, ctypes.c_int64]),
     'csi_synth_white': (ctypes.c_int, [_ctx, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, _vp, _vp]),
+    'csi_synth_structured': (ctypes.c_int, [_ctx, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, _fp, ctypes.c_int, ctypes.c_uint32,
+                                            _vp, _vp, _vp, _vp, _vp]),
     'csi_profile_enable': (ctypes.c_int, [_ctx, ctypes.c_int]),
     'csi_profile_reset': (ctypes.c_int, [_ctx]),
     'csi_profile_num_kernels': (ctypes.c_int, []),

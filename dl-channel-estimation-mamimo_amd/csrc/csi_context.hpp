@@ -23,6 +23,7 @@
 #include "metrics.hip.h"
 #include "input_pool.hip.h"
 #include "conv_frontend.hip.h"
+#include "synth_structured.hip.h"
 
 using namespace csi;
 
@@ -51,13 +52,14 @@ enum KernelId {
     K_HYB_CORR,          // hybrid weights: dictionary correlation + argmax of one matching-pursuit step (fp32 MFMA)
     K_HYB_SOLVE,         // hybrid weights: Cholesky row, coefficients and residual of one matching-pursuit step
     K_HYB_FINISH,        // hybrid weights: gain and per-packet mean of the analog part
+    K_SYNTH_STRUCTURED,  // known-channel sounding packets (synth_structured.hip.h): the power pass and the packet pass of csi_synth_structured
     K_COUNT
 };
 const char* const kKernelNames[K_COUNT] = {
     "layer0_ltf_gemm", "splitk_reduce", "pair_dense_gemm", "dense_hidden_gemm", "regressor_gemm",
     "ls_estimate", "naive_dense0_gemm", "synth_white", "pilot_table", "cast_bf16", "pair_h1_bf16", "lmmse_levinson",
     "train_gemm", "train_elementwise", "nmse_links", "pair_dense_tail", "input_pool", "conv_frontend",
-    "hybrid_svd", "hybrid_corr_argmax", "hybrid_solve", "hybrid_finish"};
+    "hybrid_svd", "hybrid_corr_argmax", "hybrid_solve", "hybrid_finish", "synth_structured"};
 
 thread_local std::string g_create_error;
 
@@ -158,6 +160,12 @@ struct csi_ctx {
     float* tw = nullptr;         // [2][256]
     int* bin_pos = nullptr;      // [234]
     float* denom = nullptr;      // [234]
+    // csi_synth_structured (synth_structured.hip.h)
+    float* ltf_nat = nullptr;    // [256] LTF sequence in FFT bin order, 0 on the null bins
+    char* synth_ws = nullptr;    // [64] tap profile | [npkt] 0.5 * 10^(-snr/10) | [npkt * nr] item powers
+    size_t synth_ws_bytes = 0;
+    std::vector<float> synth_host;   // host image of the first two parts (stays alive behind the asynchronous upload)
+    size_t synth_lds_attr = 0;   // dynamic-LDS limit already raised for its kernels
     // activation workspace
     char* ws = nullptr;
     size_t ws_bytes = 0;

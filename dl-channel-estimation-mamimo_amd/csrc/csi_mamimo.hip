@@ -554,6 +554,11 @@ int csi_create(const csi_config* cfg, csi_ctx** out) {
     if ((int)bin_pos.size() != LS_NDATA) { c->err = "internal: data-bin count"; return bail(CSI_ERR_INVALID_ARG); }
     if (upload(c, &c->tw, tw.data(), tw.size())) return bail(CSI_ERR_HIP);
     if (upload(c, &c->denom, denom.data(), denom.size())) return bail(CSI_ERR_HIP);
+    {
+        std::vector<float> ltf_nat(LS_FFT);      // the generator needs all 242 non-null bins, in FFT bin order
+        for (int k = 0; k < LS_FFT; ++k) ltf_nat[(k + LS_FFT / 2) % LS_FFT] = (float)ltf[k];
+        if (upload(c, &c->ltf_nat, ltf_nat.data(), ltf_nat.size())) return bail(CSI_ERR_HIP);
+    }
     if (hipMalloc((void**)&c->bin_pos, LS_NDATA * sizeof(int)) != hipSuccess ||
         hipMemcpy(c->bin_pos, bin_pos.data(), LS_NDATA * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
         c->err = "bin table upload failed";
@@ -590,6 +595,8 @@ void csi_destroy(csi_ctx* c) {
     if (c->tw) hipFree(c->tw);
     if (c->bin_pos) hipFree(c->bin_pos);
     if (c->denom) hipFree(c->denom);
+    if (c->ltf_nat) hipFree(c->ltf_nat);
+    if (c->synth_ws) hipFree(c->synth_ws);
     if (c->ws) hipFree(c->ws);
     if (c->stage) hipFree(c->stage);
     if (c->aux_ws) hipFree(c->aux_ws);
@@ -2179,6 +2186,59 @@ int csi_synth_white(csi_ctx* c, uint64_t seed, int64_t first_pkt, int64_t npkt, 
     const size_t n = per_pkt * (size_t)npkt;
     ProfScope ps(c, K_SYNTH_WHITE, 0.0, 8.0 * n);
     hipLaunchKernelGGL(synth_white_kernel, dim3(2048), dim3(256), 0, c->stream, seed, (uint64_t)first_pkt * per_pkt, n, d_re, d_im);
+    HIP_TRY(c, hipGetLastError());
+    return CSI_OK;
+}
+
+int csi_synth_structured(csi_ctx* c, uint64_t seed, int64_t first_pkt, int64_t npkt, const float* snr_db, int n_taps, uint32_t flags,
+                         float* d_ltf_re, float* d_ltf_im, float* d_h_re, float* d_h_im, float* d_noise_std) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    const csi_config& cf = c->cfg;
+    if (cf.nt < 4 || cf.nt % 4 != 0 || cf.len_ltf != LS_SYM * cf.nt)
+        return fail(c, CSI_ERR_INVALID_ARG, "csi_synth_structured: needs a context of nt >= 1 antennas and len_ltf = 320 nt (nt %d, len_ltf %d)", cf.nt, cf.len_ltf);
+    if (npkt < 0 || first_pkt < 0) return fail(c, CSI_ERR_INVALID_ARG, "csi_synth_structured: npkt %lld / first_pkt %lld must not be negative", (long long)npkt, (long long)first_pkt);
+    if (n_taps == 0) n_taps = 8;
+    if (n_taps < 1 || n_taps > SS_MAX_TAPS) return fail(c, CSI_ERR_INVALID_ARG, "csi_synth_structured: n_taps %d outside 1 .. %d", n_taps, SS_MAX_TAPS);
+    if (flags & ~1u) return fail(c, CSI_ERR_INVALID_ARG, "csi_synth_structured: unknown flag bits 0x%x (bit 0 = amplitude scale)", flags);
+    if (npkt == 0) return CSI_OK;
+    if (!d_ltf_re || !d_ltf_im) return fail(c, CSI_ERR_INVALID_ARG, "csi_synth_structured: null ltf planes for %lld packets", (long long)npkt);
+    if ((d_h_re == nullptr) != (d_h_im == nullptr)) return fail(c, CSI_ERR_INVALID_ARG, "csi_synth_structured: the channel planes come as a pair (one of h_re / h_im is null)");
+    if (!c->pilot_ok) return fail(c, CSI_ERR_NOT_READY, "csi_synth_structured: no pilot matrix set (csi_set_pilot)");
+    if (c->user_capture && snr_db) return fail(c, CSI_ERR_INVALID_ARG, "csi_synth_structured: a call with an SNR array uploads it and cannot be captured");
+    if (((reinterpret_cast<uintptr_t>(d_ltf_re) | reinterpret_cast<uintptr_t>(d_ltf_im) | reinterpret_cast<uintptr_t>(d_h_re) | reinterpret_cast<uintptr_t>(d_h_im)) & 15) != 0)
+        return fail(c, CSI_ERR_INVALID_ARG, "csi_synth_structured: output planes must start on 16-byte boundaries");
+    const int64_t nblk = npkt * cf.nr;
+    if (nblk > 0x7fffffff) return fail(c, CSI_ERR_INVALID_ARG, "csi_synth_structured: %lld packets x %d rx antennas exceed one launch (2^31 - 1 items)", (long long)npkt, cf.nr);
+    HIP_TRY(c, hipSetDevice(cf.device));
+    // tap profile and per-packet noise factors in double on the host, one upload; the item powers follow them in the same buffer
+    const size_t n_host = SS_MAX_TAPS + (snr_db ? (size_t)npkt : 0);
+    int rc = ensure_bytes(c, &c->synth_ws, &c->synth_ws_bytes, (n_host + (snr_db ? (size_t)nblk : 0)) * sizeof(float));
+    if (rc) return rc;
+    c->synth_host.resize(n_host);
+    for (int t = 0; t < SS_MAX_TAPS; ++t) c->synth_host[t] = (float)(std::exp(-0.5 * t) / std::sqrt(2.0));
+    for (int64_t p = 0; snr_db && p < npkt; ++p) c->synth_host[SS_MAX_TAPS + p] = (float)(0.5 * std::pow(10.0, -0.1 * (double)snr_db[p]));
+    float* ws = reinterpret_cast<float*>(c->synth_ws);
+    HIP_TRY(c, hipMemcpyAsync(ws, c->synth_host.data(), n_host * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    SynthArgs a{};
+    a.P = c->P; a.tw = c->tw; a.ltf_nat = c->ltf_nat; a.bin_pos = c->bin_pos;
+    a.decay = ws;
+    a.fac = snr_db ? ws + SS_MAX_TAPS : nullptr;
+    a.part = snr_db ? ws + n_host : nullptr;
+    a.ltf_re = d_ltf_re; a.ltf_im = d_ltf_im; a.h_re = d_h_re; a.h_im = d_h_im; a.noise_std = d_noise_std;
+    a.seed = seed; a.first_pkt = first_pkt;
+    a.nt = cf.nt; a.nr = cf.nr; a.len_ltf = cf.len_ltf; a.n_taps = n_taps;
+    a.amp = (flags & 1u) ? (float)(std::sqrt((double)(LS_FFT - 14)) / LS_FFT) : 1.0f;
+    const size_t lds = synth_lds_floats(cf.nt, n_taps) * sizeof(float);
+    if (lds > 160 * 1024) return fail(c, CSI_ERR_INVALID_ARG, "csi_synth_structured: nt %d with %d taps needs %zu bytes of LDS (160 KiB per workgroup)", cf.nt, n_taps, lds);
+    if (lds > 48 * 1024 && lds > c->synth_lds_attr) {
+        HIP_TRY(c, hipFuncSetAttribute((const void*)synth_structured_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIP_TRY(c, hipFuncSetAttribute((const void*)synth_structured_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        c->synth_lds_attr = lds;
+    }
+    const double bytes = (double)nblk * (8.0 * cf.len_ltf + (d_h_re ? 8.0 * cf.nt * LS_NDATA : 0.0));
+    ProfScope ps(c, K_SYNTH_STRUCTURED, 0.0, bytes);
+    if (snr_db) hipLaunchKernelGGL(synth_structured_kernel<true>, dim3((unsigned)nblk), dim3(SS_THREADS), lds, c->stream, a);
+    hipLaunchKernelGGL(synth_structured_kernel<false>, dim3((unsigned)nblk), dim3(SS_THREADS), lds, c->stream, a);
     HIP_TRY(c, hipGetLastError());
     return CSI_OK;
 }

@@ -18,6 +18,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rng.hip.h"
+
 namespace csi {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -1440,14 +1442,8 @@ __global__ __launch_bounds__(LS_THREADS) void ls_despread_first_kernel(const LsA
     }
 }
 
-// i.i.d. CN(0,1) samples from a counter-based generator: element index -> splitmix64 ->
+// i.i.d. CN(0,1) samples from a counter-based generator: element index -> splitmix64 (rng.hip.h) ->
 // two uniforms -> Box-Muller.  re/im each have variance 1/2.
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
 
 __global__ void synth_white_kernel(uint64_t seed, uint64_t first_elem, size_t n, float* __restrict__ re,
                                    float* __restrict__ im) {

@@ -19,22 +19,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "ls_estimate.hip.h"      // splitmix64
+#include "rng.hip.h"              // splitmix64, tr_uniform, tr_normal
 #include "input_pool.hip.h"       // pool2 (decimated-input models)
 
 namespace csi {
-
-// uniform in (0,1) and standard normal from a counter (stream, index)
-__device__ __forceinline__ float tr_uniform(uint64_t stream, uint64_t idx) {
-    const uint64_t h = splitmix64(stream ^ splitmix64(idx));
-    return ((float)(uint32_t)(h >> 40) + 0.5f) * (1.0f / 16777216.0f);
-}
-__device__ __forceinline__ float tr_normal(uint64_t stream, uint64_t idx) {
-    const uint64_t h = splitmix64(stream ^ splitmix64(idx));
-    const float u1 = ((float)(uint32_t)(h >> 32) + 0.5f) * (1.0f / 4294967296.0f);
-    const float u2 = ((float)(uint32_t)h + 0.5f) * (1.0f / 4294967296.0f);
-    return sqrtf(-2.0f * logf(u1)) * cosf(6.283185307179586f * u2);
-}
 
 // noisy input sample k of raw row b (x [B][kraw]): noise on the LTF columns (k < n_noisy), drawn with the raw element's counter
 __device__ __forceinline__ float tr_noisy(const float* __restrict__ x, int b, int kraw, int k, int n_noisy, float noise_std, uint64_t stream) {

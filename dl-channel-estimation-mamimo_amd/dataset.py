@@ -56,6 +56,27 @@ def packets_from_dataset(ds):
                 labels=y.reshape(npkt, nr, nt, -1), nt=nt, nr=nr, npkt=npkt)
 
 
+def dataset_from_packets(ltf, labels, pilot, sim_params=None):
+    """The inverse of packets_from_dataset: ltf complex [Npkt, Nr, lenLTF], labels complex [Npkt, Nr, Nt, nSubCarr] and the pilot
+    rows [Nt, Nt] (row t = what the DNN sees for tx t) as the dataset dict load_dataset returns - one LTF key per (packet, rx),
+    samples in the order s = p*Nr*Nt + iRx*Nt + iTx (mk.py:62), 'P' the transpose of the pilot rows (see :55)."""
+    ltf, labels = np.asarray(ltf), np.asarray(labels)
+    pilot = np.asarray(pilot, dtype=np.float64)
+    npkt, nr, _ = ltf.shape
+    nt = pilot.shape[0]
+    if pilot.shape != (nt, nt) or labels.shape[:3] != (npkt, nr, nt):
+        raise ValueError('ltf %s, labels %s and pilot %s do not belong together' % (ltf.shape, labels.shape, pilot.shape))
+    keys = np.arange(npkt * nr, dtype=np.int64)
+    X = np.stack([np.repeat(keys, nt), np.tile(np.arange(nt, dtype=np.int64), npkt * nr)], axis=1)
+    rows = ltf.reshape(npkt * nr, -1)
+    re, im = np.ascontiguousarray(rows.real), np.ascontiguousarray(rows.imag)
+    y = labels.reshape(npkt * nr * nt, -1)
+    sim = dict(nTX=nt, nRX=nr)
+    sim.update(sim_params or {})
+    return dict(X=X, y=dict(real=np.ascontiguousarray(y.real), imag=np.ascontiguousarray(y.imag)),
+                LTF={int(k): dict(real=re[k], imag=im[k]) for k in keys}, P=np.ascontiguousarray(pilot.T), simParams=sim)
+
+
 def label_consistency(engine, packed):
     """the stored labels are the LS estimate of the very same noisy preamble
     (generate_maMIMO_LTF.m:326-354), so LS(ltf) must reproduce them.  Runs the LS kernel and

@@ -212,6 +212,7 @@ class CsiEngine:
         self.hidden = tuple(int(h) for h in hidden)
         self.n_out = int(n_out)
         self.use_bn = bool(use_bn)
+        self.pilot = None
         cfg = _lib.CsiConfig()
         cfg.nt, cfg.nr, cfg.len_ltf = self.nt, self.nr, self.len_ltf
         if not 1 <= len(self.hidden) <= _lib.CSI_MAX_HIDDEN:
@@ -453,6 +454,7 @@ class CsiEngine:
         if P.shape != (self.nt, self.nt):
             raise CsiError(-1, f'P must be [{self.nt},{self.nt}], got {P.shape}')
         self._check(self._lib.csi_set_pilot(self._ctx, _fp(P)))
+        self.pilot = P.copy()          # what this object last set (sweep.make_dataset packs it into the dataset)
 
     # ------------------------------------------------------------------ host-buffer calls
     def _split(self, ltf, ltf_im=None):
@@ -734,6 +736,32 @@ class CsiEngine:
 
     def synth_white(self, seed, first_pkt, npkt, d_re, d_im):
         self._check(self._lib.csi_synth_white(self._ctx, int(seed), int(first_pkt), int(npkt), d_re.ptr, d_im.ptr))
+
+    def synth_structured(self, seed, first_pkt, npkt, snr_db=None, n_taps=8, amp_scale=True, want_channel=True, want_noise_std=True):
+        """Known-channel sounding packets generated on the device (csi_synth_structured): packets first_pkt .. first_pkt + npkt - 1
+        of the stream `seed`.  snr_db: None (noise-free), a scalar or one level per packet, relative to each packet's own power.
+        Returns DeviceArrays (ltf_re, ltf_im [npkt][nr][len_ltf], h_re, h_im [npkt][nr][nt][234], noise_std [npkt]); the channel
+        planes / noise_std are None when not wanted.  h is what ls_estimate_device returns for the noise-free packet when
+        P P^T = Nt I; noise_std is the deviation per real component before the amplitude scale.  Asynchronous."""
+        npkt = int(npkt)
+        if npkt < 0:
+            raise CsiError(-1, f'csi_synth_structured: npkt {npkt} must not be negative')
+        snr = None
+        if snr_db is not None:
+            snr = np.ascontiguousarray(np.broadcast_to(np.asarray(snr_db, dtype=np.float32), (npkt,)))
+        d_re, d_im = self.empty((npkt, self.nr, SYM_LEN * self.nt)), self.empty((npkt, self.nr, SYM_LEN * self.nt))
+        d_h = [self.empty((npkt, self.nr, self.nt, N_DATA)) for _ in range(2)] if want_channel else [None, None]
+        d_std = self.empty((npkt,)) if want_noise_std else None
+        self._check(self._lib.csi_synth_structured(self._ctx, int(seed), int(first_pkt), npkt, _fp(snr) if snr is not None else None,
+                                                   int(n_taps), 1 if amp_scale else 0, d_re.ptr or None, d_im.ptr or None,
+                                                   d_h[0].ptr if want_channel else None, d_h[1].ptr if want_channel else None,
+                                                   d_std.ptr if want_noise_std else None))
+        return d_re, d_im, d_h[0], d_h[1], d_std
+
+    def lmmse_estimate_device(self, d_h_re, d_h_im, npkt, d_hvec, L, d_snr_db, d_out_re, d_out_im):
+        """LMMSE smoothing of device-resident LS planes (csi_lmmse_estimate_device): d_hvec [npkt][L], d_snr_db [npkt][nr]; asynchronous."""
+        self._check(self._lib.csi_lmmse_estimate_device(self._ctx, d_h_re.ptr, d_h_im.ptr, int(npkt), d_hvec.ptr, int(L), d_snr_db.ptr,
+                                                        d_out_re.ptr, d_out_im.ptr))
 
     # ------------------------------------------------------------------ profiling
     def profile_enable(self, on=True):

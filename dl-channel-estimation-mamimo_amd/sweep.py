@@ -1,0 +1,223 @@
+"""The evaluation the reference exists for, in the order its pipeline runs it (full_pipeline_maMIMO_DNNEst.sh:40-58): a noise-free
+training set, a fit of both component models, and per SNR level the NMSE of the LS, the LMMSE and the DNN estimate against the
+true channel with 95 % confidence intervals - the "MSE" curve of snr_loop_testing.m:33-64,88-94.
+
+    python -m dl_channel_estimation_mamimo_amd.sweep -d OUT [--nTX 32 --nRX 4 --nn 1024 1024 --useBN --bs 256 ...]
+
+The module holds no arithmetic of its own: packets with a known channel come from csi_synth_structured, labels from
+csi_ls_estimate_device, the fit from trainer.fit, the estimates from csi_estimate_device / csi_lmmse_estimate_device and every
+NMSE from csi_nmse_device.  Only the per-packet mean of the per-link ratios (NMSE_subk, BER_test_maMIMO_LTF.m:675-686) and the
+confidence interval are taken on the host.  BER, EVM and the beamforming gain of BER_test_maMIMO_LTF.m are not computed."""
+import argparse
+import json
+import os
+import pickle
+import sys
+import time
+
+import numpy as np
+
+from . import dataset as ds
+from . import synth, trainer
+from .engine import N_DATA
+
+ESTIMATORS = ('LS', 'MMSE', 'DNN')
+
+
+def tap_profile(n_taps=8):
+    """The generator's tap profile exp(-0.5 t) / sqrt(2), t < n_taps (csrc/synth_structured.hip.h)."""
+    return (np.exp(-0.5 * np.arange(n_taps)) / np.sqrt(2.0)).astype(np.float32)
+
+
+def confidence_interval(x):
+    """(mean, low, high) of the 95 % interval mean +- t(0.975, n - 1) * std(x, ddof=1) / sqrt(n) (snr_loop_testing.m:112-116;
+    MATLAB's std divides by n - 1)."""
+    from scipy.stats import t
+    x = np.asarray(x, np.float64).ravel()
+    n = x.size
+    if n < 2:
+        raise ValueError('a confidence interval needs at least two values')
+    m, sem = float(x.mean()), float(x.std(ddof=1) / np.sqrt(n))
+    q = float(t.ppf(0.975, n - 1))
+    return m, m - q * sem, m + q * sem
+
+
+def make_dataset(engine, n_train, seed, n_taps=8, amp_scale=True):
+    """Noise-free training packets generated on the device (the pipeline trains on "SNR 120 ... NOISELESS" packets,
+    full_pipeline_maMIMO_DNNEst.sh:21,33) with the LS estimate of the same signal as labels, as the dataset's y is
+    (generate_maMIMO_LTF.m:342-354).  engine.set_pilot must have been called.  Returns the dict dataset.load_dataset returns."""
+    d_re, d_im, _, _, _ = engine.synth_structured(seed, 0, n_train, snr_db=None, n_taps=n_taps, amp_scale=amp_scale,
+                                                  want_channel=False, want_noise_std=False)
+    l_re, l_im = engine.empty((n_train, engine.nr, engine.nt, N_DATA)), engine.empty((n_train, engine.nr, engine.nt, N_DATA))
+    engine.ls_estimate_device(d_re, d_im, n_train, l_re, l_im)
+    engine.synchronize()
+    ltf = d_re.download() + 1j * d_im.download()
+    labels = l_re.download() + 1j * l_im.download()
+    for a in (d_re, d_im, l_re, l_im):
+        a.free()
+    return ds.dataset_from_packets(ltf, labels, engine.pilot)
+
+
+def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=True, keep=False):
+    """npkt test packets at `snr_db` (packets first_pkt ... of stream `seed`: keep them disjoint from the training packets), LS + DNN
+    (estimate_device), the LMMSE smoother on the LS planes, and NMSE_subk of the three estimates against the true channel.
+    Returns {'MSE_LS', 'MSE_MMSE', 'MSE_DNN'}: float64 [npkt], the per-link ratios averaged per packet.
+
+    LMMSE inputs: hvec is the generator's tap profile exp(-0.5 t) / sqrt(2), the impulse response LMMSE_ce.m's `h` stands for (the
+    reference hands it the scatterer delays h_tau, generate_maMIMO_LTF.m:342, which a synthetic channel does not have); snr_db[p][r]
+    is the level.  keep=True adds 'arrays': the DeviceArrays ltf_re, ltf_im, h_re, h_im, ls_re, ls_im (the caller frees them)."""
+    nr, nt = engine.nr, engine.nt
+    d_re, d_im, h_re, h_im, _ = engine.synth_structured(seed, first_pkt, npkt, snr_db=float(snr_db), n_taps=n_taps, amp_scale=amp_scale,
+                                                        want_noise_std=False)
+    shape = (npkt, nr, nt, N_DATA)
+    o_re, o_im, ls_re, ls_im, m_re, m_im = (engine.empty(shape) for _ in range(6))
+    engine.estimate_device(d_re, d_im, npkt, o_re, o_im, ls_re, ls_im, checked=True)
+    prof = tap_profile(n_taps)
+    d_hvec = engine.to_device(np.tile(prof, (npkt, 1)))
+    d_snr = engine.to_device(np.full((npkt, nr), float(snr_db), np.float32))
+    engine.lmmse_estimate_device(ls_re, ls_im, npkt, d_hvec, prof.size, d_snr, m_re, m_im)
+    d_link = engine.empty((npkt * nr * nt,))
+    out = {}
+    for name, (e_re, e_im) in zip(ESTIMATORS, ((ls_re, ls_im), (m_re, m_im), (o_re, o_im))):
+        engine.nmse_device(h_re, h_im, e_re, e_im, npkt * nr * nt, N_DATA, d_per_link=d_link)
+        out['MSE_' + name] = d_link.download().astype(np.float64).reshape(npkt, nr * nt).mean(axis=1)
+    kept = (d_re, d_im, h_re, h_im, ls_re, ls_im)
+    for a in (o_re, o_im, m_re, m_im, d_hvec, d_snr, d_link) + (() if keep else kept):
+        a.free()
+    if keep:
+        out['arrays'] = kept
+    return out
+
+
+def fit_models(engine, data, workdir, epochs=1000, lr=1e-4, bs=256, dropout=0.15, method='default_SNR', seed=0, val_ratio=0.15,
+               verbose=True):
+    """Both component models through trainer.fit on the resident dataset, saved the way cli --train saves them
+    (<d>_weights-improvement.safetensors and .hdf5 in `workdir`).  Returns {d: {'epochs', 'best_val_loss', 'seconds'}}."""
+    from .model import save_weight_file
+    os.makedirs(workdir, exist_ok=True)
+    train_ids, val_ids = ds.split_train_val(data, val_ratio)
+    info = {}
+    for d in ('real', 'imag'):
+        tr = ds.SampleGenerator(train_ids, data, d, batch_size=bs, shuffle=True, seed=seed)
+        va = ds.SampleGenerator(val_ids, data, d, batch_size=bs, shuffle=True, seed=seed + 1)
+        if min(len(tr), len(va)) == 0:
+            raise ValueError('not enough samples for one batch of %d in the training / validation split' % bs)
+        t0 = time.perf_counter()
+        hist = trainer.fit(engine, d, tr, va, epochs=epochs, lr=lr, dropout=dropout, method=method, seed=seed, verbose=verbose,
+                           resident=data)
+        info[d] = dict(epochs=len(hist['loss']), best_val_loss=hist['best_val_loss'], seconds=time.perf_counter() - t0)
+        save_weight_file(os.path.join(workdir, d + '_weights-improvement.safetensors'), hist['weights'])
+        save_weight_file(os.path.join(workdir, d + '_weights-improvement.hdf5'), hist['weights'], component=d, input_pool=None)
+    return info
+
+
+def load_models(engine, modeldir):
+    """Weights cli._find_weights finds in `modeldir`, loaded into the engine."""
+    from .cli import _find_weights
+    from .model import load_weight_file
+    for d in ('real', 'imag'):
+        engine.load_weights(d, load_weight_file(_find_weights(modeldir, d)))
+
+
+def write_metrics(path, mse):
+    """metrics.mat with MSE_LS, MSE_MMSE, MSE_DNN as 1 x npkt rows: the names BER_test_maMIMO_LTF.m:653 saves and
+    snr_loop_testing.m:37-58 loads (the BER / EVM / dtSNR fields are not written)."""
+    from scipy.io import savemat
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    savemat(path, {'MSE_' + e: np.asarray(mse['MSE_' + e], np.float64).reshape(1, -1) for e in ESTIMATORS})
+    return path
+
+
+def format_table(result):
+    lines = ['%8s' % 'SNR dB' + ''.join('  %-38s' % (e + ': mean [CI low, CI high]') for e in ESTIMATORS)]
+    for lv in result['levels']:
+        row = '%8g' % lv['snr_db']
+        for e in ESTIMATORS:
+            s = lv[e]
+            row += '  %-38s' % ('%.4e [%.4e, %.4e]' % (s['mean'], s['ci_low'], s['ci_high']))
+        lines.append(row)
+    if result.get('training'):
+        lines.append('training: ' + ', '.join('%s %d epochs in %.1f s' % (d, v['epochs'], v['seconds']) for d, v in result['training'].items()))
+    return '\n'.join(lines)
+
+
+def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500, seed=0, modeldir=None, fit_args=None, n_taps=8,
+              amp_scale=True, save_dataset=None, verbose=True):
+    """Training set -> models (loaded from `modeldir`, else fitted and saved into `out`) -> every level.  Writes
+    <out>/BS<Nt>_SNR<s>/metrics.mat per level and <out>/sweep.json, prints the table, returns the result dict (with the per-packet
+    arrays under 'per_packet' = {level: {'MSE_LS', ...}}).  Test packets come from the stream seed + 1, behind the index range of
+    the training packets, so no test packet repeats a training packet."""
+    os.makedirs(out, exist_ok=True)
+    result = dict(nt=engine.nt, nr=engine.nr, n_train=int(n_train), n_test=int(n_test), seed=int(seed), n_taps=int(n_taps),
+                  amp_scale=bool(amp_scale), levels=[], training=None)
+    if modeldir:
+        load_models(engine, modeldir)
+        if save_dataset:
+            with open(save_dataset, 'wb') as f:
+                pickle.dump(make_dataset(engine, n_train, seed, n_taps, amp_scale), f)
+    else:
+        t0 = time.perf_counter()
+        data = make_dataset(engine, n_train, seed, n_taps, amp_scale)
+        result['dataset_seconds'] = time.perf_counter() - t0
+        if save_dataset:
+            with open(save_dataset, 'wb') as f:
+                pickle.dump(data, f)
+        result['training'] = fit_models(engine, data, out, seed=seed, verbose=verbose, **(fit_args or {}))
+        del data
+    per_packet = {}
+    for i, snr in enumerate(levels):
+        t0 = time.perf_counter()
+        mse = evaluate_level(engine, snr, n_test, seed + 1, n_train + i * n_test, n_taps, amp_scale)
+        sec = time.perf_counter() - t0
+        write_metrics(os.path.join(out, 'BS%d_SNR%g' % (engine.nt, snr), 'metrics.mat'), mse)
+        lv = dict(snr_db=float(snr), seconds=sec)
+        for e in ESTIMATORS:
+            m, lo, hi = confidence_interval(mse['MSE_' + e])
+            lv[e] = dict(mean=m, ci_low=lo, ci_high=hi)
+        result['levels'].append(lv)
+        per_packet[float(snr)] = mse
+    with open(os.path.join(out, 'sweep.json'), 'w') as f:
+        json.dump(result, f, indent=1)
+    print(format_table(result))
+    return dict(result, per_packet=per_packet)
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description='NMSE-vs-SNR sweep of LS, LMMSE and the DNN on device-synthesised known-channel packets')
+    p.add_argument('-d', '--workdir', required=True, help='output folder: BS<Nt>_SNR<s>/metrics.mat, sweep.json, the fitted weights')
+    p.add_argument('--nTX', default=32, type=int)
+    p.add_argument('--nRX', default=4, type=int)
+    p.add_argument('--trainPkts', default=3000, type=int, help='training packets (setenv.sh:23)')
+    p.add_argument('--testPkts', default=500, type=int, help='test packets per level (setenv.sh:24)')
+    p.add_argument('--snr', default=list(synth.SNR_LEVELS_DB), type=float, nargs='+', help='SNR levels in dB (setenv.sh:25)')
+    p.add_argument('--modeldir', default='', help='folder with weights to evaluate instead of fitting')
+    p.add_argument('--nn', default=[1024, 1024], type=int, nargs='+')
+    p.add_argument('--useBN', action='store_true', default=True)
+    p.add_argument('--noBN', dest='useBN', action='store_false')
+    p.add_argument('--bs', default=256, type=int)
+    p.add_argument('--lr', default=0.0001, type=float)
+    p.add_argument('--epochs', default=1000, type=int)
+    p.add_argument('--dropout', default=0.15, type=float)
+    p.add_argument('--method', default='default_SNR')
+    p.add_argument('--seed', default=0, type=int)
+    p.add_argument('--taps', default=8, type=int)
+    p.add_argument('--save-dataset', default='', metavar='FILE.b', help='pickle the training set (cli --train / --test accept it)')
+    p.add_argument('--device', default=0, type=int)
+    p.add_argument('--quiet', action='store_true')
+    return p
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    from .engine import CsiEngine
+    eng = CsiEngine(args.nTX, args.nRX, hidden=args.nn, use_bn=args.useBN, device=args.device)
+    eng.set_pilot(synth.hadamard(args.nTX))
+    fit_args = dict(epochs=args.epochs, lr=args.lr, bs=args.bs, dropout=args.dropout, method=args.method)
+    run_sweep(eng, args.workdir, levels=args.snr, n_train=args.trainPkts, n_test=args.testPkts, seed=args.seed,
+              modeldir=args.modeldir or None, fit_args=fit_args, n_taps=args.taps, save_dataset=args.save_dataset or None,
+              verbose=not args.quiet)
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

@@ -21,6 +21,7 @@
  *                                                                   csi_ls_estimate[_device]
  *   LMMSE_ce per link   helperMIMOChannelEstimate.m:37-39, LMMSE_ce.m  csi_lmmse_estimate[_device]
  *   NMSE_subk           BER_test_maMIMO_LTF.m:675-686                csi_nmse[_device]
+ *   known-channel sounding packets  generate_maMIMO_LTF.m:197-342   csi_synth_structured
  *   omphybweights       BER_test_maMIMO_LTF.m:347-376                csi_hybrid_weights[_device]
  *   --execTime profiler loop                       DNN.py:441-475   csi_profile_*
  *   Model.fit step (noise, BN, dropout, Adam)       DNN.py:272-316   csi_train_*
@@ -443,6 +444,29 @@ int  csi_memcpy_d2h(csi_ctx* ctx, void* dst_host, const void* src_dev, int64_t b
  * -> value), for workloads too large to stage through the host (SURVEY.md 8d 'white'). */
 int  csi_synth_white(csi_ctx* ctx, uint64_t seed, int64_t first_pkt, int64_t npkt,
                      float* d_ltf_re, float* d_ltf_im);
+/* Sounding packets with a KNOWN channel, generated on the device (the synthetic twin of generate_maMIMO_LTF.m:197-342 and the inverse
+ * of the LS estimate; csrc/synth_structured.hip.h).  Per (packet, rx): every tx link draws an n_taps complex Gaussian impulse response
+ * with the decay exp(-0.5 t) / sqrt(2); H is its 256-point DFT; the frequency-domain LTF symbols are X[s][k] = ltf[k] sum_j H[j][k] P[j][s]
+ * on all 242 non-null bins, with P the matrix of csi_set_pilot (any real Nt x Nt matrix); then the 256-point inverse FFT, the 64-sample
+ * cyclic prefix and complex AWGN.
+ *   snr_db       HOST array [npkt], dB, relative to the packet's OWN power = the mean of |x|^2 over its nr * len_ltf complex samples
+ *                (generate_maMIMO_LTF.m:283-295); NULL = noise-free.  It is read before the call returns.
+ *   n_taps       1 .. 64; 0 selects 8
+ *   flags        bit 0: the sqrt(242) / 256 amplitude scale of :303-304 on signal and noise; other bits must be 0
+ *   d_ltf_re/im  [npkt][nr][len_ltf], what csi_estimate_device / csi_ls_estimate_device read
+ *   d_h_re/im    optional (both or neither): the true channel [npkt][nr][nt][234] in the layout and bin order of the LS output, DEFINED as
+ *                what csi_ls_estimate_device returns for the noise-free packet whenever P P^T = Nt I (so it carries the amplitude scale)
+ *   d_noise_std  optional [npkt]: sqrt(power / 10^(snr/10) / 2), the noise deviation per real component BEFORE the amplitude scale
+ *                (0 for a noise-free call)
+ * Draws are counter-based, keyed by (seed, absolute packet index first_pkt + i, position inside the packet): packets [first, first + n)
+ * are the same bits whichever call produces them and whatever the call size, noise never moves the channel draws, and the packet power
+ * is summed in a fixed order, so a call repeats bit for bit.  All arithmetic is fp32; serves fp32 and bf16 contexts alike (the planes are
+ * fp32 either way).  Asynchronous on the context's stream.  Output planes must start on 16-byte boundaries (csi_device_malloc does).
+ * Refused with text: no pilot set, negative npkt / first_pkt, n_taps outside 1 .. 64, unknown flag bits, null ltf planes with
+ * npkt > 0, one channel plane without the other, misaligned planes, a context without antennas (nt = 0), a call with an SNR array
+ * inside csi_capture_begin / _end.  Profile entry "synth_structured". */
+int  csi_synth_structured(csi_ctx* ctx, uint64_t seed, int64_t first_pkt, int64_t npkt, const float* snr_db, int n_taps, uint32_t flags,
+                          float* d_ltf_re, float* d_ltf_im, float* d_h_re, float* d_h_im, float* d_noise_std);
 
 /* ---- multi-GPU: packets shard over the GPUs of a node (one process and one context per GPU), the weights are shared and
  * read-only, outputs stay sharded.  The single collective of the path is the load-time broadcast of the
