@@ -195,9 +195,6 @@ def _build_library_locked(force, verbose):
     # run-time CPU check (csi_hostpipe.hpp)
     tmp_so = '%s.tmp.%d' % (_SO, os.getpid())
     cmd = [hipcc, '--offload-arch=gfx950', '-O3', '-std=c++17', '-shared', '-fPIC', '-Wno-unused-value', _SRC, '-o', tmp_so]
-    # CSI_BUILD_DEFINES="NAME ..." adds -DNAME: CSI_LS_RACE_VARIANTS compiles the race-hunt instantiations of the LS kernel
-    # (tools/ls_race_box*.sh); the product build carries none of them
-    cmd[1:1] = ['-D' + d for d in os.environ.get('CSI_BUILD_DEFINES', '').split()]
     if verbose:
         print(' '.join(cmd))
     res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True)

@@ -199,8 +199,6 @@ struct csi_ctx {
     uint64_t graph_epoch = 0;    // bumped by drop_graphs: graphs a caller captured before are stale
     int64_t hybrid_launches = 0; // "hybrid_launches": kernels launched by csi_hybrid_weights[_device]
     int64_t conv_launches = 0;   // "conv_launches": CONV1D front-end passes launched (conv_frontend.hip.h)
-    int debug_ls_lds_pad = 0;        // CSI_DEBUG_HOOKS=1 CSI_LS_LDS_PAD=<bytes>: the Walsh-Hadamard LS kernel asks for that much more LDS than it uses
-    int debug_bf16_fork_late = 0;    // CSI_DEBUG_HOOKS=1 CSI_BF16_FORK_LATE=1: bf16 contexts fork the second stream of a two-stream call behind the LS kernel (A/B runs)
     int debug_small_tile16 = 0;  // CSI_DEBUG_HOOKS=1 CSI_SMALL_TILE16=1, read once at csi_create (A/B runs)
     int small_fused = 1;         // "small_fused" option: 0 = the general kernels (six launches per model on two streams)
     int small_rows = 1024;       // "small_rows": pair rows up to which a call takes it (and at most 64 preambles).  Measured (profiles/r05_regime_probe.txt):
@@ -218,20 +216,6 @@ struct csi_ctx {
     int64_t small_calls = 0;     // "small_calls": calls that took it
     char* small_ws = nullptr;    // its scratch: L0 of both models + ping-pong activations
     size_t small_ws_bytes = 0;
-    // "ls_overlap_cus" = n > 0: inside csi_estimate_device the LS kernel runs on its own stream, restricted to n compute units
-    // (hipExtStreamCreateWithCUMask), BESIDE the DNN kernels of the same packets instead of in front of them: it is HBM-bound and
-    // draws little power, the matrix kernels are bound by the power budget and by one workgroup per CU - a few CUs lent to it cost
-    // them less than the 0.4 ms it occupies the whole chip for (both orders give bit-identical results)
-    int ls_overlap_cus = 0;
-    int ls_overlap_stride = 0;   // "ls_overlap_stride": CU i of the n is mask bit i * stride (0 = spread evenly over 256)
-    hipStream_t ls_stream = nullptr;
-    int ls_stream_cus = 0, ls_stream_stride = 0;
-    hipEvent_t ls_fork = nullptr, ls_join = nullptr;
-    int ls_grid_cus = 0;         // set while the LS kernel is launched for the masked stream: persistent grid = this many CUs
-    // csi_estimate_device parks the LS launch here; the DNN path fires it behind its FIRST layer-0 kernel (ls_deferred_fire), so that
-    // the LS kernel runs beside the per-pair kernels (many rounds of workgroups per CU: a few CUs less cost them nothing measurable)
-    // and not beside layer 0 (ONE round of 252 tiles on 256 CUs at config 2: any CU less costs it a whole second round)
-    struct { bool active = false, forked = false; const float *re = nullptr, *im = nullptr; int64_t npkt = 0; float *h_re = nullptr, *h_im = nullptr; } ls_deferred;
     // staging for host-buffer entry points
     char* stage = nullptr;
     size_t stage_bytes = 0;
@@ -301,7 +285,8 @@ struct csi_ctx {
                                  // ONE box of the pool, 1-3 wrong items in ~1 % of the first launches of a fresh context (always the first item of
                                  // a CU's second workgroup, lane groups of an FFT stage; 7 events in 570 cycles there, none in 1170 on two other
                                  // boxes, none ever in the other LS kernels).  Not understood, so not selected: Nt <= 32 takes
-                                 // the fp32 ring kernel (3-5 % slower); tools/ls_race_repro.py reproduces, "ls_kernel" 7 still forces it
+                                 // the fp32 ring kernel (3-5 % slower); "ls_kernel" 7 still forces it (one workgroup per CU since round 5; cause found
+                                 // in round 6)
     bool p_sylvester = false;    // csi_set_pilot saw the Sylvester Hadamard matrix (Walsh-Hadamard LS despread applies)
     // csi_set_pilot saw P = D1 Pi1 H Pi2 D2 (H Sylvester, Pi permutations, D signs; e.g. the 802.11 VHT 4x4 base doubled up): the
     // Walsh-Hadamard kernel applies with permuted / signed symbol loads and output rows.  p_perm[0][u] = source symbol of transform
@@ -479,48 +464,6 @@ void drop_graphs(csi_ctx* c) {
         if (g.exec) hipGraphExecDestroy(g.exec);
     c->graphs.clear();
     ++c->graph_epoch;
-}
-
-// the CU-masked side stream of "ls_overlap_cus"
-int ls_stream_ensure(csi_ctx* c) {
-    const int n = std::max(1, std::min(255, c->ls_overlap_cus));
-    const int stride = c->ls_overlap_stride > 0 ? c->ls_overlap_stride : std::max(1, 256 / n);
-    if (c->ls_stream && c->ls_stream_cus == n && c->ls_stream_stride == stride) return CSI_OK;
-    drop_graphs(c);
-    if (c->ls_stream) { hipStreamSynchronize(c->ls_stream); hipStreamDestroy(c->ls_stream); c->ls_stream = nullptr; }
-    uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int i = 0; i < n; ++i) {
-        const int bit = (i * stride) % 256;
-        mask[bit >> 5] |= 1u << (bit & 31);
-    }
-    HIP_TRY(c, hipExtStreamCreateWithCUMask(&c->ls_stream, 8, mask));
-    if (!c->ls_fork) HIP_TRY(c, hipEventCreateWithFlags(&c->ls_fork, hipEventDisableTiming));
-    if (!c->ls_join) HIP_TRY(c, hipEventCreateWithFlags(&c->ls_join, hipEventDisableTiming));
-    c->ls_stream_cus = n;
-    c->ls_stream_stride = stride;
-    return CSI_OK;
-}
-
-// the LS launch csi_estimate_device parked: fork the side stream behind what the main stream holds so far, launch the LS kernel
-// there, record the join event (csi_estimate_device waits for it before it returns)
-int ls_deferred_fire(csi_ctx* c) {
-    if (!c->ls_deferred.active) return CSI_OK;
-    c->ls_deferred.active = false;
-    const auto d = c->ls_deferred;
-    int r = ls_stream_ensure(c);
-    if (r) return r;
-    HIP_TRY(c, hipEventRecord(c->ls_fork, c->stream));
-    HIP_TRY(c, hipStreamWaitEvent(c->ls_stream, c->ls_fork, 0));
-    c->ls_deferred.forked = true;
-    std::swap(c->stream, c->ls_stream);
-    c->ls_grid_cus = c->ls_overlap_cus;
-    r = csi_ls_estimate_device(c, d.re, d.im, d.npkt, d.h_re, d.h_im);
-    c->ls_grid_cus = 0;
-    const hipError_t e = hipEventRecord(c->ls_join, c->stream);
-    std::swap(c->stream, c->ls_stream);
-    if (r) return r;
-    HIP_TRY(c, e);
-    return CSI_OK;
 }
 
 int ensure_bytes(csi_ctx* c, char** buf, size_t* have, size_t need) {

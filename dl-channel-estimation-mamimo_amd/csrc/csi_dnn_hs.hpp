@@ -519,7 +519,6 @@ int band_skeleton_time(csi_ctx* c, int64_t rows, int iters, double* ms_per_launc
 // ping-pong activation buffers of the fp32 path re-used as hs matrices (same 4 bytes per element)
 int hs_tail(csi_ctx* c, Model& m, const float* l0sum, int M2, float* hbuf0, float* hbuf1, float* out) {
     const csi_config& cf = c->cfg;
-    if (int rc_ls = ls_deferred_fire(c)) return rc_ls;       // csi_estimate_device with "ls_overlap_cus": the LS kernel starts here, beside the per-pair kernels
     const int nh = cf.n_hidden, h1 = cf.hidden[0];
     const Layer& l1 = m.layers[1];
     const int s0 = hs_act_shift_of(c, m, 0, true);

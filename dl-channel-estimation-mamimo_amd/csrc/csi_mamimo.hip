@@ -50,36 +50,16 @@ LsRingB ls_ringb_shape(const csi_ctx* c) {
         r.nw = W; nstg = NS; r.per_cu = MB; nf = DB ? 2 : 1;                                                       \
     }
     // shapes as measured (profiles/r03_ls_probe_generic.txt); "ls_v2" = 1 selects the runner-up for A/B runs
-    // one antenna tile (Nt <= 32).  Round 5: the product build runs this shape ONE workgroup per CU.  Its two-workgroups-per-CU form
-    // (round 3's choice, 4 % faster) showed rare wrong first items on some parts of the pool (profiles/r04_ls_ringb_variants.txt: lanes
-    // 48-63 of one packed add beside ANOTHER workgroup's bf16 MFMAs on the same SIMD; never with one workgroup per CU, whose barriers
-    // keep the two waves of a SIMD in the same phase) and was never root-caused, so the shipped library cannot select it by any option:
-    // it is compiled only into the hunt build (CSI_BUILD_DEFINES=CSI_LS_RACE_VARIANTS).  The shape is padded to > 80 KiB of LDS below so
-    // that the dispatcher cannot co-locate two of these workgroups either.
-#ifdef CSI_LS_RACE_VARIANTS
-    if (jt == 1) { if (c->ls_v2 == 1) LS_RB(1, 4, 2, 2, false) else LS_RB(1, 4, 1, 2, false) }
-#else
+    // one antenna tile (Nt <= 32): ONE workgroup per CU.  The two-workgroups-per-CU form (4 % faster) is not built: its packed +-i rotations went wrong
+    // beside another workgroup's MFMAs.  The shape is padded to > 80 KiB of LDS below so that the dispatcher cannot co-locate two either.
     if (jt == 1) { if (c->ls_v2 == 1) LS_RB(1, 4, 2, 1, false) else LS_RB(1, 4, 1, 1, false) }
-#endif
     else if (jt == 2) { if (c->ls_v2 == 1) LS_RB(2, 8, 1, 1, false) else LS_RB(2, 8, 1, 1, true) }
     else if (jt == 3) { if (c->ls_v2 == 1) LS_RB(3, 8, 2, 1, false) else LS_RB(3, 8, 1, 1, true) }
     else { if (c->ls_v2 == 1) LS_RB(4, 8, 1, 1, false) else LS_RB(4, 8, 1, 1, true) }
-    // race hunt (tools/ls_race_fast.py): ls_debug bits 0x200 ... 0x8000 select the VAR 1 ... 64 forms (and a few sums) of the
-    // two-workgroups-per-CU instantiation (ls_estimate.hip.h, lsc_stage0_write); pilots of one or two pieces only
-#ifdef CSI_LS_RACE_VARIANTS       // build with CSI_BUILD_DEFINES=CSI_LS_RACE_VARIANTS (python -c "import __graft_entry__ as g; g.build()")
-    if (jt == 1 && c->ls_v2 != 1 && npp <= 2 && (c->ls_debug & 0xfe00)) {
-        const int var = (c->ls_debug >> 9) & 127;
-#define LS_RBV(V) if (var == V) r.fn = npp == 1 ? (const void*)ls_estimate_ringb_kernel<1, 4, 1, 1, 2, false, V> : (const void*)ls_estimate_ringb_kernel<1, 4, 1, 2, 2, false, V>;
-        LS_RBV(1) LS_RBV(2) LS_RBV(4) LS_RBV(8) LS_RBV(5) LS_RBV(6) LS_RBV(12) LS_RBV(16) LS_RBV(20) LS_RBV(32) LS_RBV(36) LS_RBV(64) LS_RBV(68) LS_RBV(96) LS_RBV(48)
-#undef LS_RBV
-    }
-#endif
 #undef LS_RB
     r.lds = (size_t)(2 * LSC_NTW + nf * 16 * 2 * LSC_ROW + nstg * 16 * 2 * LS_FFT) * sizeof(float) + (size_t)(nstg + 1) * npp * jt * LSB_BLOCK * 2;
     if (r.lds > 160 * 1024) r.fn = nullptr;
-#ifndef CSI_LS_RACE_VARIANTS
     if (jt == 1) r.lds = std::max(r.lds, (size_t)(81 * 1024));      // one workgroup per CU by construction (see above)
-#endif
     r.per_cu = std::max(1, std::min(r.per_cu, (int)((160 * 1024) / r.lds)));
     return r;
 }
@@ -139,7 +119,6 @@ LsPlan ls_plan(const csi_ctx* c) {
         }
         p.lds = (size_t)(2 * LSC_NTW + nf * ch * 2 * LSC_ROW + nstg * ch * 2 * LS_FFT) * sizeof(float);
         p.threads = 256 * split;
-        p.lds += (size_t)c->debug_ls_lds_pad;              // CSI_DEBUG_HOOKS=1 CSI_LS_LDS_PAD=<bytes>: unused LDS, i.e. fewer workgroups per CU (A/B runs)
         p.per_cu = std::max(1, std::min(split == 1 ? maxcu : 1, (int)((160 * 1024) / p.lds)));
     } else if (mode == LS_RING) {
         const int jt = (nt + 31) / 32, ldp = jt * 32;
@@ -486,8 +465,6 @@ int csi_create(const csi_config* cfg, csi_ctx** out) {
 
     csi_ctx* c = new csi_ctx();
     if (const char* h = std::getenv("CSI_DEBUG_HOOKS")) if (h[0] == '1') if (const char* d = std::getenv("CSI_SMALL_TILE16")) c->debug_small_tile16 = d[0] == '1';   // (once: not in the call path)
-    if (const char* h = std::getenv("CSI_DEBUG_HOOKS")) if (h[0] == '1') if (const char* d = std::getenv("CSI_LS_LDS_PAD")) c->debug_ls_lds_pad = std::atoi(d);
-    if (const char* h = std::getenv("CSI_DEBUG_HOOKS")) if (h[0] == '1') if (const char* d = std::getenv("CSI_BF16_FORK_LATE")) c->debug_bf16_fork_late = d[0] == '1';   // A/B: bf16 contexts fork the second stream behind the LS kernel
     c->cfg = *cfg;
     c->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     if (c->cfg.bn_eps <= 0.f) c->cfg.bn_eps = 1e-3f;
@@ -606,9 +583,6 @@ void csi_destroy(csi_ctx* c) {
     if (c->aux_fork) hipEventDestroy(c->aux_fork);
     if (c->aux_join) hipEventDestroy(c->aux_join);
     if (c->aux_stream) hipStreamDestroy(c->aux_stream);
-    if (c->ls_fork) hipEventDestroy(c->ls_fork);
-    if (c->ls_join) hipEventDestroy(c->ls_join);
-    if (c->ls_stream) hipStreamDestroy(c->ls_stream);
     if (c->skbuf) hipFree(c->skbuf);
     if (c->l0skinny) hipFree(c->l0skinny);
     if (c->stream) hipStreamDestroy(c->stream);
@@ -1117,50 +1091,33 @@ int csi_estimate_device(csi_ctx* c, const float* d_ltf_re, const float* d_ltf_im
         c->use_graph = false;                      // the two calls below are the graph's content, not graphs of their own
         c->in_graph_call = g || c->user_capture;
         int r = CSI_OK;
-        if (c->ls_overlap_cus > 0) {
-            // LS beside the per-pair kernels: parked here, fired by the DNN path behind its first layer-0 kernel on a CU-masked side
-            // stream (ls_deferred_fire); joined below.  A path that never reaches the hook fires it here, behind the DNN kernels.
-            c->ls_deferred.active = true;
-            c->ls_deferred.forked = false;
-            c->ls_deferred.re = d_ltf_re; c->ls_deferred.im = d_ltf_im; c->ls_deferred.npkt = npkt; c->ls_deferred.h_re = d_h_re; c->ls_deferred.h_im = d_h_im;
-            r = csi_predict_device(c, d_ltf_re, d_ltf_im, npkt, d_out_re, d_out_im);
-            const int r2 = ls_deferred_fire(c);            // no-op when the hook has fired
-            c->ls_deferred.active = false;
-            if (c->ls_deferred.forked) {                   // also on an error: a forked stream must be joined (graph capture)
-                const hipError_t e = hipStreamWaitEvent(c->stream, c->ls_join, 0);
-                if (e != hipSuccess && !r) r = fail(c, CSI_ERR_HIP, "csi_estimate_device: joining the LS stream failed: %s", hipGetErrorString(e));
-            }
-            if (!r) r = r2;
-        } else {
-            // (one-packet calls, round 5: the LS kernel on a second stream beside the three DNN launches was built and measured -
-            // 72.5 us per call against 64.2 in this order; the fork / join events cost more than the 8.7 us kernel hides, and it
-            // runs 16.8 us beside the weight stream.  profiles/r05_small_call_trace.txt)
-            // The second stream of a two-stream call is forked HERE, in front of the LS kernel: the imag model's chain needs the
-            // preambles, not the LS result, and the cross-queue wait (6-7 us before its first kernel starts) passes under the LS kernel
-            // (Round 6, first: bf16 contexts forked BEHIND the LS kernel, because 19 of 20 calls of 500 ... 1000 packets at Nt = 64 came back with wrong LS items when
-            // the imag model's layer 0 - gemm_bf16_kernel, 64 KiB of LDS: its MFMA waves fit on an LS workgroup's CU - ran beside the LS kernel.  Root cause found
-            // later in the round (tools/pk_opsel_probe.hip, profiles/r06_pk_opsel_probe.txt): a packed-fp32 instruction whose SECOND source takes its
-            // low half from the high register (the transform's +-i rotations were v_pk_add_f32 op_sel:[0,1] op_sel_hi:[1,0]) loses that operand in lanes 48-63 while
-            // another wave of the SIMD issues MFMAs.  The rotations are single adds now (ls_estimate.hip.h, CSI_LS_VAR_DEFAULT) and every context forks here again;
-            // CSI_DEBUG_HOOKS=1 CSI_BF16_FORK_LATE=1 brings the late fork back for A/B runs.)
-            if (c->aux_fork_early && !(c->cfg.dtype == CSI_DTYPE_BF16 && c->debug_bf16_fork_late) && !small_call_ok(c, npkt) && two_stream_call(c, npkt) && aux_stream_ensure(c) == CSI_OK) {
-                hipError_t e = hipEventRecord(c->aux_fork, c->stream);
-                if (e == hipSuccess) e = hipStreamWaitEvent(c->aux_stream, c->aux_fork, 0);
-                if (e != hipSuccess) r = fail(c, CSI_ERR_HIP, "csi_estimate_device: forking the second stream failed: %s", hipGetErrorString(e));
-                else c->aux_preforked = true;
-            }
-            // one-packet calls (round 6): the LS estimate rides in the layer-0 launch of the DNN (small_l0_ls_kernel); predict_small takes it from
-            // the context - a call that does not reach that kernel after all runs the LS kernel behind the DNN
-            const bool ls_inside = !r && small_ls_fusable(c, npkt);
-            if (ls_inside) { c->small_ls_h_re = d_h_re; c->small_ls_h_im = d_h_im; }
-            else if (!r) r = csi_ls_estimate_device(c, d_ltf_re, d_ltf_im, npkt, d_h_re, d_h_im);
-            if (!r) r = csi_predict_device(c, d_ltf_re, d_ltf_im, npkt, d_out_re, d_out_im);
-            if (ls_inside && c->small_ls_h_re) {
-                c->small_ls_h_re = c->small_ls_h_im = nullptr;
-                if (!r) r = csi_ls_estimate_device(c, d_ltf_re, d_ltf_im, npkt, d_h_re, d_h_im);
-            }
-            c->aux_preforked = false;
+        // (one-packet calls, round 5: the LS kernel on a second stream beside the three DNN launches was built and measured -
+        // 72.5 us per call against 64.2 in this order; the fork / join events cost more than the 8.7 us kernel hides, and it
+        // runs 16.8 us beside the weight stream.  profiles/r05_small_call_trace.txt)
+        // The second stream of a two-stream call is forked HERE, in front of the LS kernel: the imag model's chain needs the
+        // preambles, not the LS result, and the cross-queue wait (6-7 us before its first kernel starts) passes under the LS kernel
+        // (Round 6, first: bf16 contexts forked BEHIND the LS kernel, because 19 of 20 calls of 500 ... 1000 packets at Nt = 64 came back with wrong LS items when
+        // the imag model's layer 0 - gemm_bf16_kernel, 64 KiB of LDS: its MFMA waves fit on an LS workgroup's CU - ran beside the LS kernel.  Root cause found
+        // later in the round (tools/pk_opsel_probe.hip, profiles/r06_pk_opsel_probe.txt): a packed-fp32 instruction whose SECOND source takes its
+        // low half from the high register (the transform's +-i rotations were v_pk_add_f32 op_sel:[0,1] op_sel_hi:[1,0]) loses that operand in lanes 48-63 while
+        // another wave of the SIMD issues MFMAs.  The rotations are single adds now (ls_estimate.hip.h) and every context forks here again.)
+        if (c->aux_fork_early && !small_call_ok(c, npkt) && two_stream_call(c, npkt) && aux_stream_ensure(c) == CSI_OK) {
+            hipError_t e = hipEventRecord(c->aux_fork, c->stream);
+            if (e == hipSuccess) e = hipStreamWaitEvent(c->aux_stream, c->aux_fork, 0);
+            if (e != hipSuccess) r = fail(c, CSI_ERR_HIP, "csi_estimate_device: forking the second stream failed: %s", hipGetErrorString(e));
+            else c->aux_preforked = true;
         }
+        // one-packet calls (round 6): the LS estimate rides in the layer-0 launch of the DNN (small_l0_ls_kernel); predict_small takes it from
+        // the context - a call that does not reach that kernel after all runs the LS kernel behind the DNN
+        const bool ls_inside = !r && small_ls_fusable(c, npkt);
+        if (ls_inside) { c->small_ls_h_re = d_h_re; c->small_ls_h_im = d_h_im; }
+        else if (!r) r = csi_ls_estimate_device(c, d_ltf_re, d_ltf_im, npkt, d_h_re, d_h_im);
+        if (!r) r = csi_predict_device(c, d_ltf_re, d_ltf_im, npkt, d_out_re, d_out_im);
+        if (ls_inside && c->small_ls_h_re) {
+            c->small_ls_h_re = c->small_ls_h_im = nullptr;
+            if (!r) r = csi_ls_estimate_device(c, d_ltf_re, d_ltf_im, npkt, d_h_re, d_h_im);
+        }
+        c->aux_preforked = false;
         c->use_graph = g;
         c->in_graph_call = c->user_capture;
         return r;
@@ -1195,7 +1152,7 @@ int csi_ls_estimate_device(csi_ctx* c, const float* d_ltf_re, const float* d_ltf
             hipLaunchKernelGGL(ls_despread_first_kernel, dim3((unsigned)(nb * n_jc)), dim3(LS_THREADS), plan.lds, c->stream, a, n_jc);
         } else {
             // persistent grid: as many workgroups as can reside (x256 CUs)
-            const unsigned grid = (unsigned)std::min<int64_t>(nb, (int64_t)(c->ls_grid_cus > 0 ? c->ls_grid_cus : 256) * ((c->ls_debug & 128) ? 1 : plan.per_cu));      // ls_debug 128: one workgroup per CU (race hunt)
+            const unsigned grid = (unsigned)std::min<int64_t>(nb, (int64_t)256 * plan.per_cu);
             void* kargs[] = {(void*)&a, (void*)&nb32};
             HIP_TRY(c, hipLaunchKernel(plan.fn, dim3(grid), dim3(plan.threads), kargs, plan.lds, c->stream));
         }
@@ -1424,8 +1381,7 @@ int csi_get_option(csi_ctx* c, const char* name, int64_t* value) {
     else if (n == "hp_device_weave") *value = c->hp_device_weave;
     else if (n == "hp_direct_out_calls") *value = c->hp_direct_out_calls;
     else if (n == "ls_fast_perm") *value = c->ls_fast_perm;
-    else if (n == "ls_overlap_cus") *value = c->ls_overlap_cus;
-    else if (n == "ls_overlap_stride") *value = c->ls_overlap_stride;
+    else if (n == "ls_overlap_cus") *value = 0;            // see csi_set_option
     else if (n == "ls_pilot_fast") *value = !c->p_fast_ok ? 0 : (c->p_fast_identity ? 1 : 2);     // read-only: 0 generic P, 1 Sylvester Hadamard, 2 a signed permutation of it
     else if (n == "hs_vm_cast") *value = c->hs_vm_cast;
     else if (n == "hs_vm_pair") *value = c->hs_vm_pair;
@@ -1559,18 +1515,12 @@ int csi_set_option(csi_ctx* c, const char* name, int64_t value) {
         if (value != 32 && value != 16) return fail(c, CSI_ERR_INVALID_ARG, "hs_l0_mfma must be 32 or 16");
         drop_graphs(c);
         c->hs_l0_mfma = (int)value;
-    } else if (n == "ls_overlap_cus" || n == "ls_overlap_stride") {
-        if (value < 0 || value > 255) return fail(c, CSI_ERR_INVALID_ARG, "%s must be 0 (LS in front of the DNN kernels on one stream) .. 255", name);
-#ifndef CSI_LS_RACE_VARIANTS
-        // measured slower than the serial order and it puts LS workgroups beside other kernels' MFMA waves - the one
-        // condition under which a packed add of the LS transform was ever seen wrong.  Not part of the shipped library.
-        if (n == "ls_overlap_cus" && value > 0)
-            return fail(c, CSI_ERR_INVALID_ARG, "ls_overlap_cus > 0 (the LS kernel on a CU-masked side stream beside the matrix kernels) is an experiment that "
-                                                "measured slower than the serial order and is not part of the product build; "
-                                                "rebuild with CSI_BUILD_DEFINES=CSI_LS_RACE_VARIANTS to run it");
-#endif
-        drop_graphs(c);
-        (n == "ls_overlap_cus" ? c->ls_overlap_cus : c->ls_overlap_stride) = (int)value;
+    } else if (n == "ls_overlap_cus") {
+        // the LS kernel on a CU-masked side stream beside the matrix kernels: measured slower than the serial order, and it put LS
+        // workgroups beside other kernels' MFMA waves.  The path was removed; the name stays so that callers that ask for 0 keep working.
+        if (value != 0)
+            return fail(c, CSI_ERR_INVALID_ARG, "ls_overlap_cus must be 0: the LS kernel on a side stream beside the matrix kernels was an experiment that "
+                                                "measured slower than the serial order and is not part of the product build");
     } else if (n == "hp_side_threads") {
         if (c->hostpipe) { delete c->hostpipe; c->hostpipe = nullptr; }
         c->hp_side_threads = value != 0;
@@ -2292,15 +2242,5 @@ int csi_profile_query(csi_ctx* c, int id, double* total_ms, int64_t* launches, d
     if (bytes) *bytes = c->prof_bytes[id];
     return CSI_OK;
 }
-
-#if (CSI_LS_VAR_DEFAULT) & 512
-// race-hunt build only (tools/ls_opsel_hunt.sh): the log of packed +-i rotations that differed from the scalar form
-int csi_debug_opsel_log(unsigned* host, int n_dwords, int reset) {
-    hipError_t e = hipDeviceSynchronize();
-    if (e == hipSuccess && host) e = hipMemcpyFromSymbol(host, HIP_SYMBOL(csi::g_opsel_log), (size_t)n_dwords * 4);
-    if (e == hipSuccess && reset) { const unsigned z = 0; e = hipMemcpyToSymbol(HIP_SYMBOL(csi::g_opsel_log), &z, 4); }
-    return e == hipSuccess ? 0 : -1;
-}
-#endif
 
 }  // extern "C"

@@ -588,67 +588,15 @@ __device__ __forceinline__ void ls_lds_barrier() {
 // read consecutive elements).  Every LDS access of stages 1-3 is one ds_*_b64 per complex value and the arithmetic
 // runs on the packed-fp32 pipe: v_pk_add_f32 for the butterflies, v_pk_mul_f32 + v_pk_fma_f32 per twiddle product - half the VALU and LDS
 // instructions of the planar transform (ls_fft256_wave), which is what these kernels are bound by once the ring hides the HBM latency.
-// The +-i ROTATIONS (outputs 1 and 3 of a butterfly) are two single adds each (round 6): as `v_pk_add_f32 ... op_sel:[0,1] op_sel_hi:[1,0] neg_*` - the second
-// source's halves swapped - they returned D.lo = A.lo in lanes 48-63 whenever another wave of the SIMD was issuing MFMAs (a bf16 GEMM workgroup sharing the CU):
-// on gfx950 a packed-fp32 instruction with op_sel = 1 on src1 and 0 on src0 loses that operand in the last 16-lane pass (tools/pk_opsel_probe.hip reproduces it
-// without any LS code; profiles/r06_pk_opsel_probe.txt).  Same kernel time.  The twiddle product's v_pk_fma_f32 has op_sel = 1 on src0 AND src1:
-// not affected (0 of 1e10 in the probe, never seen in a census of bad items).  tests/test_host_round4.py checks the library's machine code for the form.
-// CSI_LS_VAR_DEFAULT = the form of the transform when nothing else is asked for (the VAR bits listed at lsc_stage0_write): 128 in the product;
-// tools/ls_opsel_hunt.sh builds the library with other values (0 = the packed rotations) for the reproducible case of profiles/r06_small_calls.txt (4)
-#ifndef CSI_LS_VAR_DEFAULT
-#define CSI_LS_VAR_DEFAULT 128
-#endif
+// The +-i ROTATIONS (outputs 1 and 3 of a butterfly) are two single adds each (sc_add_mi / sc_add_pi), not one v_pk_add_f32 with the second source's halves
+// swapped: on gfx950 a packed-fp32 instruction with op_sel = 1 on src1 and 0 on src0 loses that operand in lanes 48-63 whenever another wave of the SIMD is
+// issuing MFMAs (a bf16 GEMM workgroup sharing the CU).  Same kernel time.  The twiddle product's v_pk_fma_f32 has op_sel = 1 on src0 AND src1: not affected.
+// DESIGN 4.12 has the finding (tools/pk_opsel_probe.hip reproduces it without any LS code); tests/test_host_round4.py checks the library's machine code for the form.
 constexpr int LSC_ROW = LS_FFT + LS_FFT / 4;            // 320 complex elements per padded row
 constexpr int LSC_NTW = 256;                            // twiddle table: stage 1 [3][4], stage 2 [3][16], stage 3 [3][64] (252 used)
 __device__ __forceinline__ int lsc_phys(int e) { return e + ((e >> 4) << 2); }
 
-// a - i b  and  a + i b
-__device__ __forceinline__ f32x2 pk_add_mi(f32x2 a, f32x2 b) {
-    f32x2 d;
-    asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]" : "=v"(d) : "v"(a), "v"(b));
-    return d;
-}
-__device__ __forceinline__ f32x2 pk_add_pi(f32x2 a, f32x2 b) {
-    f32x2 d;
-    asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1]" : "=v"(d) : "v"(a), "v"(b));
-    return d;
-}
-// race-hunt forms (ls_estimate_ringb_kernel<..., VAR & 2>): the destination never shares registers with a source
-__device__ __forceinline__ f32x2 pk_add_mi_ec(f32x2 a, f32x2 b) {
-    f32x2 d;
-    asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]" : "=&v"(d) : "v"(a), "v"(b));
-    return d;
-}
-__device__ __forceinline__ f32x2 pk_add_pi_ec(f32x2 a, f32x2 b) {
-    f32x2 d;
-    asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1]" : "=&v"(d) : "v"(a), "v"(b));
-    return d;
-}
-__device__ __forceinline__ f32x2 pk_cmul_ec(f32x2 x, f32x2 w) {
-    f32x2 t, d;
-    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[1,0]" : "=&v"(t) : "v"(x), "v"(w));
-    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_lo:[1,0,0]" : "=&v"(d) : "v"(x), "v"(w), "v"(t));
-    return d;
-}
-// VAR & 32: two idle cycles behind every op_sel operation (the next VALU instruction cannot follow it back to back)
-__device__ __forceinline__ f32x2 pk_add_mi_np(f32x2 a, f32x2 b) {
-    f32x2 d;
-    asm volatile("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]\n\ts_nop 1" : "=v"(d) : "v"(a), "v"(b));
-    return d;
-}
-__device__ __forceinline__ f32x2 pk_add_pi_np(f32x2 a, f32x2 b) {
-    f32x2 d;
-    asm volatile("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1]\n\ts_nop 1" : "=v"(d) : "v"(a), "v"(b));
-    return d;
-}
-__device__ __forceinline__ f32x2 pk_cmul_np(f32x2 x, f32x2 w) {
-    f32x2 t, d;
-    asm volatile("v_pk_mul_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[1,0]\n\ts_nop 1" : "=v"(t) : "v"(x), "v"(w));
-    asm volatile("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_lo:[1,0,0]\n\ts_nop 1" : "=v"(d) : "v"(x), "v"(w), "v"(t));
-    return d;
-}
-// VAR & 64: the same three operations without any op_sel / packed instruction (scalar fp32 adds and fmas; same rounding: one
-// rounding per add, the product term of the complex multiply rounded once before the fma as in the packed form)
+// a - i b  and  a + i b: one rounding per add, as the packed form had
 __device__ __forceinline__ f32x2 sc_add_mi(f32x2 a, f32x2 b) {
     float dx, dy;
     asm("v_add_f32 %0, %1, %2" : "=v"(dx) : "v"(a[0]), "v"(b[1]));
@@ -661,98 +609,12 @@ __device__ __forceinline__ f32x2 sc_add_pi(f32x2 a, f32x2 b) {
     asm("v_add_f32 %0, %1, %2" : "=v"(dy) : "v"(a[1]), "v"(b[0]));
     return f32x2{dx, dy};
 }
-__device__ __forceinline__ f32x2 sc_cmul(f32x2 x, f32x2 w) {
-    float t0, t1, dx, dy;
-    asm("v_mul_f32 %0, %1, %2" : "=v"(t0) : "v"(x[0]), "v"(w[0]));
-    asm("v_mul_f32 %0, %1, %2" : "=v"(t1) : "v"(x[1]), "v"(w[0]));
-    asm("v_fma_f32 %0, -%1, %2, %3" : "=v"(dx) : "v"(x[1]), "v"(w[1]), "v"(t0));
-    asm("v_fma_f32 %0, %1, %2, %3" : "=v"(dy) : "v"(x[0]), "v"(w[1]), "v"(t1));
-    return f32x2{dx, dy};
-}
 // x * w for w = (c, s):  (xr c - xi s, xi c + xr s)
 __device__ __forceinline__ f32x2 pk_cmul(f32x2 x, f32x2 w) {
     f32x2 t, d;
     asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[1,0]" : "=v"(t) : "v"(x), "v"(w));
     asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_lo:[1,0,0]" : "=v"(d) : "v"(x), "v"(w), "v"(t));
     return d;
-}
-// VAR & 96 == 96: the scalar forms with the same two idle cycles behind each operation group (volatile like the _np forms)
-__device__ __forceinline__ f32x2 sc_add_mi_np(f32x2 a, f32x2 b) {
-    float dx, dy;
-    asm volatile("v_add_f32 %0, %1, %2" : "=v"(dx) : "v"(a[0]), "v"(b[1]));
-    asm volatile("v_sub_f32 %0, %1, %2\n\ts_nop 1" : "=v"(dy) : "v"(a[1]), "v"(b[0]));
-    return f32x2{dx, dy};
-}
-__device__ __forceinline__ f32x2 sc_add_pi_np(f32x2 a, f32x2 b) {
-    float dx, dy;
-    asm volatile("v_sub_f32 %0, %1, %2" : "=v"(dx) : "v"(a[0]), "v"(b[1]));
-    asm volatile("v_add_f32 %0, %1, %2\n\ts_nop 1" : "=v"(dy) : "v"(a[1]), "v"(b[0]));
-    return f32x2{dx, dy};
-}
-__device__ __forceinline__ f32x2 sc_cmul_np(f32x2 x, f32x2 w) {
-    float t0, t1, dx, dy;
-    asm volatile("v_mul_f32 %0, %1, %2" : "=v"(t0) : "v"(x[0]), "v"(w[0]));
-    asm volatile("v_mul_f32 %0, %1, %2\n\ts_nop 1" : "=v"(t1) : "v"(x[1]), "v"(w[0]));
-    asm volatile("v_fma_f32 %0, -%1, %2, %3" : "=v"(dx) : "v"(x[1]), "v"(w[1]), "v"(t0));
-    asm volatile("v_fma_f32 %0, %1, %2, %3\n\ts_nop 1" : "=v"(dy) : "v"(x[0]), "v"(w[1]), "v"(t1));
-    return f32x2{dx, dy};
-}
-#if (CSI_LS_VAR_DEFAULT) & 512
-// 512 (tools/ls_opsel_hunt.sh, never in the product): every +-i rotation computed BOTH ways; a packed result that differs from the scalar one is logged
-// (operands, result, thread, workgroup) into a device buffer that csi_debug_opsel_log() copies out
-__device__ unsigned g_opsel_log[4 + 16 * 4096];
-__device__ __forceinline__ float opsel_copy(float x) { float y; asm volatile("v_mov_b32 %0, %1" : "=v"(y) : "v"(x)); return y; }
-__device__ __forceinline__ f32x2 opsel_both(unsigned kind, f32x2 a, f32x2 b) {
-    // every value that goes into the log is taken with an asm v_mov_b32 (the compiler can neither pack nor merge them): the operands BEFORE the packed
-    // operation, its result, the operands again AFTER it, and the result of the same instruction executed once more a few cycles later
-    const float a0 = opsel_copy(a[0]), a1 = opsel_copy(a[1]), b0 = opsel_copy(b[0]), b1 = opsel_copy(b[1]);
-    f32x2 p, q;
-    if (kind == 0) asm volatile("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]" : "=&v"(p) : "v"(a), "v"(b));
-    else asm volatile("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1]" : "=&v"(p) : "v"(a), "v"(b));
-    const float p0 = opsel_copy(p[0]), p1 = opsel_copy(p[1]);
-    const float a0l = opsel_copy(a[0]), a1l = opsel_copy(a[1]), b0l = opsel_copy(b[0]), b1l = opsel_copy(b[1]);
-    if (kind == 0) asm volatile("s_nop 7\n\tv_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]" : "=&v"(q) : "v"(a), "v"(b));
-    else asm volatile("s_nop 7\n\tv_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1]" : "=&v"(q) : "v"(a), "v"(b));
-    const float q0 = opsel_copy(q[0]), q1 = opsel_copy(q[1]);
-    float s0, s1;
-    if (kind == 0) { asm volatile("v_add_f32 %0, %1, %2" : "=v"(s0) : "v"(a0), "v"(b1)); asm volatile("v_sub_f32 %0, %1, %2" : "=v"(s1) : "v"(a1), "v"(b0)); }
-    else { asm volatile("v_sub_f32 %0, %1, %2" : "=v"(s0) : "v"(a0), "v"(b1)); asm volatile("v_add_f32 %0, %1, %2" : "=v"(s1) : "v"(a1), "v"(b0)); }
-    const auto u = [](float x) { return __builtin_bit_cast(unsigned, x); };
-    if (u(p0) != u(s0) || u(p1) != u(s1) || u(q0) != u(s0) || u(q1) != u(s1)) {
-        const unsigned i = atomicAdd(&g_opsel_log[0], 1u);
-        if (i < 4096) {
-            unsigned* e = g_opsel_log + 4 + 16 * i;
-            e[0] = kind | (threadIdx.x << 8); e[1] = blockIdx.x;
-            e[2] = u(a0); e[3] = u(a1); e[4] = u(b0); e[5] = u(b1); e[6] = u(p0); e[7] = u(p1);
-            e[8] = u(a0l); e[9] = u(a1l); e[10] = u(b0l); e[11] = u(b1l); e[12] = u(q0); e[13] = u(q1); e[14] = u(s0); e[15] = u(s1);
-        }
-    }
-    return p;
-}
-#endif
-template <int VAR>
-__device__ __forceinline__ f32x2 lsc_cmul_v(f32x2 x, f32x2 w) {
-    if (VAR & 256) return sc_cmul(x, w);          // 256: only the twiddle products in scalar operations
-    if ((VAR & 96) == 96) return sc_cmul_np(x, w);
-    return (VAR & 64) ? sc_cmul(x, w) : ((VAR & 32) ? pk_cmul_np(x, w) : ((VAR & 2) ? pk_cmul_ec(x, w) : pk_cmul(x, w)));
-}
-template <int VAR>
-__device__ __forceinline__ f32x2 lsc_add_mi_v(f32x2 a, f32x2 b) {
-#if (CSI_LS_VAR_DEFAULT) & 512
-    if (VAR & 512) return opsel_both(0, a, b);
-#endif
-    if (VAR & 128) return sc_add_mi(a, b);        // 128: only the +-i rotations (outputs 1 and 3 of a butterfly) in scalar operations
-    if ((VAR & 96) == 96) return sc_add_mi_np(a, b);
-    return (VAR & 64) ? sc_add_mi(a, b) : ((VAR & 32) ? pk_add_mi_np(a, b) : ((VAR & 2) ? pk_add_mi_ec(a, b) : pk_add_mi(a, b)));
-}
-template <int VAR>
-__device__ __forceinline__ f32x2 lsc_add_pi_v(f32x2 a, f32x2 b) {
-#if (CSI_LS_VAR_DEFAULT) & 512
-    if (VAR & 512) return opsel_both(1, a, b);
-#endif
-    if (VAR & 128) return sc_add_pi(a, b);
-    if ((VAR & 96) == 96) return sc_add_pi_np(a, b);
-    return (VAR & 64) ? sc_add_pi(a, b) : ((VAR & 32) ? pk_add_pi_np(a, b) : ((VAR & 2) ? pk_add_pi_ec(a, b) : pk_add_pi(a, b)));
 }
 
 // twc[off(st) + (m - 1) L + j] = exp(-2 pi i j m / (4 L)),  L = 4^st, off = 0 / 12 / 60: the three twiddles of butterfly
@@ -769,7 +631,7 @@ __device__ __forceinline__ void lsc_build_twiddles(f32x2* twc, const float* tw, 
 
 // stage 0 of the DIT transform for this wave's SPW rows of a raw (planar, natural-order) chunk slot: butterfly `lane`
 // takes samples rev3(lane) + 64 m; no twiddles
-template <int SPW, int NW, int VAR = CSI_LS_VAR_DEFAULT>
+template <int SPW, int NW>
 __device__ __forceinline__ void lsc_stage0_read(const float* srow, int rev3, f32x2 (&y)[SPW][4]) {
 #pragma unroll
     for (int u = 0; u < SPW; ++u) {
@@ -779,33 +641,26 @@ __device__ __forceinline__ void lsc_stage0_read(const float* srow, int rev3, f32
         for (int m = 0; m < 4; ++m) x[m] = f32x2{sr[64 * m], sr[LS_FFT + 64 * m]};
         const f32x2 a = x[0] + x[2], b = x[0] - x[2], c = x[1] + x[3], d = x[1] - x[3];
         y[u][0] = a + c;
-        y[u][1] = lsc_add_mi_v<VAR>(b, d);
+        y[u][1] = sc_add_mi(b, d);
         y[u][2] = a - c;
-        y[u][3] = lsc_add_pi_v<VAR>(b, d);
+        y[u][3] = sc_add_pi(b, d);
     }
 }
-// VAR (race hunt, tools/ls_race_fast.py; 0 in every product instantiation): 1 = s_waitcnt lgkmcnt(0) behind every stage's writes
-// (LDS write -> read order inside the wave), 2 = op_sel operations never in place, 4 = sixteen idle cycles per stage (the compiler
-// places them between the stage's VALU operations: a schedule perturbation, measured to RAISE the event rate ~70 x), 8 (kernel) =
-// every LDS-DMA of the wave landed before the "spectra complete" barrier, 16 = the sources of the op_sel adds stay live until the
-// stage's writes are out, 32 = two idle cycles behind every op_sel operation, 64 = no op_sel / packed operation at all (scalar forms)
-template <int SPW, int NW, int VAR = CSI_LS_VAR_DEFAULT>
+template <int SPW, int NW>
 __device__ __forceinline__ void lsc_stage0_write(f32x2* Fc, int wave, int lane, const f32x2 (&y)[SPW][4]) {
     const int p0 = 4 * lane + 4 * (lane >> 2);           // lsc_phys(4 lane): elements 4 lane .. 4 lane + 3, 32-byte aligned
-    if (VAR & 4) asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");
 #pragma unroll
     for (int u = 0; u < SPW; ++u) {
         f32x2* fc = Fc + (size_t)(wave + NW * u) * LSC_ROW + p0;
         *reinterpret_cast<f32x4*>(fc) = f32x4{y[u][0][0], y[u][0][1], y[u][1][0], y[u][1][1]};
         *reinterpret_cast<f32x4*>(fc + 2) = f32x4{y[u][2][0], y[u][2][1], y[u][3][0], y[u][3][1]};
     }
-    if (VAR & 1) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 // stages 1-3, NS rows interleaved in one instruction stream
-template <int NS, int VAR = CSI_LS_VAR_DEFAULT>
+template <int NS>
 __device__ __forceinline__ void lsc_fft_stages(f32x2* const (&fr)[NS], const f32x2* twc, int lane) {
 #pragma unroll
     for (int st = 1; st < 4; ++st) {
@@ -816,7 +671,7 @@ __device__ __forceinline__ void lsc_fft_stages(f32x2* const (&fr)[NS], const f32
         int p[4];
 #pragma unroll
         for (int m = 0; m < 4; ++m) p[m] = lsc_phys(base + m * L);
-        f32x2 x[NS][4], y[NS][4], w[4], bb[NS], dd[NS];
+        f32x2 x[NS][4], y[NS][4], w[4];
 #pragma unroll
         for (int n = 0; n < NS; ++n)
 #pragma unroll
@@ -826,48 +681,41 @@ __device__ __forceinline__ void lsc_fft_stages(f32x2* const (&fr)[NS], const f32
 #pragma unroll
         for (int n = 0; n < NS; ++n) {
 #pragma unroll
-            for (int m = 1; m < 4; ++m) x[n][m] = lsc_cmul_v<VAR>(x[n][m], w[m]);
+            for (int m = 1; m < 4; ++m) x[n][m] = pk_cmul(x[n][m], w[m]);
             const f32x2 a = x[n][0] + x[n][2], b = x[n][0] - x[n][2], c = x[n][1] + x[n][3], d = x[n][1] - x[n][3];
             y[n][0] = a + c;
-            y[n][1] = lsc_add_mi_v<VAR>(b, d);
+            y[n][1] = sc_add_mi(b, d);
             y[n][2] = a - c;
-            y[n][3] = lsc_add_pi_v<VAR>(b, d);
-            if (VAR & 16) { bb[n] = b; dd[n] = d; }
+            y[n][3] = sc_add_pi(b, d);
         }
         __builtin_amdgcn_wave_barrier();          // every lane has read before anyone overwrites
-        if (VAR & 4) asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");
 #pragma unroll
         for (int n = 0; n < NS; ++n)
 #pragma unroll
             for (int m = 0; m < 4; ++m) fr[n][p[m]] = y[n][m];
-        if (VAR & 1) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (VAR & 16) {          // the sources of the op_sel adds stay live (nothing may be allocated over them) until the stage's writes are out
-#pragma unroll
-            for (int n = 0; n < NS; ++n) asm volatile("" ::"v"(bb[n]), "v"(dd[n]) : "memory");
-        }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
 }
 // stages 1-3 of this wave's rows wave, wave + NW, ...: pairs interleaved when PAIR
-template <int SPW, int NW, bool PAIR, int VAR = CSI_LS_VAR_DEFAULT>
+template <int SPW, int NW, bool PAIR>
 __device__ __forceinline__ void lsc_fft_rows(f32x2* Fc, int wave, const f32x2* twc, int lane) {
     if (PAIR && SPW >= 2) {
 #pragma unroll
         for (int u = 0; u + 1 < SPW; u += 2) {
             f32x2* const pr[2] = {Fc + (size_t)(wave + NW * u) * LSC_ROW, Fc + (size_t)(wave + NW * (u + 1)) * LSC_ROW};
-            lsc_fft_stages<2, VAR>(pr, twc, lane);
+            lsc_fft_stages<2>(pr, twc, lane);
         }
         if (SPW & 1) {
             f32x2* const pr[1] = {Fc + (size_t)(wave + NW * (SPW - 1)) * LSC_ROW};
-            lsc_fft_stages<1, VAR>(pr, twc, lane);
+            lsc_fft_stages<1>(pr, twc, lane);
         }
     } else {
 #pragma unroll
         for (int u = 0; u < SPW; ++u) {
             f32x2* const pr[1] = {Fc + (size_t)(wave + NW * u) * LSC_ROW};
-            lsc_fft_stages<1, VAR>(pr, twc, lane);
+            lsc_fft_stages<1>(pr, twc, lane);
         }
     }
 }
@@ -1095,7 +943,7 @@ __device__ __forceinline__ void ls_bf_split2(float x0, float x1, uint32_t& p1, u
 
 constexpr int LSB_BLOCK = 512;      // bf16 elements of one (chunk, piece, antenna tile) block: [2 k-halves][32 rows][8 symbols]
 
-template <int JT, int NW, int NSTG, int NPP, int MINB = 1, bool DBF = false, int VAR = CSI_LS_VAR_DEFAULT>
+template <int JT, int NW, int NSTG, int NPP, int MINB = 1, bool DBF = false>
 __global__ __launch_bounds__(64 * NW, MINB) void ls_estimate_ringb_kernel(const LsArgs a, int nblk) {
     constexpr int CH = 16, SPW = CH / NW, QW = 8 / NW;
     constexpr int NB = NPP * JT, NPD = (NB + NW - 1) / NW;      // P blocks per chunk, LDS-DMAs per wave for them
@@ -1113,7 +961,7 @@ __global__ __launch_bounds__(64 * NW, MINB) void ls_estimate_ringb_kernel(const 
     const int nt = a.nt;
     const int nchunk = (nt + CH - 1) / CH;
     const int rev3 = ((lane & 3) << 4) | (lane & 12) | (lane >> 4);
-    if (a.dbg & 256) {        // race hunt (tools/ls_race_repro.py): the whole LDS of the workgroup starts as NaN - any read of a location this
+    if (a.dbg & 256) {        // the whole LDS of the workgroup starts as NaN - any read of a location this
                               // workgroup has not written yet turns into NaN results instead of plausible leftovers
         constexpr int NF = 2 * LSC_NTW + (DBF ? 2 : 1) * CH * 2 * LSC_ROW + NSTG * CH * 2 * LS_FFT + (NSTG + 1) * NPP * JT * LSB_BLOCK / 2;
         for (int i = tid; i < NF; i += 64 * NW) smem[i] = __builtin_bit_cast(float, 0x7fc00000u);
@@ -1223,7 +1071,7 @@ __global__ __launch_bounds__(64 * NW, MINB) void ls_estimate_ringb_kernel(const 
             else if (NSTG == 3 || younger == 2) ls_wait_vm<2 * R>();
             else ls_wait_vm<3 * R>();
             f32x2 y0[SPW][4];
-            lsc_stage0_read<SPW, NW, VAR>(S + (size_t)(((t % NSTG) * CH + wave) * 2) * LS_FFT, rev3, y0);
+            lsc_stage0_read<SPW, NW>(S + (size_t)(((t % NSTG) * CH + wave) * 2) * LS_FFT, rev3, y0);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             issue_next();
             if (ch == 0 && t > 0) store_item(blk - gridDim.x);
@@ -1235,9 +1083,8 @@ __global__ __launch_bounds__(64 * NW, MINB) void ls_estimate_ringb_kernel(const 
                 if (t > 0) ls_lds_barrier();      // spectra and P pieces of chunk t - 1 consumed
                 issue_pieces();                   // ... so the slot of those pieces takes chunk t + NSTG
             }
-            lsc_stage0_write<SPW, NW, VAR>(Fb, wave, lane, y0);
-            if (!(a.dbg & 1)) lsc_fft_rows<SPW, NW, (JT == 1), VAR>(Fb, wave, twc, lane);
-            if (VAR & 8) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");      // race hunt: no LDS-DMA of this wave in flight across the barrier
+            lsc_stage0_write<SPW, NW>(Fb, wave, lane, y0);
+            if (!(a.dbg & 1)) lsc_fft_rows<SPW, NW, (JT == 1)>(Fb, wave, twc, lane);
             ls_lds_barrier();                     // spectra complete; every wave has seen its P blocks of chunk t land
             if (DBF) issue_pieces();              // every wave is past the despread of chunk t - 1: its P slot takes chunk t + NSTG
 
@@ -1303,7 +1150,7 @@ __global__ __launch_bounds__(64 * NW, MINB) void ls_estimate_ringb_kernel(const 
             // ls_debug 64 puts the drain back for A/B runs.
             // End of round 4 (profiles/r04_ls_ringb_variants.txt): what IS seen, rarely and on some boxes only, with the
             // two-workgroups-per-CU instantiation <1, 4, 1, NPP, 2> (no longer selected: ls_ringb_min) is not a race at all - every bad
-            // item is the result of ONE v_pk_add_f32 with op_sel (pk_add_mi / pk_add_pi of a transform stage) wrong in lanes 48-63,
+            // item is the result of ONE v_pk_add_f32 with op_sel (the packed +-i rotation of a transform stage) wrong in lanes 48-63,
             // the first launch after another kernel, where a wave of the CU's OTHER workgroup runs these MFMAs on the same SIMD.
             // Round 6 closed it: that instruction form loses its swapped-in operand under exactly that condition; the rotations are
             // single adds in every instantiation now.

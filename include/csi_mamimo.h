@@ -378,9 +378,8 @@ int  csi_synchronize(csi_ctx* ctx);
  *                         cores with every fp32 value cut exactly into three bf16 pieces (one of the two is chosen
  *                         automatically for any other P, 16 <= Nt <= 128); a choice the kernel cannot serve falls back
  *   "ls_ringb_min"     the smallest Nt at which a non-Hadamard P takes kernel 7 (default 33; below, kernel 6 serves - DESIGN.md 4.2).
- *                         Kernel 7 runs ONE workgroup per CU at every Nt in the shipped library: its two-workgroups-per-CU form at
- *                         Nt <= 32 (rare wrong first items on some parts, never root-caused) exists only in the hunt build
- *                         (CSI_BUILD_DEFINES=CSI_LS_RACE_VARIANTS) and no option of the product build selects it
+ *                         Kernel 7 runs ONE workgroup per CU at every Nt: a two-workgroups-per-CU form at Nt <= 32 is not built
+ *                          and no option selects one
  *   get only: "ls_mode" (the kernel the next LS call runs), "ls_per_cu" (its resident workgroups per CU),
  *                         "ls_pilot_pieces" (bf16 pieces the entries of P need: 1 - 3)
  *   "ls_v2"            1: the runner-up shape (chunk length / ring depth) of kernels 5 and 6, for A/B runs
@@ -410,10 +409,9 @@ int  csi_synchronize(csi_ctx* ctx);
  *                         (parts in 1e-7).  Read-only: "hs_l0_mfma16_launches" counts the launches of the 16 form.
  *   "ls_fast_perm"     1 (default): a pilot matrix that is a signed row / column permutation of the Sylvester Hadamard matrix
  *                         takes the Walsh-Hadamard LS kernel through permutation tables; 0: the generic kernels (A/B runs)
- *   "ls_overlap_cus", "ls_overlap_stride"  csi_estimate_device: run the LS kernel on a side stream masked to this many CUs beside
- *                         the DNN kernels.  An experiment that measured slower than the serial order: the product
- *                         build REFUSES "ls_overlap_cus" > 0 (CSI_ERR_INVALID_ARG with text); the hunt build
- *                         (CSI_BUILD_DEFINES=CSI_LS_RACE_VARIANTS) accepts it
+ *   "ls_overlap_cus"   always 0.  It ran the LS kernel of csi_estimate_device on a side stream masked to this many CUs beside the DNN
+ *                         kernels: an experiment that measured slower than the serial order and was removed.
+ *                         Setting 0 succeeds, anything else is refused (CSI_ERR_INVALID_ARG with text)
  *   "hp_side_threads"  host-buffer entry points: 1 (default) input staging and result staging on their own threads beside the
  *                         caller's enqueue loop; 0: inline on the calling thread, in turn (A/B runs)
  *   "hp_chunk_packets" packets per pipeline slot of csi_estimate_c128 (0 = automatic)
@@ -421,7 +419,7 @@ int  csi_synchronize(csi_ctx* ctx);
  *   "train_rank"       0 (default) .. 2^20 - 1: rank of this process in a data-parallel fit.  The trainers fold it into the noise and
  *                         dropout streams (not into the Glorot initialisation), so every rank draws its own noise and masks for its
  *                         shard of the global batch; rank 0 has the streams of a single process.  Takes effect at the next step.
- *   "ls_debug"         development switches of the LS kernels (tools/ls_race_*.py); write-only, 0 in production */
+ *   "ls_debug"         development switches of the LS kernels (skip phases for timing: tools/ls_probe.py); write-only, 0 in production */
 int  csi_set_option(csi_ctx* ctx, const char* name, int64_t value);
 /* Current value of an option, or of the read-only values: "hs_launches" (split-engine GEMMs launched), "hs_range_fallbacks"
  * (csi_predict calls repeated on the fp32 MFMA kernels), "hs_weight_pins" / "hs_weight_err_e12" (layers pinned to the fp32 kernels

@@ -136,7 +136,6 @@ hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) {
     *s = reinterpret_cast<hipStream_t>(p);
     return hipSuccess;
 }
-hipError_t hipExtStreamCreateWithCUMask(hipStream_t* s, uint32_t, const uint32_t*) { return hipStreamCreateWithFlags(s, 0); }
 hipError_t hipStreamDestroy(hipStream_t s) {
     {
         std::lock_guard<std::mutex> lk(mock::g_mu);

@@ -601,8 +601,8 @@ def test_profile_entry_points(pkg, oracle):
 
 
 def test_engine_close_frees_its_device_arrays(pkg, oracle):
-    """A DeviceArray that is still alive when its engine closes is freed by close() (it used to survive as leaked HBM: the loop of
-    tools/ls_race_fast.py ran a 288 GB part out of memory), and freeing it again afterwards is harmless."""
+    """A DeviceArray that is still alive when its engine closes is freed by close() (it used to survive as leaked HBM: a probe that made
+    a fresh engine per cycle ran a 288 GB part out of memory), and freeing it again afterwards is harmless."""
     e = pkg.CsiEngine(4, 2, hidden=(8,))
     a = e.empty((3, 5))
     b = e.to_device(np.arange(12, dtype=np.float32).reshape(3, 4))

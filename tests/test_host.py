@@ -575,20 +575,26 @@ def test_probe_tools_still_compile(src, tmp_path):
 
 
 def test_pkadd_probe_uses_the_kernels_own_instructions(tmp_path):
-    """tools/pkadd_mfma_probe.hip re-states the three op_sel operations of the LS kernels' transform (every rare bad item
-    of the two-workgroups-per-CU kernel is one of their results): the instruction strings must stay the product's, and it must compile."""
+    """tools/pkadd_mfma_probe.hip re-states the three op_sel operations the LS kernels' transform had (every rare bad item
+    of the two-workgroups-per-CU kernel was one of their results).  The twiddle product's instruction strings must stay the product's; the
+    packed +-i rotations left the product (single adds), so the probe's must stay, string for string, the form that went wrong -
+    the one tools/opsel_census.py looks for in the library's machine code.  And it must compile."""
     import re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     prod = open(os.path.join(root, 'dl-channel-estimation-mamimo_amd', 'csrc', 'ls_estimate.hip.h')).read()
     probe = open(os.path.join(root, 'tools', 'pkadd_mfma_probe.hip')).read()
+    sys.path.insert(0, os.path.join(root, 'tools'))
+    import opsel_census
 
     def ops(text, fn):
         body = text[text.index('f32x2 %s(' % fn):]
         body = body[:body.index('return d;')]
         return re.findall(r'asm\("([^"]+)"', body)
-    for fn, n in (('pk_add_mi', 1), ('pk_add_pi', 1), ('pk_cmul', 2)):
-        a, b = ops(prod, fn), ops(probe, fn)
-        assert len(a) == n and a == b, (fn, a, b)
+    a, b = ops(prod, 'pk_cmul'), ops(probe, 'pk_cmul')
+    assert len(a) == 2 and a == b, (a, b)
+    assert ops(probe, 'pk_rot_mi') == ['v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]']
+    assert ops(probe, 'pk_rot_pi') == ['v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1]']
+    assert all(opsel_census.vulnerable(ops(probe, fn)[0]) for fn in ('pk_rot_mi', 'pk_rot_pi'))
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
     if not os.path.exists(hipcc):
         pytest.skip('no hipcc')

@@ -2,7 +2,7 @@
 // return a wrong value in its last quarter-wave when the SIMD's other wave, of ANOTHER workgroup, issues bf16 MFMAs?
 //
 // Why: DESIGN.md 4.2 / profiles/r04_ls_ringb_variants.txt.  Every one of the rare bad items of ls_estimate_ringb_kernel<1, 4, 1, NPP, 2>
-// (two workgroups per CU) is the result of ONE such instruction (pk_add_mi / pk_add_pi of a radix-4 butterfly) wrong in lanes 48-63,
+// (two workgroups per CU) is the result of ONE such instruction (the packed +-i rotation of a radix-4 butterfly) wrong in lanes 48-63,
 // at the first launch after another kernel, on some boxes of the pool.  The LS kernel executes a few hundred of these operations per
 // item; this probe executes ~10^9 per second per CU under the suspected conditions and checks every result in the kernel:
 //   * grid of 2 x 256 workgroups of 4 waves, 78 KiB of LDS each, so that two share a CU (one wave of each per SIMD);
@@ -38,13 +38,14 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
         }                                                                                          \
     } while (0)
 
-// ---- the LS kernel's operations, string for string (ls_estimate.hip.h: pk_add_mi, pk_add_pi, pk_cmul)
-__device__ __forceinline__ f32x2 pk_add_mi(f32x2 a, f32x2 b) {
+// ---- the LS kernel's operations, string for string: the twiddle product as it is today (ls_estimate.hip.h: pk_cmul) and the packed +-i rotations as they
+// were until the product took single adds in their place
+__device__ __forceinline__ f32x2 pk_rot_mi(f32x2 a, f32x2 b) {
     f32x2 d;
     asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]" : "=v"(d) : "v"(a), "v"(b));
     return d;
 }
-__device__ __forceinline__ f32x2 pk_add_pi(f32x2 a, f32x2 b) {
+__device__ __forceinline__ f32x2 pk_rot_pi(f32x2 a, f32x2 b) {
     f32x2 d;
     asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1]" : "=v"(d) : "v"(a), "v"(b));
     return d;
@@ -107,9 +108,9 @@ __device__ void check_role(ProbeOut* o, int iters, uint32_t rep) {
             for (int m = 1; m < 4; ++m) t[m] = pk_cmul(x[n][m], w[m]);
             const f32x2 a = t[0] + t[2], b = t[0] - t[2], c = t[1] + t[3], d = t[1] - t[3];
             y[n][0] = a + c;
-            y[n][1] = pk_add_mi(b, d);
+            y[n][1] = pk_rot_mi(b, d);
             y[n][2] = a - c;
-            y[n][3] = pk_add_pi(b, d);
+            y[n][3] = pk_rot_pi(b, d);
         }
         // scalar form
 #pragma unroll
