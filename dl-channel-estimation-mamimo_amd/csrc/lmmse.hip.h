@@ -11,7 +11,10 @@
 //     R (R + s I)^-1 H = H - s (R + s I)^-1 H, so only ONE Hermitian-Toeplitz system with Nt
 //     right-hand sides is solved per (packet, rx) - no inverse, no 234x234 matrix in memory.
 //   * Levinson recursion (O(n^2) per right-hand side, O(n) storage), in fp64 (the vector fp64
-//     rate of gfx950 makes this cheap; R + s I has condition numbers up to ~1e4).
+//     rate of gfx950 makes this cheap).  The condition number of R + s I grows with the SNR and
+//     as tau_rms shrinks: hundreds for tau_rms of 20-30 bins, but with the sweep's 8-tap profile
+//     (tau_rms 0.95) 1.3e3 at 10 dB, 4e4 at 25 dB and 1.3e6 at 40 dB, and 234 / s for one tap
+//     (2.3e8 at 60 dB) - fp32 would not do.
 //   * one workgroup per (packet, rx, 32 tx antennas): 8 lanes per right-hand side, each lane keeps
 //     30 solution entries in registers; the shared forward vector lives in LDS (ping-pong, one
 //     barrier per recursion step); the LS columns are staged in LDS and reused for the output.
@@ -74,8 +77,12 @@ __global__ __launch_bounds__(LM_THREADS) void lmmse_levinson_kernel(const LmmseA
         s1 += w * k;
         s2 += w * k * (double)k;
     }
-    const double r = s1 / hh, r2 = s2 / hh;
-    const double tau_rms = sqrt(fmax(r2 - r * r, 0.0));
+    // an all-zero h has no delay spread: tau_rms = 0 (LMMSE_ce.m divides 0 by 0 there and returns NaN)
+    double tau_rms = 0.0;
+    if (hh > 0.0) {
+        const double r = s1 / hh, r2 = s2 / hh;
+        tau_rms = sqrt(fmax(r2 - r * r, 0.0));
+    }
     const double c = 2.0 * M_PI * tau_rms / LM_N;                       // :31-32, df = 1/Nfft
     const double sig2 = pow(10.0, -0.1 * (double)a.snr_db[blk]);        // 1/snr
     const double t0 = 1.0 + sig2;                                       // diagonal of Rpp

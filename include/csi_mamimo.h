@@ -196,7 +196,9 @@ int  csi_estimate_c64(csi_ctx* ctx, const float* ltf_c64, int64_t npkt, float* d
 /* LMMSE smoothing of an LS estimate (the 'hDmmse' output of helperMIMOChannelEstimate.m:37-39,
  * LMMSE_ce.m:23-39 with Nfft = Np = 234, Nps = 1).  h_re / h_im: LS estimate [npkt][nr][nt][234];
  * hvec [npkt][L]: the vector the reference passes as LMMSE_ce's 'h' (generate_maMIMO_LTF.m:342
- * hands it the scatterer delays h_tau); snr_db [npkt][nr]: SNR(i) in dB; out like h. */
+ * hands it the scatterer delays h_tau); snr_db [npkt][nr]: SNR(i) in dB; out like h.
+ * An all-zero hvec row is taken as zero delay spread (tau_rms = 0, the result for a one-tap row); the reference formula
+ * divides 0 by 0 there (LMMSE_ce.m:28-29) and yields NaN. */
 int  csi_lmmse_estimate(csi_ctx* ctx, const float* h_re, const float* h_im, int64_t npkt, const float* hvec, int L,
                         const float* snr_db, float* out_re, float* out_im);
 int  csi_lmmse_estimate_device(csi_ctx* ctx, const float* d_h_re, const float* d_h_im, int64_t npkt, const float* d_hvec,

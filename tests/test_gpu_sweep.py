@@ -110,7 +110,7 @@ def _link_bound(ref, est, eps):
     return ((2 * eps * e * d + eps ** 2 * e ** 2) / r2).reshape(ref.shape[0], -1).mean(axis=1)
 
 
-@pytest.mark.parametrize('snr', [-10.0, 5.0])
+@pytest.mark.parametrize('snr', [-10.0, 5.0, 10.0, 40.0])      # 10 dB: the top of the default sweep; 40 dB: where the smoother is hardest
 def test_a_level_against_the_oracle(pkg, oracle, snr):
     from dl_channel_estimation_mamimo_amd import sweep
     nt, nr, npkt, hidden = 8, 2, 6, (64, 64)
