@@ -72,6 +72,10 @@ SYMBOLS = {
     'csi_hybrid_set_dictionary': (ctypes.c_int, [_ctx, _fp, _fp, ctypes.c_int]),
     'csi_hybrid_weights': (ctypes.c_int, [_ctx, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_vp] * 7),
     'csi_hybrid_weights_device': (ctypes.c_int, [_ctx, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_vp] * 7),
+    'csi_link_frame_bits': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
+    'csi_viterbi_decode_device': (ctypes.c_int, [_ctx, _vp, ctypes.c_int64, ctypes.c_int64, _vp]),
+    'csi_link_sim_device': (ctypes.c_int, [_ctx] + [_vp] * 7 + [ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                              ctypes.c_int] + [_vp] * 8),
     'csi_capture_begin': (ctypes.c_int, [_ctx]),
     'csi_capture_end': (ctypes.c_int, [_ctx, ctypes.POINTER(ctypes.c_void_p)]),
     'csi_capture_launch': (ctypes.c_int, [_ctx, _vp]),

@@ -24,6 +24,7 @@
 #include "input_pool.hip.h"
 #include "conv_frontend.hip.h"
 #include "synth_structured.hip.h"
+#include "link_sim.hip.h"
 
 using namespace csi;
 
@@ -53,13 +54,15 @@ enum KernelId {
     K_HYB_SOLVE,         // hybrid weights: Cholesky row, coefficients and residual of one matching-pursuit step
     K_HYB_FINISH,        // hybrid weights: gain and per-packet mean of the analog part
     K_SYNTH_STRUCTURED,  // known-channel sounding packets (synth_structured.hip.h): the power pass and the packet pass of csi_synth_structured
+    K_LINK_TXRX,         // link simulation: encoder, precoder, true channel, zero forcing and soft bits per (packet, subcarrier) (link_sim.hip.h)
+    K_LINK_VITERBI,      // link simulation: one-wavefront Viterbi decoder per codeword, traceback and bit errors
     K_COUNT
 };
 const char* const kKernelNames[K_COUNT] = {
     "layer0_ltf_gemm", "splitk_reduce", "pair_dense_gemm", "dense_hidden_gemm", "regressor_gemm",
     "ls_estimate", "naive_dense0_gemm", "synth_white", "pilot_table", "cast_bf16", "pair_h1_bf16", "lmmse_levinson",
     "train_gemm", "train_elementwise", "nmse_links", "pair_dense_tail", "input_pool", "conv_frontend",
-    "hybrid_svd", "hybrid_corr_argmax", "hybrid_solve", "hybrid_finish", "synth_structured"};
+    "hybrid_svd", "hybrid_corr_argmax", "hybrid_solve", "hybrid_finish", "synth_structured", "link_txrx", "link_viterbi"};
 
 thread_local std::string g_create_error;
 
@@ -193,6 +196,9 @@ struct csi_ctx {
     int hyb_rays = 0, hyb_rp = 0;
     char* hyb_ws = nullptr;
     size_t hyb_ws_bytes = 0;
+    char* link_ws = nullptr;     // link simulation (csi_link.hpp): coded bits and, when the caller keeps none, the soft bits of a packet chunk
+    size_t link_ws_bytes = 0;
+    int64_t link_launches = 0;   // "link_launches": kernels launched by csi_link_sim_device / csi_viterbi_decode_device
     bool user_capture = false;   // between csi_capture_begin and csi_capture_end (csi_hybrid.hpp): device-pointer calls are recorded, not run
     bool user_capture_use_graph = false;
     int64_t user_capture_hs0 = 0;

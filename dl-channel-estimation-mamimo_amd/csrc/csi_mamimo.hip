@@ -19,6 +19,7 @@
 #include "csi_hostpipe.hpp"
 #include "csi_comm.hpp"
 #include "csi_hybrid.hpp"
+#include "csi_link.hpp"
 
 namespace {
 
@@ -562,6 +563,7 @@ void csi_destroy(csi_ctx* c) {
     if (c->P) hipFree(c->P);
     if (c->hyb_at_re) hipFree(c->hyb_at_re);
     if (c->hyb_ws) hipFree(c->hyb_ws);
+    if (c->link_ws) hipFree(c->link_ws);
     if (c->hs_peak) hipFree(c->hs_peak);
     if (c->hs_zero) hipFree(c->hs_zero);
     if (c->fuse_ws) hipFree(c->fuse_ws);
@@ -1261,6 +1263,25 @@ void csi_capture_free(csi_ctx* c, void* graph) {
     delete g;
 }
 
+// ---------------------------------------------------------------- link simulation (csi_link.hpp, link_sim.hip.h)
+int csi_link_frame_bits(int ns, int n_sym, int bps, int64_t* n_info, int64_t* n_coded) {
+    return link_frame(ns, n_sym, bps, n_info, n_coded) ? CSI_OK : CSI_ERR_INVALID_ARG;
+}
+
+int csi_viterbi_decode_device(csi_ctx* c, const float* d_llr, int64_t ncw, int64_t n_steps, uint8_t* d_bits) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return viterbi_decode_device(c, d_llr, ncw, n_steps, d_bits);
+}
+
+int csi_link_sim_device(csi_ctx* c, const float* d_h_re, const float* d_h_im, const float* d_fbb_re, const float* d_fbb_im, const float* d_frf_re,
+                        const float* d_frf_im, const float* d_noise_var, uint64_t seed, int64_t first_pkt, int64_t npkt, int ns, int ntrf, int n_sym,
+                        int bps, int32_t* d_bit_errors, float* d_evm_rms, float* d_dt_snr_db, float* d_xeq_re, float* d_xeq_im, float* d_csi,
+                        float* d_llr, uint8_t* d_bits) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return link_sim_device(c, d_h_re, d_h_im, d_fbb_re, d_fbb_im, d_frf_re, d_frf_im, d_noise_var, seed, first_pkt, npkt, ns, ntrf, n_sym, bps,
+                           d_bit_errors, d_evm_rms, d_dt_snr_db, d_xeq_re, d_xeq_im, d_csi, d_llr, d_bits);
+}
+
 // ---------------------------------------------------------------- accuracy metric
 int csi_nmse_device(csi_ctx* c, const float* d_ref_re, const float* d_ref_im, const float* d_est_re, const float* d_est_im,
                     int64_t nlinks, int n_bins, float* d_per_link, double* mean_out) {
@@ -1334,6 +1355,7 @@ int csi_get_option(csi_ctx* c, const char* name, int64_t* value) {
     else if (n == "model_type") *value = c->model_type;
     else if (n == "conv_launches") *value = c->conv_launches;
     else if (n == "hybrid_launches") *value = c->hybrid_launches;
+    else if (n == "link_launches") *value = c->link_launches;
     else if (n == "small_rows") *value = c->small_rows;
     else if (n == "small_rows_band") *value = c->small_rows_band;
     else if (n == "f32_engine") *value = c->f32_engine;

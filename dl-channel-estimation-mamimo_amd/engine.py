@@ -66,6 +66,7 @@ class DeviceArray:
 
 
 HybridWeights = collections.namedtuple('HybridWeights', 'fbb idx n_atoms gain frf_mean')
+LinkResult = collections.namedtuple('LinkResult', 'bit_errors evm_rms dt_snr_db n_info xeq csi llr bits')
 
 
 def frf_from_idx(At, idx):
@@ -621,6 +622,80 @@ class CsiEngine:
         self._check(self._lib.csi_hybrid_weights_device(self._ctx, d_h_re.ptr, d_h_im.ptr, ptr(d_eval_re), ptr(d_eval_im), int(npkt), int(ns), int(ntrf),
                                                         float(stop_tol), d_fbb_re.ptr, d_fbb_im.ptr, d_idx.ptr, ptr(d_n_atoms), ptr(d_gain),
                                                         ptr(d_frf_mean_re), ptr(d_frf_mean_im)))
+
+    # ------------------------------------------------------------------ link simulation (csrc/link_sim.hip.h)
+    def link_frame_bits(self, ns, n_sym=10, bps=2):
+        """(n_info, n_coded) of one packet's codeword: n_coded = ns n_sym 234 bps, n_info = n_coded / 3 - 6."""
+        n_info, n_coded = ctypes.c_int64(0), ctypes.c_int64(0)
+        if self._lib.csi_link_frame_bits(int(ns), int(n_sym), int(bps), ctypes.byref(n_info), ctypes.byref(n_coded)) != 0:
+            raise CsiError(-1, f'csi_link_frame_bits: ns {ns} outside 1 .. 4, n_sym {n_sym} < 1 or bps {bps} not in (2, 4)')
+        return int(n_info.value), int(n_coded.value)
+
+    def link_sim_device(self, d_h_re, d_h_im, d_fbb_re, d_fbb_im, d_frf_re, d_frf_im, d_noise_var, seed, first_pkt, npkt, ns, ntrf,
+                        d_bit_errors, d_evm_rms, d_dt_snr_db, n_sym=10, bps=2, d_xeq_re=None, d_xeq_im=None, d_csi=None, d_llr=None,
+                        d_bits=None):
+        """Coded QAM through the true channel planes d_h ([npkt,nr,nt,234]) with the hybrid weights d_fbb ([npkt,234,ns,ntrf]) and
+        d_frf ([npkt,ntrf,nt], the frf_mean planes) as hybrid_weights_device writes them, noise of variance d_noise_var[p], zero forcing,
+        soft bits and Viterbi decoding (csi_link_sim_device).  Asynchronous, on the engine's stream.  d_bit_errors [npkt] holds int32
+        (``download().view(np.int32)``); d_bits holds npkt * n_info bytes (``download().view(np.uint8)``); the optional arrays may be None."""
+        ptr = lambda a: None if a is None else a.ptr
+        self._check(self._lib.csi_link_sim_device(self._ctx, d_h_re.ptr, d_h_im.ptr, d_fbb_re.ptr, d_fbb_im.ptr, d_frf_re.ptr, d_frf_im.ptr,
+                                                  d_noise_var.ptr, int(seed), int(first_pkt), int(npkt), int(ns), int(ntrf), int(n_sym), int(bps),
+                                                  d_bit_errors.ptr, d_evm_rms.ptr, d_dt_snr_db.ptr, ptr(d_xeq_re), ptr(d_xeq_im), ptr(d_csi),
+                                                  ptr(d_llr), ptr(d_bits)))
+
+    def link_sim(self, h, fbb, frf_mean, noise_var, seed=0, first_pkt=0, n_sym=10, bps=2, details=False):
+        """The same from numpy arrays: h complex [npkt,nr,nt,234], fbb complex [npkt,234,ns,ntrf], frf_mean complex [npkt,ntrf,nt],
+        noise_var [npkt] (or a scalar).  Returns LinkResult(bit_errors int32 [npkt], evm_rms, dt_snr_db float32 [npkt], n_info, ...);
+        with details=True also xeq complex64 [npkt,ns,n_sym,234], csi [npkt,ns,234], llr [npkt,n_coded] and the decoded bits uint8
+        [npkt,n_info] (None otherwise)."""
+        h, fbb, frf_mean = np.asarray(h), np.asarray(fbb), np.asarray(frf_mean)
+        npkt = h.shape[0] if h.ndim else 0
+        if h.shape != (npkt, self.nr, self.nt, N_DATA):
+            raise CsiError(-1, f'h must be [npkt,{self.nr},{self.nt},{N_DATA}], got {h.shape}')
+        if fbb.ndim != 4 or fbb.shape[:2] != (npkt, N_DATA):
+            raise CsiError(-1, f'fbb must be [{npkt},{N_DATA},ns,ntrf], got {fbb.shape}')
+        ns, ntrf = fbb.shape[2:]
+        if frf_mean.shape != (npkt, ntrf, self.nt):
+            raise CsiError(-1, f'frf_mean must be [{npkt},{ntrf},{self.nt}], got {frf_mean.shape}')
+        nv = np.ascontiguousarray(np.broadcast_to(np.asarray(noise_var, np.float32), (npkt,)))
+        n_info, n_coded = self.link_frame_bits(ns, n_sym, bps)
+        dev = [self.to_device(_f32c(a)) for a in (h.real, h.imag, fbb.real, fbb.imag, frf_mean.real, frf_mean.imag, nv)]
+        outs = [self.empty((npkt,)) for _ in range(3)]
+        extra = [None] * 5
+        if details:
+            extra = [self.empty((npkt, ns, n_sym, N_DATA)), self.empty((npkt, ns, n_sym, N_DATA)), self.empty((npkt, ns, N_DATA)),
+                     self.empty((npkt, n_coded)), self.empty(((npkt * n_info + 3) // 4,))]
+        try:
+            self.link_sim_device(*dev, seed, first_pkt, npkt, ns, ntrf, *outs, n_sym=n_sym, bps=bps, d_xeq_re=extra[0], d_xeq_im=extra[1],
+                                 d_csi=extra[2], d_llr=extra[3], d_bits=extra[4])
+            self.synchronize()
+            res = LinkResult(outs[0].download().view(np.int32), outs[1].download(), outs[2].download(), n_info,
+                             (extra[0].download() + 1j * extra[1].download()).astype(np.complex64) if details else None,
+                             extra[2].download() if details else None, extra[3].download() if details else None,
+                             extra[4].download().view(np.uint8)[:npkt * n_info].reshape(npkt, n_info).copy() if details else None)
+        finally:
+            for a in dev + outs + extra:
+                if a is not None:
+                    a.free()
+        return res
+
+    def viterbi_decode(self, llr):
+        """Viterbi decoding of terminated codewords of the rate-1/3 K = 7 code (133, 171, 165): llr float [ncw, 3 n_steps], positive = 0
+        -> uint8 [ncw, n_steps - 6] (csi_viterbi_decode_device; fp32 metrics, ties to the predecessor with the lower state number)."""
+        llr = _f32c(llr)
+        if llr.ndim != 2 or llr.shape[1] % 3:
+            raise CsiError(-1, f'llr must be [ncw, 3 n_steps], got {llr.shape}')
+        ncw, n_steps = llr.shape[0], llr.shape[1] // 3
+        n_info = max(n_steps - 6, 0)
+        d_llr, d_bits = self.to_device(llr), self.empty(((ncw * n_info + 3) // 4,))
+        try:
+            self._check(self._lib.csi_viterbi_decode_device(self._ctx, d_llr.ptr or None, ncw, n_steps, d_bits.ptr or None))
+            self.synchronize()
+            return d_bits.download().view(np.uint8)[:ncw * n_info].reshape(ncw, n_info).copy()
+        finally:
+            d_llr.free()
+            d_bits.free()
 
     def capture_begin(self):
         """Record the device-pointer calls that follow (estimate_device, hybrid_weights_device, ...) into one hipGraph instead of

@@ -1,13 +1,17 @@
 """The evaluation the reference exists for, in the order its pipeline runs it (full_pipeline_maMIMO_DNNEst.sh:40-58): a noise-free
 training set, a fit of both component models, and per SNR level the NMSE of the LS, the LMMSE and the DNN estimate against the
-true channel with 95 % confidence intervals - the "MSE" curve of snr_loop_testing.m:33-64,88-94.
+true channel with 95 % confidence intervals - the "MSE" curve of snr_loop_testing.m:33-64,88-94.  With --ber the data phase of
+BER_test_maMIMO_LTF.m:408-646 follows per level: the hybrid weights of every estimate (and of the true channel, "perfect") precode
+coded QAM through the true channel, giving the bers_ / EVM_rms_ / dtSNR_ families of metrics.mat.
 
     python -m dl_channel_estimation_mamimo_amd.sweep -d OUT [--nTX 32 --nRX 4 --nn 1024 1024 --useBN --bs 256 ...]
+                                                            [--ber --numSTS 1 --rays 500 --dataSymbols 10 --bps 2]
 
 The module holds no arithmetic of its own: packets with a known channel come from csi_synth_structured, labels from
 csi_ls_estimate_device, the fit from trainer.fit, the estimates from csi_estimate_device / csi_lmmse_estimate_device and every
-NMSE from csi_nmse_device.  Only the per-packet mean of the per-link ratios (NMSE_subk, BER_test_maMIMO_LTF.m:675-686) and the
-confidence interval are taken on the host.  BER, EVM and the beamforming gain of BER_test_maMIMO_LTF.m are not computed."""
+NMSE from csi_nmse_device; the hybrid weights from csi_hybrid_weights_device and bit errors, EVM and beamforming gain from
+csi_link_sim_device, with the noise level of a data symbol from synth.link_noise_var.  Only the per-packet mean of the per-link
+ratios (NMSE_subk, BER_test_maMIMO_LTF.m:675-686), errors / n_info and the confidence interval are taken on the host."""
 import argparse
 import json
 import os
@@ -22,6 +26,8 @@ from . import synth, trainer
 from .engine import N_DATA
 
 ESTIMATORS = ('LS', 'MMSE', 'DNN')
+SOURCES = ESTIMATORS + ('perfect',)      # --ber: whose hybrid weights precode the data phase (perfect = the true channel)
+LINK_FIELDS = ('bers_', 'EVM_rms_', 'dtSNR_')
 
 
 def tap_profile(n_taps=8):
@@ -58,17 +64,20 @@ def make_dataset(engine, n_train, seed, n_taps=8, amp_scale=True):
     return ds.dataset_from_packets(ltf, labels, engine.pilot)
 
 
-def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=True, keep=False):
+def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=True, keep=False, ber=None):
     """npkt test packets at `snr_db` (packets first_pkt ... of stream `seed`: keep them disjoint from the training packets), LS + DNN
     (estimate_device), the LMMSE smoother on the LS planes, and NMSE_subk of the three estimates against the true channel.
     Returns {'MSE_LS', 'MSE_MMSE', 'MSE_DNN'}: float64 [npkt], the per-link ratios averaged per packet.
 
     LMMSE inputs: hvec is the generator's tap profile exp(-0.5 t) / sqrt(2), the impulse response LMMSE_ce.m's `h` stands for (the
     reference hands it the scatterer delays h_tau, generate_maMIMO_LTF.m:342, which a synthetic channel does not have); snr_db[p][r]
-    is the level.  keep=True adds 'arrays': the DeviceArrays ltf_re, ltf_im, h_re, h_im, ls_re, ls_im (the caller frees them)."""
+    is the level.  keep=True adds 'arrays': the DeviceArrays ltf_re, ltf_im, h_re, h_im, ls_re, ls_im (the caller frees them).
+
+    ber = dict(ns, ntrf, n_sym, bps) adds the data phase (link_level): 'bers_X', 'EVM_rms_X', 'dtSNR_X' float64 [npkt] for X in SOURCES
+    and 'MSE_perfect' (zeros).  The engine needs a dictionary (set_dictionary)."""
     nr, nt = engine.nr, engine.nt
-    d_re, d_im, h_re, h_im, _ = engine.synth_structured(seed, first_pkt, npkt, snr_db=float(snr_db), n_taps=n_taps, amp_scale=amp_scale,
-                                                        want_noise_std=False)
+    d_re, d_im, h_re, h_im, d_std = engine.synth_structured(seed, first_pkt, npkt, snr_db=float(snr_db), n_taps=n_taps, amp_scale=amp_scale,
+                                                            want_noise_std=ber is not None)
     shape = (npkt, nr, nt, N_DATA)
     o_re, o_im, ls_re, ls_im, m_re, m_im = (engine.empty(shape) for _ in range(6))
     engine.estimate_device(d_re, d_im, npkt, o_re, o_im, ls_re, ls_im, checked=True)
@@ -81,11 +90,41 @@ def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=Tr
     for name, (e_re, e_im) in zip(ESTIMATORS, ((ls_re, ls_im), (m_re, m_im), (o_re, o_im))):
         engine.nmse_device(h_re, h_im, e_re, e_im, npkt * nr * nt, N_DATA, d_per_link=d_link)
         out['MSE_' + name] = d_link.download().astype(np.float64).reshape(npkt, nr * nt).mean(axis=1)
+    if ber is not None:
+        planes = dict(LS=(ls_re, ls_im), MMSE=(m_re, m_im), DNN=(o_re, o_im), perfect=(h_re, h_im))
+        out.update(link_level(engine, planes, h_re, h_im, d_std, npkt, seed, first_pkt, amp_scale=amp_scale, **ber))
+        out['MSE_perfect'] = np.zeros(npkt)
+        d_std.free()
     kept = (d_re, d_im, h_re, h_im, ls_re, ls_im)
     for a in (o_re, o_im, m_re, m_im, d_hvec, d_snr, d_link) + (() if keep else kept):
         a.free()
     if keep:
         out['arrays'] = kept
+    return out
+
+
+def link_level(engine, planes, h_re, h_im, d_noise_std, npkt, seed, first_pkt, ns=1, ntrf=None, n_sym=10, bps=2, amp_scale=True):
+    """The data phase of one level on resident planes: for every source X of `planes` = {X: (re, im) DeviceArrays [npkt,nr,nt,234]} the
+    hybrid weights of X's planes (hybrid_weights_device) precode coded QAM through the TRUE channel h (link_sim_device) - the same
+    bits and the same noise for every source, a paired comparison.  The noise level of a data symbol is that of the sounding phase
+    (synth.link_noise_var of the packets' noise_std).  Returns {'bers_X': errors / n_info, 'EVM_rms_X', 'dtSNR_X'}: float64 [npkt]."""
+    ntrf = int(ns if ntrf is None else ntrf)
+    n_info, _ = engine.link_frame_bits(ns, n_sym, bps)
+    d_nv = engine.to_device(synth.link_noise_var(d_noise_std.download(), amp_scale))
+    fbb = [engine.empty((npkt, N_DATA, ns, ntrf)) for _ in range(2)]
+    frf = [engine.empty((npkt, ntrf, engine.nt)) for _ in range(2)]
+    d_idx = engine.empty((npkt, N_DATA, ntrf))
+    d_err, d_evm, d_gain = (engine.empty((npkt,)) for _ in range(3))
+    out = {}
+    for name, (e_re, e_im) in planes.items():
+        engine.hybrid_weights_device(e_re, e_im, npkt, ns, ntrf, fbb[0], fbb[1], d_idx, d_frf_mean_re=frf[0], d_frf_mean_im=frf[1])
+        engine.link_sim_device(h_re, h_im, fbb[0], fbb[1], frf[0], frf[1], d_nv, seed, first_pkt, npkt, ns, ntrf, d_err, d_evm, d_gain,
+                               n_sym=n_sym, bps=bps)
+        out['bers_' + name] = d_err.download().view(np.int32).astype(np.float64) / n_info
+        out['EVM_rms_' + name] = d_evm.download().astype(np.float64)
+        out['dtSNR_' + name] = d_gain.download().astype(np.float64)
+    for a in fbb + frf + [d_idx, d_err, d_evm, d_gain, d_nv]:
+        a.free()
     return out
 
 
@@ -121,18 +160,23 @@ def load_models(engine, modeldir):
 
 def write_metrics(path, mse):
     """metrics.mat with MSE_LS, MSE_MMSE, MSE_DNN as 1 x npkt rows: the names BER_test_maMIMO_LTF.m:653 saves and
-    snr_loop_testing.m:37-58 loads (the BER / EVM / dtSNR fields are not written)."""
+    snr_loop_testing.m:37-58 loads.  A level evaluated with the data phase (evaluate_level(ber=...)) also carries bers_X, EVM_rms_X
+    and dtSNR_X for X in SOURCES - with the MSE rows the names of :653 - and MSE_perfect (zeros), which are then written the same way."""
     from scipy.io import savemat
     os.makedirs(os.path.dirname(path), exist_ok=True)
-    savemat(path, {'MSE_' + e: np.asarray(mse['MSE_' + e], np.float64).reshape(1, -1) for e in ESTIMATORS})
+    fields = ['MSE_' + e for e in ESTIMATORS]
+    if 'bers_perfect' in mse:
+        fields += [f + x for x in SOURCES for f in LINK_FIELDS] + ['MSE_perfect']
+    savemat(path, {f: np.asarray(mse[f], np.float64).reshape(1, -1) for f in fields})
     return path
 
 
 def format_table(result):
-    lines = ['%8s' % 'SNR dB' + ''.join('  %-38s' % (e + ': mean [CI low, CI high]') for e in ESTIMATORS)]
+    cols = list(ESTIMATORS) + (['BER_' + x for x in SOURCES] if result.get('ber') else [])
+    lines = ['%8s' % 'SNR dB' + ''.join('  %-38s' % (e + ': mean [CI low, CI high]') for e in cols)]
     for lv in result['levels']:
         row = '%8g' % lv['snr_db']
-        for e in ESTIMATORS:
+        for e in cols:
             s = lv[e]
             row += '  %-38s' % ('%.4e [%.4e, %.4e]' % (s['mean'], s['ci_low'], s['ci_high']))
         lines.append(row)
@@ -142,14 +186,17 @@ def format_table(result):
 
 
 def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500, seed=0, modeldir=None, fit_args=None, n_taps=8,
-              amp_scale=True, save_dataset=None, verbose=True):
+              amp_scale=True, save_dataset=None, verbose=True, ber=None):
     """Training set -> models (loaded from `modeldir`, else fitted and saved into `out`) -> every level.  Writes
     <out>/BS<Nt>_SNR<s>/metrics.mat per level and <out>/sweep.json, prints the table, returns the result dict (with the per-packet
     arrays under 'per_packet' = {level: {'MSE_LS', ...}}).  Test packets come from the stream seed + 1, behind the index range of
-    the training packets, so no test packet repeats a training packet."""
+    the training packets, so no test packet repeats a training packet.  ber = dict(ns, ntrf, n_sym, bps) adds the data phase per level
+    (evaluate_level): the BER / EVM / dtSNR fields in metrics.mat and 'BER_X' columns with the same confidence interval."""
     os.makedirs(out, exist_ok=True)
     result = dict(nt=engine.nt, nr=engine.nr, n_train=int(n_train), n_test=int(n_test), seed=int(seed), n_taps=int(n_taps),
                   amp_scale=bool(amp_scale), levels=[], training=None)
+    if ber is not None:
+        result['ber'] = {k: (None if v is None else int(v)) for k, v in ber.items()}
     if modeldir:
         load_models(engine, modeldir)
         if save_dataset:
@@ -167,13 +214,16 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
     per_packet = {}
     for i, snr in enumerate(levels):
         t0 = time.perf_counter()
-        mse = evaluate_level(engine, snr, n_test, seed + 1, n_train + i * n_test, n_taps, amp_scale)
+        mse = evaluate_level(engine, snr, n_test, seed + 1, n_train + i * n_test, n_taps, amp_scale, ber=ber)
         sec = time.perf_counter() - t0
         write_metrics(os.path.join(out, 'BS%d_SNR%g' % (engine.nt, snr), 'metrics.mat'), mse)
         lv = dict(snr_db=float(snr), seconds=sec)
         for e in ESTIMATORS:
             m, lo, hi = confidence_interval(mse['MSE_' + e])
             lv[e] = dict(mean=m, ci_low=lo, ci_high=hi)
+        for x in SOURCES if ber is not None else ():
+            m, lo, hi = confidence_interval(mse['bers_' + x])
+            lv['BER_' + x] = dict(mean=m, ci_low=lo, ci_high=hi)
         result['levels'].append(lv)
         per_packet[float(snr)] = mse
     with open(os.path.join(out, 'sweep.json'), 'w') as f:
@@ -204,6 +254,11 @@ def build_parser():
     p.add_argument('--save-dataset', default='', metavar='FILE.b', help='pickle the training set (cli --train / --test accept it)')
     p.add_argument('--device', default=0, type=int)
     p.add_argument('--quiet', action='store_true')
+    p.add_argument('--ber', action='store_true', help='run the beamformed data phase per level: bers_ / EVM_rms_ / dtSNR_ (BER_test_maMIMO_LTF.m:408-646)')
+    p.add_argument('--numSTS', default=1, type=int, help='--ber: data streams (the RF chains are as many)')
+    p.add_argument('--rays', default=500, type=int, help='--ber: random rays of the dictionary of array responses')
+    p.add_argument('--dataSymbols', default=10, type=int, help='--ber: OFDM data symbols per packet')
+    p.add_argument('--bps', default=2, type=int, help='--ber: bits per QAM symbol (2 or 4)')
     return p
 
 
@@ -213,9 +268,14 @@ def main(argv=None):
     eng = CsiEngine(args.nTX, args.nRX, hidden=args.nn, use_bn=args.useBN, device=args.device)
     eng.set_pilot(synth.hadamard(args.nTX))
     fit_args = dict(epochs=args.epochs, lr=args.lr, bs=args.bs, dropout=args.dropout, method=args.method)
+    ber = None
+    if args.ber:
+        az, el = synth.random_rays(np.random.default_rng(args.seed), args.rays)
+        eng.set_dictionary(synth.steering_ula(args.nTX, az, el))
+        ber = dict(ns=args.numSTS, ntrf=args.numSTS, n_sym=args.dataSymbols, bps=args.bps)
     run_sweep(eng, args.workdir, levels=args.snr, n_train=args.trainPkts, n_test=args.testPkts, seed=args.seed,
               modeldir=args.modeldir or None, fit_args=fit_args, n_taps=args.taps, save_dataset=args.save_dataset or None,
-              verbose=not args.quiet)
+              verbose=not args.quiet, ber=ber)
     return 0
 
 

@@ -96,6 +96,16 @@ def structured_packets(rng, npkt, nr, P, snr_db, n_taps=8):
     return ltf
 
 
+def link_noise_var(noise_std, amp_scale=True):
+    """Noise variance per complex frequency-domain sample, in the units of the channel planes h, that goes with a sounding packet
+    of csi_synth_structured: the time samples carry amp * noise_std per real component (2 amp^2 noise_std^2 per complex sample), and
+    the 256-point transform the LS kernel takes sums 256 of them: 512 amp^2 noise_std^2 (csrc/synth_structured.hip.h:6-11).  The LS
+    estimate of a link averages Nt such bins (P P^T = Nt I), so its error variance is this value / Nt.  `noise_std` is the array
+    synth_structured returns (before the amplitude scale); a data symbol of the link simulation sees the same level."""
+    amp = float(np.float32(AMP_SCALE)) if amp_scale else 1.0
+    return (2.0 * FFT_LEN * amp * amp) * np.asarray(noise_std, dtype=np.float64) ** 2
+
+
 def mixed_snr_jobs(seed, per_level=500, levels=SNR_LEVELS_DB, block=250):
     """BASELINE config 2's defining input: `per_level` test packets at EACH of the pipeline's SNR levels
     (setenv.sh:19-25, full_pipeline_maMIMO_DNNEst.sh:44-48), level after level (lowest SNR first), so

@@ -241,6 +241,36 @@ int  csi_capture_end(csi_ctx* ctx, void** graph);
 int  csi_capture_launch(csi_ctx* ctx, void* graph);
 void csi_capture_free(csi_ctx* ctx, void* graph);
 
+/* Link-level simulation of a beamformed data phase (BER_test_maMIMO_LTF.m:408-646; model and deviations: DESIGN.md 4.17,
+ * csrc/link_sim.hip.h).  Per packet p one terminated codeword of the rate-1/3, K = 7 code (133, 171, 165 octal) over
+ * n_info = n_steps - 6 counter-based random bits, n_steps = ns n_sym 234 bps / 3; square Gray QAM (bps 2 or 4), coded bit
+ * c = ((s n_sym + n) 234 + k) bps + b; precoder W_k = sqrt(Nt) F_k / |F_k|_F with F_k = frf_mean^T fbb_k^T from the planes
+ * csi_hybrid_weights_device writes (fbb [npkt][234][ns][ntrf], frf_mean [npkt][ntrf][Nt]); y = H_k W_k d + w through the TRUE
+ * channel planes h [npkt][Nr][Nt][234] of csi_synth_structured with noise of variance noise_var[p] per complex sample (draws of
+ * the stream `seed`, absolute packet index first_pkt + p: packets are the same bits whichever call holds them); zero forcing with
+ * the exact effective channel, max-log soft bits (positive = 0), Viterbi decoding.
+ * Outputs per packet: bit_errors int32 (against the information bits), evm_rms (100 sqrt(mean |x - nearest point|^2)),
+ * dt_snr_db (10 log10(sum_k |H_k W_k|_F^2 / sum_k |H_k|_F^2)).  Optional (may be NULL): xeq planes [npkt][ns][n_sym][234] (as a
+ * pair), csi [npkt][ns][234] (1 / [(G^H G)^-1]_ss; 0 and x = 0 where G^H G is singular), llr [npkt][n_coded], bits uint8
+ * [npkt][n_info] (the decoded bits).
+ * csi_link_frame_bits: n_info and n_coded of (ns, n_sym, bps); -1 for ns outside 1 .. 4, n_sym < 1 or bps not in {2, 4}.
+ * csi_viterbi_decode_device: the decoder alone, llr [ncw][3 n_steps] -> bits uint8 [ncw][n_steps - 6].  fp32 path metrics; the
+ * larger sum survives, on equal sums the predecessor with the lower state number; start and end state 0.
+ * Both device calls are asynchronous on the context's stream, usable inside csi_capture_begin / _end (after one eager call of
+ * the same shape) and serve fp32 and bf16 contexts alike (every plane is fp32).  csi_link_sim_device runs in packet chunks
+ * against the context's workspace_bytes (default 1 GiB for this stage) with the same bits whatever the chunking.
+ * Refused with text: null required pointers, bps not in {2, 4}, ns outside 1 .. min(4, Nr, ntrf), ntrf < 1, n_sym < 1,
+ * n_steps > 8190 (csi_viterbi_decode_device: outside 7 .. 8190), negative npkt / first_pkt / ncw, one xeq plane without the other,
+ * a single-input context, shapes whose per-packet LDS image (Nr ns and ns ntrf) passes 160 KiB.  A null context returns -1.
+ * Profile entries "link_txrx" (encoder + transmit / receive pass) and "link_viterbi"; "link_launches" (csi_get_option) counts
+ * the kernels launched. */
+int  csi_link_frame_bits(int ns, int n_sym, int bps, int64_t* n_info, int64_t* n_coded);
+int  csi_viterbi_decode_device(csi_ctx* ctx, const float* d_llr, int64_t ncw, int64_t n_steps, uint8_t* d_bits);
+int  csi_link_sim_device(csi_ctx* ctx, const float* d_h_re, const float* d_h_im, const float* d_fbb_re, const float* d_fbb_im,
+                         const float* d_frf_re, const float* d_frf_im, const float* d_noise_var, uint64_t seed, int64_t first_pkt,
+                         int64_t npkt, int ns, int ntrf, int n_sym, int bps, int32_t* d_bit_errors, float* d_evm_rms,
+                         float* d_dt_snr_db, float* d_xeq_re, float* d_xeq_im, float* d_csi, float* d_llr, uint8_t* d_bits);
+
 /* Accuracy metric of the reference's evaluation, NMSE_subk (BER_test_maMIMO_LTF.m:675-686): per link
  * ||ref - est||^2 / ||ref||^2 over the n_bins bins, mean over the nlinks links ([link][n_bins] planes, e.g.
  * the [npkt][nr][nt][234] outputs of csi_predict / csi_ls_estimate with nlinks = npkt*nr*nt).  Synchronous;
