@@ -40,6 +40,11 @@ class CsiTensor(ctypes.Structure):
                 ('rows', ctypes.c_int64), ('cols', ctypes.c_int64)]
 
 
+class CsiScatterConfig(ctypes.Structure):
+    _fields_ = [('n_scat', ctypes.c_int32), ('flags', ctypes.c_uint32), ('range_m', ctypes.c_float), ('az_deg', ctypes.c_float),
+                ('el_deg', ctypes.c_float), ('box_frac', ctypes.c_float), ('sample_rate_hz', ctypes.c_float)]
+
+
 class CsiTrainConfig(ctypes.Structure):
     _fields_ = [('lr', ctypes.c_float), ('beta1', ctypes.c_float), ('beta2', ctypes.c_float), ('eps', ctypes.c_float),
                 ('bn_momentum', ctypes.c_float), ('dropout', ctypes.c_float), ('seed', ctypes.c_uint64)]
@@ -106,6 +111,8 @@ SYMBOLS = {
     'csi_synth_white': (ctypes.c_int, [_ctx, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, _vp, _vp]),
     'csi_synth_structured': (ctypes.c_int, [_ctx, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, _fp, ctypes.c_int, ctypes.c_uint32,
                                             _vp, _vp, _vp, _vp, _vp]),
+    'csi_synth_scattering': (ctypes.c_int, [_ctx, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, _fp, ctypes.POINTER(CsiScatterConfig),
+                                            _vp, _vp, _vp, _vp, _vp, _vp]),
     'csi_profile_enable': (ctypes.c_int, [_ctx, ctypes.c_int]),
     'csi_profile_reset': (ctypes.c_int, [_ctx]),
     'csi_profile_num_kernels': (ctypes.c_int, []),

@@ -24,6 +24,7 @@
 #include "input_pool.hip.h"
 #include "conv_frontend.hip.h"
 #include "synth_structured.hip.h"
+#include "synth_scattering.hip.h"
 #include "link_sim.hip.h"
 
 using namespace csi;
@@ -56,13 +57,15 @@ enum KernelId {
     K_SYNTH_STRUCTURED,  // known-channel sounding packets (synth_structured.hip.h): the power pass and the packet pass of csi_synth_structured
     K_LINK_TXRX,         // link simulation: encoder, precoder, true channel, zero forcing and soft bits per (packet, subcarrier) (link_sim.hip.h)
     K_LINK_VITERBI,      // link simulation: one-wavefront Viterbi decoder per codeword, traceback and bit errors
+    K_SYNTH_SCATTERING,  // known-channel sounding packets of the scattering channel (synth_scattering.hip.h): the power pass and the packet pass of csi_synth_scattering
     K_COUNT
 };
 const char* const kKernelNames[K_COUNT] = {
     "layer0_ltf_gemm", "splitk_reduce", "pair_dense_gemm", "dense_hidden_gemm", "regressor_gemm",
     "ls_estimate", "naive_dense0_gemm", "synth_white", "pilot_table", "cast_bf16", "pair_h1_bf16", "lmmse_levinson",
     "train_gemm", "train_elementwise", "nmse_links", "pair_dense_tail", "input_pool", "conv_frontend",
-    "hybrid_svd", "hybrid_corr_argmax", "hybrid_solve", "hybrid_finish", "synth_structured", "link_txrx", "link_viterbi"};
+    "hybrid_svd", "hybrid_corr_argmax", "hybrid_solve", "hybrid_finish", "synth_structured", "link_txrx", "link_viterbi",
+    "synth_scattering"};
 
 thread_local std::string g_create_error;
 
@@ -169,6 +172,8 @@ struct csi_ctx {
     size_t synth_ws_bytes = 0;
     std::vector<float> synth_host;   // host image of the first two parts (stays alive behind the asynchronous upload)
     size_t synth_lds_attr = 0;   // dynamic-LDS limit already raised for its kernels
+    size_t scatter_lds_attr = 0; // the same for the kernels of csi_synth_scattering (csi_scatter.hpp), which shares synth_ws / synth_host
+    int64_t scatter_launches = 0;   // "scatter_launches": kernels launched by csi_synth_scattering
     // activation workspace
     char* ws = nullptr;
     size_t ws_bytes = 0;

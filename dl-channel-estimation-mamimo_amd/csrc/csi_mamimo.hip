@@ -20,6 +20,7 @@
 #include "csi_comm.hpp"
 #include "csi_hybrid.hpp"
 #include "csi_link.hpp"
+#include "csi_scatter.hpp"
 
 namespace {
 
@@ -1356,6 +1357,7 @@ int csi_get_option(csi_ctx* c, const char* name, int64_t* value) {
     else if (n == "conv_launches") *value = c->conv_launches;
     else if (n == "hybrid_launches") *value = c->hybrid_launches;
     else if (n == "link_launches") *value = c->link_launches;
+    else if (n == "scatter_launches") *value = c->scatter_launches;
     else if (n == "small_rows") *value = c->small_rows;
     else if (n == "small_rows_band") *value = c->small_rows_band;
     else if (n == "f32_engine") *value = c->f32_engine;
@@ -2213,6 +2215,12 @@ int csi_synth_structured(csi_ctx* c, uint64_t seed, int64_t first_pkt, int64_t n
     hipLaunchKernelGGL(synth_structured_kernel<false>, dim3((unsigned)nblk), dim3(SS_THREADS), lds, c->stream, a);
     HIP_TRY(c, hipGetLastError());
     return CSI_OK;
+}
+
+int csi_synth_scattering(csi_ctx* c, uint64_t seed, int64_t first_pkt, int64_t npkt, const float* snr_db, const csi_scatter_config* cfg,
+                         float* d_ltf_re, float* d_ltf_im, float* d_h_re, float* d_h_im, float* d_noise_std, float* d_tau) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return synth_scattering(c, seed, first_pkt, npkt, snr_db, cfg, d_ltf_re, d_ltf_im, d_h_re, d_h_im, d_noise_std, d_tau);
 }
 
 // ---- profiling

@@ -833,6 +833,39 @@ class CsiEngine:
                                                    d_std.ptr if want_noise_std else None))
         return d_re, d_im, d_h[0], d_h[1], d_std
 
+    def synth_scattering(self, seed, first_pkt, npkt, snr_db=None, n_scat=100, range_m=100.0, az_deg=30.0, el_deg=0.0, box_frac=0.1,
+                         random_users=False, amp_scale=True, want_channel=True, want_noise_std=True, want_tau=False,
+                         sample_rate_hz=100e6):
+        """Known-channel sounding packets of the geometric single-bounce scattering channel (csi_synth_scattering):
+        n_scat scatterers in a box of half edge box_frac * range around a user at (range_m, az_deg, el_deg) - or at a position
+        drawn per packet (random_users) - seen from half-wavelength ULAs.  Everything else as synth_structured, whose tuple it
+        returns plus tau: a DeviceArray [npkt][n_scat] of the absolute path delays in samples (None unless want_tau), the hvec
+        rows the reference hands its LMMSE smoother.  Asynchronous."""
+        npkt, n_scat = int(npkt), int(n_scat)
+        if npkt < 0:
+            raise CsiError(-1, f'csi_synth_scattering: npkt {npkt} must not be negative')
+        if n_scat < 1 or n_scat > 256:
+            raise CsiError(-1, f'csi_synth_scattering: n_scat {n_scat} outside 1 .. 256')
+        for name, val in (('range_m', range_m), ('box_frac', box_frac), ('sample_rate_hz', sample_rate_hz)):
+            if not (np.isfinite(val) and val > 0):      # a zero would select the default of the C configuration
+                raise CsiError(-1, f'csi_synth_scattering: {name} {val} must be finite and positive')
+        snr = None
+        if snr_db is not None:
+            snr = np.ascontiguousarray(np.broadcast_to(np.asarray(snr_db, dtype=np.float32), (npkt,)))
+        az = float(az_deg)
+        cfg = _lib.CsiScatterConfig(n_scat=n_scat, flags=(1 if amp_scale else 0) | (2 if random_users else 0), range_m=float(range_m),
+                                    az_deg=360.0 if az == 0.0 else az, el_deg=float(el_deg), box_frac=float(box_frac),
+                                    sample_rate_hz=float(sample_rate_hz))
+        d_re, d_im = self.empty((npkt, self.nr, SYM_LEN * self.nt)), self.empty((npkt, self.nr, SYM_LEN * self.nt))
+        d_h = [self.empty((npkt, self.nr, self.nt, N_DATA)) for _ in range(2)] if want_channel else [None, None]
+        d_std = self.empty((npkt,)) if want_noise_std else None
+        d_tau = self.empty((npkt, n_scat)) if want_tau else None
+        self._check(self._lib.csi_synth_scattering(self._ctx, int(seed), int(first_pkt), npkt, _fp(snr) if snr is not None else None,
+                                                   ctypes.byref(cfg), d_re.ptr or None, d_im.ptr or None,
+                                                   d_h[0].ptr if want_channel else None, d_h[1].ptr if want_channel else None,
+                                                   d_std.ptr if want_noise_std else None, d_tau.ptr if want_tau else None))
+        return d_re, d_im, d_h[0], d_h[1], d_std, d_tau
+
     def lmmse_estimate_device(self, d_h_re, d_h_im, npkt, d_hvec, L, d_snr_db, d_out_re, d_out_im):
         """LMMSE smoothing of device-resident LS planes (csi_lmmse_estimate_device): d_hvec [npkt][L], d_snr_db [npkt][nr]; asynchronous."""
         self._check(self._lib.csi_lmmse_estimate_device(self._ctx, d_h_re.ptr, d_h_im.ptr, int(npkt), d_hvec.ptr, int(L), d_snr_db.ptr,

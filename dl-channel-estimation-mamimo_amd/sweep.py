@@ -6,8 +6,10 @@ coded QAM through the true channel, giving the bers_ / EVM_rms_ / dtSNR_ familie
 
     python -m dl_channel_estimation_mamimo_amd.sweep -d OUT [--nTX 32 --nRX 4 --nn 1024 1024 --useBN --bs 256 ...]
                                                             [--ber --numSTS 1 --rays 500 --dataSymbols 10 --bps 2]
+                                                            [--channel scattering --scatterers 100 --range 100 --userAz 30 --userEl 0 --randomUsers]
 
-The module holds no arithmetic of its own: packets with a known channel come from csi_synth_structured, labels from
+The module holds no arithmetic of its own: packets with a known channel come from csi_synth_structured (--channel scattering: from
+csi_synth_scattering, whose path delays then feed the LMMSE smoother as the reference's h_tau does), labels from
 csi_ls_estimate_device, the fit from trainer.fit, the estimates from csi_estimate_device / csi_lmmse_estimate_device and every
 NMSE from csi_nmse_device; the hybrid weights from csi_hybrid_weights_device and bit errors, EVM and beamforming gain from
 csi_link_sim_device, with the noise level of a data symbol from synth.link_noise_var.  Only the per-packet mean of the per-link
@@ -48,12 +50,31 @@ def confidence_interval(x):
     return m, m - q * sem, m + q * sem
 
 
-def make_dataset(engine, n_train, seed, n_taps=8, amp_scale=True):
+def scattering_args(channel):
+    """`channel` as make_dataset / evaluate_level / run_sweep take it: None = the tap channel of csi_synth_structured; a dict (may be
+    empty) = the scattering channel of csi_synth_scattering with these keyword arguments of CsiEngine.synth_scattering (n_scat,
+    range_m, az_deg, el_deg, box_frac, random_users).  Returns the dict with every default filled in, or None."""
+    if channel is None:
+        return None
+    out = dict(n_scat=100, range_m=100.0, az_deg=30.0, el_deg=0.0, box_frac=0.1, random_users=False)
+    unknown = set(channel) - set(out)
+    if unknown:
+        raise ValueError('unknown scattering channel parameters: %s' % sorted(unknown))
+    out.update(channel)
+    return out
+
+
+def make_dataset(engine, n_train, seed, n_taps=8, amp_scale=True, channel=None):
     """Noise-free training packets generated on the device (the pipeline trains on "SNR 120 ... NOISELESS" packets,
     full_pipeline_maMIMO_DNNEst.sh:21,33) with the LS estimate of the same signal as labels, as the dataset's y is
-    (generate_maMIMO_LTF.m:342-354).  engine.set_pilot must have been called.  Returns the dict dataset.load_dataset returns."""
-    d_re, d_im, _, _, _ = engine.synth_structured(seed, 0, n_train, snr_db=None, n_taps=n_taps, amp_scale=amp_scale,
-                                                  want_channel=False, want_noise_std=False)
+    (generate_maMIMO_LTF.m:342-354).  engine.set_pilot must have been called.  channel: scattering_args.  Returns the dict
+    dataset.load_dataset returns."""
+    if channel is None:
+        d_re, d_im, _, _, _ = engine.synth_structured(seed, 0, n_train, snr_db=None, n_taps=n_taps, amp_scale=amp_scale,
+                                                      want_channel=False, want_noise_std=False)
+    else:
+        d_re, d_im = engine.synth_scattering(seed, 0, n_train, snr_db=None, amp_scale=amp_scale, want_channel=False,
+                                             want_noise_std=False, **scattering_args(channel))[:2]
     l_re, l_im = engine.empty((n_train, engine.nr, engine.nt, N_DATA)), engine.empty((n_train, engine.nr, engine.nt, N_DATA))
     engine.ls_estimate_device(d_re, d_im, n_train, l_re, l_im)
     engine.synchronize()
@@ -64,7 +85,7 @@ def make_dataset(engine, n_train, seed, n_taps=8, amp_scale=True):
     return ds.dataset_from_packets(ltf, labels, engine.pilot)
 
 
-def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=True, keep=False, ber=None):
+def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=True, keep=False, ber=None, channel=None):
     """npkt test packets at `snr_db` (packets first_pkt ... of stream `seed`: keep them disjoint from the training packets), LS + DNN
     (estimate_device), the LMMSE smoother on the LS planes, and NMSE_subk of the three estimates against the true channel.
     Returns {'MSE_LS', 'MSE_MMSE', 'MSE_DNN'}: float64 [npkt], the per-link ratios averaged per packet.
@@ -74,17 +95,29 @@ def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=Tr
     is the level.  keep=True adds 'arrays': the DeviceArrays ltf_re, ltf_im, h_re, h_im, ls_re, ls_im (the caller frees them).
 
     ber = dict(ns, ntrf, n_sym, bps) adds the data phase (link_level): 'bers_X', 'EVM_rms_X', 'dtSNR_X' float64 [npkt] for X in SOURCES
-    and 'MSE_perfect' (zeros).  The engine needs a dictionary (set_dictionary)."""
+    and 'MSE_perfect' (zeros).  The engine needs a dictionary (set_dictionary).
+
+    channel (scattering_args) takes the packets from csi_synth_scattering instead; hvec is then the generator's path delays tau
+    (L = n_scat), the input the reference gives LMMSE_ce."""
     nr, nt = engine.nr, engine.nt
-    d_re, d_im, h_re, h_im, d_std = engine.synth_structured(seed, first_pkt, npkt, snr_db=float(snr_db), n_taps=n_taps, amp_scale=amp_scale,
-                                                            want_noise_std=ber is not None)
+    d_tau = None
+    if channel is None:
+        d_re, d_im, h_re, h_im, d_std = engine.synth_structured(seed, first_pkt, npkt, snr_db=float(snr_db), n_taps=n_taps, amp_scale=amp_scale,
+                                                                want_noise_std=ber is not None)
+    else:
+        d_re, d_im, h_re, h_im, d_std, d_tau = engine.synth_scattering(seed, first_pkt, npkt, snr_db=float(snr_db), amp_scale=amp_scale,
+                                                                       want_noise_std=ber is not None, want_tau=True,
+                                                                       **scattering_args(channel))
     shape = (npkt, nr, nt, N_DATA)
     o_re, o_im, ls_re, ls_im, m_re, m_im = (engine.empty(shape) for _ in range(6))
     engine.estimate_device(d_re, d_im, npkt, o_re, o_im, ls_re, ls_im, checked=True)
-    prof = tap_profile(n_taps)
-    d_hvec = engine.to_device(np.tile(prof, (npkt, 1)))
+    if d_tau is None:
+        prof = tap_profile(n_taps)
+        d_hvec, L = engine.to_device(np.tile(prof, (npkt, 1))), prof.size
+    else:
+        d_hvec, L = d_tau, scattering_args(channel)['n_scat']
     d_snr = engine.to_device(np.full((npkt, nr), float(snr_db), np.float32))
-    engine.lmmse_estimate_device(ls_re, ls_im, npkt, d_hvec, prof.size, d_snr, m_re, m_im)
+    engine.lmmse_estimate_device(ls_re, ls_im, npkt, d_hvec, L, d_snr, m_re, m_im)
     d_link = engine.empty((npkt * nr * nt,))
     out = {}
     for name, (e_re, e_im) in zip(ESTIMATORS, ((ls_re, ls_im), (m_re, m_im), (o_re, o_im))):
@@ -186,25 +219,29 @@ def format_table(result):
 
 
 def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500, seed=0, modeldir=None, fit_args=None, n_taps=8,
-              amp_scale=True, save_dataset=None, verbose=True, ber=None):
+              amp_scale=True, save_dataset=None, verbose=True, ber=None, channel=None):
     """Training set -> models (loaded from `modeldir`, else fitted and saved into `out`) -> every level.  Writes
     <out>/BS<Nt>_SNR<s>/metrics.mat per level and <out>/sweep.json, prints the table, returns the result dict (with the per-packet
     arrays under 'per_packet' = {level: {'MSE_LS', ...}}).  Test packets come from the stream seed + 1, behind the index range of
     the training packets, so no test packet repeats a training packet.  ber = dict(ns, ntrf, n_sym, bps) adds the data phase per level
-    (evaluate_level): the BER / EVM / dtSNR fields in metrics.mat and 'BER_X' columns with the same confidence interval."""
+    (evaluate_level): the BER / EVM / dtSNR fields in metrics.mat and 'BER_X' columns with the same confidence interval.
+    channel (scattering_args) takes training and test packets from csi_synth_scattering; sweep.json then records its parameters under
+    'channel'."""
     os.makedirs(out, exist_ok=True)
     result = dict(nt=engine.nt, nr=engine.nr, n_train=int(n_train), n_test=int(n_test), seed=int(seed), n_taps=int(n_taps),
                   amp_scale=bool(amp_scale), levels=[], training=None)
     if ber is not None:
         result['ber'] = {k: (None if v is None else int(v)) for k, v in ber.items()}
+    if channel is not None:
+        result['channel'] = dict(scattering_args(channel), model='scattering')
     if modeldir:
         load_models(engine, modeldir)
         if save_dataset:
             with open(save_dataset, 'wb') as f:
-                pickle.dump(make_dataset(engine, n_train, seed, n_taps, amp_scale), f)
+                pickle.dump(make_dataset(engine, n_train, seed, n_taps, amp_scale, channel=channel), f)
     else:
         t0 = time.perf_counter()
-        data = make_dataset(engine, n_train, seed, n_taps, amp_scale)
+        data = make_dataset(engine, n_train, seed, n_taps, amp_scale, channel=channel)
         result['dataset_seconds'] = time.perf_counter() - t0
         if save_dataset:
             with open(save_dataset, 'wb') as f:
@@ -214,7 +251,7 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
     per_packet = {}
     for i, snr in enumerate(levels):
         t0 = time.perf_counter()
-        mse = evaluate_level(engine, snr, n_test, seed + 1, n_train + i * n_test, n_taps, amp_scale, ber=ber)
+        mse = evaluate_level(engine, snr, n_test, seed + 1, n_train + i * n_test, n_taps, amp_scale, ber=ber, channel=channel)
         sec = time.perf_counter() - t0
         write_metrics(os.path.join(out, 'BS%d_SNR%g' % (engine.nt, snr), 'metrics.mat'), mse)
         lv = dict(snr_db=float(snr), seconds=sec)
@@ -259,7 +296,21 @@ def build_parser():
     p.add_argument('--rays', default=500, type=int, help='--ber: random rays of the dictionary of array responses')
     p.add_argument('--dataSymbols', default=10, type=int, help='--ber: OFDM data symbols per packet')
     p.add_argument('--bps', default=2, type=int, help='--ber: bits per QAM symbol (2 or 4)')
+    p.add_argument('--channel', default='taps', choices=('taps', 'scattering'),
+                   help='taps: i.i.d. impulse responses (csi_synth_structured); scattering: the geometric single-bounce channel (csi_synth_scattering)')
+    p.add_argument('--scatterers', default=100, type=int, help='--channel scattering: scatterers (N_chan_taps, generate_maMIMO_LTF.m:9)')
+    p.add_argument('--range', default=100.0, type=float, help='--channel scattering: distance of the user in metres')
+    p.add_argument('--userAz', default=30.0, type=float, help='--channel scattering: azimuth of the user in degrees')
+    p.add_argument('--userEl', default=0.0, type=float, help='--channel scattering: elevation of the user in degrees')
+    p.add_argument('--randomUsers', action='store_true', help='--channel scattering: draw the user position per packet (generate_maMIMO_LTF.m:48-51)')
     return p
+
+
+def channel_from_args(args):
+    """The `channel` argument of run_sweep that the command line asks for: None for --channel taps."""
+    if args.channel == 'taps':
+        return None
+    return dict(n_scat=args.scatterers, range_m=args.range, az_deg=args.userAz, el_deg=args.userEl, random_users=bool(args.randomUsers))
 
 
 def main(argv=None):
@@ -275,7 +326,7 @@ def main(argv=None):
         ber = dict(ns=args.numSTS, ntrf=args.numSTS, n_sym=args.dataSymbols, bps=args.bps)
     run_sweep(eng, args.workdir, levels=args.snr, n_train=args.trainPkts, n_test=args.testPkts, seed=args.seed,
               modeldir=args.modeldir or None, fit_args=fit_args, n_taps=args.taps, save_dataset=args.save_dataset or None,
-              verbose=not args.quiet, ber=ber)
+              verbose=not args.quiet, ber=ber, channel=channel_from_args(args))
     return 0
 
 

@@ -96,6 +96,84 @@ def structured_packets(rng, npkt, nr, P, snr_db, n_taps=8):
     return ltf
 
 
+# ---- geometric single-bounce scattering channel (csi_synth_scattering) -----------
+LIGHT_SPEED = 299792458.0
+
+
+def scattering_channel(u, g, R, az_deg, el_deg, nr, nt, box_frac=0.1, sample_rate_hz=100e6, details=False):
+    """The channel model of csi_synth_scattering in float64 (include/csi_mamimo.h states it; what phased.ScatteringMIMOChannel
+    models in helperApplyMUChannel.m:44-143, restated from the physics).  u [S][3]: the uniform draws in (0, 1) that place the
+    scatterers in the box of half edge box_frac * R around the receiver; g [S] complex reflection coefficients; the user sits at
+    distance R in direction (az_deg, el_deg) of the transmitter; both arrays are half-wavelength ULAs along y.
+
+        e = (cos el cos az, cos el sin az, sin el),  o_s = box_frac R (2 u_s - 1),  q_s = R e + o_s
+        x_s = (2 R (e . o_s) + |o_s|^2) / (|q_s| + R) + |o_s|           excess path, = |q_s| - R + |o_s| without the cancellation
+        tau_s = (x_s - min x) fs / c                                      excess delay in samples: the first path sits at 0
+        v_s = q_s,y / |q_s|,  w_s = o_s,y / |o_s|                         direction cosines along the array axis
+        H[r][j][k] = S^(-1/2) sum_s g_s exp(2 pi i z_r w_s) exp(-2 pi i y_j v_s) exp(-2 pi i f_k tau_s / 256)
+
+    with y_j = (j - (nt - 1) / 2) / 2, z_r = (r - (nr - 1) / 2) / 2 and f_k the SIGNED index of FFT bin k (k < 128: k, else k - 256).
+    The transmit factor is the conjugate of steering_ula: a single scatterer's H has steering_ula at (v_s) as its dominant right
+    singular vector.  Returns (H complex128 [nr][nt][256] in FFT bin order, tau [S] = (R + x_s) fs / c, the absolute path delays in
+    samples); details=True adds a dict with x, tau_excess, v, w."""
+    u = np.asarray(u, np.float64).reshape(-1, 3)
+    g = np.asarray(g, np.complex128).reshape(-1)
+    S = g.size
+    if u.shape[0] != S or S < 1:
+        raise ValueError('u must be [S][3] and g [S] with S >= 1')
+    R, az, el = float(R), np.deg2rad(float(az_deg)), np.deg2rad(float(el_deg))
+    e = np.array([np.cos(el) * np.cos(az), np.cos(el) * np.sin(az), np.sin(el)])
+    o = box_frac * R * (2.0 * u - 1.0)
+    q = R * e + o
+    on, qn = np.linalg.norm(o, axis=1), np.linalg.norm(q, axis=1)
+    x = (2.0 * R * (o @ e) + on ** 2) / (qn + R) + on
+    spm = float(sample_rate_hz) / LIGHT_SPEED
+    tau_ex = (x - x.min()) * spm
+    v = q[:, 1] / qn
+    w = np.divide(o[:, 1], on, out=np.zeros(S), where=on > 0)
+    y = (np.arange(nt) - (nt - 1) / 2.0) / 2.0
+    z = (np.arange(nr) - (nr - 1) / 2.0) / 2.0
+    f = np.fft.fftfreq(FFT_LEN, 1.0 / FFT_LEN)                                # 0 .. 127, -128 .. -1
+    rx = g[None, :] * np.exp(2j * np.pi * z[:, None] * w[None, :])             # [r, s]
+    tx = np.exp(-2j * np.pi * y[:, None] * v[None, :])                         # [j, s]
+    dl = np.exp(-2j * np.pi * f[:, None] * tau_ex[None, :] / FFT_LEN)          # [k, s]
+    H = np.einsum('rs,js,ks->rjk', rx, tx, dl) / np.sqrt(S)
+    tau = (R + x) * spm
+    if details:
+        return H, tau, dict(x=x, tau_excess=tau_ex, v=v, w=w)
+    return H, tau
+
+
+def scattering_packets(rng, npkt, nr, P, snr_db, n_scat=100, range_m=100.0, az_deg=30.0, el_deg=0.0, box_frac=0.1, random_users=False,
+                       sample_rate_hz=100e6, return_channel=False):
+    """Host twin of csi_synth_scattering's distribution (not of its stream), as structured_packets is of the tap model's: per
+    packet n_scat scatterers uniform in the box, CN(0, 1) reflection coefficients, the user fixed or - random_users - drawn as
+    generate_maMIMO_LTF.m:48-51 draws it (range 1 .. range_m, azimuth +-180, elevation +-90 degrees); the LTF symbols mapped by P,
+    OFDM-modulated with the cyclic prefix, AWGN at `snr_db` (scalar or per packet; None = noise-free) relative to each packet's own
+    power, then the sub-carrier power scaling.  Returns complex64 [npkt, nr, 320 nt]; return_channel=True returns
+    (ltf, H complex128 [npkt, nr, nt, 256] before the scaling, tau [npkt, n_scat])."""
+    P = np.asarray(P, dtype=np.float64)
+    nt = P.shape[0]
+    ltf_seq = np.fft.ifftshift(vht_ltf_sequence()).astype(np.float64)
+    out = np.empty((npkt, nr, nt * SYM_LEN), np.complex64)
+    Hs, taus = np.empty((npkt, nr, nt, FFT_LEN), np.complex128), np.empty((npkt, n_scat))
+    snr = None if snr_db is None else np.broadcast_to(np.asarray(snr_db, dtype=np.float64), (npkt,))
+    for p in range(npkt):
+        R, az, el = float(range_m), float(az_deg), float(el_deg)
+        if random_users:
+            R, az, el = 1.0 + (range_m - 1.0) * rng.random(), rng.uniform(-180.0, 180.0), rng.uniform(-90.0, 90.0)
+        g = (rng.standard_normal(n_scat) + 1j * rng.standard_normal(n_scat)) / np.sqrt(2.0)
+        H, tau = scattering_channel(rng.random((n_scat, 3)), g, R, az, el, nr, nt, box_frac, sample_rate_hz)
+        x = np.fft.ifft(np.einsum('rjk,js->rsk', H, P) * ltf_seq, axis=-1)
+        ltf = np.concatenate([x[..., -CP_LEN:], x], axis=-1).reshape(nr, nt * SYM_LEN)
+        if snr is not None:
+            nstd = np.sqrt(np.mean(np.abs(ltf) ** 2) / 10.0 ** (snr[p] / 10.0) / 2.0)
+            ltf = ltf + nstd * (rng.standard_normal(ltf.shape) + 1j * rng.standard_normal(ltf.shape))
+        out[p] = ltf * AMP_SCALE
+        Hs[p], taus[p] = H, tau
+    return (out, Hs, taus) if return_channel else out
+
+
 def link_noise_var(noise_std, amp_scale=True):
     """Noise variance per complex frequency-domain sample, in the units of the channel planes h, that goes with a sounding packet
     of csi_synth_structured: the time samples carry amp * noise_std per real component (2 amp^2 noise_std^2 per complex sample), and

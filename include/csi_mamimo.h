@@ -22,6 +22,7 @@
  *   LMMSE_ce per link   helperMIMOChannelEstimate.m:37-39, LMMSE_ce.m  csi_lmmse_estimate[_device]
  *   NMSE_subk           BER_test_maMIMO_LTF.m:675-686                csi_nmse[_device]
  *   known-channel sounding packets  generate_maMIMO_LTF.m:197-342   csi_synth_structured
+ *   phased.ScatteringMIMOChannel    helperApplyMUChannel.m:44-143   csi_synth_scattering
  *   omphybweights       BER_test_maMIMO_LTF.m:347-376                csi_hybrid_weights[_device]
  *   --execTime profiler loop                       DNN.py:441-475   csi_profile_*
  *   Model.fit step (noise, BN, dropout, Adam)       DNN.py:272-316   csi_train_*
@@ -497,6 +498,51 @@ int  csi_synth_white(csi_ctx* ctx, uint64_t seed, int64_t first_pkt, int64_t npk
  * inside csi_capture_begin / _end.  Profile entry "synth_structured". */
 int  csi_synth_structured(csi_ctx* ctx, uint64_t seed, int64_t first_pkt, int64_t npkt, const float* snr_db, int n_taps, uint32_t flags,
                           float* d_ltf_re, float* d_ltf_im, float* d_h_re, float* d_h_im, float* d_noise_std);
+
+/* The same packets from a geometric single-bounce scattering channel: what phased.ScatteringMIMOChannel models in the reference
+ * (helperApplyMUChannel.m:44-143; csrc/synth_scattering.hip.h).  The toolbox object is not part of the reference tree, so
+ * its random stream and sign conventions cannot be pinned; the model is restated from the physics.  A zero in a field of the
+ * configuration selects its default (an azimuth of exactly 0 is written 360). */
+typedef struct {
+    int32_t  n_scat;           /* scatterers S, 1 .. 256; default 100 (N_chan_taps, generate_maMIMO_LTF.m:9) */
+    uint32_t flags;            /* bit 0: the sqrt(242) / 256 amplitude scale, as in csi_synth_structured; bit 1: the user position is drawn
+                                  per packet; other bits must be 0 */
+    float    range_m;          /* distance R transmitter - receiver, default 100 (with bit 1: the upper end of the draw) */
+    float    az_deg, el_deg;   /* direction of the user seen from the transmitter, default 30 and 0; |el| <= 90 */
+    float    box_frac;         /* half edge of the scatterer box around the receiver in units of R, default 0.1 (helperApplyMUChannel.m:90) */
+    float    sample_rate_hz;   /* default 100e6 (:89) */
+} csi_scatter_config;
+/* Per packet p = first_pkt + i (absolute index) the channel stream kc = key(seed, p, 0) of csi_synth_structured is read as follows
+ * (tr_uniform / tr_normal of csrc/rng.hip.h; no tap is drawn in this mode):
+ *   user        flag bit 1: u0..u2 = uniform(kc, 0..2), R = 1 + (range_m - 1) u0, az = 180 (2 u1 - 1), el = 90 (2 u2 - 1) degrees
+ *               (generate_maMIMO_LTF.m:48-51); otherwise R, az, el as configured.  e = (cos el cos az, cos el sin az, sin el)
+ *   scatterer s base index b = 8 (s + 1): offset from the receiver o_s[i] = box_frac R (2 uniform(kc, b + i) - 1), i = 0, 1, 2;
+ *               reflection coefficient g_s = (normal(kc, b + 3) + i normal(kc, b + 4)) / sqrt(2).  The carrier phase 2 pi fc tau is
+ *               absorbed in g_s (uniform for positions random at the scale of metres), so fc does not enter.
+ *   geometry    q_s = R e + o_s;  excess path x_s = (2 R (e . o_s) + |o_s|^2) / (|q_s| + R) + |o_s| (= |q_s| - R + |o_s|, without the
+ *               cancellation);  excess delay tau_s = (x_s - min_s' x_s') fs / c samples, c = 299792458: the first path sits at delay 0
+ *               (the reference removes floor(min tau) samples);  direction cosines along the array axis y: v_s = q_s,y / |q_s| at the
+ *               transmitter, w_s = o_s,y / |o_s| at the receiver (0 for a zero offset)
+ *   arrays      ULAs along y at half a wavelength: y_j = (j - (Nt - 1) / 2) / 2, z_r = (r - (Nr - 1) / 2) / 2 (URAs are out of scope)
+ *   response    H[r][j][f] = S^(-1/2) sum_s g_s exp(2 pi i z_r w_s) exp(-2 pi i y_j v_s) exp(-2 pi i f tau_s / 256),  f the SIGNED bin
+ *               index -128 .. 127 (FFT bins 128 .. 255 are f - 256; the delays are fractional).  The transmit factor is the conjugate
+ *               of synth.steering_ula: the dominant right singular vector of a one-scatterer H is steering_ula at its direction.
+ *               E|H|^2 = 1.
+ * Everything behind H is csi_synth_structured's: the LTF symbols on the 242 non-null bins mapped by P, the inverse transform, the
+ * prefix, the amplitude scale, noise relative to the packet's own power from key(p, 1) at the same indices, h = amp H on the 234 data
+ * bins DEFINED as what csi_ls_estimate_device returns for the noise-free packet when P P^T = Nt I.  Packets [first, first + n) are the
+ * same bits whichever call holds them, a noisy call leaves the channel bits of the noise-free call unchanged, and a call repeats bit
+ * for bit.  The configuration is fp32, the per-scatterer geometry is evaluated in fp64 and rounded once, all per-bin arithmetic is fp32.
+ *   snr_db, d_ltf_re/im, d_h_re/im, d_noise_std   as in csi_synth_structured
+ *   cfg          NULL = all defaults
+ *   d_tau        optional [npkt][S]: (R + x_s) fs / c, the absolute path delays in samples - the TAU the reference hands LMMSE_ce
+ *                (generate_maMIMO_LTF.m:342)
+ * Asynchronous on the context's stream; serves fp32 and bf16 contexts alike.  Refused with text: everything csi_synth_structured
+ * refuses, S outside 1 .. 256, a non-finite or non-positive range, box fraction or sample rate, a non-finite azimuth, |el| > 90, unknown
+ * flag bits, a call with an SNR array inside csi_capture_begin / _end.  A null context returns -1.  Profile entry "synth_scattering";
+ * "scatter_launches" (csi_get_option) counts the kernels launched. */
+int  csi_synth_scattering(csi_ctx* ctx, uint64_t seed, int64_t first_pkt, int64_t npkt, const float* snr_db, const csi_scatter_config* cfg,
+                          float* d_ltf_re, float* d_ltf_im, float* d_h_re, float* d_h_im, float* d_noise_std, float* d_tau);
 
 /* ---- multi-GPU: packets shard over the GPUs of a node (one process and one context per GPU), the weights are shared and
  * read-only, outputs stay sharded.  The single collective of the path is the load-time broadcast of the
