@@ -21,8 +21,20 @@
 #include "csi_hybrid.hpp"
 #include "csi_link.hpp"
 #include "csi_scatter.hpp"
+#include <initializer_list>
 
 namespace {
+
+// The pointer contract of the device-pointer entry points (include/csi_mamimo.h, "Device pointers"): every re / im plane starts on a
+// 16-byte boundary - the LS and layer-0 kernels load and store the caller's rows as 16-byte words and through LDS-DMA.  Checked on the
+// host before anything is launched or counted; a null pointer (an optional plane) passes.
+struct PlaneArg { const char* name; const void* p; };
+int planes_aligned(csi_ctx* c, const char* who, std::initializer_list<PlaneArg> planes) {
+    for (const PlaneArg& a : planes)
+        if (reinterpret_cast<uintptr_t>(a.p) & 15)
+            return fail(c, CSI_ERR_INVALID_ARG, "%s: %s must start on a 16-byte boundary (got %p)", who, a.name, a.p);
+    return CSI_OK;
+}
 
 // Which LS kernel serves this context.  With the Sylvester Hadamard pilot matrix the Walsh-Hadamard kernel on the
 // LDS-DMA ring.  Any other P: FFT-first (all Nt spectra in LDS) up to ls_fft_first_max antennas, the ring kernels with
@@ -1031,6 +1043,7 @@ int csi_predict_device(csi_ctx* c, const float* d_ltf_re, const float* d_ltf_im,
     if (npkt < 0 || (npkt > 0 && (!d_ltf_re || !d_ltf_im || !d_out_re || !d_out_im)))
         return fail(c, CSI_ERR_INVALID_ARG, "csi_predict_device: bad argument");
     if (npkt == 0) return CSI_OK;
+    if ((rc = planes_aligned(c, "csi_predict_device", {{"d_ltf_re", d_ltf_re}, {"d_ltf_im", d_ltf_im}, {"d_out_re", d_out_re}, {"d_out_im", d_out_im}}))) return rc;
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     auto run = [&]() -> int {
         const bool bf16 = c->cfg.dtype == CSI_DTYPE_BF16;
@@ -1088,6 +1101,8 @@ int csi_estimate_device(csi_ctx* c, const float* d_ltf_re, const float* d_ltf_im
     if (npkt < 0 || (npkt > 0 && (!d_ltf_re || !d_ltf_im || !d_out_re || !d_out_im || !d_h_re || !d_h_im)))
         return fail(c, CSI_ERR_INVALID_ARG, "csi_estimate_device: bad argument");
     if (npkt == 0) return CSI_OK;
+    if ((rc = planes_aligned(c, "csi_estimate_device", {{"d_ltf_re", d_ltf_re}, {"d_ltf_im", d_ltf_im}, {"d_out_re", d_out_re}, {"d_out_im", d_out_im},
+                                                        {"d_h_re", d_h_re}, {"d_h_im", d_h_im}}))) return rc;
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     auto run = [&]() -> int {
         const bool g = c->use_graph;
@@ -1135,6 +1150,7 @@ int csi_ls_estimate_device(csi_ctx* c, const float* d_ltf_re, const float* d_ltf
     if (npkt < 0 || (npkt > 0 && (!d_ltf_re || !d_ltf_im || !d_h_re || !d_h_im)))
         return fail(c, CSI_ERR_INVALID_ARG, "csi_ls_estimate_device: bad argument");
     if (npkt == 0) return CSI_OK;
+    if ((rc = planes_aligned(c, "csi_ls_estimate_device", {{"d_ltf_re", d_ltf_re}, {"d_ltf_im", d_ltf_im}, {"d_h_re", d_h_re}, {"d_h_im", d_h_im}}))) return rc;
     const csi_config& cf = c->cfg;
     const LsPlan plan = ls_plan(c);
     const int n_jc = (cf.nt + LSD_ROWS - 1) / LSD_ROWS;
@@ -1171,6 +1187,7 @@ int csi_lmmse_estimate_device(csi_ctx* c, const float* d_h_re, const float* d_h_
     if (npkt < 0 || L < 1 || (npkt > 0 && (!d_h_re || !d_h_im || !d_hvec || !d_snr_db || !d_out_re || !d_out_im)))
         return fail(c, CSI_ERR_INVALID_ARG, "csi_lmmse_estimate_device: bad argument");
     if (npkt == 0) return CSI_OK;
+    if (int rc = planes_aligned(c, "csi_lmmse_estimate_device", {{"d_h_re", d_h_re}, {"d_h_im", d_h_im}, {"d_out_re", d_out_re}, {"d_out_im", d_out_im}})) return rc;
     const csi_config& cf = c->cfg;
     HIP_TRY(c, hipSetDevice(cf.device));
     const int n_jc = (cf.nt + LM_RHS - 1) / LM_RHS;
@@ -1239,6 +1256,10 @@ int csi_hybrid_weights_device(csi_ctx* c, const float* d_h_re, const float* d_h_
                               int ns, int ntrf, float stop_tol, float* d_fbb_re, float* d_fbb_im, int32_t* d_idx, int32_t* d_n_atoms,
                               float* d_gain, float* d_frf_mean_re, float* d_frf_mean_im) {
     if (!c) return CSI_ERR_INVALID_ARG;
+    if (npkt > 0)
+        if (int rc = planes_aligned(c, "csi_hybrid_weights_device", {{"d_h_re", d_h_re}, {"d_h_im", d_h_im}, {"d_eval_re", d_eval_re}, {"d_eval_im", d_eval_im},
+                                                                  {"d_fbb_re", d_fbb_re}, {"d_fbb_im", d_fbb_im}, {"d_frf_mean_re", d_frf_mean_re},
+                                                                  {"d_frf_mean_im", d_frf_mean_im}})) return rc;
     return hybrid_weights_device(c, d_h_re, d_h_im, d_eval_re, d_eval_im, npkt, ns, ntrf, stop_tol, d_fbb_re, d_fbb_im, d_idx, d_n_atoms, d_gain,
                                  d_frf_mean_re, d_frf_mean_im);
 }
@@ -1279,6 +1300,9 @@ int csi_link_sim_device(csi_ctx* c, const float* d_h_re, const float* d_h_im, co
                         int bps, int32_t* d_bit_errors, float* d_evm_rms, float* d_dt_snr_db, float* d_xeq_re, float* d_xeq_im, float* d_csi,
                         float* d_llr, uint8_t* d_bits) {
     if (!c) return CSI_ERR_INVALID_ARG;
+    if (npkt > 0)
+        if (int rc = planes_aligned(c, "csi_link_sim_device", {{"d_h_re", d_h_re}, {"d_h_im", d_h_im}, {"d_fbb_re", d_fbb_re}, {"d_fbb_im", d_fbb_im},
+                                                            {"d_frf_re", d_frf_re}, {"d_frf_im", d_frf_im}, {"d_xeq_re", d_xeq_re}, {"d_xeq_im", d_xeq_im}})) return rc;
     return link_sim_device(c, d_h_re, d_h_im, d_fbb_re, d_fbb_im, d_frf_re, d_frf_im, d_noise_var, seed, first_pkt, npkt, ns, ntrf, n_sym, bps,
                            d_bit_errors, d_evm_rms, d_dt_snr_db, d_xeq_re, d_xeq_im, d_csi, d_llr, d_bits);
 }
@@ -2155,6 +2179,7 @@ int csi_synth_white(csi_ctx* c, uint64_t seed, int64_t first_pkt, int64_t npkt, 
     if (!c) return CSI_ERR_INVALID_ARG;
     if (npkt < 0 || first_pkt < 0 || (npkt > 0 && (!d_re || !d_im))) return fail(c, CSI_ERR_INVALID_ARG, "csi_synth_white: bad argument");
     if (npkt == 0) return CSI_OK;
+    if (int rc = planes_aligned(c, "csi_synth_white", {{"d_re", d_re}, {"d_im", d_im}})) return rc;
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     const size_t per_pkt = (size_t)c->cfg.nr * c->cfg.len_ltf;
     const size_t n = per_pkt * (size_t)npkt;

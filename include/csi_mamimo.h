@@ -35,6 +35,18 @@
  * has pinned (hipHostMalloc / hipHostRegister).  *_device entry points take device pointers, enqueue on the
  * context's stream and return without waiting; call csi_synchronize before reading results.
  *
+ * Device pointers (csi_predict_device, csi_ls_estimate_device, csi_estimate_device, csi_lmmse_estimate_device, csi_nmse_device,
+ * csi_hybrid_weights_device, csi_link_sim_device, csi_viterbi_decode_device, csi_synth_*).  An array of exactly the documented
+ * size suffices: it may be a slice of a larger allocation whose neighbours hold live data of any value (NaN and 1e38 included).
+ * Nothing outside the arrays is written, nothing outside them reaches a result, and input arrays are not modified.  Every re / im
+ * PLANE (the preambles [npkt][Nr][len_ltf], the CSI planes [npkt][Nr][Nt][234 or n_out], fbb, frf_mean, xeq) starts on a 16-byte
+ * boundary: the LS and layer-0 kernels move the caller's rows as 16-byte words and by LDS-DMA; hipMalloc, csi_device_malloc and
+ * whole torch tensors satisfy that, and so does every packet range of a preamble or CSI plane (Nt is a multiple of 4).  A
+ * misaligned plane is refused with CSI_ERR_INVALID_ARG and a text that names the argument, before anything is launched or counted.
+ * The remaining arrays - hvec, snr_db, noise_var, noise_std, tau, the per-packet and per-link results, idx, n_atoms, gain, csi,
+ * llr, bits - and the four planes of csi_nmse_device ([nlinks][n_bins] for ANY n_bins) are read and written element by element and
+ * need the alignment of their element type only.
+ *
  * Sample / output order everywhere: s = p*Nr*Nt + iRx*Nt + iTx
  * (create_massiveMIMO_CSIest_dnn_dataset.py:62), i.e. outputs are [Npkt][Nr][Nt][n_out],
  * which is MATLAB CSI(:, iTx, iRx) of packet p (BER_test_maMIMO_LTF.m:191-195).
