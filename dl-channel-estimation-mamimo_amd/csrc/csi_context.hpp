@@ -140,6 +140,15 @@ struct csi_trainer;          // csi_train.hpp
 struct csi_hostpipe;         // csi_hostpipe.hpp
 struct csi_comm;             // csi_comm.hpp
 
+// The forms of the fused band kernel (gemm_hs_band.hip.h) a context can launch, per arithmetic mode: the 8-wave kernel of band_kernel_gen.py with the
+// L0 / T streams staged through LDS, with per-lane global loads of them (nt outside the staged range), in its column-split launch (grid (bands, splits),
+// split y computes N1 / splits of the hidden features), and the register-blocked kernel of band4_kernel_gen.py (staged only) unsplit / column-split.
+enum BandForm { BAND_EIGHT, BAND_EIGHT_NOSTAGE, BAND_EIGHT_CS, BAND_FOUR, BAND_FOUR_CS, BAND_FORMS };
+struct BandKernel {
+    hipFunction_t fn;         // null: the code object does not hold this form
+    unsigned threads;         // its workgroup size
+};
+
 struct csi_ctx {
     csi_config cfg;
     int d_in = 0;                // layer-0 input width: l0_k + nt
@@ -220,7 +229,7 @@ struct csi_ctx {
     int l0_stream_max_rows = 1280;     // "l0_stream_max_rows": the largest call (rx preambles) the kernel takes (<= 4096), beyond 256 in row blocks (gridDim.z).
                                        // Measured (profiles/r05_band_split_probe.txt): 128 packets 400 -> 323 us, 256: 693 -> 595, 320: 862 -> 790; 500 packets 1108 -> 1134 (not taken)
     int l0_stream_prepass_rows = 64;   // "l0_stream_prepass_rows": beyond this many preambles the row scales come from l0_row_max_kernel
-    int small_rows_band = 256;   // "small_rows_band": the same limit where the column-split band kernel serves the model (csi_dnn_hs.hpp): the general
+    int small_rows_band = 256;   // "small_rows_band": the same limit where the column-split band kernel serves the model (csi_band.hpp): the general
                                  // path with it and the weight-streaming layer 0 takes 102 us at 3 ... 5 packets against 117-121 here (2 packets: 111 / 61)
     bool in_host_pipeline = false;   // a chunk of a host-buffer entry point is being enqueued: no second-stream fork inside (measured: the
                                  // two-stream arrangement costs the PCIe-bound pipeline 6 % - profiles/r05_regime_probe.txt)
@@ -255,22 +264,10 @@ struct csi_ctx {
                                  // kernel of band_kernel_gen.py (h2 stays in registers; measured -4 .. -7 % against the two kernels,
                                  // profiles/r03_band_probe.txt); 0 = the separate pair and regressor kernels
     hipModule_t band_mod = nullptr;          // its code object (embedded in the library, loaded on first use)
-    hipFunction_t band_fn = nullptr;
-    hipFunction_t band_fn_bf16 = nullptr;
-    hipFunction_t band_fn_bf16_ns = nullptr;   // bf16 form without the staged T / L0 streams (nt outside 32 .. 64)
-    hipFunction_t band_fn_ns = nullptr;        // split-f16 form without them (nt outside 16 .. 128)
-    hipFunction_t band_fn_bf16_cs = nullptr;   // ... of the bf16 form
-    hipFunction_t band_fn_cs = nullptr;        // column-split form: grid (bands, splits), split y computes N1 / splits of the hidden features
-    hipFunction_t band_fn4_cs = nullptr;       // column-split launches of the register-blocked forms (csi_band4_cs / csi_band4_bf16_cs)
-    hipFunction_t band_fn4_bf16_cs = nullptr;
-    hipFunction_t band_fn4_p = nullptr, band_fn4_bf16_p = nullptr;      // persistent forms (one workgroup per CU walks the bands)
-    bool band_hs_persist = false, band_bf16_persist = false;            // hooked A/B runs: CSI_BAND8_NAME / CSI_BAND8_BF16_NAME name a persistent form
-    int n_cu = 256;                                                      // compute units of the device (csi_create)
-    hipFunction_t band_fn4 = nullptr;          // register-blocked split-f16 form (band4_kernel_gen.py "csi_band4"), staged, 16 <= nt <= 128
-    int band_hs_threads = 512;                 // workgroup size of band_fn (a CSI_BAND8_NAME variant named csi_band4* has 256)
-    hipFunction_t band_fn4_bf16 = nullptr;     // register-blocked bf16 form (band4_kernel_gen.py: 4 waves x 512 registers, 256 threads), staged, 32 <= nt <= 64
-    int band_bf16_threads = 512;               // workgroup size of band_fn_bf16 (a CSI_BAND8_BF16_NAME variant named csi_band4* has 256)
-    int band4 = 1;                             // "band4": bf16 contexts take the register-blocked form where it applies (0 = csi_band8_bf16; A/B)
+    BandKernel band_kernel[2][BAND_FORMS] = {};   // its kernels by [bf16 context][form] (csi_band.hpp: band_load fills the table, band_plan chooses from it)
+    int n_cu = 256;                          // compute units of the device (csi_create)
+    int band4 = 1;                           // "band4": staged shapes with at most 2 column splits take the register-blocked forms csi_band4* (band4_kernel_gen.py:
+                                             // 4 waves x 512 registers) in fp32 and bf16 contexts alike; 0 = the 8-wave forms csi_band8* everywhere (A/B)
     bool band_failed = false;                // the code object could not be loaded: separate kernels from then on
     int64_t band_launches = 0;
     int band_split = -1;         // "band_split": calls with fewer bands than CUs split every band's hidden features over 2 / 4 workgroups (the

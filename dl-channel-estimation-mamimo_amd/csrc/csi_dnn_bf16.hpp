@@ -1,6 +1,7 @@
 // csi_dnn_bf16.hpp - host orchestration of the bf16-operand DNN path (BASELINE config 3).
 #pragma once
 #include "csi_context.hpp"
+#include "csi_band.hpp"
 
 namespace {
 
@@ -334,8 +335,8 @@ int predict_plane_bf16(csi_ctx* c, Model& m, const float* d_ltf, int64_t npkt, f
             };
             PairSrc src{l0sum, m.T, h1, nt};
             const Layer& lr = m.layers[nh];
-            hipFunction_t fn = nullptr;
             BandArgs ba{};
+            bool band = false, staged = false;
             if (nh == 2 && c->hs_band && lr.Wb_p) {
                 // first per-pair layer + regressor as one kernel, h2 in registers: the bf16 form of the assembly band kernel.  With the
                 // L0 / T values of the fragments streamed through LDS (32 <= nt <= 64) it replaces the two bf16 kernels by default: 3.52
@@ -346,52 +347,18 @@ int predict_plane_bf16(csi_ctx* c, Model& m, const float* d_ltf, int64_t npkt, f
                 ba.acc_scale1 = 1.f; ba.out_scale = 1.f;
                 ba.W2p = reinterpret_cast<const uint16_t*>(lr.Wb_p); ba.ldb2 = lr.ldwb; ba.bias2 = lr.bias; ba.n2 = cf.n_out; ba.acc_scale2 = 1.f;
                 ba.out = d_out + (size_t)p0 * nr * nt * cf.n_out; ba.ldo = cf.n_out; ba.peak = nullptr;
-                if (band8_serves(ba, true) && (c->hs_band >= 2 || band8_staged(ba)) && l1.in == h1 && lr.in == l1.out && l1.ldwb == h1 && lr.ldwb == l1.out) {
-                    rc = band8_function(c, &fn, true, band8_staged(ba) && c->hs_band != 3);
-                    if (rc) return rc;
-                }
-                if (fn && band8_staged(ba) && c->hs_band != 3) {       // the kernel streams the pilot table slab by slab through LDS: its slab-ordered copy
-                    if (!m.T_sw_ok) {
-                        const size_t floats = (size_t)(h1 / 32 + 1) * nt * 32;
-                        if (!m.T_sw && hipMalloc((void**)&m.T_sw, (floats + 512) * sizeof(float)) != hipSuccess)
-                            return fail(c, CSI_ERR_NOMEM, "device allocation of the slab-ordered pilot table failed");
-                        hipLaunchKernelGGL(band_tsw_kernel<32>, dim3(256), dim3(256), 0, c->stream, m.T, h1, nt, h1, m.T_sw);
-                        HIP_TRY(c, hipGetLastError());
-                        m.T_sw_ok = true;
-                    }
-                    ba.Ts = m.T_sw;
-                }
+                staged = band8_staged(ba) && c->hs_band != 3;
+                band = band8_serves(ba, true) && (c->hs_band >= 2 || band8_staged(ba)) && l1.in == h1 && lr.in == l1.out && l1.ldwb == h1 && lr.ldwb == l1.out &&
+                       band_load(c);
             }
-            if (fn) {
-                rc = sum_slabs();
+            if (band) {
+                if (staged) rc = band_pilot_slabs(c, m, ba, true);          // (in front of the slab sum, where it has always been queued)
+                if (!rc) rc = sum_slabs();
                 if (rc) return rc;
                 const double flops = 2.0 * (double)M2 * l1.out * h1 + 2.0 * (double)M2 * cf.n_out * l1.out;
                 const double bytes = 4.0 * ((double)M2 / nt * h1 + (double)nt * h1) + 2.0 * ((double)l1.out * h1 + (double)cf.n_out * l1.out) + 4.0 * (double)M2 * cf.n_out;
-                // small calls: the column-split launch (csi_dnn_hs.hpp); its partial outputs live in the h1 / activation buffers this path leaves unused
-                const bool staged_fn = fn == c->band_fn_bf16;
-                const int Sb = (staged_fn && ba.ldo == ba.n2 && (ba.N1 * (long)ba.ldb1 * 2 < 0x7fffffffL)) ?
-                                   band8_splits(c, ba, ((size_t)M2 * h1 + (size_t)M2 * maxh) / 2, true) : 1;
-                // round 6: the register-blocked form (4 waves x 512 registers) serves the same staged shapes with the same operand buffers
-                const bool hooked4 = c->band_bf16_threads == 256;          // (CSI_DEBUG_HOOKS: a csi_band4* variant named in place of csi_band8_bf16)
-                const bool blocked = staged_fn && c->band4 && c->band_fn4_bf16 && !ba.stamps;
-                if (Sb > 1) {
-                    const bool b4 = blocked && c->band_fn4_bf16_cs && Sb == 2;      // (4 splits: the 8-wave form, as in fp32 contexts - csi_dnn_hs.hpp)
-                    if (b4) rc = band4_prepare(c, m, ba, true);
-                    if (!rc) rc = band8_launch_split(c, ba, Sb, reinterpret_cast<float*>(h1b), flops, bytes, true, b4);
-                } else {
-                    const BandArgs ba_plain = ba;          // (band4_prepare puts the tiled weight copies into ba)
-                    if (blocked || (staged_fn && hooked4 && !ba.stamps)) {
-                        rc = band4_prepare(c, m, ba, true);
-                        if (blocked) fn = c->band_fn4_bf16;
-                    }
-                    long r0 = 0;
-                    const int St = (!rc && staged_fn && (ba.N1 * (long)ba.ldb1 * 2 < 0x7fffffffL)) ?
-                                       band_tail_plan(c, ba, ((size_t)M2 * h1 + (size_t)M2 * maxh) / 2, true, &r0) : 0;
-                    if (St) {
-                        const bool b4 = blocked && c->band_fn4_bf16_cs && St == 2;
-                        rc = band_tail_launch(c, fn, ba, b4 ? ba : ba_plain, b4, St, r0, reinterpret_cast<float*>(h1b), flops, bytes, true);
-                    } else if (!rc) rc = band8_launch(c, fn, ba, flops, bytes);
-                }
+                // (the partial outputs of column splits live in the h1 / activation buffers this path leaves unused)
+                rc = band_run(c, m, ba, true, staged, reinterpret_cast<float*>(h1b), ((size_t)M2 * h1 + (size_t)M2 * maxh) / 2, flops, bytes);
                 done = true;
             } else if (fused_ok) {
                 rc = sum_slabs();

@@ -4,6 +4,7 @@
 // the layer-0 product L0 is plain fp32 either way the two engines mix freely per layer.
 #pragma once
 #include "csi_context.hpp"
+#include "csi_band.hpp"
 
 namespace {
 
@@ -256,207 +257,6 @@ int hs_launch_gemm(csi_ctx* c, int kid, GemmHsArgs g) {
     return CSI_OK;
 }
 
-// ---- the fused band kernel (gemm_hs_band.hip.h, band_kernel_gen.py): code object embedded at build time
-#if __has_include("band8_hsaco.inc")
-#include "band8_hsaco.inc"
-#define CSI_HAVE_BAND8 1
-#else
-#warning "band8_hsaco.inc not found: this build has NO fused band kernel (the separate pair + regressor kernels serve every call; option band_available reads 0).  _lib.build_library() generates it: band_kernel_gen.py -> clang -x assembler -mcpu=gfx950 -> ld.lld"
-#endif
-
-int band8_function(csi_ctx* c, hipFunction_t* fn, bool bf16 = false, bool staged = false) {
-    *fn = nullptr;
-#ifdef CSI_HAVE_BAND8
-    if (c->band_failed) return CSI_OK;
-    if (!c->band_mod) {
-        // timing experiments (tools/): CSI_BAND8_HSACO = a code object built by tools/build_band8.sh (every ablation variant of
-        // band_kernel_gen.py), CSI_BAND8_NAME / CSI_BAND8_BF16_NAME = the variants to run in place of the two product kernels
-        // Honoured only together with CSI_DEBUG_HOOKS=1: a production process never loads a code object named by its environment.
-        const char* hooks = std::getenv("CSI_DEBUG_HOOKS");
-        const char* ext = hooks && hooks[0] == '1' ? std::getenv("CSI_BAND8_HSACO") : nullptr;
-        const char* n_hs = std::getenv("CSI_BAND8_NAME");
-        const char* n_bf = std::getenv("CSI_BAND8_BF16_NAME");
-        const hipError_t le = ext && *ext ? hipModuleLoad(&c->band_mod, ext) : hipModuleLoadData(&c->band_mod, band8_hsaco);
-        if (le != hipSuccess || hipModuleGetFunction(&c->band_fn, c->band_mod, ext && n_hs ? n_hs : "csi_band8") != hipSuccess ||
-            hipModuleGetFunction(&c->band_fn_bf16, c->band_mod, ext && n_bf ? n_bf : "csi_band8_bf16") != hipSuccess ||
-            hipModuleGetFunction(&c->band_fn_bf16_ns, c->band_mod, "csi_band8_bf16_nostage") != hipSuccess ||
-            hipModuleGetFunction(&c->band_fn_ns, c->band_mod, "csi_band8_nostage") != hipSuccess) {
-            (void)hipGetLastError();
-            c->band_failed = true;       // not fatal: the separate kernels serve the call
-            c->band_fn = c->band_fn_bf16 = c->band_fn_bf16_ns = c->band_fn_ns = nullptr;
-            return CSI_OK;
-        }
-        if (hipModuleGetFunction(&c->band_fn_cs, c->band_mod, "csi_band8_cs") != hipSuccess) {      // (an external code object may lack it)
-            (void)hipGetLastError();
-            c->band_fn_cs = nullptr;
-        }
-        if (hipModuleGetFunction(&c->band_fn_bf16_cs, c->band_mod, "csi_band8_bf16_cs") != hipSuccess) {
-            (void)hipGetLastError();
-            c->band_fn_bf16_cs = nullptr;
-        }
-        if (hipModuleGetFunction(&c->band_fn4, c->band_mod, "csi_band4") != hipSuccess) {
-            (void)hipGetLastError();
-            c->band_fn4 = nullptr;
-        }
-        c->band_hs_threads = (ext && n_hs && std::strncmp(n_hs, "csi_band4", 9) == 0) ? 256 : BAND8_THREADS;
-        const auto ends_p = [](const char* n) { const size_t l = n ? std::strlen(n) : 0; return l > 2 && n[l - 2] == '_' && n[l - 1] == 'p'; };
-        c->band_hs_persist = ext && ends_p(n_hs);          // hooked A/B runs of the persistent forms (csi_band4_p / csi_band4_bf16_p)
-        c->band_bf16_persist = ext && ends_p(n_bf);
-        if (hipModuleGetFunction(&c->band_fn4_p, c->band_mod, "csi_band4_p") != hipSuccess) { (void)hipGetLastError(); c->band_fn4_p = nullptr; }
-        if (hipModuleGetFunction(&c->band_fn4_bf16_p, c->band_mod, "csi_band4_bf16_p") != hipSuccess) { (void)hipGetLastError(); c->band_fn4_bf16_p = nullptr; }
-        if (hipModuleGetFunction(&c->band_fn4_cs, c->band_mod, "csi_band4_cs") != hipSuccess) { (void)hipGetLastError(); c->band_fn4_cs = nullptr; }
-        if (hipModuleGetFunction(&c->band_fn4_bf16_cs, c->band_mod, "csi_band4_bf16_cs") != hipSuccess) { (void)hipGetLastError(); c->band_fn4_bf16_cs = nullptr; }
-        if (hipModuleGetFunction(&c->band_fn4_bf16, c->band_mod, "csi_band4_bf16") != hipSuccess) {
-            (void)hipGetLastError();
-            c->band_fn4_bf16 = nullptr;
-        }
-        c->band_bf16_threads = (ext && n_bf && std::strncmp(n_bf, "csi_band4", 9) == 0) ? 256 : BAND8_THREADS;
-    }
-    *fn = bf16 ? (staged ? c->band_fn_bf16 : c->band_fn_bf16_ns) : (staged ? c->band_fn : c->band_fn_ns);
-#endif
-    return CSI_OK;
-}
-
-// Static part of "the column-split band kernel serves this model's per-pair layers" (band8_serves + band8_staged + band8_splits on
-// the shapes alone): with it a call of a few hundred pair rows is faster on the split engine than on the fp32 MFMA kernels -
-// 5 ... 20 packets of the shipped shape 136-142 us against 155-260 (profiles/r05_band_split_probe.txt)
-bool band_split_static_ok(csi_ctx* c, const Model& m) {
-    const csi_config& cf = c->cfg;
-    if (cf.n_hidden != 2 || !c->hs_band || c->hs_band == 3 || c->hs_fuse_regressor || c->band_split == 0 || c->band_split == 1 ||
-        c->force_pair_tile == 128)
-        return false;
-    if (m.layers.size() < 3 || !m.layers[2].Wh_p) return false;
-    const int h1 = cf.hidden[0], n1 = cf.hidden[1];
-    if (cf.nt < 16 || cf.nt > 128 || h1 < 128 || (h1 % 64) != 0 || (n1 % 512) != 0 || n1 > BAND8_MAX_N1 || cf.n_out < 1 || cf.n_out > 256) return false;
-    hipFunction_t fn = nullptr;
-    if (band8_function(c, &fn, false, true) != CSI_OK || !fn) return false;
-    return c->band_fn_cs != nullptr;
-}
-
-// The register-blocked band kernels (band4_kernel_gen.py) stream PRE-TILED weights: built once per model at first use (band4_tile_kernel), then the
-// argument record's W1 / W2p point at the tiled copies.  bf16: sub-tiles of 32 k, 8 regressor fragments per column step; split-f16: 16 k, 16 fragments.
-int band4_prepare(csi_ctx* c, Model& m, BandArgs& ba, bool bf16) {
-    if (!m.tiled_ok) {
-        const int ncol = ba.N1 / 256, nsub = ba.K1 / (bf16 ? 32 : 16), nq = bf16 ? 8 : 16;
-        const size_t b1 = (size_t)(ncol * nsub + 4) * BAND_SLOT_BYTES, b2 = (size_t)ncol * nq * BAND_SLOT_BYTES;
-        if (b1 >= 0x7fffffffull) return fail(c, CSI_ERR_INVALID_ARG, "band weights of %zu bytes: beyond what the tiled copy addresses", b1);
-        if ((!m.Wt1 && hipMalloc((void**)&m.Wt1, b1) != hipSuccess) || (!m.Wt2 && hipMalloc((void**)&m.Wt2, b2) != hipSuccess))
-            return fail(c, CSI_ERR_NOMEM, "device allocation of the tiled band weights failed");
-        hipLaunchKernelGGL(band4_tile_kernel, dim3(512), dim3(256), 0, c->stream, ba.W1, ba.ldb1, ncol, nsub, 0, 4, m.Wt1);
-        hipLaunchKernelGGL(band4_tile_kernel, dim3(512), dim3(256), 0, c->stream, ba.W2p, ba.ldb2, ncol, nq, bf16 ? 1 : 2, 0, m.Wt2);
-        HIP_TRY(c, hipGetLastError());
-        m.tiled_ok = true;
-    }
-    ba.W1 = m.Wt1;
-    ba.W2p = m.Wt2;
-    return CSI_OK;
-}
-
-int band8_launch(csi_ctx* c, hipFunction_t fn, const BandArgs& ba, double flops, double bytes) {
-    ++c->band_launches;
-    ProfScope ps(c, K_PAIR_DENSE, flops, bytes);
-    Band8ArgsCs a8{band8_args(ba), nullptr, 0};
-    const unsigned bands = (unsigned)((ba.M + BAND_ROWS - 1) / BAND_ROWS);
-    // the persistent forms (round 6: csi_band4_p / csi_band4_bf16_p): one workgroup per CU walks bands x, x + P, ...; P travels in the record's last quadword
-    const bool persist = fn == c->band_fn4_p || fn == c->band_fn4_bf16_p || (fn == c->band_fn && c->band_hs_persist) || (fn == c->band_fn_bf16 && c->band_bf16_persist);
-    const unsigned grid = persist ? std::min(bands, (unsigned)std::max(c->n_cu, 1)) : bands;
-    a8.pad = grid;
-    size_t sz = persist ? sizeof(a8) : sizeof(a8.a);
-    void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a8, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-    // the register-blocked form is a workgroup of 4 waves (band4_kernel_gen.py), the others of 8
-    const unsigned threads = (fn == c->band_fn4_bf16 || fn == c->band_fn4 || fn == c->band_fn4_p || fn == c->band_fn4_bf16_p) ? 256u :
-                             (fn == c->band_fn_bf16 ? (unsigned)c->band_bf16_threads : (fn == c->band_fn ? (unsigned)c->band_hs_threads : (unsigned)BAND8_THREADS));
-    HIP_TRY(c, hipModuleLaunchKernel(fn, grid, 1, 1, threads, 1, 1, 0, c->stream, nullptr, extra));
-    return CSI_OK;
-}
-
-// Column splits of a call of `bands` bands: a band is one workgroup's work for ~200 us, so a call with fewer bands than CUs leaves
-// CUs idle for that long - 2 or 4 workgroups per band, each over N1 / splits hidden features, fill them ("band_split";
-// profiles/r05_band_split_probe.txt: 24 packets 248 -> 149 us, 64 packets 299 -> 251 us)
-int band8_splits(const csi_ctx* c, const BandArgs& ba, size_t part_capacity_floats, bool bf16 = false) {
-    if (!(bf16 ? c->band_fn_bf16_cs : c->band_fn_cs) || c->band_split == 0 || c->band_split == 1 || ba.stamps) return 1;
-    const long bands = (ba.M + BAND_ROWS - 1) / BAND_ROWS;
-    int S = 1;
-    if (c->band_split > 1) {
-        S = c->band_split;
-    } else {
-        const long in_flight = bands * std::max(c->models_in_flight, 1);
-        while (S < 4 && in_flight * (2 * S) <= 256) S *= 2;
-        // a second round of workgroups that is at most a quarter full (129 ... 160 packets of the shipped shape): half-size workgroups
-        // fill it better - 144 packets 502 -> 460 us, 160: 511 -> 476; from 192 packets on the split only costs (profiles/r05_band_split_probe.txt)
-        if (S == 1 && in_flight > 256 && in_flight <= 320) S = 2;
-    }
-    while (S > 1 && (ba.N1 % (256 * S)) != 0) S >>= 1;
-    const unsigned long long part = (unsigned long long)(S - 1) * (unsigned long long)ba.M * (unsigned long long)ba.ldo;
-    if (S > 1 && (part > part_capacity_floats || part * 4ull >= 0xffffffffull || (unsigned long long)ba.N1 * ba.ldb1 * 2ull >= 0x7fffffffull)) return 1;
-    return S;
-}
-
-// the column-split launch: partial outputs of splits 1 .. in `part`, added to split 0's output in split order
-int band8_launch_split(csi_ctx* c, const BandArgs& ba, int S, float* part, double flops, double bytes, bool bf16 = false, bool blocked = false,
-                       int kid = K_PAIR_DENSE) {
-    ++c->band_launches;
-    ++c->band_split_launches;
-    BandArgs one = ba;
-    one.N1 = ba.N1 / S;
-    Band8ArgsCs a{};
-    a.a = band8_args(one);
-    a.part = part;
-    size_t sz = sizeof(a);
-    void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-    {
-        ProfScope ps(c, kid, flops, bytes);
-        // blocked: the register-blocked form (4 waves; ba.W1 / W2p are the tiled copies of the WHOLE layer: split y starts at its own column steps)
-        const hipFunction_t fn = blocked ? (bf16 ? c->band_fn4_bf16_cs : c->band_fn4_cs) : (bf16 ? c->band_fn_bf16_cs : c->band_fn_cs);
-        HIP_TRY(c, hipModuleLaunchKernel(fn, (unsigned)((ba.M + BAND_ROWS - 1) / BAND_ROWS), (unsigned)S, 1, blocked ? 256u : (unsigned)BAND8_THREADS, 1, 1, 0, c->stream, nullptr, extra));
-    }
-    const size_t n = (size_t)ba.M * ba.ldo;
-    ProfScope ps(c, K_SPLITK_REDUCE, (double)(S - 1) * n, 4.0 * (S + 1) * (double)n);
-    hipLaunchKernelGGL(band_split_sum_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 2048)), dim3(256), 0, c->stream, ba.out, part, n, n, S - 1);
-    HIP_TRY(c, hipGetLastError());
-    return CSI_OK;
-}
-
-// "band_tail_split" (round 6): one workgroup per CU computes a band for 75-190 us, so a call of `bands` bands runs in ceil(bands / CUs) rounds and a last
-// round of a few bands costs a whole one (configs[2]: 10 000 bands = 39 rounds + 16 bands = 2.5 % of the kernel's time for 0.16 % of the work).  When that
-// round holds at most half (a quarter) of the CUs' worth of bands it is launched separately in 2 (4) column splits - the rows of the full rounds through
-// the unsplit kernel, the rest through the column-split one on shifted operand pointers.  Returns the split count of the tail (0: one launch) and its first row.
-inline int band_tail_plan(const csi_ctx* c, const BandArgs& ba, size_t part_capacity_floats, bool bf16, long* row0) {
-    // measured (tools/band_tail_ab.py, profiles/r06_band_probe.txt (G)): fp32 contexts -2.8 ... -3.2 % per call where it applies (2100 / 2600 / 3100 / 4150 packets of the
-    // shipped shape); bf16 contexts 0 ... +1 % (bands of 75 us backfill the last round well enough; the 8-wave split kernels and the extra sum eat the rest): fp32 only
-    if (bf16) return 0;
-    if (!c->band_tail_split || c->models_in_flight > 1 || ba.stamps || c->band_split == 0 || c->band_split == 1) return 0;
-    if (!(bf16 ? c->band_fn_bf16_cs : c->band_fn_cs) || ba.ldo != ba.n2) return 0;
-    const long ncu = std::max(c->n_cu, 1), bands = (ba.M + BAND_ROWS - 1) / BAND_ROWS;
-    const long full = bands / ncu * ncu, tail = bands - full;
-    if (full < ncu || tail == 0) return 0;
-    int S = 0;
-    for (int s = 4; s >= 2; s >>= 1)
-        if (tail * s <= ncu && (ba.N1 % (256 * s)) == 0) { S = s; break; }
-    const long r0 = full * BAND_ROWS;
-    if (!S || ba.nt < 1 || (r0 % ba.nt) != 0) return 0;
-    const unsigned long long part = (unsigned long long)(S - 1) * (unsigned long long)(ba.M - r0) * (unsigned long long)ba.ldo;
-    if (part > part_capacity_floats || (unsigned long long)ba.N1 * ba.ldb1 * 2ull >= 0x7fffffffull) return 0;
-    *row0 = r0;
-    return S;
-}
-// the two launches of a tail-split call: `full` = the arguments the unsplit kernel `fn` takes (tiled weights if it is a register-blocked form), `cs` = the
-// arguments of the column-split launch (tiled weights iff cs_blocked)
-inline int band_tail_launch(csi_ctx* c, hipFunction_t fn, const BandArgs& full, const BandArgs& cs, bool cs_blocked, int S, long r0, float* part, double flops,
-                            double bytes, bool bf16) {
-    const double f0 = (double)r0 / (double)full.M;
-    BandArgs a0 = full;
-    a0.M = (int)r0;
-    int rc = band8_launch(c, fn, a0, flops * f0, bytes * f0);
-    if (rc) return rc;
-    BandArgs a1 = cs;
-    a1.M = cs.M - (int)r0;
-    a1.L0 = cs.L0 + (size_t)(r0 / cs.nt) * cs.ldl;
-    a1.out = cs.out + (size_t)r0 * cs.ldo;
-    ++c->band_tail_launches;
-    return band8_launch_split(c, a1, S, part, flops * (1.0 - f0), bytes * (1.0 - f0), bf16, cs_blocked, K_PAIR_DENSE_TAIL);
-}
-
 // csi_profile_band_skeleton: the band kernel's MFMA + barrier skeleton (band_kernel_gen.py 'skeleton_rnd': no operand conversion, no
 // L0 / T streams, no LDS-DMA, no fragment reads; its 48 operand registers filled once from the model's own split weights, relu-like
 // zeros in the activation fragments) on `rows` pair rows of the loaded real model.  What it measures is the rate the matrix pipe of
@@ -468,17 +268,14 @@ int band_skeleton_time(csi_ctx* c, int64_t rows, int iters, double* ms_per_launc
     Model& m = c->model[0];
     if (cf.dtype != CSI_DTYPE_F32 || cf.n_hidden != 2 || !m.loaded || !m.layers[2].Wh_p || rows <= 0 || rows > (1 << 30) || iters < 1)
         return fail(c, CSI_ERR_INVALID_ARG, "csi_profile_band_skeleton: needs an fp32 context with the two-hidden-layer model loaded, rows > 0");
-    hipFunction_t fn = nullptr;
-    int rc = band8_function(c, &fn, false, true);
-    if (rc) return rc;
     hipFunction_t sk = nullptr;
-    if (!fn || hipModuleGetFunction(&sk, c->band_mod, "csi_band8_skeleton_rnd") != hipSuccess || !sk) {
+    if (!band_load(c) || hipModuleGetFunction(&sk, c->band_mod, "csi_band8_skeleton_rnd") != hipSuccess || !sk) {
         (void)hipGetLastError();
         return fail(c, CSI_ERR_NOT_READY, "csi_profile_band_skeleton: the band kernel's code object holds no skeleton variant");
     }
     const Layer &l1 = m.layers[1], &lr = m.layers[2];
     const int h1 = cf.hidden[0], M2 = (int)rows;
-    rc = ensure_bytes(c, &c->ws, &c->ws_bytes, (size_t)M2 * cf.n_out * sizeof(float) + ((size_t)M2 / std::max(cf.nt, 1) + 256) * h1 * sizeof(float));
+    int rc = ensure_bytes(c, &c->ws, &c->ws_bytes, (size_t)M2 * cf.n_out * sizeof(float) + ((size_t)M2 / std::max(cf.nt, 1) + 256) * h1 * sizeof(float));
     if (rc) return rc;
     BandArgs ba{};
     ba.out = reinterpret_cast<float*>(c->ws); ba.ldo = cf.n_out;
@@ -550,7 +347,7 @@ int hs_tail(csi_ctx* c, Model& m, const float* l0sum, int M2, float* hbuf0, floa
     }
     const Layer& lr = m.layers[nh];
     if (nh == 2 && c->hs_band && !c->hs_fuse_regressor && lr.Wh_p) {
-        // first per-pair layer + regressor in one kernel, h2 in registers: the assembly band kernel (8 waves per 128-row band)
+        // first per-pair layer + regressor in one kernel, h2 in registers: the assembly band kernels (csi_band.hpp chooses the form)
         const int s1 = hs_act_shift_of(c, m, 1, true);
         BandArgs ba{};
         ba.L0 = l0sum; ba.Ts = m.T_hs; ba.ldl = h1; ba.nt = cf.nt; ba.in_scale = std::ldexp(1.f, s0);
@@ -558,54 +355,13 @@ int hs_tail(csi_ctx* c, Model& m, const float* l0sum, int M2, float* hbuf0, floa
         ba.acc_scale1 = std::ldexp(1.f, -(s0 + l1.wshift)); ba.out_scale = std::ldexp(1.f, s1);
         ba.W2p = lr.Wh_p; ba.ldb2 = lr.ldwh; ba.bias2 = lr.bias_hs; ba.n2 = cf.n_out; ba.acc_scale2 = std::ldexp(1.f, -(s1 + lr.wshift_f));
         ba.out = out; ba.ldo = cf.n_out; ba.peak = c->hs_peak;
-        hipFunction_t fn = nullptr;
         const bool staged = band8_staged(ba, false) && c->hs_band != 3;       // "hs_band" = 3: the form with per-lane global loads of L0 / T (A/B runs)
-        if (band8_serves(ba) && h1 == l1.in && lr.in == l1.out) {
-            int rc = band8_function(c, &fn, false, staged);
-            if (rc) return rc;
-        }
-        if (fn && staged) {     // the kernel streams the (pre-scaled) pilot table slab by slab through LDS: its slab-ordered copy
-            if (!m.T_sw_ok) {
-                // (+ 2 KiB: the last 1-KiB DMA chunk of a slab may reach past it, and the kernel requests one slab past the column step)
-                const size_t floats = (size_t)(h1 / 16 + 1) * cf.nt * 16;
-                if (!m.T_sw && hipMalloc((void**)&m.T_sw, (floats + 512) * sizeof(float)) != hipSuccess)
-                    return fail(c, CSI_ERR_NOMEM, "device allocation of the slab-ordered pilot table failed");
-                hipLaunchKernelGGL(band_tsw_kernel<16>, dim3(256), dim3(256), 0, c->stream, m.T_hs, h1, cf.nt, h1, m.T_sw);
-                HIP_TRY(c, hipGetLastError());
-                m.T_sw_ok = true;
-            }
-            ba.Ts = m.T_sw;
-        }
-        if (fn) {
+        if (band8_serves(ba) && h1 == l1.in && lr.in == l1.out && band_load(c)) {
             ++c->hs_launches;
             const double flops = 2.0 * (double)M2 * l1.out * h1 + 2.0 * (double)M2 * cf.n_out * l1.out;
             const double bytes = 4.0 * ((double)M2 / cf.nt * h1 + (double)cf.nt * h1 + (double)l1.out * h1 + (double)cf.n_out * l1.out + (double)M2 * cf.n_out);
-            // (the band path leaves the activation buffers unused: hbuf0 - M2 x 1024 floats here - holds the partial outputs)
-            const int S = (fn == c->band_fn && staged && ba.ldo == ba.n2) ? band8_splits(c, ba, (size_t)M2 * l1.out) : 1;
-            // round 6: the register-blocked forms (band4_kernel_gen.py "csi_band4" / "csi_band4_cs": 4 waves x 512 registers, every weight fragment against two
-            // row groups) on the same operands, their weight streams pre-tiled once per model
-            const bool hooked4 = c->band_hs_threads == 256;
-            const bool blocked = fn == c->band_fn && staged && c->band4 && c->band_fn4 && !ba.stamps;
-            if (S > 1) {
-                // (measured, tools/regime_probe.py band4=1 / 0 alternating: 2 splits - 64 packets - 192 against 195 us, 128 packets unsplit 304 against 315; 4 splits -
-                // 24 packets - 120 against 117 us: a quarter band on four waves has less to hide its waits behind)
-                const bool b4 = blocked && c->band_fn4_cs && S == 2;
-                if (b4) { const int rc = band4_prepare(c, m, ba, false); if (rc) return rc; }
-                return band8_launch_split(c, ba, S, hbuf0, flops, bytes, false, b4);
-            }
-            const BandArgs ba_plain = ba;          // (band4_prepare puts the tiled weight copies into ba)
-            if (blocked || (fn == c->band_fn && staged && hooked4 && !ba.stamps)) {
-                const int rc = band4_prepare(c, m, ba, false);
-                if (rc) return rc;
-                if (blocked) fn = c->band_fn4;
-            }
-            long r0 = 0;
-            const int St = (fn == c->band_fn4 || (fn == c->band_fn && staged)) ? band_tail_plan(c, ba, (size_t)M2 * l1.out, false, &r0) : 0;
-            if (St) {
-                const bool b4 = blocked && c->band_fn4_cs && St == 2;
-                return band_tail_launch(c, fn, ba, b4 ? ba : ba_plain, b4, St, r0, hbuf0, flops, bytes, false);
-            }
-            return band8_launch(c, fn, ba, flops, bytes);
+            // (the band path leaves the activation buffers unused: hbuf0 - M2 x 1024 floats here - holds the partial outputs of column splits)
+            return band_run(c, m, ba, false, staged, hbuf0, (size_t)M2 * l1.out, flops, bytes);
         }
     }
     if (nh == 2 && c->hs_fuse_regressor && lr.Wh_f && cf.n_out <= PP_BN && l1.out % PP_BN == 0) {

@@ -1387,7 +1387,7 @@ int csi_get_option(csi_ctx* c, const char* name, int64_t* value) {
     else if (n == "f32_engine") *value = c->f32_engine;
     else if (n == "hs_band") *value = c->hs_band;
     else if (n == "band4") *value = c->band4;
-    else if (n == "band4_available") *value = (c->cfg.dtype == CSI_DTYPE_BF16 ? c->band_fn4_bf16 : c->band_fn4) != nullptr;
+    else if (n == "band4_available") *value = c->band_kernel[c->cfg.dtype == CSI_DTYPE_BF16][BAND_FOUR].fn != nullptr;
     else if (n == "band_launches") *value = c->band_launches;
     else if (n == "band_split") *value = c->band_split;
     else if (n == "aux_fork_early") *value = c->aux_fork_early;
@@ -1440,15 +1440,7 @@ int csi_get_option(csi_ctx* c, const char* name, int64_t* value) {
     else if (n == "hs_range_fallbacks") *value = c->hs_range_fallbacks;
     else if (n == "hs_weight_pins") *value = c->hs_weight_pins;                  // models pinned to the fp32 MFMA kernels by the load-time check of their split copies
     else if (n == "hs_weight_err_e12") *value = (int64_t)(1e12 * std::max(c->model[0].hs_repr_err, c->model[1].hs_repr_err));    // worst relative representation error x 1e12
-    else if (n == "band_available") {                                            // 1: the fused band kernel's code object is embedded in this build and loads
-#ifdef CSI_HAVE_BAND8
-        hipFunction_t f = nullptr;
-        band8_function(c, &f, false, true);
-        *value = f != nullptr;
-#else
-        *value = 0;
-#endif
-    }
+    else if (n == "band_available") *value = band_load(c);                      // 1: the fused band kernel's code object is embedded in this build and loads
     else return fail(c, CSI_ERR_INVALID_ARG, "csi_get_option: unknown option '%s'", name);
     return CSI_OK;
 }

@@ -1,8 +1,9 @@
 // gemm_hs_band.hip.h - host / device pieces the library needs for the fused band kernel (first per-pair layer + regressor of the
 // shipped network, massiveMIMO_CSI_prediction_DNN.py:211-227, as ONE kernel with h2 in registers): its argument records, the
 // shape predicates, the k permutation of the regressor weights, the weight converter and the slab-ordered pilot table.
-// The kernel the library launches is generated assembly (band_kernel_gen.py: 8 waves, two per SIMD); the first form of the
-// idea - C++, 4 waves x 512 registers - lives in tools/gemm_hs_band4.hip.h (probe only: it is slower).
+// The kernels the library launches are generated assembly: band_kernel_gen.py (8 waves, two per SIMD) and the register-blocked
+// band4_kernel_gen.py (4 waves x 512 registers; the product's choice for staged shapes with at most 2 column splits); csi_band.hpp
+// chooses between them.  The first form of the idea - C++, 4 waves - lives in tools/gemm_hs_band4.hip.h (probe only).
 #pragma once
 #include "gemm_hs.hip.h"
 #include <type_traits>

@@ -434,10 +434,12 @@ int  csi_synchronize(csi_ctx* ctx);
  *                         32 <= nt <= 64 (streamed form); 0: the separate kernels (A/B runs); 2: bf16 contexts take the per-lane form
  *                         at any other nt as well (measured slower than the separate kernels); 3: only the per-lane forms (A/B runs).
  *                         Read-only: "band_launches".
- *   "band4"            1 (default): bf16 contexts take the REGISTER-BLOCKED form of that kernel where its streamed form applies (32 <= nt <= 64;
- *                         csrc/band4_kernel_gen.py "csi_band4_bf16": 4 waves x 512 registers, every weight fragment against two row
- *                         groups, weights pre-tiled at first use); 0: the 8-wave form "csi_band8_bf16" (A/B runs; same bf16 roundings,
- *                         fp32 sums in another order).  Read-only: "band4_available".
+ *   "band4"            1 (default): fp32 and bf16 contexts take the REGISTER-BLOCKED form of that kernel where its streamed form applies
+ *                         (fp32: 16 <= nt <= 128, bf16: 32 <= nt <= 64) and the call runs unsplit or in 2 column splits
+ *                         (csrc/band4_kernel_gen.py "csi_band4" / "csi_band4_bf16" and their "_cs" launches: 4 waves x 512 registers,
+ *                         every weight fragment against two row groups, weights pre-tiled at first use); 4 column splits stay on the
+ *                         8-wave form; 0: the 8-wave forms "csi_band8*" everywhere (A/B runs; same operand roundings, fp32 sums in
+ *                         another order).  Read-only: "band4_available".
  *   "band_split"       -1 (default): a call with fewer bands of 128 pair rows than the part has CUs (24 ... 64 packets of the shipped
  *                         shape) splits every band's hidden features over 2 or 4 workgroups ("csi_band8_cs") and adds their regressor
  *                         sums in split order - same arithmetic, the final fp32 sums associate differently (1 ulp class);

@@ -7,8 +7,11 @@
 //     hipEventSynchronize / hipStreamSynchronize / hipDeviceSynchronize block the caller - the happens-before edges HIP guarantees;
 //   * "device" and pinned memory are host memory; hipMalloc fills a buffer with a pattern derived from a global counter, so that two
 //     allocations never look alike by accident;
-//   * kernel launches (hipLaunchKernel, hipModuleLaunchKernel) go to mock::launch_hook when it is set and are otherwise counted and
+//   * kernel launches go to a hook when it is set (hipLaunchKernel: mock::launch_hook; hipModuleLaunchKernel: mock::module_launch_hook,
+//     which gets the NAME the function was looked up by and the HIP_LAUNCH_PARAM argument record) and are otherwise counted and
 //     dropped - a harness of host logic does not need what the kernels compute;
+//   * with MOCK_HIP_FAIL_MODULE_LOAD set in the environment hipModuleLoad / hipModuleLoadData fail, and - as in the real runtime - the
+//     error stays the thread's last error until hipGetLastError reads it;
 //   * one "node" of mock::n_devices gfx950 devices.
 // Test scaffolding only; it is not a stand-in for anything of the reference.
 #pragma once
@@ -23,6 +26,7 @@
 #include <map>
 #include <memory>
 #include <set>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -91,8 +95,12 @@ inline std::set<Stream*> g_streams;
 inline std::map<const char*, size_t> g_pinned;          // base -> bytes
 inline std::atomic<long> g_copies{0}, g_peer_copies{0}, g_waits{0}, g_launches{0}, g_allocs{0};
 inline int n_devices = 8;
+inline thread_local hipError_t last_error = hipSuccess;      // what hipGetLastError returns and clears
 inline thread_local long fail_alloc_in = -1;        // > 0: the n-th hipMalloc of THIS thread from now on fails (out of memory), once
 inline std::function<hipError_t(const void* fn, void** args, hipStream_t st)> launch_hook;
+struct Function { std::string name; };              // what hipModuleGetFunction hands out: the symbol name it was asked for
+// a module launch: kernel name, grid x / y, block x, the HIP_LAUNCH_PARAM buffer (null / 0 when the launch passed none), stream
+inline std::function<void(const char* name, unsigned gx, unsigned gy, unsigned bx, const void* params, size_t bytes, hipStream_t st)> module_launch_hook;
 
 inline Stream* null_stream() {
     static Stream* s = [] {
@@ -127,7 +135,7 @@ hipError_t hipGetDeviceProperties(hipDeviceProp_t* p, int d) {
     p->warpSize = 64;
     return hipSuccess;
 }
-hipError_t hipGetLastError(void) { return hipSuccess; }
+hipError_t hipGetLastError(void) { const hipError_t e = mock::last_error; mock::last_error = hipSuccess; return e; }
 const char* hipGetErrorString(hipError_t) { return "mock HIP error"; }
 hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) {
     auto* p = new mock::Stream();
@@ -281,12 +289,28 @@ hipError_t hipMemset2DAsync(void* d, size_t pitch, int v, size_t w, size_t h, hi
     return hipSuccess;
 }
 hipError_t hipFuncSetAttribute(const void*, hipFuncAttribute, int) { return hipSuccess; }
-hipError_t hipModuleLoadData(hipModule_t* m, const void*) { *m = reinterpret_cast<hipModule_t>(new int(1)); return hipSuccess; }
-hipError_t hipModuleLoad(hipModule_t* m, const char*) { *m = reinterpret_cast<hipModule_t>(new int(1)); return hipSuccess; }
+hipError_t hipModuleLoadData(hipModule_t* m, const void*) {
+    if (std::getenv("MOCK_HIP_FAIL_MODULE_LOAD")) { *m = nullptr; return mock::last_error = hipErrorInvalidImage; }
+    *m = reinterpret_cast<hipModule_t>(new int(1));
+    return hipSuccess;
+}
+hipError_t hipModuleLoad(hipModule_t* m, const char*) { return hipModuleLoadData(m, nullptr); }
 hipError_t hipModuleUnload(hipModule_t m) { delete reinterpret_cast<int*>(m); return hipSuccess; }
-hipError_t hipModuleGetFunction(hipFunction_t* f, hipModule_t, const char*) { *f = reinterpret_cast<hipFunction_t>(new int(2)); return hipSuccess; }
-hipError_t hipModuleLaunchKernel(hipFunction_t, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, hipStream_t, void**, void**) {
+hipError_t hipModuleGetFunction(hipFunction_t* f, hipModule_t, const char* name) {
+    *f = reinterpret_cast<hipFunction_t>(new mock::Function{name});          // (lives as long as the process, like the int it replaces)
+    return hipSuccess;
+}
+hipError_t hipModuleLaunchKernel(hipFunction_t f, unsigned gx, unsigned gy, unsigned, unsigned bx, unsigned, unsigned, unsigned, hipStream_t st, void**, void** extra) {
     ++mock::g_launches;
+    if (mock::module_launch_hook) {
+        const void* params = nullptr;
+        size_t bytes = 0;
+        for (void** e = extra; e && *e != HIP_LAUNCH_PARAM_END; e += 2) {
+            if (*e == HIP_LAUNCH_PARAM_BUFFER_POINTER) params = e[1];
+            else if (*e == HIP_LAUNCH_PARAM_BUFFER_SIZE) bytes = *static_cast<const size_t*>(e[1]);
+        }
+        mock::module_launch_hook(reinterpret_cast<mock::Function*>(f)->name.c_str(), gx, gy, bx, params, bytes, st);
+    }
     return hipSuccess;
 }
 static thread_local struct { dim3 g, b; size_t sh; hipStream_t st; } mock_cfg_;
