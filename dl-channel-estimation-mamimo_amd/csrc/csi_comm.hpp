@@ -20,6 +20,7 @@
 #include <dlfcn.h>
 
 #include "csi_context.hpp"
+#include "csi_ls.hpp"
 
 namespace {
 
@@ -129,9 +130,6 @@ void model_blobs(const csi_config& cf, int l0_k, Model& m, const WireLayer* wl, 
     if (has_conv) v.push_back({(void**)&m.conv, (size_t)CONV_PRM_FLOATS * 4 + slack});
 }
 
-int ls_prepare(csi_ctx* c);                     // csi_mamimo.hip
-int pilot_fast_tables(csi_ctx* c);              // csi_mamimo.hip: device tables of a Hadamard-equivalent pilot from c->p_perm
-
 // ---- the protocol, transport-independent -------------------------------------------------------------------------------------
 // sender: what the context holds -> record
 void wire_fill(const csi_ctx* c, WireMeta& w) {
@@ -180,7 +178,7 @@ void wire_blobs(csi_ctx* c, const WireMeta& w, std::vector<WBlob>& blobs) {
         const size_t ldp = (size_t)(cf.nt + 31) / 32 * 32, slack = G_SLACK_FLOATS * sizeof(float);
         blobs.push_back({(void**)&c->P, (size_t)cf.nt * cf.nt * 4 + slack});
         blobs.push_back({(void**)&c->Ppad, ldp * ldp * 4 + slack});
-        blobs.push_back({(void**)&c->Pbf, (size_t)((cf.nt + 15) / 16) * 3 * ((cf.nt + 31) / 32) * LSB_BLOCK * 2 + slack});
+        blobs.push_back({(void**)&c->Pbf, pilot_packed_elems(cf.nt) * 2 + slack});
     }
 }
 

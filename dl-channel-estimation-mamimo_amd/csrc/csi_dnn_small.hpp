@@ -6,6 +6,7 @@
 // predict of massiveMIMO_CSI_prediction_DNN.py:339-346.
 #pragma once
 #include "csi_context.hpp"
+#include "csi_ls.hpp"
 #include "small_call.hip.h"
 
 namespace {
@@ -32,10 +33,6 @@ bool small_call_ok(csi_ctx* c, int64_t npkt) {
         return false;
     return true;
 }
-
-// (defined in csi_mamimo.hip behind the LS plan) the LS kernel of this context is the Walsh-Hadamard one in its default shape: its LDS bytes
-bool ls_default_fwht2(const csi_ctx* c, size_t* lds_bytes);
-LsArgs ls_args(const csi_ctx* c, const float* d_ltf_re, const float* d_ltf_im, float* d_h_re, float* d_h_im);
 
 // csi_estimate_device: may the LS estimate of this call ride in the layer-0 launch?  The weight-streaming layer 0 (at most 8 preambles), the
 // Walsh-Hadamard LS kernel in its default one-thread-per-bin shape on the Sylvester order itself (Nt = 16 / 32 / 64)

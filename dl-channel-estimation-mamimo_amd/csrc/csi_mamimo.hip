@@ -13,6 +13,7 @@
 #include "csi_context.hpp"
 #include "csi_dnn_hs.hpp"
 #include "csi_dnn_f32.hpp"
+#include "csi_ls.hpp"
 #include "csi_dnn_small.hpp"
 #include "csi_dnn_bf16.hpp"
 #include "csi_train.hpp"
@@ -33,285 +34,6 @@ int planes_aligned(csi_ctx* c, const char* who, std::initializer_list<PlaneArg> 
     for (const PlaneArg& a : planes)
         if (reinterpret_cast<uintptr_t>(a.p) & 15)
             return fail(c, CSI_ERR_INVALID_ARG, "%s: %s must start on a 16-byte boundary (got %p)", who, a.name, a.p);
-    return CSI_OK;
-}
-
-// Which LS kernel serves this context.  With the Sylvester Hadamard pilot matrix the Walsh-Hadamard kernel on the
-// LDS-DMA ring.  Any other P: FFT-first (all Nt spectra in LDS) up to ls_fft_first_max antennas, the ring kernels with
-// the matrix-core despread up to Nt = 128 - bf16-split (ls_estimate_ringb_kernel) except for a pilot matrix of arbitrary
-// floats at Nt <= 32, where the fp32 despread of ls_estimate_ring_kernel is as fast (profiles/r03_ls_probe_generic.txt) -
-// the despread-first kernel beyond.  The older chunked
-// kernel stays selectable through the "ls_kernel" option (tests, A/B runs).
-enum LsMode { LS_AUTO = 0, LS_FFT_FIRST = 1, LS_CHUNKED = 2, LS_DESPREAD_FIRST = 3, LS_FWHT = 4, LS_FWHT2 = 5, LS_RING = 6, LS_RINGB = 7 };
-struct LsPlan {
-    int mode;
-    const void* fn;
-    size_t lds;
-    int threads;
-    int per_cu;           // resident workgroups per CU (persistent grids)
-};
-// the bf16-split ring kernel (ls_estimate_ringb_kernel) for this Nt / pilot: its shape and LDS need; fn == nullptr when Nt is outside 16 ... 128
-struct LsRingB { const void* fn; size_t lds; int nw, per_cu; };
-LsRingB ls_ringb_shape(const csi_ctx* c) {
-    const int nt = c->cfg.nt, jt = (nt + 31) / 32, npp = std::min(3, std::max(1, c->p_pieces));
-    LsRingB r{nullptr, 0, 8, 1};
-    if (nt < 16 || nt > 128) return r;
-    int nstg = 1, nf = 1;
-#define LS_RB(J, W, NS, MB, DB)                                                                                    \
-    {                                                                                                              \
-        r.fn = npp == 1 ? (const void*)ls_estimate_ringb_kernel<J, W, NS, 1, MB, DB>                               \
-               : (npp == 2 ? (const void*)ls_estimate_ringb_kernel<J, W, NS, 2, MB, DB> : (const void*)ls_estimate_ringb_kernel<J, W, NS, 3, MB, DB>); \
-        r.nw = W; nstg = NS; r.per_cu = MB; nf = DB ? 2 : 1;                                                       \
-    }
-    // shapes as measured (profiles/r03_ls_probe_generic.txt); "ls_v2" = 1 selects the runner-up for A/B runs
-    // one antenna tile (Nt <= 32): ONE workgroup per CU.  The two-workgroups-per-CU form (4 % faster) is not built: its packed +-i rotations went wrong
-    // beside another workgroup's MFMAs.  The shape is padded to > 80 KiB of LDS below so that the dispatcher cannot co-locate two either.
-    if (jt == 1) { if (c->ls_v2 == 1) LS_RB(1, 4, 2, 1, false) else LS_RB(1, 4, 1, 1, false) }
-    else if (jt == 2) { if (c->ls_v2 == 1) LS_RB(2, 8, 1, 1, false) else LS_RB(2, 8, 1, 1, true) }
-    else if (jt == 3) { if (c->ls_v2 == 1) LS_RB(3, 8, 2, 1, false) else LS_RB(3, 8, 1, 1, true) }
-    else { if (c->ls_v2 == 1) LS_RB(4, 8, 1, 1, false) else LS_RB(4, 8, 1, 1, true) }
-#undef LS_RB
-    r.lds = (size_t)(2 * LSC_NTW + nf * 16 * 2 * LSC_ROW + nstg * 16 * 2 * LS_FFT) * sizeof(float) + (size_t)(nstg + 1) * npp * jt * LSB_BLOCK * 2;
-    if (r.lds > 160 * 1024) r.fn = nullptr;
-    if (jt == 1) r.lds = std::max(r.lds, (size_t)(81 * 1024));      // one workgroup per CU by construction (see above)
-    r.per_cu = std::max(1, std::min(r.per_cu, (int)((160 * 1024) / r.lds)));
-    return r;
-}
-LsPlan ls_plan(const csi_ctx* c) {
-    const int nt = c->cfg.nt;
-    int mode = c->ls_kernel;
-    // Walsh-Hadamard despread: the Sylvester matrix itself, or (round 4) any signed row / column permutation of it - the kernel
-    // then fetches the symbols and stores the antennas through the tables csi_set_pilot derived (PERM form)
-    const bool perm = c->p_fast_ok && !c->p_fast_identity;
-    const bool fwht_ok = (c->p_sylvester || (c->p_fast_ok && (c->p_fast_identity || c->ls_fast_perm))) && (nt == 16 || nt == 32 || nt == 64 || nt == 128);
-    if ((mode == LS_FWHT || mode == LS_FWHT2) && !fwht_ok) mode = LS_AUTO;
-    if (mode == LS_FWHT && perm) mode = LS_FWHT2;            // the round-1 kernel knows the Sylvester order only
-    const LsRingB rb = ls_ringb_shape(c);
-    if (mode == LS_RINGB && !rb.fn) mode = LS_AUTO;
-    if (mode == LS_AUTO)
-        mode = fwht_ok ? LS_FWHT2 : (nt <= c->ls_fft_first_max ? LS_FFT_FIRST : (nt <= 128 ? (rb.fn && nt >= c->ls_ringb_min && (c->p_pieces < 3 || nt > 32) ? LS_RINGB : LS_RING) : LS_DESPREAD_FIRST));
-    if (mode == LS_FFT_FIRST && nt > 64) mode = LS_CHUNKED;
-    if ((mode == LS_CHUNKED || mode == LS_RING) && (nt < 16 || nt > 128)) mode = nt < 16 ? LS_FFT_FIRST : LS_DESPREAD_FIRST;
-    LsPlan p{};
-    p.mode = mode;
-    if (mode == LS_RINGB) {
-        p.fn = rb.fn; p.lds = rb.lds; p.threads = 64 * rb.nw; p.per_cu = rb.per_cu;
-        return p;
-    }
-    if (mode == LS_FWHT2) {
-        // shape per Nt as measured (profiles/r02_ls_probe.txt); "ls_v2" = 1 selects the runner-up for A/B runs
-        const int v = c->ls_v2;
-        int split = 1, ch = 16, nstg = 1, nf = 1, maxcu = 2;
-#define LS_V2(NTV, SP, CHV, NS, DB) { p.fn = (const void*)ls_estimate_fwht2_kernel<NTV, SP, CHV, NS, DB>; split = SP; ch = CHV; nstg = NS; nf = DB ? 2 : 1; }
-        if (nt == 16) {
-            if (v == 1) LS_V2(16, 1, 16, 1, false)
-            else if (v == 3) { p.fn = (const void*)ls_estimate_fwht2_kernel<16, 1, 8, 1, false, 4>; split = 1; ch = 8; nstg = 1; nf = 1; maxcu = 4; }      // A/B: vector-address stores (round 3)
-            else { p.fn = (const void*)ls_estimate_fwht2_kernel<16, 1, 8, 1, false, 4, false, true>; split = 1; ch = 8; nstg = 1; nf = 1; maxcu = 4; }
-        }
-        else if (nt == 32) {       // 8-symbol chunks, one slot: 38 KiB of LDS and 122 VGPRs - four workgroups per CU (0.379 ms; two with 16-symbol chunks: 0.402)
-            if (v == 1) LS_V2(32, 1, 16, 1, false)
-            else if (v == 3) { p.fn = (const void*)ls_estimate_fwht2_kernel<32, 1, 8, 1, false, 4>; split = 1; ch = 8; nstg = 1; nf = 1; maxcu = 4; }   // A/B: vector-address stores (round 3)
-            // round 4: stores with the row base in scalar registers (SST): -3 ... -5 % at Nt = 32 / 64 (profiles/r04_ls_probe.txt)
-            else { p.fn = (const void*)ls_estimate_fwht2_kernel<32, 1, 8, 1, false, 4, false, true>; split = 1; ch = 8; nstg = 1; nf = 1; maxcu = 4; }
-        }
-        else if (nt == 64) {
-            if (v == 1) LS_V2(64, 1, 16, 1, false)
-            else if (v == 3) LS_V2(64, 1, 8, 3, false)
-            else { p.fn = (const void*)ls_estimate_fwht2_kernel<64, 1, 8, 3, false, 2, false, true>; split = 1; ch = 8; nstg = 3; nf = 1; }
-        }
-        else {
-            if (v == 1) LS_V2(128, 2, 16, 3, false)
-            else if (v == 3) LS_V2(128, 2, 16, 2, true)       // two spectra images: -6 %; vector-address stores
-            else { p.fn = (const void*)ls_estimate_fwht2_kernel<128, 2, 16, 2, true, 1, false, true>; split = 2; ch = 16; nstg = 2; nf = 2; }    // + scalar-base stores: -1 ... -1.9 %
-        }
-#undef LS_V2
-        if (perm) {        // same shapes as the defaults above, table-driven symbol fetch / antenna store
-            if (nt == 16) { p.fn = (const void*)ls_estimate_fwht2_kernel<16, 1, 8, 1, false, 4, true>; split = 1; ch = 8; nstg = 1; nf = 1; maxcu = 4; }
-            else if (nt == 32) { p.fn = (const void*)ls_estimate_fwht2_kernel<32, 1, 8, 1, false, 4, true>; split = 1; ch = 8; nstg = 1; nf = 1; maxcu = 4; }
-            else if (nt == 64) { p.fn = (const void*)ls_estimate_fwht2_kernel<64, 1, 8, 3, false, 2, true>; split = 1; ch = 8; nstg = 3; nf = 1; maxcu = 2; }
-            else { p.fn = (const void*)ls_estimate_fwht2_kernel<128, 2, 16, 2, true, 1, true>; split = 2; ch = 16; nstg = 2; nf = 2; maxcu = 2; }
-        }
-        p.lds = (size_t)(2 * LSC_NTW + nf * ch * 2 * LSC_ROW + nstg * ch * 2 * LS_FFT) * sizeof(float);
-        p.threads = 256 * split;
-        p.per_cu = std::max(1, std::min(split == 1 ? maxcu : 1, (int)((160 * 1024) / p.lds)));
-    } else if (mode == LS_RING) {
-        const int jt = (nt + 31) / 32, ldp = jt * 32;
-        int nw = 4, nstg = 1, chs = 16, ringcu = 2;
-#define LS_RING_K(J, W, C, NS) { p.fn = (const void*)ls_estimate_ring_kernel<J, W, C, NS>; nw = W; nstg = NS; chs = C; }
-        // 8-symbol chunks where they waste fewer padded symbols (Nt = 24, 40, ...) and for two antenna tiles, where they let
-        // two workgroups share a CU (measured: profiles/r02_ls_probe.txt); "ls_v2" = 1 flips the choice for A/B runs
-        bool ch8 = jt == 2 || (jt == 1 && (nt + 7) / 8 * 8 < (nt + 15) / 16 * 16);
-        if (c->ls_v2 == 1) ch8 = !ch8;
-        // one antenna tile: 8-symbol chunks and one slot leave room for three workgroups per CU (Nt = 32: 0.438 against 0.470 ms)
-        if (jt == 1 && c->ls_v2 == 0) { p.fn = (const void*)ls_estimate_ring_kernel<1, 4, 8, 1, 3>; nw = 4; nstg = 1; chs = 8; ringcu = 3; }
-        else if (jt == 1) { if (c->ls_v2 == 2) LS_RING_K(1, 4, 8, 3) else LS_RING_K(1, 4, 16, 1) }
-        else if (jt == 2) { if (ch8) LS_RING_K(2, 4, 8, 2) else LS_RING_K(2, 8, 16, 3) }
-        else if (jt == 3) LS_RING_K(3, 8, 16, 2)
-        else LS_RING_K(4, 8, 16, 1)
-#undef LS_RING_K
-        p.lds = (size_t)(2 * LSC_NTW + chs * 2 * LSC_ROW + nstg * chs * 2 * LS_FFT + 32 * jt * (ldp + 1)) * sizeof(float);
-        p.threads = 64 * nw;
-        p.per_cu = std::max(1, std::min(nw == 4 ? ringcu : 1, (int)((160 * 1024) / p.lds)));
-    } else if (mode == LS_FWHT) {
-        p.fn = nt == 16 ? (const void*)ls_estimate_fwht_kernel<16> : nt == 32 ? (const void*)ls_estimate_fwht_kernel<32>
-               : nt == 64 ? (const void*)ls_estimate_fwht_kernel<64> : (const void*)ls_estimate_fwht_kernel<128, 2>;
-        p.lds = (size_t)(16 * 2 * LS_PLANE + 2 * LS_FFT) * sizeof(float);
-        p.threads = nt == 128 ? 512 : 256;
-        p.per_cu = nt == 16 ? 3 : (nt == 128 ? 1 : 2);
-    } else if (mode == LS_FFT_FIRST) {
-        p.fn = nt <= 32 ? (const void*)ls_estimate_kernel<8> : (const void*)ls_estimate_kernel<16>;
-        p.lds = (size_t)(nt * 2 * LS_PLANE + 2 * LS_FFT) * sizeof(float);
-        p.threads = LS_THREADS;
-        p.per_cu = std::max(1, std::min(8, (int)((160 * 1024) / p.lds)));
-    } else if (mode == LS_CHUNKED) {
-        const int jt = (nt + 31) / 32;
-        p.fn = jt == 1 ? (const void*)ls_estimate_chunked_kernel<1, 4, 16>
-               : jt == 2 ? (const void*)ls_estimate_chunked_kernel<2, 4, 16>
-                       : (jt == 3 ? (const void*)ls_estimate_chunked_kernel<3, 8, 32> : (const void*)ls_estimate_chunked_kernel<4, 8, 32>);
-        p.lds = (size_t)((jt <= 2 ? 16 : 32) * 2 * LS_PLANE + 2 * LS_FFT) * sizeof(float);
-        p.threads = jt <= 2 ? 256 : 512;
-        p.per_cu = jt <= 2 ? 2 : 1;                       // register-limited: 2 waves per SIMD
-    } else {
-        p.fn = (const void*)ls_despread_first_kernel;
-        p.lds = (size_t)(LSD_ROWS * 2 * LS_PLANE + 2 * LS_FFT) * sizeof(float);
-        p.threads = LS_THREADS;
-        p.per_cu = 2;
-    }
-    return p;
-}
-bool ls_default_fwht2(const csi_ctx* c, size_t* lds_bytes) {
-    if (c->ls_v2 != 0 || c->ls_debug != 0 || c->ls_kernel != LS_AUTO || (c->p_fast_ok && !c->p_fast_identity)) return false;
-    const LsPlan p = ls_plan(c);
-    *lds_bytes = p.lds;
-    return p.mode == LS_FWHT2 && p.threads == 256;
-}
-LsArgs ls_args(const csi_ctx* c, const float* d_ltf_re, const float* d_ltf_im, float* d_h_re, float* d_h_im) {
-    const csi_config& cf = c->cfg;
-    LsArgs a{};
-    a.P = c->P; a.Ppad = c->Ppad; a.Pbf = reinterpret_cast<const uint16_t*>(c->Pbf); a.ldp = (cf.nt + 31) / 32 * 32; a.dbg = c->ls_debug;
-    a.tw = c->tw; a.bin_pos = c->bin_pos; a.denom = c->denom;
-    a.nt = cf.nt; a.len_ltf = cf.len_ltf;
-    a.perm = c->p_tables;
-    a.ltf_re = d_ltf_re; a.ltf_im = d_ltf_im; a.h_re = d_h_re; a.h_im = d_h_im;
-    return a;
-}
-int ls_prepare(csi_ctx* c) {
-    if (c->cfg.nt == 0) return CSI_OK;
-    const LsPlan p = ls_plan(c);
-    HIP_TRY(c, hipFuncSetAttribute(p.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
-    return CSI_OK;
-}
-
-// Is P a signed row / column permutation of the Sylvester Hadamard matrix H[a][u] = (-1)^popcount(a & u)?  (helperGetP of the
-// reference's toolbox is un-vendored, helperMIMOChannelEstimate.m:13; the 802.11 VHT mapping matrix [1 -1 1 1; 1 1 -1 1; 1 1 1 -1;
-// -1 1 1 1] doubled up recursively is of this kind without being in the Sylvester order.)  Normalise: cs[s] = P[0][s] makes the first
-// row +1, then rs[j] = P[j][0] cs[0] the first column; the normalised matrix N = diag(rs) P diag(cs) of such a P is H with rows and
-// columns PERMUTED only: N[j][s] = H[sigma(j)][tau(s)] (rows of H multiply like XOR of their indices).  Label log2(nt) independent
-// rows of N with the unit vectors (any basis does: sigma' = A sigma, tau' = A^-T tau leave the inner product alone), read tau(s) off
-// their signs in column s and sigma(j) off row j's signs in the columns whose tau is a unit vector, then VERIFY every entry.
-// On success perm[0][u] = tau^-1(u) | (cs < 0 ? 256 : 0), perm[1][r] = sigma^-1(r) | (rs < 0 ? 256 : 0).
-bool pilot_decompose(const float* P, int nt, int perm[2][CSI_WIRE_MAX_NT], bool* identity) {
-    if (nt < 2 || nt > CSI_WIRE_MAX_NT || (nt & (nt - 1))) return false;
-    for (size_t i = 0; i < (size_t)nt * nt; ++i)
-        if (P[i] != 1.0f && P[i] != -1.0f) return false;
-    int n = 0;
-    while ((1 << n) < nt) ++n;
-    std::vector<int> cs(nt), rs(nt);
-    for (int s = 0; s < nt; ++s) cs[s] = P[s] < 0 ? -1 : 1;
-    for (int j = 0; j < nt; ++j) rs[j] = (P[(size_t)j * nt] < 0 ? -1 : 1) * cs[0];
-    typedef std::pair<uint64_t, uint64_t> bits;              // a row of N as the set of its -1 columns
-    std::vector<bits> row(nt);
-    for (int j = 0; j < nt; ++j) {
-        bits b{0, 0};
-        for (int s = 0; s < nt; ++s)
-            if (P[(size_t)j * nt + s] * (float)(rs[j] * cs[s]) < 0) (s < 64 ? b.first : b.second) |= (uint64_t)1 << (s & 63);
-        row[j] = b;
-    }
-    // greedy basis: a row outside the group generated so far extends it
-    std::vector<bits> span{bits{0, 0}};
-    std::vector<int> basis;
-    for (int j = 0; j < nt && (int)basis.size() < n; ++j) {
-        if (std::find(span.begin(), span.end(), row[j]) != span.end()) continue;
-        basis.push_back(j);
-        const size_t m = span.size();
-        for (size_t k = 0; k < m; ++k) span.push_back(bits{span[k].first ^ row[j].first, span[k].second ^ row[j].second});
-    }
-    if ((int)basis.size() != n) return false;
-    std::vector<int> tau(nt), sigma(nt), tau_inv(nt, -1), sigma_inv(nt, -1);
-    for (int s = 0; s < nt; ++s) {
-        int t = 0;
-        for (int i = 0; i < n; ++i)
-            if (((s < 64 ? row[basis[i]].first : row[basis[i]].second) >> (s & 63)) & 1) t |= 1 << i;
-        tau[s] = t;
-        if (tau_inv[t] >= 0) return false;
-        tau_inv[t] = s;
-    }
-    for (int j = 0; j < nt; ++j) {
-        int g = 0;
-        for (int i = 0; i < n; ++i) {
-            const int col = tau_inv[1 << i];
-            if (((col < 64 ? row[j].first : row[j].second) >> (col & 63)) & 1) g |= 1 << i;
-        }
-        sigma[j] = g;
-        if (sigma_inv[g] >= 0) return false;
-        sigma_inv[g] = j;
-    }
-    for (int j = 0; j < nt; ++j)
-        for (int s = 0; s < nt; ++s) {
-            const float want = (float)(rs[j] * cs[s]) * ((__builtin_popcount(sigma[j] & tau[s]) & 1) ? -1.0f : 1.0f);
-            if (P[(size_t)j * nt + s] != want) return false;
-        }
-    bool ident = true;
-    for (int u = 0; u < nt; ++u) {
-        perm[0][u] = tau_inv[u] | (cs[tau_inv[u]] < 0 ? 256 : 0);
-        perm[1][u] = sigma_inv[u] | (rs[sigma_inv[u]] < 0 ? 256 : 0);
-        ident = ident && perm[0][u] == u && perm[1][u] == u;
-    }
-    *identity = ident;
-    return true;
-}
-
-// device tables of the PERM Walsh-Hadamard kernel from c->p_perm: [4][nt] = source symbol, its sign, byte offset of the output antenna's row, its sign
-int pilot_fast_tables(csi_ctx* c) {
-    const int nt = c->cfg.nt;
-    if (c->p_tables) { hipFree(c->p_tables); c->p_tables = nullptr; }
-    if (!c->p_fast_ok || nt <= 0 || nt > CSI_WIRE_MAX_NT) return CSI_OK;
-    c->p_fast_identity = true;
-    std::vector<int> t((size_t)4 * nt);
-    const float one = 1.0f, minus = -1.0f;
-    for (int k = 0; k < 2; ++k)
-        for (int u = 0; u < nt; ++u) {
-            const int v = c->p_perm[k][u];
-            if ((v & 255) >= nt) return fail(c, CSI_ERR_INVALID_ARG, "pilot permutation table entry %d out of range", v);
-            t[(size_t)(2 * k) * nt + u] = k == 0 ? (v & 255) : (v & 255) * LS_NDATA * (int)sizeof(float);      // source symbol; BYTE offset of the output antenna's row inside an item
-            std::memcpy(&t[(size_t)(2 * k + 1) * nt + u], (v & 256) ? &minus : &one, 4);
-            c->p_fast_identity = c->p_fast_identity && v == u;
-        }
-    // Row 1 as the Walsh-Hadamard kernels consume it (ls_estimate_fwht2_kernel, PERM): the input signs S of a chunk of CH symbols are
-    // multiplied out into butterfly coefficients, so that the kernel spends no instruction on them.  Per chunk: [S_r S_{r+8}, r < 8:
-    // the fold of the two-threads-per-bin kernel (Nt = 128, CH = 16)], S_0, then for the levels of stride hh = 1, 2, 4 of the
-    // 8-point transform one coefficient S_{i0} S_{i0+hh} per group i0 = 0, 2 hh, ..
-    if (nt >= 16) {
-        const int CH = nt == 128 ? 16 : 8, CHH = 8, L0 = CH - CHH;
-        std::vector<float> sg(nt), cf(nt);
-        std::memcpy(sg.data(), &t[(size_t)nt], sizeof(float) * nt);
-        for (int ch = 0; ch < nt / CH; ++ch) {
-            const float* s = sg.data() + ch * CH;
-            float* o = cf.data() + ch * CH;
-            float pend[8];
-            for (int r = 0; r < CHH; ++r) { pend[r] = s[r]; if (L0) o[r] = s[r] * s[r + CHH]; }
-            o[L0] = pend[0];
-            int idx = L0 + 1;
-            for (int hh = 1; hh < CHH; hh <<= 1) {
-                for (int grp = 0; grp < CHH / (2 * hh); ++grp) o[idx + grp] = pend[grp * 2 * hh] * pend[grp * 2 * hh + hh];
-                idx += CHH / (2 * hh);
-            }
-        }
-        std::memcpy(&t[(size_t)nt], cf.data(), sizeof(float) * nt);
-    }
-    if (hipMalloc((void**)&c->p_tables, t.size() * sizeof(int)) != hipSuccess)
-        return fail(c, CSI_ERR_NOMEM, "device allocation of %zu bytes failed", t.size() * sizeof(int));
-    HIP_TRY(c, hipMemcpy(c->p_tables, t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice));
     return CSI_OK;
 }
 
@@ -953,58 +675,18 @@ int csi_set_pilot(csi_ctx* c, const float* P) {
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     drop_graphs(c);
-    int rc = upload(c, &c->P, P, (size_t)c->cfg.nt * c->cfg.nt);
+    const int nt = c->cfg.nt;
+    int rc = upload(c, &c->P, P, (size_t)nt * nt);
     if (rc) return rc;
-    {   // Sylvester Hadamard?  P[j][s] == (-1)^popcount(j & s) exactly -> the Walsh-Hadamard despread applies
-        const int nt = c->cfg.nt;
-        bool syl = nt >= 2 && (nt & (nt - 1)) == 0;
-        for (int j = 0; syl && j < nt; ++j)
-            for (int q = 0; q < nt; ++q)
-                if (P[(size_t)j * nt + q] != ((__builtin_popcount(j & q) & 1) ? -1.0f : 1.0f)) { syl = false; break; }
-        c->p_sylvester = syl;
-        bool ident = true;
-        c->p_fast_ok = pilot_decompose(P, nt, c->p_perm, &ident);
-        c->p_fast_identity = ident;
-        rc = pilot_fast_tables(c);
-        if (rc) return rc;
-        // how many bf16 pieces (8 significand bits each, truncation) the entries need: the bf16-split LS despread keeps that many
-        int pieces = 1;
-        for (size_t i = 0; i < (size_t)nt * nt && pieces < 3; ++i) {
-            uint32_t u; std::memcpy(&u, &P[i], 4);
-            uint32_t t = u & 0xffff0000u; float f1; std::memcpy(&f1, &t, 4);
-            const float r1 = P[i] - f1;
-            if (r1 != 0.f) {
-                std::memcpy(&u, &r1, 4); t = u & 0xffff0000u; float f2; std::memcpy(&f2, &t, 4);
-                pieces = std::max(pieces, r1 - f2 != 0.f ? 3 : 2);
-            }
-        }
-        c->p_pieces = pieces;
-        // the pieces in the operand order of v_mfma_f32_32x32x16_bf16: block (chunk of 16 symbols, piece, antenna tile) =
-        // [k half][row 32][8 symbols], what lane (row + 32 half) of a wave reads as one 16-byte LDS word
-        const int jt = (nt + 31) / 32, nch = (nt + 15) / 16;
-        std::vector<uint16_t> pb((size_t)nch * 3 * jt * LSB_BLOCK, 0);
-        for (int j = 0; j < nt; ++j)
-            for (int s = 0; s < nt; ++s) {
-                float x = P[(size_t)j * nt + s];
-                for (int k = 0; k < 3; ++k) {
-                    uint32_t u; std::memcpy(&u, &x, 4);
-                    const uint32_t t = u & 0xffff0000u; float f; std::memcpy(&f, &t, 4);
-                    pb[(((size_t)(s >> 4) * 3 + k) * jt + (j >> 5)) * LSB_BLOCK + (((s >> 3) & 1) * 32 + (j & 31)) * 8 + (s & 7)] = (uint16_t)(t >> 16);
-                    x -= f;
-                }
-            }
-        std::vector<float> pbf((pb.size() + 1) / 2);
-        std::memcpy(pbf.data(), pb.data(), pb.size() * 2);
-        rc = upload(c, &c->Pbf, pbf.data(), pbf.size());
-        if (rc) return rc;
-    }
-    {   // zero-padded copy for the chunked LS kernel (rows / columns up to the next multiple of 32)
-        const int nt = c->cfg.nt, ldp = (nt + 31) / 32 * 32;
-        std::vector<float> pad((size_t)ldp * ldp, 0.f);
-        for (int j = 0; j < nt; ++j) std::memcpy(&pad[(size_t)j * ldp], P + (size_t)j * nt, sizeof(float) * nt);
-        rc = upload(c, &c->Ppad, pad.data(), pad.size());
-        if (rc) return rc;
-    }
+    // what the plan reads (csi_ls.hpp): Sylvester order, a signed permutation of it (-> the tables of the PERM kernel), bf16 pieces
+    c->p_sylvester = pilot_is_sylvester(P, nt);
+    c->p_fast_identity = true;
+    c->p_fast_ok = pilot_decompose(P, nt, c->p_perm, &c->p_fast_identity);
+    if ((rc = pilot_fast_tables(c))) return rc;
+    c->p_pieces = pilot_pieces(P, nt);
+    const std::vector<float> packed = pilot_packed(P, nt), padded = pilot_padded(P, nt);
+    if ((rc = upload(c, &c->Pbf, packed.data(), packed.size()))) return rc;
+    if ((rc = upload(c, &c->Ppad, padded.data(), padded.size()))) return rc;
     rc = ls_prepare(c);
     if (rc) return rc;
     c->pilot_ok = true;
@@ -1151,33 +833,7 @@ int csi_ls_estimate_device(csi_ctx* c, const float* d_ltf_re, const float* d_ltf
         return fail(c, CSI_ERR_INVALID_ARG, "csi_ls_estimate_device: bad argument");
     if (npkt == 0) return CSI_OK;
     if ((rc = planes_aligned(c, "csi_ls_estimate_device", {{"d_ltf_re", d_ltf_re}, {"d_ltf_im", d_ltf_im}, {"d_h_re", d_h_re}, {"d_h_im", d_h_im}}))) return rc;
-    const csi_config& cf = c->cfg;
-    const LsPlan plan = ls_plan(c);
-    const int n_jc = (cf.nt + LSD_ROWS - 1) / LSD_ROWS;
-    HIP_TRY(c, hipSetDevice(cf.device));
-    const int64_t nblk = npkt * cf.nr;
-    LsArgs a = ls_args(c, d_ltf_re, d_ltf_im, d_h_re, d_h_im);
-    const int64_t max_grid = ((int64_t)1 << 30) / n_jc;      // also keeps nb inside an int
-    for (int64_t b0 = 0; b0 < nblk; b0 += max_grid) {
-        const int64_t nb = std::min(max_grid, nblk - b0);
-        a.ltf_re = d_ltf_re + (size_t)b0 * cf.len_ltf;
-        a.ltf_im = d_ltf_im + (size_t)b0 * cf.len_ltf;
-        a.h_re = d_h_re + (size_t)b0 * cf.nt * LS_NDATA;
-        a.h_im = d_h_im + (size_t)b0 * cf.nt * LS_NDATA;
-        const double pairs = (double)nb * cf.nt;
-        int nb32 = (int)nb;
-        ProfScope ps(c, K_LS_ESTIMATE, pairs * (10240.0 + 8.0 * LS_NDATA * cf.nt), pairs * (2560.0 + 1872.0));
-        if (plan.mode == LS_DESPREAD_FIRST) {
-            hipLaunchKernelGGL(ls_despread_first_kernel, dim3((unsigned)(nb * n_jc)), dim3(LS_THREADS), plan.lds, c->stream, a, n_jc);
-        } else {
-            // persistent grid: as many workgroups as can reside (x256 CUs)
-            const unsigned grid = (unsigned)std::min<int64_t>(nb, (int64_t)256 * plan.per_cu);
-            void* kargs[] = {(void*)&a, (void*)&nb32};
-            HIP_TRY(c, hipLaunchKernel(plan.fn, dim3(grid), dim3(plan.threads), kargs, plan.lds, c->stream));
-        }
-        HIP_TRY(c, hipGetLastError());
-    }
-    return CSI_OK;
+    return ls_run(c, d_ltf_re, d_ltf_im, npkt, d_h_re, d_h_im);
 }
 
 int csi_lmmse_estimate_device(csi_ctx* c, const float* d_h_re, const float* d_h_im, int64_t npkt, const float* d_hvec, int L,
@@ -1580,8 +1236,10 @@ int csi_set_option(csi_ctx* c, const char* name, int64_t value) {
         c->ls_v2 = (int)value;
         return ls_prepare(c);
     } else if (n == "ls_debug") {
-        c->ls_debug = (int)value;          // timing experiments: results are wrong when non-zero (bits 1 / 2 / 4)
-        return ls_prepare(c);              // bits 0x200 ... 0x1000 select another instantiation (ls_ringb_shape)
+        // timing experiments: the LS kernels get it as LsArgs::dbg and skip or instrument a phase per bit (1 transforms, 2 despread, 4 stores, ...: ls_estimate.hip.h) - results are wrong when
+        // non-zero.  It selects no kernel; a non-zero value keeps the LS estimate of a one-packet call out of the layer-0 launch (ls_default_fwht2).
+        c->ls_debug = (int)value;
+        return ls_prepare(c);
     } else if (n == "ls_kernel") {
         if (value < 0 || value > 7)
             return fail(c, CSI_ERR_INVALID_ARG, "ls_kernel must be 0 (auto), 1 (FFT first), 2 (chunked), 3 (despread first), 4 (Walsh-Hadamard), "

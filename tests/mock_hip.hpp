@@ -9,7 +9,8 @@
 //     allocations never look alike by accident;
 //   * kernel launches go to a hook when it is set (hipLaunchKernel: mock::launch_hook; hipModuleLaunchKernel: mock::module_launch_hook,
 //     which gets the NAME the function was looked up by and the HIP_LAUNCH_PARAM argument record) and are otherwise counted and
-//     dropped - a harness of host logic does not need what the kernels compute;
+//     dropped - a harness of host logic does not need what the kernels compute; mock::launch_shape_hook sees every hipLaunchKernel with
+//     its grid, workgroup size and dynamic LDS bytes, mock::func_attribute_hook every hipFuncSetAttribute;
 //   * with MOCK_HIP_FAIL_MODULE_LOAD set in the environment hipModuleLoad / hipModuleLoadData fail, and - as in the real runtime - the
 //     error stays the thread's last error until hipGetLastError reads it;
 //   * one "node" of mock::n_devices gfx950 devices.
@@ -98,6 +99,8 @@ inline int n_devices = 8;
 inline thread_local hipError_t last_error = hipSuccess;      // what hipGetLastError returns and clears
 inline thread_local long fail_alloc_in = -1;        // > 0: the n-th hipMalloc of THIS thread from now on fails (out of memory), once
 inline std::function<hipError_t(const void* fn, void** args, hipStream_t st)> launch_hook;
+inline std::function<void(const void* fn, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st)> launch_shape_hook;      // called in front of launch_hook
+inline std::function<void(const void* fn, hipFuncAttribute attr, int value)> func_attribute_hook;
 struct Function { std::string name; };              // what hipModuleGetFunction hands out: the symbol name it was asked for
 // a module launch: kernel name, grid x / y, block x, the HIP_LAUNCH_PARAM buffer (null / 0 when the launch passed none), stream
 inline std::function<void(const char* name, unsigned gx, unsigned gy, unsigned bx, const void* params, size_t bytes, hipStream_t st)> module_launch_hook;
@@ -288,7 +291,10 @@ hipError_t hipMemset2DAsync(void* d, size_t pitch, int v, size_t w, size_t h, hi
     mock::S(st)->push([d, pitch, v, w, h] { for (size_t r = 0; r < h; ++r) std::memset(static_cast<char*>(d) + r * pitch, v, w); });
     return hipSuccess;
 }
-hipError_t hipFuncSetAttribute(const void*, hipFuncAttribute, int) { return hipSuccess; }
+hipError_t hipFuncSetAttribute(const void* fn, hipFuncAttribute attr, int value) {
+    if (mock::func_attribute_hook) mock::func_attribute_hook(fn, attr, value);
+    return hipSuccess;
+}
 hipError_t hipModuleLoadData(hipModule_t* m, const void*) {
     if (std::getenv("MOCK_HIP_FAIL_MODULE_LOAD")) { *m = nullptr; return mock::last_error = hipErrorInvalidImage; }
     *m = reinterpret_cast<hipModule_t>(new int(1));
@@ -322,8 +328,9 @@ hipError_t __hipPopCallConfiguration(dim3* g, dim3* b, size_t* sh, hipStream_t* 
     *g = mock_cfg_.g; *b = mock_cfg_.b; *sh = mock_cfg_.sh; *st = mock_cfg_.st;
     return hipSuccess;
 }
-hipError_t hipLaunchKernel(const void* fn, dim3, dim3, void** args, size_t, hipStream_t st) {
+hipError_t hipLaunchKernel(const void* fn, dim3 grid, dim3 block, void** args, size_t lds_bytes, hipStream_t st) {
     ++mock::g_launches;
+    if (mock::launch_shape_hook) mock::launch_shape_hook(fn, grid, block, lds_bytes, st);
     return mock::launch_hook ? mock::launch_hook(fn, args, st) : hipSuccess;
 }
 // stream capture / graphs, as far as csi_estimate_device + "use_graph" needs them: while a stream captures, what is pushed onto it

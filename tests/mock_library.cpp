@@ -5,12 +5,14 @@
 #include "../dl-channel-estimation-mamimo_amd/csrc/csi_mamimo.hip"
 
 #include "mock_hip.hpp"
+#include <cxxabi.h>
+#include <dlfcn.h>
 
 // ---- which band kernel served a call (tests/test_band_routes_host.py): one text line per module launch whose argument record is a
 // Band8Args (128 bytes) or a Band8ArgsCs (144 bytes) -
 //   <kernel name> grid=<x>,<y> block=<x> bytes=<record> M=<> N1=<> nt=<> tiled=<1 tiled copy | 0 plain weights | ?> [part=<0 | 1>]
 // The record's W1 is kept and named when the log is read: a model's tiled copy (Model::Wt1) is allocated once and stays.
-// Test-only entry points of THIS translation unit; the product header does not know them.
+// Test-only entry points of THIS translation unit; the product header does not know them.  (Further down: the log of the LS kernels.)
 #if !defined(__HIP_DEVICE_COMPILE__)
 namespace {
 struct BandLaunch { std::string name; unsigned gx, gy, bx; size_t bytes; Band8ArgsCs rec; };
@@ -26,9 +28,80 @@ const bool band_log_hooked = [] {
     };
     return true;
 }();
+
+// ---- which LS kernel served a call, and what csi_set_pilot uploaded (tests/test_ls_routes_host.py).  One text line per
+// hipFuncSetAttribute and per hipLaunchKernel of an LS kernel -
+//   attr value=<bytes> kernel=<name>
+//   launch grid=<x>,<y> block=<x> lds=<dynamic bytes> attr=<1: the last attribute line names this kernel and these bytes | 0> kernel=<name>
+// <name> is what the dynamic linker knows the kernel's host handle by, demangled, without the return type and the namespace:
+// "ls_estimate_ring_kernel<1, 4, 8, 1, 3>(csi::LsArgs, int)".  Kernels whose name does not start with ls_ or small_l0_ls_kernel stay out.
+std::mutex ls_log_mu;
+std::vector<std::string> ls_log;
+const void* ls_attr_fn = nullptr;
+int ls_attr_value = -1;
+std::string ls_kernel_name(const void* fn) {
+    Dl_info info{};
+    if (!dladdr(fn, &info) || !info.dli_sname || info.dli_saddr != fn) return "";
+    int status = 0;
+    char* d = abi::__cxa_demangle(info.dli_sname, nullptr, nullptr, &status);
+    std::string s = status == 0 && d ? d : info.dli_sname;
+    std::free(d);
+    for (const char* prefix : {"void ", "csi::"})
+        if (s.compare(0, std::strlen(prefix), prefix) == 0) s.erase(0, std::strlen(prefix));
+    return s.compare(0, 3, "ls_") == 0 || s.compare(0, 18, "small_l0_ls_kernel") == 0 ? s : "";
+}
+const bool ls_log_hooked = [] {
+    mock::func_attribute_hook = [](const void* fn, hipFuncAttribute attr, int value) {
+        const std::string name = ls_kernel_name(fn);
+        if (name.empty() || attr != hipFuncAttributeMaxDynamicSharedMemorySize) return;
+        std::lock_guard<std::mutex> lk(ls_log_mu);
+        ls_attr_fn = fn;
+        ls_attr_value = value;
+        ls_log.push_back("attr value=" + std::to_string(value) + " kernel=" + name);
+    };
+    mock::launch_shape_hook = [](const void* fn, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t) {
+        const std::string name = ls_kernel_name(fn);
+        if (name.empty()) return;
+        std::lock_guard<std::mutex> lk(ls_log_mu);
+        char line[160];
+        std::snprintf(line, sizeof line, "launch grid=%u,%u block=%u lds=%zu attr=%d kernel=", grid.x, grid.y, block.x, lds_bytes,
+                      fn == ls_attr_fn && (size_t)ls_attr_value == lds_bytes);
+        ls_log.push_back(line + name);
+    };
+    return true;
+}();
+int64_t text_out(const std::string& text, char* buf, int64_t cap) {
+    if (buf && cap > 0) {
+        const size_t n = std::min<size_t>(text.size(), (size_t)cap - 1);
+        std::memcpy(buf, text.data(), n);
+        buf[n] = 0;
+    }
+    return (int64_t)text.size() + 1;
+}
 }  // namespace
 
 extern "C" {
+// the LS log as text into buf (at most cap bytes incl. the terminator); returns the bytes the whole text needs
+int64_t csi_mock_ls_log_read(char* buf, int64_t cap) {
+    std::string text;
+    std::lock_guard<std::mutex> lk(ls_log_mu);
+    for (const std::string& l : ls_log) text += l + '\n';
+    return text_out(text, buf, cap);
+}
+void csi_mock_ls_log_clear(void) {
+    std::lock_guard<std::mutex> lk(ls_log_mu);
+    ls_log.clear();
+}
+// what csi_set_pilot left on the "device" (host memory here): which = 0 P, 1 Ppad, 2 Pbf, 3 p_tables; returns the payload bytes (without the
+// slack behind them; 0: the context has no such buffer) and the address in *ptr.  The sizes are written out here, not taken from the library.
+int64_t csi_mock_pilot_buffer(csi_ctx* c, int which, const void** ptr) {
+    const size_t nt = (size_t)c->cfg.nt, jt = (nt + 31) / 32, nch = (nt + 15) / 16;
+    const void* p[4] = {c->P, c->Ppad, c->Pbf, c->p_tables};
+    const size_t bytes[4] = {nt * nt * 4, jt * 32 * jt * 32 * 4, (nch * 3 * jt * 512 + 1) / 2 * 4, 4 * nt * 4};
+    if (which < 0 || which > 3 || !p[which]) return 0;
+    *ptr = p[which];
+    return (int64_t)bytes[which];
+}
 // the log as text into buf (at most cap bytes incl. the terminator); returns the bytes the whole text needs
 int64_t csi_mock_band_log_read(csi_ctx* c, char* buf, int64_t cap) {
     std::string text;
@@ -47,12 +120,7 @@ int64_t csi_mock_band_log_read(csi_ctx* c, char* buf, int64_t cap) {
         text += line;
         text += '\n';
     }
-    if (buf && cap > 0) {
-        const size_t n = std::min<size_t>(text.size(), (size_t)cap - 1);
-        std::memcpy(buf, text.data(), n);
-        buf[n] = 0;
-    }
-    return (int64_t)text.size() + 1;
+    return text_out(text, buf, cap);
 }
 void csi_mock_band_log_clear(void) {
     std::lock_guard<std::mutex> lk(band_log_mu);

@@ -119,7 +119,7 @@ def _ls_pilot(oracle, rng, nt, kind):
     return oracle.hadamard(nt)
 
 
-# id, nt, nr, npkt, pilot, options, the ls_mode the call must run (csi_mamimo.hip: 1 FFT-first, 2 chunked, 3 despread-first, 4 / 5 Walsh-Hadamard
+# id, nt, nr, npkt, pilot, options, the ls_mode the call must run (LsMode of csrc/csi_ls.hpp: 1 FFT-first, 2 chunked, 3 despread-first, 4 / 5 Walsh-Hadamard
 # register prefetch / LDS-DMA ring, 6 generic P on the ring, 7 generic P with the bf16-split despread)
 LS_CASES = [
     ('fft_first_generic_partial_tile', 12, 2, 2, 'generic', {}, 1),
