@@ -58,6 +58,9 @@ enum KernelId {
     K_LINK_TXRX,         // link simulation: encoder, precoder, true channel, zero forcing and soft bits per (packet, subcarrier) (link_sim.hip.h)
     K_LINK_VITERBI,      // link simulation: one-wavefront Viterbi decoder per codeword, traceback and bit errors
     K_SYNTH_SCATTERING,  // known-channel sounding packets of the scattering channel (synth_scattering.hip.h): the power pass and the packet pass of csi_synth_scattering
+    K_LMMSE_NULL_NOISE,  // blind LMMSE smoother (csi_lmmse_blind, lmmse.hip.h): noise variance from the null carriers of the sounding symbols
+    K_LMMSE_FREQ_CORR,   // blind LMMSE smoother: sample frequency correlation of the LS rows
+    K_LMMSE_BLIND,       // blind LMMSE smoother: Levinson solve on the measured first column (+ the fallback count)
     K_COUNT
 };
 const char* const kKernelNames[K_COUNT] = {
@@ -65,7 +68,7 @@ const char* const kKernelNames[K_COUNT] = {
     "ls_estimate", "naive_dense0_gemm", "synth_white", "pilot_table", "cast_bf16", "pair_h1_bf16", "lmmse_levinson",
     "train_gemm", "train_elementwise", "nmse_links", "pair_dense_tail", "input_pool", "conv_frontend",
     "hybrid_svd", "hybrid_corr_argmax", "hybrid_solve", "hybrid_finish", "synth_structured", "link_txrx", "link_viterbi",
-    "synth_scattering"};
+    "synth_scattering", "lmmse_null_noise", "lmmse_freq_corr", "lmmse_blind"};
 
 thread_local std::string g_create_error;
 
@@ -212,6 +215,12 @@ struct csi_ctx {
     size_t hyb_ws_bytes = 0;
     char* link_ws = nullptr;     // link simulation (csi_link.hpp): coded bits and, when the caller keeps none, the soft bits of a packet chunk
     size_t link_ws_bytes = 0;
+    // blind LMMSE smoother (csi_lmmse_blind[_device]): fp64-pair twiddles exp(-2 pi i u / 256), the statistics of a call the caller keeps
+    // none of ([nblk] nv | [nblk][234] c | [nblk] fallback flags; sized by eager calls) and the device word behind "lmmse_blind_fallbacks"
+    LmbTwiddle* lmb_tw = nullptr;
+    char* lmb_ws = nullptr;
+    size_t lmb_ws_bytes = 0;
+    long long* lmb_count = nullptr;
     int64_t link_launches = 0;   // "link_launches": kernels launched by csi_link_sim_device / csi_viterbi_decode_device
     bool user_capture = false;   // between csi_capture_begin and csi_capture_end (csi_hybrid.hpp): device-pointer calls are recorded, not run
     bool user_capture_use_graph = false;

@@ -277,6 +277,26 @@ int csi_create(const csi_config* cfg, csi_ctx** out) {
         c->err = "bin table upload failed";
         return bail(CSI_ERR_HIP);
     }
+    {
+        // the blind LMMSE smoother's null-carrier sums run in fp64 pairs: their own twiddle table (the fp32 one above is the LS kernels'),
+        // from the quarter wave by symmetry: u = 64 q + r, phi = 2 pi r / 256, cos phi = C[r], sin phi = C[64 - r]
+        std::vector<LmbTwiddle> tw64(LMB_FFT);
+        for (int u = 0; u < LMB_FFT; ++u) {
+            const int q = u >> 6, r = u & 63;
+            const double* cs = kLmbQuarterCos[r];
+            const double* sn = kLmbQuarterCos[64 - r];
+            const double* co = (q & 1) ? sn : cs;                    // |cos theta|, |sin theta|
+            const double* si = (q & 1) ? cs : sn;
+            const double sc = (q == 1 || q == 2) ? -1.0 : 1.0, ss = q >= 2 ? -1.0 : 1.0;      // signs of cos theta, sin theta
+            tw64[u] = LmbTwiddle{sc * co[0], sc * co[1], -ss * si[0], -ss * si[1]};             // exp(-i theta)
+        }
+        if (hipMalloc((void**)&c->lmb_tw, LMB_FFT * sizeof(LmbTwiddle)) != hipSuccess ||
+            hipMemcpy(c->lmb_tw, tw64.data(), LMB_FFT * sizeof(LmbTwiddle), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMalloc((void**)&c->lmb_count, 256) != hipSuccess || hipMemset(c->lmb_count, 0, 256) != hipSuccess) {
+            c->err = "blind LMMSE constants: device allocation failed";
+            return bail(CSI_ERR_NOMEM);
+        }
+    }
     if (ls_prepare(c) != CSI_OK) return bail(CSI_ERR_HIP);
     *out = c;
     return CSI_OK;
@@ -299,6 +319,9 @@ void csi_destroy(csi_ctx* c) {
     if (c->hyb_at_re) hipFree(c->hyb_at_re);
     if (c->hyb_ws) hipFree(c->hyb_ws);
     if (c->link_ws) hipFree(c->link_ws);
+    if (c->lmb_tw) hipFree(c->lmb_tw);
+    if (c->lmb_ws) hipFree(c->lmb_ws);
+    if (c->lmb_count) hipFree(c->lmb_count);
     if (c->hs_peak) hipFree(c->hs_peak);
     if (c->hs_zero) hipFree(c->hs_zero);
     if (c->fuse_ws) hipFree(c->fuse_ws);
@@ -902,6 +925,107 @@ int csi_lmmse_estimate(csi_ctx* c, const float* h_re, const float* h_im, int64_t
     return CSI_OK;
 }
 
+// ---------------------------------------------------------------- LMMSE smoothing from the packet's own statistics (lmmse.hip.h, second half)
+int csi_lmmse_blind_device(csi_ctx* c, const float* d_ltf_re, const float* d_ltf_im, const float* d_h_re, const float* d_h_im, int64_t npkt,
+                           float* d_out_re, float* d_out_im, double* d_noise_var, double* d_corr) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    static const char* who = "csi_lmmse_blind_device";
+    const csi_config& cf = c->cfg;
+    if (cf.nt == 0) return fail(c, CSI_ERR_INVALID_ARG, "single-input context (nt=0): no LMMSE estimate");
+    if (npkt <= 0) return fail(c, CSI_ERR_INVALID_ARG, "%s: npkt %lld must be positive", who, (long long)npkt);
+    if (!d_ltf_re || !d_ltf_im || !d_h_re || !d_h_im || !d_out_re || !d_out_im)
+        return fail(c, CSI_ERR_INVALID_ARG, "%s: null required pointer (ltf, h, out)", who);
+    if (cf.len_ltf < LMB_SYM * cf.nt || cf.len_ltf % 4 != 0)
+        return fail(c, CSI_ERR_INVALID_ARG, "%s: len_ltf %d does not hold %d sounding symbols of 320 samples in 16-byte words", who, cf.len_ltf, cf.nt);
+    if (int rc = planes_aligned(c, who, {{"d_ltf_re", d_ltf_re}, {"d_ltf_im", d_ltf_im}, {"d_h_re", d_h_re}, {"d_h_im", d_h_im},
+                                         {"d_out_re", d_out_re}, {"d_out_im", d_out_im}})) return rc;
+    if ((reinterpret_cast<uintptr_t>(d_noise_var) | reinterpret_cast<uintptr_t>(d_corr)) & 7)
+        return fail(c, CSI_ERR_INVALID_ARG, "%s: d_noise_var / d_corr must be aligned for doubles (got %p / %p)", who, (void*)d_noise_var, (void*)d_corr);
+    HIP_TRY(c, hipSetDevice(cf.device));
+    const int n_jc = (cf.nt + LM_RHS - 1) / LM_RHS;
+    const int64_t nblk = npkt * cf.nr;
+    // the statistics the caller does not keep, and the fallback flags, live in the context ([nblk] nv | [nblk][234] c | [nblk] flags)
+    const size_t ws_need = (size_t)nblk * (sizeof(double) + LM_N * sizeof(cd) + sizeof(int));
+    if (int rc = ensure_bytes(c, &c->lmb_ws, &c->lmb_ws_bytes, ws_need)) return rc;
+    double* nv = d_noise_var ? d_noise_var : reinterpret_cast<double*>(c->lmb_ws);
+    cd* corr = d_corr ? reinterpret_cast<cd*>(d_corr) : reinterpret_cast<cd*>(c->lmb_ws + (size_t)nblk * sizeof(double));
+    int* flags = reinterpret_cast<int*>(c->lmb_ws + (size_t)nblk * (sizeof(double) + LM_N * sizeof(cd)));
+    const int64_t max_items = ((int64_t)1 << 30) / n_jc / cf.nr * cf.nr;      // whole packets per launch
+    for (int64_t b0 = 0; b0 < nblk; b0 += max_items) {
+        const int64_t nb = std::min(max_items, nblk - b0);
+        const size_t ho = (size_t)b0 * cf.nt * LM_N;
+        {
+            LmmseNoiseArgs a{};
+            a.ltf_re = d_ltf_re + (size_t)b0 * cf.len_ltf; a.ltf_im = d_ltf_im + (size_t)b0 * cf.len_ltf;
+            a.tw = c->lmb_tw; a.nv = nv + b0; a.nt = cf.nt; a.len_ltf = cf.len_ltf;
+            // per (symbol, null bin): 256 complex multiply-adds in fp64 pairs = 4 x 11 flop each
+            ProfScope ps(c, K_LMMSE_NULL_NOISE, (double)nb * cf.nt * LMB_NULLS * LMB_FFT * 44.0, (double)nb * cf.nt * LMB_FFT * 8.0);
+            hipLaunchKernelGGL(lmmse_null_noise_kernel, dim3((unsigned)nb), dim3(LMB_THREADS), 0, c->stream, a);
+            HIP_TRY(c, hipGetLastError());
+        }
+        {
+            LmmseCorrArgs a{};
+            a.h_re = d_h_re + ho; a.h_im = d_h_im + ho; a.corr = corr + (size_t)b0 * LM_N; a.nt = cf.nt;
+            ProfScope ps(c, K_LMMSE_FREQ_CORR, (double)nb * cf.nt * (LM_N * (LM_N + 1) / 2) * 8.0, (double)nb * cf.nt * LM_N * 8.0);
+            hipLaunchKernelGGL(lmmse_freq_corr_kernel, dim3((unsigned)nb), dim3(LMB_THREADS), 0, c->stream, a);
+            HIP_TRY(c, hipGetLastError());
+        }
+        {
+            LmmseBlindArgs a{};
+            a.h_re = d_h_re + ho; a.h_im = d_h_im + ho; a.nv = nv + b0; a.corr = corr + (size_t)b0 * LM_N;
+            a.o_re = d_out_re + ho; a.o_im = d_out_im + ho; a.fallback = flags + b0; a.nt = cf.nt; a.nr = cf.nr;
+            ProfScope ps(c, K_LMMSE_BLIND, (double)nb * (cf.nt + n_jc) * 16.0 * LM_N * LM_N, (double)nb * cf.nt * LM_N * 16.0);
+            hipLaunchKernelGGL(lmmse_blind_kernel, dim3((unsigned)(nb * n_jc)), dim3(LM_THREADS), 0, c->stream, a, n_jc);
+            HIP_TRY(c, hipGetLastError());
+            hipLaunchKernelGGL(lmmse_blind_count_kernel, dim3(1), dim3(LMB_THREADS), 0, c->stream, flags + b0, (long long)nb, c->lmb_count);
+            HIP_TRY(c, hipGetLastError());
+        }
+    }
+    return CSI_OK;
+}
+
+int csi_lmmse_blind(csi_ctx* c, const float* ltf_re, const float* ltf_im, const float* h_re, const float* h_im, int64_t npkt,
+                    float* out_re, float* out_im, double* noise_var, double* corr) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    if (npkt <= 0) return fail(c, CSI_ERR_INVALID_ARG, "csi_lmmse_blind: npkt %lld must be positive", (long long)npkt);
+    if (!ltf_re || !ltf_im || !h_re || !h_im || !out_re || !out_im)
+        return fail(c, CSI_ERR_INVALID_ARG, "csi_lmmse_blind: null required pointer (ltf, h, out)");
+    const csi_config& cf = c->cfg;
+    if (cf.nt == 0) return fail(c, CSI_ERR_INVALID_ARG, "single-input context (nt=0): no LMMSE estimate");
+    HIP_TRY(c, hipSetDevice(cf.device));
+    const size_t pkt_f = (size_t)cf.nr * cf.nt * LM_N;                     // floats per packet and CSI plane
+    const size_t ltf_f = (size_t)cf.nr * cf.len_ltf;                       // floats per packet and preamble plane
+    int64_t chunk = std::max<int64_t>(1, ((int64_t)256 << 20) / (int64_t)(4 * pkt_f * sizeof(float)));      // the chunk of csi_lmmse_estimate
+    chunk = std::min(chunk, npkt);
+    const size_t stat_d = (size_t)cf.nr * (1 + 2 * LM_N);                  // doubles per packet: nv and c
+    const size_t need = ((4 * pkt_f + 2 * ltf_f) * sizeof(float) + stat_d * sizeof(double)) * (size_t)chunk;
+    int rc = ensure_bytes(c, &c->stage, &c->stage_bytes, need);
+    if (rc) return rc;
+    float* d_lre = reinterpret_cast<float*>(c->stage);
+    float* d_lim = d_lre + ltf_f * chunk;
+    float* d_re = d_lim + ltf_f * chunk;
+    float* d_im = d_re + pkt_f * chunk;
+    float* d_ore = d_im + pkt_f * chunk;
+    float* d_oim = d_ore + pkt_f * chunk;
+    double* d_nv = reinterpret_cast<double*>(d_oim + pkt_f * chunk);       // behind float planes of whole packets: a multiple of 8 bytes
+    double* d_c = d_nv + (size_t)cf.nr * chunk;
+    for (int64_t p0 = 0; p0 < npkt; p0 += chunk) {
+        const int64_t np = std::min(chunk, npkt - p0);
+        HIP_TRY(c, hipMemcpyAsync(d_lre, ltf_re + p0 * ltf_f, ltf_f * np * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(d_lim, ltf_im + p0 * ltf_f, ltf_f * np * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(d_re, h_re + p0 * pkt_f, pkt_f * np * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(d_im, h_im + p0 * pkt_f, pkt_f * np * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        rc = csi_lmmse_blind_device(c, d_lre, d_lim, d_re, d_im, np, d_ore, d_oim, d_nv, d_c);
+        if (rc) return rc;
+        HIP_TRY(c, hipMemcpyAsync(out_re + p0 * pkt_f, d_ore, pkt_f * np * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(out_im + p0 * pkt_f, d_oim, pkt_f * np * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        if (noise_var) HIP_TRY(c, hipMemcpyAsync(noise_var + p0 * cf.nr, d_nv, (size_t)cf.nr * np * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (corr) HIP_TRY(c, hipMemcpyAsync(corr + p0 * cf.nr * 2 * LM_N, d_c, (size_t)cf.nr * np * 2 * LM_N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    return CSI_OK;
+}
+
 // ---------------------------------------------------------------- hybrid beamforming weights (csi_hybrid.hpp, hybrid_weights.hip.h)
 int csi_hybrid_set_dictionary(csi_ctx* c, const float* at_re, const float* at_im, int n_rays) {
     if (!c) return CSI_ERR_INVALID_ARG;
@@ -1037,6 +1161,15 @@ int csi_get_option(csi_ctx* c, const char* name, int64_t* value) {
     else if (n == "conv_launches") *value = c->conv_launches;
     else if (n == "hybrid_launches") *value = c->hybrid_launches;
     else if (n == "link_launches") *value = c->link_launches;
+    else if (n == "lmmse_blind_fallbacks") {
+        // counted on the device behind every launch (lmmse_blind_count_kernel): reading it waits for the stream
+        if (c->user_capture) return fail(c, CSI_ERR_INVALID_ARG, "csi_get_option: lmmse_blind_fallbacks cannot be read while a capture is open");
+        long long v = 0;
+        HIP_TRY(c, hipSetDevice(c->cfg.device));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipMemcpy(&v, c->lmb_count, sizeof v, hipMemcpyDeviceToHost));
+        *value = v;
+    }
     else if (n == "scatter_launches") *value = c->scatter_launches;
     else if (n == "small_rows") *value = c->small_rows;
     else if (n == "small_rows_band") *value = c->small_rows_band;

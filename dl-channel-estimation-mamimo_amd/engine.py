@@ -573,6 +573,32 @@ class CsiEngine:
                                                  _fp(o_re), _fp(o_im)))
         return o_re + 1j * o_im
 
+    def lmmse_blind(self, ltf, h_ls=None, details=False):
+        """LMMSE smoothing from the packet's own statistics (csi_lmmse_blind): the noise level from the null carriers of the sounding
+        symbols, the frequency correlation from the LS rows of each (packet, rx) - nothing a receiver does not have.  ltf complex
+        [npkt,nr,len_ltf]; h_ls complex [npkt,nr,nt,234], or None to run the LS estimate first.  Returns complex64 [npkt,nr,nt,234];
+        with ``details`` also noise_var float64 [npkt,nr] and corr complex128 [npkt,nr,234]."""
+        re, im = self._split(ltf, None)
+        npkt = re.shape[0]
+        if h_ls is None:
+            h_re, h_im = self.ls_estimate(re, im, out=self._out_planes(None, npkt, N_DATA))
+        else:
+            h_ls = np.asarray(h_ls)
+            h_re, h_im = _f32c(h_ls.real), _f32c(h_ls.imag)
+        if h_re.shape != (npkt, self.nr, self.nt, N_DATA):
+            raise CsiError(-1, f'h_ls must be [{npkt},{self.nr},{self.nt},{N_DATA}], got {h_re.shape}')
+        o_re, o_im = np.empty_like(h_re), np.empty_like(h_re)
+        nv = np.empty((npkt, self.nr), np.float64) if details else None
+        corr = np.empty((npkt, self.nr, N_DATA, 2), np.float64) if details else None
+        _dp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if a is not None else None
+        self._check(self._lib.csi_lmmse_blind(self._ctx, _fp(re), _fp(im), _fp(h_re), _fp(h_im), npkt, _fp(o_re), _fp(o_im), _dp(nv), _dp(corr)))
+        out = np.empty(o_re.shape, dtype=np.complex64)
+        out.real = o_re
+        out.imag = o_im
+        if details:
+            return out, nv, corr[..., 0] + 1j * corr[..., 1]
+        return out
+
     # ------------------------------------------------------------------ hybrid beamforming weights
     def set_dictionary(self, At):
         """Dictionary of array responses for hybrid_weights: complex [Nt][rays] (for instance synth.steering_ula), kept on the
@@ -870,6 +896,14 @@ class CsiEngine:
         """LMMSE smoothing of device-resident LS planes (csi_lmmse_estimate_device): d_hvec [npkt][L], d_snr_db [npkt][nr]; asynchronous."""
         self._check(self._lib.csi_lmmse_estimate_device(self._ctx, d_h_re.ptr, d_h_im.ptr, int(npkt), d_hvec.ptr, int(L), d_snr_db.ptr,
                                                         d_out_re.ptr, d_out_im.ptr))
+
+    def lmmse_blind_device(self, d_ltf_re, d_ltf_im, d_h_re, d_h_im, npkt, d_out_re, d_out_im, d_noise_var=None, d_corr=None):
+        """LMMSE smoothing of device-resident LS planes from the packets' own statistics (csi_lmmse_blind_device): the preamble planes the
+        LS estimate was made from, out planes like h (they may be the h planes themselves); optional d_noise_var [npkt][nr] and d_corr
+        [npkt][nr][234][2] receive the statistics as float64 (arrays of 2 and 2 * 468 float32 words per (packet, rx)); asynchronous."""
+        self._check(self._lib.csi_lmmse_blind_device(self._ctx, d_ltf_re.ptr, d_ltf_im.ptr, d_h_re.ptr, d_h_im.ptr, int(npkt), d_out_re.ptr,
+                                                     d_out_im.ptr, d_noise_var.ptr if d_noise_var is not None else None,
+                                                     d_corr.ptr if d_corr is not None else None))
 
     # ------------------------------------------------------------------ profiling
     def profile_enable(self, on=True):

@@ -20,6 +20,8 @@
  *        generate_maMIMO_LTF.m:336-342, helperMIMOChannelEstimate.m:24-36
  *                                                                   csi_ls_estimate[_device]
  *   LMMSE_ce per link   helperMIMOChannelEstimate.m:37-39, LMMSE_ce.m  csi_lmmse_estimate[_device]
+ *   the same call site, helperMIMOChannelEstimate.m:37-39, for a receiver that has
+ *        neither the impulse response nor the SNR                   csi_lmmse_blind[_device]
  *   NMSE_subk           BER_test_maMIMO_LTF.m:675-686                csi_nmse[_device]
  *   known-channel sounding packets  generate_maMIMO_LTF.m:197-342   csi_synth_structured
  *   phased.ScatteringMIMOChannel    helperApplyMUChannel.m:44-143   csi_synth_scattering
@@ -35,7 +37,7 @@
  * has pinned (hipHostMalloc / hipHostRegister).  *_device entry points take device pointers, enqueue on the
  * context's stream and return without waiting; call csi_synchronize before reading results.
  *
- * Device pointers (csi_predict_device, csi_ls_estimate_device, csi_estimate_device, csi_lmmse_estimate_device, csi_nmse_device,
+ * Device pointers (csi_predict_device, csi_ls_estimate_device, csi_estimate_device, csi_lmmse_estimate_device, csi_lmmse_blind_device, csi_nmse_device,
  * csi_hybrid_weights_device, csi_link_sim_device, csi_viterbi_decode_device, csi_synth_*).  An array of exactly the documented
  * size suffices: it may be a slice of a larger allocation whose neighbours hold live data of any value (NaN and 1e38 included).
  * Nothing outside the arrays is written, nothing outside them reaches a result, and input arrays are not modified.  Every re / im
@@ -216,6 +218,33 @@ int  csi_lmmse_estimate(csi_ctx* ctx, const float* h_re, const float* h_im, int6
                         const float* snr_db, float* out_re, float* out_im);
 int  csi_lmmse_estimate_device(csi_ctx* ctx, const float* d_h_re, const float* d_h_im, int64_t npkt, const float* d_hvec,
                                int L, const float* d_snr_db, float* d_out_re, float* d_out_im);
+
+/* LMMSE smoothing from the packet's own statistics: the 'hDmmse' output of helperMIMOChannelEstimate.m:37-39 for a receiver that has
+ * only the preamble and its LS estimate - no impulse response, no SNR (csrc/lmmse.hip.h).  Per (packet p, rx r), in
+ * the contiguous-index convention of csi_lmmse_estimate (Nfft = Np = 234, Nps = 1):
+ *   noise        nv = sum_{s < Nt} sum_b |Y[s][b]|^2 / (14 Nt),  Y[s][b] = sum_{n < 256} x[320 s + 64 + n] exp(-2 pi i b n / 256) over the
+ *                14 null carriers b (1-based shifted bins [1:7 129 251:256] = FFT bins 0 and 122 ... 134), where the VHT-LTF is zero.
+ *                The DC bin IS counted.  nv is the variance per complex bin of one sounding symbol in the units of h (what
+ *                synth.link_noise_var models); the error variance of an LS row is nv / Nt.
+ *   correlation  c[d] = 1 / (234 Nt) sum_j sum_{k < 234 - d} h_ls[j][k + d] conj(h_ls[j][k]),  d = 0 .. 233: the Nt links of an rx antenna
+ *                share one delay profile.  The biased estimate: T = Toeplitz(c) is positive definite for any non-zero input.
+ *   smoother     out[j] = h_ls[j] - (nv / Nt) T^-1 h_ls[j]   (T estimates R_h + (nv / Nt) I as it stands).
+ *   guards       all-zero LS rows (c[0] == 0): out = h_ls.  A step of the Levinson recursion whose 1 - |ef|^2 is not positive or
+ *                not finite: that (packet, rx)'s LS rows go out unchanged and the read-only option "lmmse_blind_fallbacks" counts
+ *                it (the count is kept on the device: reading it waits for the context's stream).  Non-finite inputs are not
+ *                screened; they end in that fallback.
+ * ltf_re / ltf_im [npkt][nr][len_ltf] (len_ltf >= 320 Nt); h_re / h_im: LS estimate [npkt][nr][nt][234]; out like h and may alias h
+ * (re with re, im with im); noise_var [npkt][nr] and corr [npkt][nr][234][2] (re, im) doubles, either may be NULL.  All three kernels
+ * compute in fp64 with sums in a fixed order: a packet's bits do not depend on the call or chunk that holds it.
+ * csi_lmmse_blind_device: planes as for csi_lmmse_estimate_device (16-byte boundaries; the two double arrays 8); asynchronous on the
+ * context's stream; usable inside csi_capture_begin / _end after one eager call of the same shape (statistics the caller does not
+ * keep live in a context workspace sized by eager calls).  csi_lmmse_blind: host buffers, packet chunks of csi_lmmse_estimate's size.
+ * Refused with text: npkt <= 0, null ltf / h / out pointers, misaligned planes, a single-input context.  A null context returns -1.
+ * Profile entries "lmmse_null_noise", "lmmse_freq_corr", "lmmse_blind". */
+int  csi_lmmse_blind(csi_ctx* ctx, const float* ltf_re, const float* ltf_im, const float* h_re, const float* h_im, int64_t npkt,
+                     float* out_re, float* out_im, double* noise_var, double* corr);
+int  csi_lmmse_blind_device(csi_ctx* ctx, const float* d_ltf_re, const float* d_ltf_im, const float* d_h_re, const float* d_h_im,
+                            int64_t npkt, float* d_out_re, float* d_out_im, double* d_noise_var, double* d_corr);
 
 /* Hybrid beamforming weights from a CSI tensor (BER_test_maMIMO_LTF.m:347-376, generate_maMIMO_LTF.m:414-425: the toolbox's
  * SVD + orthogonal-matching-pursuit split of the optimal precoder into an analog and a digital part).  One item = one
@@ -471,7 +500,7 @@ int  csi_set_option(csi_ctx* ctx, const char* name, int64_t value);
 /* Current value of an option, or of the read-only values: "hs_launches" (split-engine GEMMs launched), "hs_range_fallbacks"
  * (csi_predict calls repeated on the fp32 MFMA kernels), "hs_weight_pins" / "hs_weight_err_e12" (layers pinned to the fp32 kernels
  * at load because their split copies were not fp32-grade; worst relative error x 1e12), "band_available" (the assembly band kernel
- * is embedded in this build), "graph_replays", "ls_pilot_fast" (0 generic / 1 Sylvester / 2 permuted pilot), "comm_world",
+ * is embedded in this build), "graph_replays", "lmmse_blind_fallbacks" ((packet, rx) pairs csi_lmmse_blind[_device] handed back unsmoothed), "ls_pilot_fast" (0 generic / 1 Sylvester / 2 permuted pilot), "comm_world",
  * "comm_rank", "comm_blobs", "comm_bytes" (communicator and last broadcast), "hp_direct_out_calls", and where the last pipelined
  * host-buffer call spent its time in microseconds: "hp_total_us", "hp_stage_us", "hp_wait_stage_us", "hp_wait_out_us", "hp_weave_us". */
 int  csi_get_option(csi_ctx* ctx, const char* name, int64_t* value);
