@@ -83,6 +83,9 @@ SYMBOLS = {
     'csi_viterbi_decode_device': (ctypes.c_int, [_ctx, _vp, ctypes.c_int64, ctypes.c_int64, _vp]),
     'csi_link_sim_device': (ctypes.c_int, [_ctx] + [_vp] * 7 + [ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                               ctypes.c_int] + [_vp] * 8),
+    'csi_link_preamble_symbols': (ctypes.c_int, [ctypes.c_int]),
+    'csi_link_sim_rx_device': (ctypes.c_int, [_ctx] + [_vp] * 7 + [ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                                 ctypes.c_int] + [_vp] * 11),
     'csi_capture_begin': (ctypes.c_int, [_ctx]),
     'csi_capture_end': (ctypes.c_int, [_ctx, ctypes.POINTER(ctypes.c_void_p)]),
     'csi_capture_launch': (ctypes.c_int, [_ctx, _vp]),

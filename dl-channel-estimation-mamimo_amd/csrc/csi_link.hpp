@@ -1,5 +1,6 @@
 // csi_link.hpp - host side of the link simulation (kernels: link_sim.hip.h): frame sizes, the argument checks and
-// the chunked launch sequence of csi_link_sim_device, and the decoder alone (csi_viterbi_decode_device).
+// the chunked launch sequence of csi_link_sim_device and csi_link_sim_rx_device (one sequence, two transmit / receive kernels), and the
+// decoder alone (csi_viterbi_decode_device).
 #pragma once
 #include "csi_context.hpp"
 #include "link_sim.hip.h"
@@ -41,11 +42,16 @@ int viterbi_decode_device(csi_ctx* c, const float* d_llr, int64_t ncw, int64_t n
 template <int NS>
 const void* link_txrx_fn(int bps) { return bps == 2 ? (const void*)link_txrx_kernel<NS, 1> : (const void*)link_txrx_kernel<NS, 2>; }
 
-int link_sim_device(csi_ctx* c, const float* d_h_re, const float* d_h_im, const float* d_fbb_re, const float* d_fbb_im, const float* d_frf_re,
-                    const float* d_frf_im, const float* d_noise_var, uint64_t seed, int64_t first_pkt, int64_t npkt, int ns, int ntrf, int n_sym,
-                    int bps, int32_t* d_bit_errors, float* d_evm_rms, float* d_dt_snr_db, float* d_xeq_re, float* d_xeq_im, float* d_csi,
-                    float* d_llr, uint8_t* d_bits) {
-    static const char* who = "csi_link_sim_device";
+template <int NS>
+const void* link_txrx_rx_fn(int bps) { return bps == 2 ? (const void*)link_txrx_rx_kernel<NS, 1> : (const void*)link_txrx_rx_kernel<NS, 2>; }
+
+// rx = false: csi_link_sim_device (the three last pointers are not read).  rx = true: csi_link_sim_rx_device, the receiver that estimates
+// the effective channel from a precoded preamble - the same checks in the same words, the same chunks, the same three launches per chunk.
+int link_sim_run(csi_ctx* c, bool rx, const float* d_h_re, const float* d_h_im, const float* d_fbb_re, const float* d_fbb_im, const float* d_frf_re,
+                 const float* d_frf_im, const float* d_noise_var, uint64_t seed, int64_t first_pkt, int64_t npkt, int ns, int ntrf, int n_sym,
+                 int bps, int32_t* d_bit_errors, float* d_evm_rms, float* d_dt_snr_db, float* d_xeq_re, float* d_xeq_im, float* d_csi,
+                 float* d_llr, uint8_t* d_bits, float* d_g_nmse, float* d_gest_re, float* d_gest_im) {
+    const char* who = rx ? "csi_link_sim_rx_device" : "csi_link_sim_device";
     const csi_config& cf = c->cfg;
     const int nt = cf.nt, nr = cf.nr;
     if (nt == 0) return fail(c, CSI_ERR_INVALID_ARG, "single-input context (nt=0): no link simulation");
@@ -63,15 +69,21 @@ int link_sim_device(csi_ctx* c, const float* d_h_re, const float* d_h_im, const 
         return fail(c, CSI_ERR_INVALID_ARG, "%s: n_steps %lld = ns %d x n_sym %d x 234 x bps %d / 3 exceeds %d (one codeword per packet, 8 bytes of LDS per step)",
                     who, (long long)n_steps, ns, n_sym, bps, LK_MAX_STEPS);
     if ((d_xeq_re == nullptr) != (d_xeq_im == nullptr)) return fail(c, CSI_ERR_INVALID_ARG, "%s: the xeq planes come as a pair", who);
-    if (npkt > 0 && (!d_h_re || !d_h_im || !d_fbb_re || !d_fbb_im || !d_frf_re || !d_frf_im || !d_noise_var || !d_bit_errors || !d_evm_rms || !d_dt_snr_db))
-        return fail(c, CSI_ERR_INVALID_ARG, "%s: null required pointer (h, fbb, frf_mean, noise_var, bit_errors, evm_rms, dt_snr_db)", who);
+    if (rx && (d_gest_re == nullptr) != (d_gest_im == nullptr)) return fail(c, CSI_ERR_INVALID_ARG, "%s: the gest planes come as a pair", who);
+    if (npkt > 0 && (!d_h_re || !d_h_im || !d_fbb_re || !d_fbb_im || !d_frf_re || !d_frf_im || !d_noise_var || !d_bit_errors || !d_evm_rms || !d_dt_snr_db ||
+                     (rx && !d_g_nmse)))
+        return fail(c, CSI_ERR_INVALID_ARG, "%s: null required pointer (h, fbb, frf_mean, noise_var, bit_errors, evm_rms, dt_snr_db%s)", who,
+                    rx ? ", g_nmse" : "");
     if (npkt > 0x7fffffff) return fail(c, CSI_ERR_INVALID_ARG, "%s: %lld packets exceed one launch (2^31 - 1)", who, (long long)npkt);
-    const size_t lds = link_txrx_lds_bytes(nr, ns, ntrf);
+    const size_t lds = rx ? link_txrx_rx_lds_bytes(nr, ns, ntrf) : link_txrx_lds_bytes(nr, ns, ntrf);
     if (lds > LK_MAX_LDS)
         return fail(c, CSI_ERR_INVALID_ARG, "%s: Nr %d, ns %d, ntrf %d need %zu bytes of LDS (160 KiB per workgroup)", who, nr, ns, ntrf, lds);
     if (npkt == 0) return CSI_OK;
     HIP_TRY(c, hipSetDevice(cf.device));
-    const void* fn = ns == 1 ? link_txrx_fn<1>(bps) : ns == 2 ? link_txrx_fn<2>(bps) : ns == 3 ? link_txrx_fn<3>(bps) : link_txrx_fn<4>(bps);
+    // the kernels of csi_link_sim_device are named first: instantiated in this order, they keep their place in the code object
+    const void* fn = !rx ? (ns == 1 ? link_txrx_fn<1>(bps) : ns == 2 ? link_txrx_fn<2>(bps) : ns == 3 ? link_txrx_fn<3>(bps) : link_txrx_fn<4>(bps))
+                         : (ns == 1 ? link_txrx_rx_fn<1>(bps) : ns == 2 ? link_txrx_rx_fn<2>(bps) : ns == 3 ? link_txrx_rx_fn<3>(bps) : link_txrx_rx_fn<4>(bps));
+    const int n_ltf = rx ? link_preamble_symbols(ns) : 0;
     if (lds > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     // packet chunks against the workspace limit: the coded bits, and the soft bits when the caller keeps none
     const size_t coded_b = ((size_t)n_coded + 15) / 16 * 16;
@@ -87,7 +99,8 @@ int link_sim_device(csi_ctx* c, const float* d_h_re, const float* d_h_im, const 
         const int64_t np = std::min(chunk, npkt - p0);
         uint8_t* coded = reinterpret_cast<uint8_t*>(c->link_ws);
         float* llr = d_llr ? d_llr + (size_t)p0 * n_coded : reinterpret_cast<float*>(c->link_ws + coded_b * (size_t)chunk);
-        LinkArgs a{};
+        LinkRxArgs b{};
+        LinkArgs& a = b.a;
         a.h_re = d_h_re + p0 * pkt_h; a.h_im = d_h_im + p0 * pkt_h;
         a.fbb_re = d_fbb_re + (size_t)p0 * LK_N * ns * ntrf; a.fbb_im = d_fbb_im + (size_t)p0 * LK_N * ns * ntrf;
         a.frf_re = d_frf_re + (size_t)p0 * ntrf * nt; a.frf_im = d_frf_im + (size_t)p0 * ntrf * nt;
@@ -100,14 +113,19 @@ int link_sim_device(csi_ctx* c, const float* d_h_re, const float* d_h_im, const 
         a.seed = seed; a.first_pkt = first_pkt + p0;
         a.nt = nt; a.nr = nr; a.ns = ns; a.ntrf = ntrf; a.n_sym = n_sym; a.bps = bps;
         a.fstride = (ns * ntrf) | 1;
+        if (rx) {
+            b.g_nmse = d_g_nmse + p0;
+            b.gest_re = d_gest_re ? d_gest_re + (size_t)p0 * LK_N * nr * ns : nullptr;
+            b.gest_im = d_gest_im ? d_gest_im + (size_t)p0 * LK_N * nr * ns : nullptr;
+        }
         {
             const double items = (double)np * LK_N;
-            ProfScope ps(c, K_LINK_TXRX, items * (8.0 * nt * ns * (ntrf + nr) + (double)n_sym * 16.0 * nr * ns),
+            ProfScope ps(c, K_LINK_TXRX, items * (8.0 * nt * ns * (ntrf + nr) + (double)(n_sym + n_ltf) * 16.0 * nr * ns),
                          items * nr * nt * 8.0 + (double)np * n_coded * 5.0);
             const int64_t steps = np * n_steps;
             hipLaunchKernelGGL(link_encode_kernel, dim3((unsigned)((steps + 255) / 256)), dim3(256), 0, c->stream, coded, seed, a.first_pkt, np, (int)n_steps);
             HIP_TRY(c, hipGetLastError());
-            void* kargs[] = {&a};
+            void* kargs[] = {&b};      // LinkArgs is the head of LinkRxArgs: link_txrx_kernel reads its own part
             HIP_TRY(c, hipLaunchKernel(fn, dim3((unsigned)np), dim3(LK_THREADS), kargs, lds, c->stream));
             c->link_launches += 2;
         }
@@ -115,6 +133,14 @@ int link_sim_device(csi_ctx* c, const float* d_h_re, const float* d_h_im, const 
         if (rc) return rc;
     }
     return CSI_OK;
+}
+
+int link_sim_device(csi_ctx* c, const float* d_h_re, const float* d_h_im, const float* d_fbb_re, const float* d_fbb_im, const float* d_frf_re,
+                    const float* d_frf_im, const float* d_noise_var, uint64_t seed, int64_t first_pkt, int64_t npkt, int ns, int ntrf, int n_sym,
+                    int bps, int32_t* d_bit_errors, float* d_evm_rms, float* d_dt_snr_db, float* d_xeq_re, float* d_xeq_im, float* d_csi,
+                    float* d_llr, uint8_t* d_bits) {
+    return link_sim_run(c, false, d_h_re, d_h_im, d_fbb_re, d_fbb_im, d_frf_re, d_frf_im, d_noise_var, seed, first_pkt, npkt, ns, ntrf, n_sym, bps,
+                        d_bit_errors, d_evm_rms, d_dt_snr_db, d_xeq_re, d_xeq_im, d_csi, d_llr, d_bits, nullptr, nullptr, nullptr);
 }
 
 }  // namespace

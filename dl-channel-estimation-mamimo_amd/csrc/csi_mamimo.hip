@@ -1087,6 +1087,21 @@ int csi_link_sim_device(csi_ctx* c, const float* d_h_re, const float* d_h_im, co
                            d_bit_errors, d_evm_rms, d_dt_snr_db, d_xeq_re, d_xeq_im, d_csi, d_llr, d_bits);
 }
 
+int csi_link_preamble_symbols(int ns) { return link_preamble_symbols(ns); }
+
+int csi_link_sim_rx_device(csi_ctx* c, const float* d_h_re, const float* d_h_im, const float* d_fbb_re, const float* d_fbb_im, const float* d_frf_re,
+                           const float* d_frf_im, const float* d_noise_var, uint64_t seed, int64_t first_pkt, int64_t npkt, int ns, int ntrf, int n_sym,
+                           int bps, int32_t* d_bit_errors, float* d_evm_rms, float* d_dt_snr_db, float* d_xeq_re, float* d_xeq_im, float* d_csi,
+                           float* d_llr, uint8_t* d_bits, float* d_g_nmse, float* d_gest_re, float* d_gest_im) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    if (npkt > 0)
+        if (int rc = planes_aligned(c, "csi_link_sim_rx_device", {{"d_h_re", d_h_re}, {"d_h_im", d_h_im}, {"d_fbb_re", d_fbb_re}, {"d_fbb_im", d_fbb_im},
+                                                               {"d_frf_re", d_frf_re}, {"d_frf_im", d_frf_im}, {"d_xeq_re", d_xeq_re}, {"d_xeq_im", d_xeq_im},
+                                                               {"d_gest_re", d_gest_re}, {"d_gest_im", d_gest_im}})) return rc;
+    return link_sim_run(c, true, d_h_re, d_h_im, d_fbb_re, d_fbb_im, d_frf_re, d_frf_im, d_noise_var, seed, first_pkt, npkt, ns, ntrf, n_sym, bps,
+                        d_bit_errors, d_evm_rms, d_dt_snr_db, d_xeq_re, d_xeq_im, d_csi, d_llr, d_bits, d_g_nmse, d_gest_re, d_gest_im);
+}
+
 // ---------------------------------------------------------------- accuracy metric
 int csi_nmse_device(csi_ctx* c, const float* d_ref_re, const float* d_ref_im, const float* d_est_re, const float* d_est_im,
                     int64_t nlinks, int n_bins, float* d_per_link, double* mean_out) {

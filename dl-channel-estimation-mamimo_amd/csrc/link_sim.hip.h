@@ -39,6 +39,21 @@
 //     wave-uniform values (v_readlane).  The 64 decisions of a step are one __ballot word in LDS (8 n_steps bytes); lane 0 traces back from
 //     state 0, then all lanes write the bits and count the errors against the regenerated information bits.
 // re and im stay in separate registers and planes (no complex types), and the complex arithmetic (link_txrx_kernel) is compiled without packed fp32.
+//
+// The receiver that estimates its channel (link_txrx_rx_kernel, csi_link_sim_rx_device; generate_maMIMO_LTF_SINR.m:433-435, 528-533): a
+// precoded preamble of n_ltf(ns) = 1, 2, 4, 4 symbols passes through the same G, and the equaliser is built on its LS estimate.
+//   pilots    P = P4[0:ns][0:n_ltf],  P4 = [[1,-1,1,1],[1,1,-1,1],[1,1,1,-1],[-1,1,1,1]] (802.11): P P^T = n_ltf I
+//   preamble  Ypre[m][r] = sum_s G[r][s] P[s][m] + w[m][r], m < n_ltf.  w continues the data noise stream: preamble symbol m takes the
+//             draws of symbol index n_sym + m, i = (((n_sym + m) 234 + k) Nr + r) 2 and i + 1, at the same sqrt(noise_var / 2) scale.
+//             The data symbols see the draws they see in link_txrx_kernel: the two receivers are a paired comparison.  The LTF sign
+//             of the bin is left out: it cancels in the signal term and only flips the sign of a symmetric draw.
+//   estimate  Ghat[r][s] = (1 / n_ltf) sum_m Ypre[m][r] P[s][m]  = G + e,  e ~ CN(0, noise_var / n_ltf)
+//   equaliser the same Cholesky path with A = Ghat^H Ghat, z = Ghat^H y, csi_s = 1 / [A^-1]_ss; y is still G d + w.  The singular rule
+//             is unchanged.  Soft bits, decoder, evm_rms as above; dt_snr_db is still that of the true G.
+//   outputs   g_nmse = sum_{k,r,s} |Ghat - G|^2 / sum_{k,r,s} |G|^2 (per lane in (r, s) order, then the tree over the lanes; 0 when both
+//             sums are 0, otherwise the IEEE quotient); optional planes gest [p][234][Nr][ns] (as a pair).
+// One body serves both kernels (link_txrx_body.inc, included with LK_RX 0 and 1); LK_RX adds a second [2 Nr ns][256] LDS array for Ghat and a
+// fourth row of sums.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -89,6 +104,21 @@ struct LinkArgs {
 __host__ __device__ inline size_t link_txrx_lds_bytes(int nr, int ns, int ntrf) {
     const int fstride = (ns * ntrf) | 1;
     return sizeof(float) * ((size_t)2 * nr * ns * LK_THREADS + (size_t)2 * LK_N * fstride + 3 * LK_THREADS);
+}
+
+// the receiver with an estimated channel: the arguments above and its own outputs
+struct LinkRxArgs {
+    LinkArgs a;
+    float* g_nmse;            // [pkts]
+    float* gest_re;           // [pkts][234][nr][ns] or null
+    float* gest_im;
+};
+
+__host__ __device__ inline int link_preamble_symbols(int ns) { return ns == 1 ? 1 : ns == 2 ? 2 : (ns == 3 || ns == 4) ? 4 : -1; }
+
+// link_txrx_rx_kernel: Ghat beside G, and one more row of lane sums
+__host__ __device__ inline size_t link_txrx_rx_lds_bytes(int nr, int ns, int ntrf) {
+    return link_txrx_lds_bytes(nr, ns, ntrf) + sizeof(float) * ((size_t)2 * nr * ns * LK_THREADS + LK_THREADS);
 }
 
 __device__ __forceinline__ int lk_info_bit(uint64_t kbits, uint64_t i) { return (int)(splitmix64(kbits ^ splitmix64(i)) >> 63); }
@@ -149,252 +179,23 @@ LK_DEV float lk_pam_soft(float x, float a, float* diff) {
 }
 
 // ------------------------------------------------------------------------------------------------ transmit, channel, equalise, demap
+// sign of P4[s][m]: the one -1 of row s stands in column (s + 1) mod 4
+LK_DEV float lk_p4(int s, int m) { return m == ((s + 1) & 3) ? -1.f : 1.f; }
+
 template <int NS, int M>
 LK_KERNEL __launch_bounds__(LK_THREADS) void link_txrx_kernel(const LinkArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float lk_smem[];
-    const int nt = a.nt, nr = a.nr, ntrf = a.ntrf, n_sym = a.n_sym, fs = a.fstride;
-    constexpr int BPS = 2 * M;
-    float* G = lk_smem;                                       // [2 (r NS + s) + z][LK_THREADS]
-    float* fb_re = G + (size_t)2 * nr * NS * LK_THREADS;      // [234][fs]
-    float* fb_im = fb_re + (size_t)LK_N * fs;
-    float* red = fb_im + (size_t)LK_N * fs;                   // [3][LK_THREADS]
-    const int k = threadIdx.x;
-    const bool live = k < LK_N;
-    const int kk = live ? k : LK_N - 1;                       // idle lanes repeat the last subcarrier and add nothing
-    const size_t p = blockIdx.x;
-    const float a_unit = M == 1 ? 0.70710678118654752f : 0.31622776601683794f;
+#define LK_RX 0
+#include "link_txrx_body.inc"
+#undef LK_RX
+}
 
-    {   // fbb of the packet -> LDS, pitch fs per subcarrier
-        const int per = NS * ntrf;
-        const float* gre = a.fbb_re + p * (size_t)LK_N * per;
-        const float* gim = a.fbb_im + p * (size_t)LK_N * per;
-        for (int i = k; i < LK_N * per; i += LK_THREADS) {
-            const int q = i / per, e = i - q * per;
-            fb_re[q * fs + e] = gre[i];
-            fb_im[q * fs + e] = gim[i];
-        }
-        for (int i = 0; i < 2 * nr * NS; ++i) G[(size_t)i * LK_THREADS + k] = 0.f;
-    }
-    __syncthreads();
-#define LK_G(r, s, z) G[(size_t)(2 * ((r) * NS + (s)) + (z)) * LK_THREADS + k]
-
-    // ---- G = H F (unscaled), |F|_F^2, |H|_F^2
-    const float* hre = a.h_re + p * (size_t)nr * nt * LK_N + kk;
-    const float* him = a.h_im + p * (size_t)nr * nt * LK_N + kk;
-    const float* qre = a.frf_re + p * (size_t)ntrf * nt;
-    const float* qim = a.frf_im + p * (size_t)ntrf * nt;
-    const float* mre = fb_re + kk * fs;
-    const float* mim = fb_im + kk * fs;
-    float f2 = 0.f, h2 = 0.f;
-    for (int j = 0; j < nt; ++j) {
-        float fr[NS], fi[NS];
-#pragma unroll
-        for (int s = 0; s < NS; ++s) fr[s] = fi[s] = 0.f;
-        for (int m = 0; m < ntrf; ++m) {
-            const float ur = qre[(size_t)m * nt + j], ui = qim[(size_t)m * nt + j];
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                const float br = mre[s * ntrf + m], bi = mim[s * ntrf + m];
-                fr[s] = fmaf(ur, br, fmaf(-ui, bi, fr[s]));
-                fi[s] = fmaf(ur, bi, fmaf(ui, br, fi[s]));
-            }
-        }
-#pragma unroll
-        for (int s = 0; s < NS; ++s) f2 = fmaf(fr[s], fr[s], fmaf(fi[s], fi[s], f2));
-        for (int r = 0; r < nr; ++r) {
-            const float xr = hre[((size_t)r * nt + j) * LK_N], xi = him[((size_t)r * nt + j) * LK_N];
-            h2 = fmaf(xr, xr, fmaf(xi, xi, h2));
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                LK_G(r, s, 0) = fmaf(xr, fr[s], fmaf(-xi, fi[s], LK_G(r, s, 0)));
-                LK_G(r, s, 1) = fmaf(xr, fi[s], fmaf(xi, fr[s], LK_G(r, s, 1)));
-            }
-        }
-    }
-    // ---- W = sqrt(Nt) F / |F|_F:  G scaled, A = G^H G (lower triangle), |G|_F^2
-    const float wscale = f2 > 0.f ? sqrtf((float)nt / f2) : 0.f;
-    float Ar[NS][NS], Ai[NS][NS];
-#pragma unroll
-    for (int i = 0; i < NS; ++i)
-#pragma unroll
-        for (int c = 0; c < NS; ++c) Ar[i][c] = Ai[i][c] = 0.f;
-    float g2 = 0.f;
-    for (int r = 0; r < nr; ++r) {
-        float gr[NS], gi[NS];
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            gr[s] = LK_G(r, s, 0) * wscale;
-            gi[s] = LK_G(r, s, 1) * wscale;
-            LK_G(r, s, 0) = gr[s];
-            LK_G(r, s, 1) = gi[s];
-            g2 = fmaf(gr[s], gr[s], fmaf(gi[s], gi[s], g2));
-        }
-#pragma unroll
-        for (int i = 0; i < NS; ++i)
-#pragma unroll
-            for (int c = 0; c <= i; ++c) {                     // A[i][c] += conj(g_i) g_c
-                Ar[i][c] = fmaf(gr[i], gr[c], fmaf(gi[i], gi[c], Ar[i][c]));
-                Ai[i][c] = fmaf(gr[i], gi[c], fmaf(-gi[i], gr[c], Ai[i][c]));
-            }
-    }
-    // ---- Cholesky A = L L^H in place, then Li = L^-1 (lower); [A^-1]_ss = sum_{i >= s} |Li[i][s]|^2
-    bool ok = true;
-    float dinv[NS];
-#pragma unroll
-    for (int c = 0; c < NS; ++c) {
-        float d = Ar[c][c];
-#pragma unroll
-        for (int q = 0; q < c; ++q) d -= Ar[c][q] * Ar[c][q] + Ai[c][q] * Ai[c][q];
-        if (!(d > 0.f) || !(d <= 3.0e38f)) ok = false;
-        const float l = sqrtf(ok ? d : 1.f);
-        dinv[c] = 1.f / l;
-        Ar[c][c] = l;
-        Ai[c][c] = 0.f;
-#pragma unroll
-        for (int i = c + 1; i < NS; ++i) {
-            float sr = Ar[i][c], si = Ai[i][c];
-#pragma unroll
-            for (int q = 0; q < c; ++q) {                      // - L[i][q] conj(L[c][q])
-                sr -= Ar[i][q] * Ar[c][q] + Ai[i][q] * Ai[c][q];
-                si -= Ai[i][q] * Ar[c][q] - Ar[i][q] * Ai[c][q];
-            }
-            Ar[i][c] = sr * dinv[c];
-            Ai[i][c] = si * dinv[c];
-        }
-    }
-    float Lr[NS][NS], Lm[NS][NS];                              // Li, lower triangle
-#pragma unroll
-    for (int c = 0; c < NS; ++c) {
-        Lr[c][c] = dinv[c];
-        Lm[c][c] = 0.f;
-#pragma unroll
-        for (int i = c + 1; i < NS; ++i) {                     // Li[i][c] = - (sum_{q = c}^{i - 1} L[i][q] Li[q][c]) / L[i][i]
-            float sr = 0.f, si = 0.f;
-#pragma unroll
-            for (int q = c; q < i; ++q) {
-                sr += Ar[i][q] * Lr[q][c] - Ai[i][q] * Lm[q][c];
-                si += Ar[i][q] * Lm[q][c] + Ai[i][q] * Lr[q][c];
-            }
-            Lr[i][c] = -sr * dinv[i];
-            Lm[i][c] = -si * dinv[i];
-        }
-    }
-    float csi[NS];
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        float v = 0.f;
-#pragma unroll
-        for (int i = s; i < NS; ++i) v += Lr[i][s] * Lr[i][s] + Lm[i][s] * Lm[i][s];
-        csi[s] = ok ? 1.f / v : 0.f;
-        if (!(csi[s] <= 3.0e38f)) { csi[s] = 0.f; ok = false; }
-    }
-    if (!ok) {
-#pragma unroll
-        for (int s = 0; s < NS; ++s) csi[s] = 0.f;
-    }
-    if (a.csi && live) {
-#pragma unroll
-        for (int s = 0; s < NS; ++s) a.csi[(p * NS + s) * LK_N + k] = csi[s];
-    }
-
-    // ---- the data symbols
-    const float nv = a.noise_var[p];
-    const float nstd = sqrtf(0.5f * nv);
-    float lscale[NS];
-#pragma unroll
-    for (int s = 0; s < NS; ++s) lscale[s] = nv > 0.f ? csi[s] / nv : csi[s];
-    const uint64_t kn = ss_key(a.seed, (uint64_t)(a.first_pkt + (int64_t)p), LK_KIND_NOISE);
-    const size_t n_coded = (size_t)NS * n_sym * LK_N * BPS;
-    const uint8_t* cb = a.coded + p * n_coded;
-    float* lo = a.llr + p * n_coded;
-    float evm = 0.f;
-    for (int n = 0; n < n_sym; ++n) {
-        float dr[NS], di[NS], zr[NS], zi[NS];
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const uint8_t* c = cb + ((size_t)(s * n_sym + n) * LK_N + kk) * BPS;
-            int b[BPS];
-#pragma unroll
-            for (int i = 0; i < BPS; ++i) b[i] = c[i];
-            dr[s] = a_unit * lk_pam_level<M>(b);
-            di[s] = a_unit * lk_pam_level<M>(b + M);
-            zr[s] = zi[s] = 0.f;
-        }
-        const uint64_t base = ((uint64_t)(n * LK_N + kk) * nr) * 2;
-        for (int r = 0; r < nr; ++r) {
-            float yr = nstd * tr_normal(kn, base + 2 * r), yi = nstd * tr_normal(kn, base + 2 * r + 1);
-            float gr[NS], gi[NS];
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                gr[s] = LK_G(r, s, 0);
-                gi[s] = LK_G(r, s, 1);
-                yr = fmaf(gr[s], dr[s], fmaf(-gi[s], di[s], yr));
-                yi = fmaf(gr[s], di[s], fmaf(gi[s], dr[s], yi));
-            }
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {                     // z += conj(g) y
-                zr[s] = fmaf(gr[s], yr, fmaf(gi[s], yi, zr[s]));
-                zi[s] = fmaf(gr[s], yi, fmaf(-gi[s], yr, zi[s]));
-            }
-        }
-        // x = Li^H (Li z)
-        float vr[NS], vi[NS];
-#pragma unroll
-        for (int i = 0; i < NS; ++i) {
-            float sr = 0.f, si = 0.f;
-#pragma unroll
-            for (int c = 0; c <= i; ++c) {
-                sr += Lr[i][c] * zr[c] - Lm[i][c] * zi[c];
-                si += Lr[i][c] * zi[c] + Lm[i][c] * zr[c];
-            }
-            vr[i] = sr;
-            vi[i] = si;
-        }
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            float xr = 0.f, xi = 0.f;
-#pragma unroll
-            for (int i = s; i < NS; ++i) {                     // conj(Li[i][s]) v_i
-                xr += Lr[i][s] * vr[i] + Lm[i][s] * vi[i];
-                xi += Lr[i][s] * vi[i] - Lm[i][s] * vr[i];
-            }
-            if (!ok) xr = xi = 0.f;
-            float dI[M], dQ[M];
-            const float eI = lk_pam_soft<M>(xr, a_unit, dI), eQ = lk_pam_soft<M>(xi, a_unit, dQ);
-            if (live) {
-                evm += eI + eQ;
-                float* l = lo + ((size_t)(s * n_sym + n) * LK_N + k) * BPS;
-#pragma unroll
-                for (int i = 0; i < M; ++i) {
-                    l[i] = lscale[s] * dI[i];
-                    l[M + i] = lscale[s] * dQ[i];
-                }
-                if (a.xeq_re) {
-                    const size_t o = ((p * NS + s) * n_sym + n) * LK_N + k;
-                    a.xeq_re[o] = xr;
-                    a.xeq_im[o] = xi;
-                }
-            }
-        }
-    }
-#undef LK_G
-    // ---- the packet's sums: a fixed tree over the lanes
-    red[k] = live ? evm : 0.f;
-    red[LK_THREADS + k] = live ? g2 : 0.f;
-    red[2 * LK_THREADS + k] = live ? h2 : 0.f;
-    __syncthreads();
-    for (int w = LK_THREADS / 2; w > 0; w >>= 1) {
-        if (k < w) {
-            red[k] += red[k + w];
-            red[LK_THREADS + k] += red[LK_THREADS + k + w];
-            red[2 * LK_THREADS + k] += red[2 * LK_THREADS + k + w];
-        }
-        __syncthreads();
-    }
-    if (k == 0) {
-        a.evm_rms[p] = 100.f * sqrtf(red[0] / ((float)NS * (float)n_sym * (float)LK_N));
-        a.dt_snr_db[p] = 10.f * log10f(red[LK_THREADS] / red[2 * LK_THREADS]);
-    }
+// the receiver that estimates G from the preamble: the same body with the LK_RX parts
+template <int NS, int M>
+LK_KERNEL __launch_bounds__(LK_THREADS) void link_txrx_rx_kernel(const LinkRxArgs b) {
+    const LinkArgs& a = b.a;
+#define LK_RX 1
+#include "link_txrx_body.inc"
+#undef LK_RX
 }
 
 // ------------------------------------------------------------------------------------------------ Viterbi decoder

@@ -67,6 +67,7 @@ class DeviceArray:
 
 HybridWeights = collections.namedtuple('HybridWeights', 'fbb idx n_atoms gain frf_mean')
 LinkResult = collections.namedtuple('LinkResult', 'bit_errors evm_rms dt_snr_db n_info xeq csi llr bits')
+LinkRxResult = collections.namedtuple('LinkRxResult', LinkResult._fields + ('g_nmse', 'gest'))
 
 
 def frf_from_idx(At, idx):
@@ -675,6 +676,10 @@ class CsiEngine:
         noise_var [npkt] (or a scalar).  Returns LinkResult(bit_errors int32 [npkt], evm_rms, dt_snr_db float32 [npkt], n_info, ...);
         with details=True also xeq complex64 [npkt,ns,n_sym,234], csi [npkt,ns,234], llr [npkt,n_coded] and the decoded bits uint8
         [npkt,n_info] (None otherwise)."""
+        return self._link_sim_host(False, h, fbb, frf_mean, noise_var, seed, first_pkt, n_sym, bps, details)
+
+    def _link_sim_host(self, rx, h, fbb, frf_mean, noise_var, seed, first_pkt, n_sym, bps, details):
+        """link_sim (rx False) and link_sim_rx (rx True): upload, one device call, download"""
         h, fbb, frf_mean = np.asarray(h), np.asarray(fbb), np.asarray(frf_mean)
         npkt = h.shape[0] if h.ndim else 0
         if h.shape != (npkt, self.nr, self.nt, N_DATA):
@@ -687,24 +692,56 @@ class CsiEngine:
         nv = np.ascontiguousarray(np.broadcast_to(np.asarray(noise_var, np.float32), (npkt,)))
         n_info, n_coded = self.link_frame_bits(ns, n_sym, bps)
         dev = [self.to_device(_f32c(a)) for a in (h.real, h.imag, fbb.real, fbb.imag, frf_mean.real, frf_mean.imag, nv)]
-        outs = [self.empty((npkt,)) for _ in range(3)]
-        extra = [None] * 5
+        outs = [self.empty((npkt,)) for _ in range(4 if rx else 3)]
+        extra = [None] * 7
         if details:
             extra = [self.empty((npkt, ns, n_sym, N_DATA)), self.empty((npkt, ns, n_sym, N_DATA)), self.empty((npkt, ns, N_DATA)),
                      self.empty((npkt, n_coded)), self.empty(((npkt * n_info + 3) // 4,))]
+            extra += [self.empty((npkt, N_DATA, self.nr, ns)) for _ in range(2)] if rx else [None, None]
         try:
-            self.link_sim_device(*dev, seed, first_pkt, npkt, ns, ntrf, *outs, n_sym=n_sym, bps=bps, d_xeq_re=extra[0], d_xeq_im=extra[1],
-                                 d_csi=extra[2], d_llr=extra[3], d_bits=extra[4])
+            if rx:
+                self.link_sim_rx_device(*dev, seed, first_pkt, npkt, ns, ntrf, *outs, n_sym=n_sym, bps=bps, d_xeq_re=extra[0], d_xeq_im=extra[1],
+                                        d_csi=extra[2], d_llr=extra[3], d_bits=extra[4], d_gest_re=extra[5], d_gest_im=extra[6])
+            else:
+                self.link_sim_device(*dev, seed, first_pkt, npkt, ns, ntrf, *outs, n_sym=n_sym, bps=bps, d_xeq_re=extra[0], d_xeq_im=extra[1],
+                                     d_csi=extra[2], d_llr=extra[3], d_bits=extra[4])
             self.synchronize()
             res = LinkResult(outs[0].download().view(np.int32), outs[1].download(), outs[2].download(), n_info,
                              (extra[0].download() + 1j * extra[1].download()).astype(np.complex64) if details else None,
                              extra[2].download() if details else None, extra[3].download() if details else None,
                              extra[4].download().view(np.uint8)[:npkt * n_info].reshape(npkt, n_info).copy() if details else None)
+            if rx:
+                res = LinkRxResult(*res, outs[3].download(),
+                                   (extra[5].download() + 1j * extra[6].download()).astype(np.complex64) if details else None)
         finally:
             for a in dev + outs + extra:
                 if a is not None:
                     a.free()
         return res
+
+    def link_sim_rx_device(self, d_h_re, d_h_im, d_fbb_re, d_fbb_im, d_frf_re, d_frf_im, d_noise_var, seed, first_pkt, npkt, ns, ntrf,
+                           d_bit_errors, d_evm_rms, d_dt_snr_db, d_g_nmse, n_sym=10, bps=2, d_xeq_re=None, d_xeq_im=None, d_csi=None, d_llr=None,
+                           d_bits=None, d_gest_re=None, d_gest_im=None):
+        """link_sim_device with a receiver that estimates the effective channel from a precoded preamble of link_preamble_symbols(ns)
+        symbols and equalises with the estimate (csi_link_sim_rx_device): the same bits and the same data noise.  d_g_nmse [npkt]
+        receives |Ghat - G|^2 / |G|^2 per packet; the optional pair d_gest_re / d_gest_im [npkt,234,nr,ns] the estimate itself."""
+        ptr = lambda a: None if a is None else a.ptr
+        self._check(self._lib.csi_link_sim_rx_device(self._ctx, d_h_re.ptr, d_h_im.ptr, d_fbb_re.ptr, d_fbb_im.ptr, d_frf_re.ptr, d_frf_im.ptr,
+                                                     d_noise_var.ptr, int(seed), int(first_pkt), int(npkt), int(ns), int(ntrf), int(n_sym), int(bps),
+                                                     d_bit_errors.ptr, d_evm_rms.ptr, d_dt_snr_db.ptr, ptr(d_xeq_re), ptr(d_xeq_im), ptr(d_csi),
+                                                     ptr(d_llr), ptr(d_bits), d_g_nmse.ptr, ptr(d_gest_re), ptr(d_gest_im)))
+
+    def link_preamble_symbols(self, ns):
+        """Symbols of the precoded preamble of ns streams: 1, 2, 4, 4."""
+        n = self._lib.csi_link_preamble_symbols(int(ns))
+        if n < 0:
+            raise CsiError(-1, f'csi_link_preamble_symbols: ns {ns} outside 1 .. 4')
+        return int(n)
+
+    def link_sim_rx(self, h, fbb, frf_mean, noise_var, seed=0, first_pkt=0, n_sym=10, bps=2, details=False):
+        """link_sim with the estimating receiver (link_sim_rx_device).  Returns LinkRxResult: the fields of LinkResult, then g_nmse
+        float32 [npkt] and, with details=True, gest complex64 [npkt,234,nr,ns] (None otherwise)."""
+        return self._link_sim_host(True, h, fbb, frf_mean, noise_var, seed, first_pkt, n_sym, bps, details)
 
     def viterbi_decode(self, llr):
         """Viterbi decoding of terminated codewords of the rate-1/3 K = 7 code (133, 171, 165): llr float [ncw, 3 n_steps], positive = 0

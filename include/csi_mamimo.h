@@ -38,10 +38,10 @@
  * context's stream and return without waiting; call csi_synchronize before reading results.
  *
  * Device pointers (csi_predict_device, csi_ls_estimate_device, csi_estimate_device, csi_lmmse_estimate_device, csi_lmmse_blind_device, csi_nmse_device,
- * csi_hybrid_weights_device, csi_link_sim_device, csi_viterbi_decode_device, csi_synth_*).  An array of exactly the documented
+ * csi_hybrid_weights_device, csi_link_sim_device, csi_link_sim_rx_device, csi_viterbi_decode_device, csi_synth_*).  An array of exactly the documented
  * size suffices: it may be a slice of a larger allocation whose neighbours hold live data of any value (NaN and 1e38 included).
  * Nothing outside the arrays is written, nothing outside them reaches a result, and input arrays are not modified.  Every re / im
- * PLANE (the preambles [npkt][Nr][len_ltf], the CSI planes [npkt][Nr][Nt][234 or n_out], fbb, frf_mean, xeq) starts on a 16-byte
+ * PLANE (the preambles [npkt][Nr][len_ltf], the CSI planes [npkt][Nr][Nt][234 or n_out], fbb, frf_mean, xeq, gest) starts on a 16-byte
  * boundary: the LS and layer-0 kernels move the caller's rows as 16-byte words and by LDS-DMA; hipMalloc, csi_device_malloc and
  * whole torch tensors satisfy that, and so does every packet range of a preamble or CSI plane (Nt is a multiple of 4).  A
  * misaligned plane is refused with CSI_ERR_INVALID_ARG and a text that names the argument, before anything is launched or counted.
@@ -312,6 +312,25 @@ int  csi_link_sim_device(csi_ctx* ctx, const float* d_h_re, const float* d_h_im,
                          const float* d_frf_re, const float* d_frf_im, const float* d_noise_var, uint64_t seed, int64_t first_pkt,
                          int64_t npkt, int ns, int ntrf, int n_sym, int bps, int32_t* d_bit_errors, float* d_evm_rms,
                          float* d_dt_snr_db, float* d_xeq_re, float* d_xeq_im, float* d_csi, float* d_llr, uint8_t* d_bits);
+
+/* The same data phase with a receiver that does not know the effective channel (BER_test_maMIMO_LTF.m / generate_maMIMO_LTF_SINR.m:
+ * 433-435, 528-533: a precoded preamble in front of the data).  n_ltf = csi_link_preamble_symbols(ns) = 1, 2, 4, 4 preamble symbols
+ * with the pilot matrix P = P4[0:ns][0:n_ltf] (the 802.11 matrix) pass through the same G_k = H_k W_k:
+ * Ypre[m][r] = sum_s G[r][s] P[s][m] + w[m][r]; the receiver forms Ghat[r][s] = (1 / n_ltf) sum_m Ypre[m][r] P[s][m] and equalises
+ * the data with Ghat in place of G (A = Ghat^H Ghat, z = Ghat^H y, csi_s = 1 / [A^-1]_ss; the same singular rule).  The preamble noise
+ * continues the packet's data noise stream at symbol index n_sym + m, so the data symbols are, draw for draw, those of
+ * csi_link_sim_device: the two entries are a paired comparison, and with noise_var = 0 and ns = 1 they agree bit for bit.
+ * dt_snr_db is that of the true G.  Arguments, refusals and chunking of csi_link_sim_device, then
+ *   d_g_nmse [npkt] (required): sum_{k,r,s} |Ghat - G|^2 / sum_{k,r,s} |G|^2; 0 when both sums are 0, otherwise the IEEE quotient
+ *   d_gest_re / d_gest_im [npkt][234][Nr][ns] (optional, as a pair): Ghat.
+ * Also refused: one gest plane without the other, a null d_g_nmse; the LDS image holds G twice.  Profile entries and counter as above.
+ * csi_link_preamble_symbols: n_ltf of ns; -1 for ns outside 1 .. 4. */
+int  csi_link_preamble_symbols(int ns);
+int  csi_link_sim_rx_device(csi_ctx* ctx, const float* d_h_re, const float* d_h_im, const float* d_fbb_re, const float* d_fbb_im,
+                            const float* d_frf_re, const float* d_frf_im, const float* d_noise_var, uint64_t seed, int64_t first_pkt,
+                            int64_t npkt, int ns, int ntrf, int n_sym, int bps, int32_t* d_bit_errors, float* d_evm_rms,
+                            float* d_dt_snr_db, float* d_xeq_re, float* d_xeq_im, float* d_csi, float* d_llr, uint8_t* d_bits,
+                            float* d_g_nmse, float* d_gest_re, float* d_gest_im);
 
 /* Accuracy metric of the reference's evaluation, NMSE_subk (BER_test_maMIMO_LTF.m:675-686): per link
  * ||ref - est||^2 / ||ref||^2 over the n_bins bins, mean over the nlinks links ([link][n_bins] planes, e.g.
