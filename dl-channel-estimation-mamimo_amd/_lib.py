@@ -76,6 +76,9 @@ SYMBOLS = {
     'csi_lmmse_estimate_device': (ctypes.c_int, [_ctx, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_int, _vp, _vp, _vp]),
     'csi_lmmse_blind': (ctypes.c_int, [_ctx, _fp, _fp, _fp, _fp, ctypes.c_int64, _fp, _fp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     'csi_lmmse_blind_device': (ctypes.c_int, [_ctx, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp]),
+    'csi_subspace_set_basis': (ctypes.c_int, [_ctx, _fp, _fp, ctypes.c_int]),
+    'csi_subspace_smooth': (ctypes.c_int, [_ctx, _fp, _fp, ctypes.c_int64, _fp, _fp, _fp]),
+    'csi_subspace_smooth_device': (ctypes.c_int, [_ctx, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp]),
     'csi_hybrid_set_dictionary': (ctypes.c_int, [_ctx, _fp, _fp, ctypes.c_int]),
     'csi_hybrid_weights': (ctypes.c_int, [_ctx, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_vp] * 7),
     'csi_hybrid_weights_device': (ctypes.c_int, [_ctx, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_vp] * 7),

@@ -26,6 +26,7 @@
 #include "synth_structured.hip.h"
 #include "synth_scattering.hip.h"
 #include "link_sim.hip.h"
+#include "subspace_smooth.hip.h"
 
 using namespace csi;
 
@@ -57,6 +58,9 @@ enum KernelId {
     K_SYNTH_STRUCTURED,  // known-channel sounding packets (synth_structured.hip.h): the power pass and the packet pass of csi_synth_structured
     K_LINK_TXRX,         // link simulation: encoder, precoder, true channel, zero forcing and soft bits per (packet, subcarrier) (link_sim.hip.h)
     K_LINK_VITERBI,      // link simulation: one-wavefront Viterbi decoder per codeword, traceback and bit errors
+    K_SUBSPACE_SMOOTH,   // delay-subspace smoother y = Q diag(w) Q^H x of a CSI tensor (csi_subspace_smooth, subspace_smooth.hip.h).  In front of the
+                         // ids below, not behind them: tests/test_blind_lmmse_host.py pins the last four names of the table, and every reader
+                         // of the table looks an id up by its name (csi_profile_kernel_name)
     K_SYNTH_SCATTERING,  // known-channel sounding packets of the scattering channel (synth_scattering.hip.h): the power pass and the packet pass of csi_synth_scattering
     K_LMMSE_NULL_NOISE,  // blind LMMSE smoother (csi_lmmse_blind, lmmse.hip.h): noise variance from the null carriers of the sounding symbols
     K_LMMSE_FREQ_CORR,   // blind LMMSE smoother: sample frequency correlation of the LS rows
@@ -68,7 +72,7 @@ const char* const kKernelNames[K_COUNT] = {
     "ls_estimate", "naive_dense0_gemm", "synth_white", "pilot_table", "cast_bf16", "pair_h1_bf16", "lmmse_levinson",
     "train_gemm", "train_elementwise", "nmse_links", "pair_dense_tail", "input_pool", "conv_frontend",
     "hybrid_svd", "hybrid_corr_argmax", "hybrid_solve", "hybrid_finish", "synth_structured", "link_txrx", "link_viterbi",
-    "synth_scattering", "lmmse_null_noise", "lmmse_freq_corr", "lmmse_blind"};
+    "subspace_smooth", "synth_scattering", "lmmse_null_noise", "lmmse_freq_corr", "lmmse_blind"};
 
 thread_local std::string g_create_error;
 
@@ -221,6 +225,12 @@ struct csi_ctx {
     char* lmb_ws = nullptr;
     size_t lmb_ws_bytes = 0;
     long long* lmb_count = nullptr;
+    // delay-subspace smoother (csi_subspace.hpp): the basis as the kernel's two images, qa re | qa im [234][rp] then qb re | qb im [rp][256],
+    // in one allocation of the largest size (rank 128) that a second csi_subspace_set_basis overwrites; rank 0 = none set
+    float* sub_q = nullptr;
+    int sub_rank = 0, sub_rp = 0;
+    size_t sub_lds_attr = 0;
+    int64_t subspace_launches = 0;   // "subspace_launches": kernels launched by csi_subspace_smooth_device
     int64_t link_launches = 0;   // "link_launches": kernels launched by csi_link_sim_device / csi_viterbi_decode_device
     bool user_capture = false;   // between csi_capture_begin and csi_capture_end (csi_hybrid.hpp): device-pointer calls are recorded, not run
     bool user_capture_use_graph = false;

@@ -22,6 +22,7 @@
 #include "csi_hybrid.hpp"
 #include "csi_link.hpp"
 #include "csi_scatter.hpp"
+#include "csi_subspace.hpp"
 #include <initializer_list>
 
 namespace {
@@ -322,6 +323,7 @@ void csi_destroy(csi_ctx* c) {
     if (c->lmb_tw) hipFree(c->lmb_tw);
     if (c->lmb_ws) hipFree(c->lmb_ws);
     if (c->lmb_count) hipFree(c->lmb_count);
+    if (c->sub_q) hipFree(c->sub_q);
     if (c->hs_peak) hipFree(c->hs_peak);
     if (c->hs_zero) hipFree(c->hs_zero);
     if (c->fuse_ws) hipFree(c->fuse_ws);
@@ -1026,6 +1028,26 @@ int csi_lmmse_blind(csi_ctx* c, const float* ltf_re, const float* ltf_im, const 
     return CSI_OK;
 }
 
+// ---------------------------------------------------------------- delay-subspace smoother (csi_subspace.hpp, subspace_smooth.hip.h)
+int csi_subspace_set_basis(csi_ctx* c, const float* q_re, const float* q_im, int rank) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return subspace_set_basis(c, q_re, q_im, rank);
+}
+
+int csi_subspace_smooth_device(csi_ctx* c, const float* d_h_re, const float* d_h_im, int64_t npkt, const float* d_w, float* d_out_re, float* d_out_im) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    static const char* who = "csi_subspace_smooth_device";
+    if (int rc = subspace_check(c, who, d_h_re, d_h_im, npkt, d_out_re, d_out_im)) return rc;
+    if (int rc = planes_aligned(c, who, {{"d_h_re", d_h_re}, {"d_h_im", d_h_im}, {"d_out_re", d_out_re}, {"d_out_im", d_out_im}})) return rc;
+    if (reinterpret_cast<uintptr_t>(d_w) & 3) return fail(c, CSI_ERR_INVALID_ARG, "%s: d_w must be aligned for floats (got %p)", who, (const void*)d_w);
+    return subspace_smooth_device(c, who, d_h_re, d_h_im, npkt, d_w, d_out_re, d_out_im);
+}
+
+int csi_subspace_smooth(csi_ctx* c, const float* h_re, const float* h_im, int64_t npkt, const float* w, float* out_re, float* out_im) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return subspace_smooth_host(c, h_re, h_im, npkt, w, out_re, out_im);
+}
+
 // ---------------------------------------------------------------- hybrid beamforming weights (csi_hybrid.hpp, hybrid_weights.hip.h)
 int csi_hybrid_set_dictionary(csi_ctx* c, const float* at_re, const float* at_im, int n_rays) {
     if (!c) return CSI_ERR_INVALID_ARG;
@@ -1176,6 +1198,7 @@ int csi_get_option(csi_ctx* c, const char* name, int64_t* value) {
     else if (n == "conv_launches") *value = c->conv_launches;
     else if (n == "hybrid_launches") *value = c->hybrid_launches;
     else if (n == "link_launches") *value = c->link_launches;
+    else if (n == "subspace_launches") *value = c->subspace_launches;
     else if (n == "lmmse_blind_fallbacks") {
         // counted on the device behind every launch (lmmse_blind_count_kernel): reading it waits for the stream
         if (c->user_capture) return fail(c, CSI_ERR_INVALID_ARG, "csi_get_option: lmmse_blind_fallbacks cannot be read while a capture is open");

@@ -600,6 +600,38 @@ class CsiEngine:
             return out, nv, corr[..., 0] + 1j * corr[..., 1]
         return out
 
+    # ------------------------------------------------------------------ delay-subspace smoother
+    def subspace_set_basis(self, Q):
+        """Basis of the subspace smoother: complex [234][r] with orthonormal columns, r = 1 .. 128 (for instance
+        subspace.delay_basis(L)[0]), kept on the device in float32; a second call replaces it."""
+        Q = np.asarray(Q)
+        if Q.ndim != 2 or Q.shape[0] != N_DATA:
+            raise CsiError(-1, f'basis must be [{N_DATA}][rank], got {Q.shape}')
+        re, im = _f32c(Q.real), _f32c(Q.imag)
+        self._check(self._lib.csi_subspace_set_basis(self._ctx, _fp(re), _fp(im), Q.shape[1]))
+        self.subspace_rank = int(Q.shape[1])
+
+    def subspace_smooth(self, h, weights=None):
+        """y = Q diag(w) Q^H x for every row of h complex [npkt,nr,nt,234] (csi_subspace_smooth; Q from subspace_set_basis).
+        weights float [npkt,nr,rank], or None for the plain projection.  Returns complex64 [npkt,nr,nt,234]."""
+        h = np.asarray(h)
+        re, im = _f32c(h.real), _f32c(h.imag)
+        npkt = re.shape[0] if re.ndim else 0
+        if re.shape != (npkt, self.nr, self.nt, N_DATA):
+            raise CsiError(-1, f'h must be [npkt,{self.nr},{self.nt},{N_DATA}], got {re.shape}')
+        w = None
+        if weights is not None:
+            w = _f32c(weights)
+            rank = getattr(self, 'subspace_rank', 0)
+            if w.shape != (npkt, self.nr, rank):
+                raise CsiError(-1, f'weights must be [{npkt},{self.nr},{rank}], got {w.shape}')
+        o_re, o_im = np.empty_like(re), np.empty_like(re)
+        self._check(self._lib.csi_subspace_smooth(self._ctx, _fp(re), _fp(im), npkt, _fp(w) if w is not None else None, _fp(o_re), _fp(o_im)))
+        out = np.empty(o_re.shape, dtype=np.complex64)
+        out.real = o_re
+        out.imag = o_im
+        return out
+
     # ------------------------------------------------------------------ hybrid beamforming weights
     def set_dictionary(self, At):
         """Dictionary of array responses for hybrid_weights: complex [Nt][rays] (for instance synth.steering_ula), kept on the
@@ -941,6 +973,12 @@ class CsiEngine:
         self._check(self._lib.csi_lmmse_blind_device(self._ctx, d_ltf_re.ptr, d_ltf_im.ptr, d_h_re.ptr, d_h_im.ptr, int(npkt), d_out_re.ptr,
                                                      d_out_im.ptr, d_noise_var.ptr if d_noise_var is not None else None,
                                                      d_corr.ptr if d_corr is not None else None))
+
+    def subspace_smooth_device(self, d_h_re, d_h_im, npkt, d_out_re, d_out_im, d_w=None):
+        """Subspace smoother on device-resident planes (csi_subspace_smooth_device): out planes like h (they may be the h planes
+        themselves), d_w [npkt][nr][rank] or None for the plain projection; one launch, asynchronous."""
+        self._check(self._lib.csi_subspace_smooth_device(self._ctx, d_h_re.ptr, d_h_im.ptr, int(npkt), d_w.ptr if d_w is not None else None,
+                                                         d_out_re.ptr, d_out_im.ptr))
 
     # ------------------------------------------------------------------ profiling
     def profile_enable(self, on=True):

@@ -9,13 +9,15 @@ a precoded preamble (csi_link_sim_rx_device), and adds the bersRx_ / EVM_rmsRx_ 
     python -m dl_channel_estimation_mamimo_amd.sweep -d OUT [--nTX 32 --nRX 4 --nn 1024 1024 --useBN --bs 256 ...]
                                                             [--ber --numSTS 1 --rays 500 --dataSymbols 10 --bps 2 [--rxEstimate]]
                                                             [--channel scattering --scatterers 100 --range 100 --userAz 30 --userEl 0 --randomUsers]
-                                                            [--blind]
+                                                            [--blind] [--delayTaps L [--delayPre P]]
 
 The module holds no arithmetic of its own: packets with a known channel come from csi_synth_structured (--channel scattering: from
 csi_synth_scattering, whose path delays then feed the LMMSE smoother as the reference's h_tau does), labels from
 csi_ls_estimate_device, the fit from trainer.fit, the estimates from csi_estimate_device / csi_lmmse_estimate_device and every
 NMSE from csi_nmse_device (--blind adds the estimator MMSEb: csi_lmmse_blind_device, the smoother that takes its noise level and its
-frequency correlation from the packet itself instead of from the generator); the hybrid weights from csi_hybrid_weights_device and bit errors, EVM and beamforming gain from
+frequency correlation from the packet itself instead of from the generator; --delayTaps L adds the estimator DLY:
+csi_subspace_smooth_device with w = 1, the projection of the LS rows onto the channels of at most L delay taps, which uses nothing
+from the generator either - the basis comes from subspace.delay_basis); the hybrid weights from csi_hybrid_weights_device and bit errors, EVM and beamforming gain from
 csi_link_sim_device, with the noise level of a data symbol from synth.link_noise_var.  Only the per-packet mean of the per-link
 ratios (NMSE_subk, BER_test_maMIMO_LTF.m:675-686), errors / n_info and the confidence interval are taken on the host."""
 import argparse
@@ -28,13 +30,14 @@ import time
 import numpy as np
 
 from . import dataset as ds
-from . import synth, trainer
+from . import subspace, synth, trainer
 from .engine import N_DATA
 
 ESTIMATORS = ('LS', 'MMSE', 'DNN')
 SOURCES = ESTIMATORS + ('perfect',)      # --ber: whose hybrid weights precode the data phase (perfect = the true channel)
 LINK_FIELDS = ('bers_', 'EVM_rms_', 'dtSNR_')
 RX_FIELDS = ('bersRx_', 'EVM_rmsRx_', 'gNMSE_')     # --rxEstimate: the same data phase equalised with the preamble's estimate of H W
+DELAY = 'DLY'                            # --delayTaps: the LS rows projected onto a window of delay taps (csi_subspace_smooth_device, w = 1)
 BLIND = 'MMSEb'                          # --blind: the LMMSE smoother on the packet's own statistics (csi_lmmse_blind_device)
 
 
@@ -92,7 +95,7 @@ def make_dataset(engine, n_train, seed, n_taps=8, amp_scale=True, channel=None):
 
 
 def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=True, keep=False, ber=None, channel=None, blind=False,
-                   rx_estimate=False):
+                   rx_estimate=False, delay=None):
     """npkt test packets at `snr_db` (packets first_pkt ... of stream `seed`: keep them disjoint from the training packets), LS + DNN
     (estimate_device), the LMMSE smoother on the LS planes, and NMSE_subk of the three estimates against the true channel.
     Returns {'MSE_LS', 'MSE_MMSE', 'MSE_DNN'}: float64 [npkt], the per-link ratios averaged per packet.
@@ -110,7 +113,10 @@ def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=Tr
     blind=True adds 'MSE_MMSEb': the smoother that needs neither hvec nor the level (lmmse_blind_device on the preambles and the LS
     planes), and with `ber` the source MMSEb of the data phase.  Nothing else changes.
 
-    rx_estimate=True (with `ber`) adds 'bersRx_X', 'EVM_rmsRx_X' and 'gNMSE_X' per source (link_level)."""
+    rx_estimate=True (with `ber`) adds 'bersRx_X', 'EVM_rmsRx_X' and 'gNMSE_X' per source (link_level).
+
+    delay=(L, pre) adds 'MSE_DLY': the LS planes projected onto the channels with taps at delays -pre .. L - pre - 1
+    (subspace.delay_basis, subspace_smooth_device without weights).  It is no source of the data phase.  Nothing else changes."""
     nr, nt = engine.nr, engine.nt
     d_tau = None
     if channel is None:
@@ -138,6 +144,12 @@ def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=Tr
         b_planes = (engine.empty(shape), engine.empty(shape))
         engine.lmmse_blind_device(d_re, d_im, ls_re, ls_im, npkt, b_planes[0], b_planes[1])
         estimates.append((BLIND, b_planes))
+    d_planes = ()
+    if delay is not None:
+        d_planes = (engine.empty(shape), engine.empty(shape))
+        engine.subspace_set_basis(subspace.delay_basis(delay[0], delay[1])[0])
+        engine.subspace_smooth_device(ls_re, ls_im, npkt, d_planes[0], d_planes[1])
+        estimates.append((DELAY, d_planes))
     for name, (e_re, e_im) in estimates:
         engine.nmse_device(h_re, h_im, e_re, e_im, npkt * nr * nt, N_DATA, d_per_link=d_link)
         out['MSE_' + name] = d_link.download().astype(np.float64).reshape(npkt, nr * nt).mean(axis=1)
@@ -149,7 +161,7 @@ def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=Tr
         out['MSE_perfect'] = np.zeros(npkt)
         d_std.free()
     kept = (d_re, d_im, h_re, h_im, ls_re, ls_im)
-    for a in (o_re, o_im, m_re, m_im, d_hvec, d_snr, d_link) + b_planes + (() if keep else kept):
+    for a in (o_re, o_im, m_re, m_im, d_hvec, d_snr, d_link) + b_planes + d_planes + (() if keep else kept):
         a.free()
     if keep:
         out['arrays'] = kept
@@ -232,6 +244,8 @@ def metric_fields(mse):
         fields += ['MSE_' + BLIND] + ([f + BLIND for f in LINK_FIELDS] if 'bers_' + BLIND in mse else [])
     if RX_FIELDS[0] + 'perfect' in mse:
         fields += [f + x for x in SOURCES + ((BLIND,) if RX_FIELDS[0] + BLIND in mse else ()) for f in RX_FIELDS]
+    if 'MSE_' + DELAY in mse:
+        fields += ['MSE_' + DELAY]
     return fields
 
 
@@ -240,7 +254,8 @@ def write_metrics(path, mse):
     snr_loop_testing.m:37-58 loads.  A level evaluated with the data phase (evaluate_level(ber=...)) also carries bers_X, EVM_rms_X
     and dtSNR_X for X in SOURCES - with the MSE rows the names of :653 - and MSE_perfect (zeros), which are then written the same way.
     A level evaluated with blind=True carries MSE_MMSEb (and with the data phase bers_MMSEb, EVM_rms_MMSEb, dtSNR_MMSEb): written behind
-    those.  A level evaluated with rx_estimate=True carries bersRx_X, EVM_rmsRx_X and gNMSE_X: written last (metric_fields)."""
+    those.  A level evaluated with rx_estimate=True carries bersRx_X, EVM_rmsRx_X and gNMSE_X: written behind those, and MSE_DLY of a level evaluated
+    with delay=(L, pre) last (metric_fields)."""
     from scipy.io import savemat
     os.makedirs(os.path.dirname(path), exist_ok=True)
     savemat(path, {f: np.asarray(mse[f], np.float64).reshape(1, -1) for f in metric_fields(mse)})
@@ -249,7 +264,7 @@ def write_metrics(path, mse):
 
 def format_table(result):
     blind = [BLIND] if result.get('blind') else []
-    cols = list(ESTIMATORS) + blind + (['BER_' + x for x in list(SOURCES) + blind] if result.get('ber') else [])
+    cols = list(ESTIMATORS) + blind + ([DELAY] if result.get('delay') else []) + (['BER_' + x for x in list(SOURCES) + blind] if result.get('ber') else [])
     cols += [RX_FIELDS[0] + x for x in list(SOURCES) + blind] if result.get('rx_estimate') else []
     lines = ['%8s' % 'SNR dB' + ''.join('  %-38s' % (e + ': mean [CI low, CI high]') for e in cols)]
     for lv in result['levels']:
@@ -264,7 +279,8 @@ def format_table(result):
 
 
 def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500, seed=0, modeldir=None, fit_args=None, n_taps=8,
-              amp_scale=True, save_dataset=None, verbose=True, ber=None, channel=None, blind=False, rx_estimate=False):
+              amp_scale=True, save_dataset=None, verbose=True, ber=None, channel=None, blind=False, rx_estimate=False,
+              delay_taps=None, delay_pre=0):
     """Training set -> models (loaded from `modeldir`, else fitted and saved into `out`) -> every level.  Writes
     <out>/BS<Nt>_SNR<s>/metrics.mat per level and <out>/sweep.json, prints the table, returns the result dict (with the per-packet
     arrays under 'per_packet' = {level: {'MSE_LS', ...}}).  Test packets come from the stream seed + 1, behind the index range of
@@ -275,7 +291,10 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
     entry per level of sweep.json, which then records 'blind': true; with `ber` also the source MMSEb.  Without it every output is
     what it is without the argument.  rx_estimate=True (needs `ber`) adds the receiver that estimates the effective channel
     (link_level): bersRx_X, EVM_rmsRx_X and gNMSE_X in metrics.mat and, with the same confidence interval, as the last entries per level of
-    sweep.json, which then records 'rx_estimate': true; every other field is what it is without the argument."""
+    sweep.json, which then records 'rx_estimate': true; every other field is what it is without the argument.
+    delay_taps=L (with delay_pre=P) adds the estimator DLY per level (evaluate_level(delay=(L, P))): MSE_DLY in metrics.mat, a column of
+    the table and an entry per level of sweep.json, which then records 'delay': {taps, pre, rank}; without it every output is what it
+    is without the argument."""
     if rx_estimate and ber is None:
         raise ValueError('rx_estimate needs the data phase (ber)')
     os.makedirs(out, exist_ok=True)
@@ -289,6 +308,10 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
         result['blind'] = True
     if rx_estimate:
         result['rx_estimate'] = True
+    delay = None
+    if delay_taps:
+        delay = (int(delay_taps), int(delay_pre))
+        result['delay'] = dict(taps=delay[0], pre=delay[1], rank=int(subspace.delay_basis(*delay)[0].shape[1]))
     if modeldir:
         load_models(engine, modeldir)
         if save_dataset:
@@ -307,11 +330,11 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
     for i, snr in enumerate(levels):
         t0 = time.perf_counter()
         mse = evaluate_level(engine, snr, n_test, seed + 1, n_train + i * n_test, n_taps, amp_scale, ber=ber, channel=channel, blind=blind,
-                             rx_estimate=rx_estimate)
+                             rx_estimate=rx_estimate, delay=delay)
         sec = time.perf_counter() - t0
         write_metrics(os.path.join(out, 'BS%d_SNR%g' % (engine.nt, snr), 'metrics.mat'), mse)
         lv = dict(snr_db=float(snr), seconds=sec)
-        for e in ESTIMATORS + ((BLIND,) if blind else ()):
+        for e in ESTIMATORS + ((BLIND,) if blind else ()) + ((DELAY,) if delay else ()):
             m, lo, hi = confidence_interval(mse['MSE_' + e])
             lv[e] = dict(mean=m, ci_low=lo, ci_high=hi)
         for x in (SOURCES + ((BLIND,) if blind else ())) if ber is not None else ():
@@ -367,6 +390,9 @@ def build_parser():
     p.add_argument('--randomUsers', action='store_true', help='--channel scattering: draw the user position per packet (generate_maMIMO_LTF.m:48-51)')
     p.add_argument('--blind', action='store_true',
                    help='add the estimator MMSEb: LMMSE smoothing from the packet\'s own statistics (csi_lmmse_blind_device) - MSE_MMSEb, and with --ber its link metrics')
+    p.add_argument('--delayTaps', default=0, type=int, metavar='L',
+                   help='add the estimator DLY: the LS rows projected onto the channels of at most L delay taps (csi_subspace_smooth_device, 1 .. 128) - MSE_DLY')
+    p.add_argument('--delayPre', default=0, type=int, metavar='P', help='--delayTaps: taps of the window in front of delay 0 (0 .. L)')
     return p
 
 
@@ -383,6 +409,10 @@ def parse_args(argv=None):
     args = parser.parse_args(argv)
     if args.rxEstimate and not args.ber:
         parser.error('--rxEstimate needs --ber')
+    if args.delayTaps and not (1 <= args.delayTaps <= subspace.MAX_RANK and 0 <= args.delayPre <= args.delayTaps):
+        parser.error('--delayTaps takes 1 .. %d and --delayPre 0 .. L' % subspace.MAX_RANK)
+    if args.delayPre and not args.delayTaps:
+        parser.error('--delayPre needs --delayTaps')
     return args
 
 
@@ -400,7 +430,7 @@ def main(argv=None):
     run_sweep(eng, args.workdir, levels=args.snr, n_train=args.trainPkts, n_test=args.testPkts, seed=args.seed,
               modeldir=args.modeldir or None, fit_args=fit_args, n_taps=args.taps, save_dataset=args.save_dataset or None,
               verbose=not args.quiet, ber=ber, channel=channel_from_args(args), blind=bool(args.blind),
-              rx_estimate=bool(args.rxEstimate))
+              rx_estimate=bool(args.rxEstimate), delay_taps=args.delayTaps or None, delay_pre=args.delayPre)
     return 0
 
 

@@ -22,6 +22,8 @@
  *   LMMSE_ce per link   helperMIMOChannelEstimate.m:37-39, LMMSE_ce.m  csi_lmmse_estimate[_device]
  *   the same call site, helperMIMOChannelEstimate.m:37-39, for a receiver that has
  *        neither the impulse response nor the SNR                   csi_lmmse_blind[_device]
+ *   (an addition, no reference counterpart: the delay-subspace
+ *        smoother of an LS estimate, same place in the chain)       csi_subspace_set_basis, csi_subspace_smooth[_device]
  *   NMSE_subk           BER_test_maMIMO_LTF.m:675-686                csi_nmse[_device]
  *   known-channel sounding packets  generate_maMIMO_LTF.m:197-342   csi_synth_structured
  *   phased.ScatteringMIMOChannel    helperApplyMUChannel.m:44-143   csi_synth_scattering
@@ -37,7 +39,7 @@
  * has pinned (hipHostMalloc / hipHostRegister).  *_device entry points take device pointers, enqueue on the
  * context's stream and return without waiting; call csi_synchronize before reading results.
  *
- * Device pointers (csi_predict_device, csi_ls_estimate_device, csi_estimate_device, csi_lmmse_estimate_device, csi_lmmse_blind_device, csi_nmse_device,
+ * Device pointers (csi_predict_device, csi_ls_estimate_device, csi_estimate_device, csi_lmmse_estimate_device, csi_lmmse_blind_device, csi_subspace_smooth_device, csi_nmse_device,
  * csi_hybrid_weights_device, csi_link_sim_device, csi_link_sim_rx_device, csi_viterbi_decode_device, csi_synth_*).  An array of exactly the documented
  * size suffices: it may be a slice of a larger allocation whose neighbours hold live data of any value (NaN and 1e38 included).
  * Nothing outside the arrays is written, nothing outside them reaches a result, and input arrays are not modified.  Every re / im
@@ -45,7 +47,7 @@
  * boundary: the LS and layer-0 kernels move the caller's rows as 16-byte words and by LDS-DMA; hipMalloc, csi_device_malloc and
  * whole torch tensors satisfy that, and so does every packet range of a preamble or CSI plane (Nt is a multiple of 4).  A
  * misaligned plane is refused with CSI_ERR_INVALID_ARG and a text that names the argument, before anything is launched or counted.
- * The remaining arrays - hvec, snr_db, noise_var, noise_std, tau, the per-packet and per-link results, idx, n_atoms, gain, csi,
+ * The remaining arrays - hvec, snr_db, the weights w of csi_subspace_smooth_device, noise_var, noise_std, tau, the per-packet and per-link results, idx, n_atoms, gain, csi,
  * llr, bits - and the four planes of csi_nmse_device ([nlinks][n_bins] for ANY n_bins) are read and written element by element and
  * need the alignment of their element type only.
  *
@@ -245,6 +247,38 @@ int  csi_lmmse_blind(csi_ctx* ctx, const float* ltf_re, const float* ltf_im, con
                      float* out_re, float* out_im, double* noise_var, double* corr);
 int  csi_lmmse_blind_device(csi_ctx* ctx, const float* d_ltf_re, const float* d_ltf_im, const float* d_h_re, const float* d_h_im,
                             int64_t npkt, float* d_out_re, float* d_out_im, double* d_noise_var, double* d_corr);
+
+/* Delay-subspace smoother of a CSI tensor (csrc/subspace_smooth.hip.h, csrc/csi_subspace.hpp).  An addition: the
+ * reference has no such estimator.  It stands where LMMSE_ce stands (helperMIMOChannelEstimate.m:37-39) and needs no SNR, no
+ * power-delay profile and no training: fit the LS row with a channel of at most L delay taps and evaluate the fit on the data carriers.
+ *   carriers   ind = the 234 data carriers in 1-based shifted bins as generate_maMIMO_LTF.m:72-78 has them: 1 .. 256 without the nulls
+ *              [1:7 129 251:256] and the pilots [26 54 90 118 140 168 204 232]; f_k = ind_k - 129, in -128 .. 127.
+ *   basis      for a window (L, pre), 1 <= L <= 128, 0 <= pre <= L:  F[k][l] = exp(-2 pi i f_k (l - pre) / 256), l < L;  thin SVD
+ *              F = U S V^H in fp64;  r = number of s_j > 1e-10 s_0;  Q = U[:, :r];  lam_j = s_j^2 / L  (subspace.delay_basis of the
+ *              Python package).  The sign is that of the generators: H[b] = sum_l c_l exp(-2 pi i b l / 256).
+ *   smoother   for every row x of 234 values of the [npkt][Nr][Nt][234] planes:
+ *                  t_j = sum_k conj(Q[k][j]) x_k,   y_k = sum_j Q[k][j] w[p][rx][j] t_j
+ *              w float32 [npkt][Nr][r]; NULL means all ones (the projection onto the window).  With
+ *              w_j = lam_j / (lam_j + nu)  (subspace.robust_weights) the map is R (R + nu I)^-1 for R = F F^H / L written in its
+ *              eigenbasis Q: the robust LMMSE smoother for a uniform delay profile.
+ * csi_subspace_set_basis: host planes q_re / q_im [234][rank], rank 1 .. 128, kept on the context as device copies; a second call
+ * replaces them (it waits for the stream; graphs captured with the earlier basis must be captured again).  Refused with text: rank
+ * outside 1 .. 128, null planes, a non-finite entry, a Q^H Q further than 1e-4 from the identity in any entry, an open capture.
+ * ANY orthonormal Q is accepted; the delay window is what the Python package builds.
+ * csi_subspace_smooth_device: d_h_re / d_h_im [npkt][Nr][Nt][234], d_out like d_h, d_w [npkt][Nr][rank] or NULL.  One kernel launch on
+ * the context's stream, asynchronous, no workspace, usable inside csi_capture_begin / _end.  Exact fp32 products with fp32
+ * accumulation (v_mfma_f32_32x32x2_f32) in a fixed order: a packet's bits do not depend on the call, the chunk or its position in
+ * the batch.  out may be the input planes themselves, re with re and im with im; any other overlap of an output plane with an
+ * input plane or with the other output plane is refused.
+ * csi_subspace_smooth: host buffers, in the packet chunks of csi_lmmse_estimate (256 MiB of staging; the context's workspace_bytes
+ * when that is smaller), w [npkt][Nr][rank] or NULL; same bits as the device entry point.
+ * Refused with text, before anything is launched or counted: no basis set (CSI_ERR_NOT_READY), npkt < 0, null h / out pointers,
+ * planes off a 16-byte boundary, overlapping planes, a single-input context.  npkt == 0 returns 0 and launches nothing.  A null
+ * context returns -1.  Read-only option "subspace_launches"; profile entry "subspace_smooth" (16 * rows * 234 * rank flop). */
+int  csi_subspace_set_basis(csi_ctx* ctx, const float* q_re, const float* q_im, int rank);
+int  csi_subspace_smooth(csi_ctx* ctx, const float* h_re, const float* h_im, int64_t npkt, const float* w, float* out_re, float* out_im);
+int  csi_subspace_smooth_device(csi_ctx* ctx, const float* d_h_re, const float* d_h_im, int64_t npkt, const float* d_w,
+                                float* d_out_re, float* d_out_im);
 
 /* Hybrid beamforming weights from a CSI tensor (BER_test_maMIMO_LTF.m:347-376, generate_maMIMO_LTF.m:414-425: the toolbox's
  * SVD + orthogonal-matching-pursuit split of the optimal precoder into an analog and a digital part).  One item = one
@@ -519,7 +553,7 @@ int  csi_set_option(csi_ctx* ctx, const char* name, int64_t value);
 /* Current value of an option, or of the read-only values: "hs_launches" (split-engine GEMMs launched), "hs_range_fallbacks"
  * (csi_predict calls repeated on the fp32 MFMA kernels), "hs_weight_pins" / "hs_weight_err_e12" (layers pinned to the fp32 kernels
  * at load because their split copies were not fp32-grade; worst relative error x 1e12), "band_available" (the assembly band kernel
- * is embedded in this build), "graph_replays", "lmmse_blind_fallbacks" ((packet, rx) pairs csi_lmmse_blind[_device] handed back unsmoothed), "ls_pilot_fast" (0 generic / 1 Sylvester / 2 permuted pilot), "comm_world",
+ * is embedded in this build), "graph_replays", "subspace_launches" (kernels launched by csi_subspace_smooth[_device]), "lmmse_blind_fallbacks" ((packet, rx) pairs csi_lmmse_blind[_device] handed back unsmoothed), "ls_pilot_fast" (0 generic / 1 Sylvester / 2 permuted pilot), "comm_world",
  * "comm_rank", "comm_blobs", "comm_bytes" (communicator and last broadcast), "hp_direct_out_calls", and where the last pipelined
  * host-buffer call spent its time in microseconds: "hp_total_us", "hp_stage_us", "hp_wait_stage_us", "hp_wait_out_us", "hp_weave_us". */
 int  csi_get_option(csi_ctx* ctx, const char* name, int64_t* value);
