@@ -23,6 +23,7 @@
 #include "csi_link.hpp"
 #include "csi_scatter.hpp"
 #include "csi_subspace.hpp"
+#include "csi_mu.hpp"
 #include <initializer_list>
 
 namespace {
@@ -1124,6 +1125,22 @@ int csi_link_sim_rx_device(csi_ctx* c, const float* d_h_re, const float* d_h_im,
                         d_bit_errors, d_evm_rms, d_dt_snr_db, d_xeq_re, d_xeq_im, d_csi, d_llr, d_bits, d_g_nmse, d_gest_re, d_gest_im);
 }
 
+// ---------------------------------------------------------------- multi-user downlink (csi_mu.hpp, mu_link.hip.h)
+int csi_mu_precoder_device(csi_ctx* c, int n_users, const float* const* d_hest_re, const float* const* d_hest_im, int64_t npkt, int ns,
+                           const float* d_reg, float* d_w_re, float* d_w_im) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return mu_precoder_device(c, n_users, d_hest_re, d_hest_im, npkt, ns, d_reg, d_w_re, d_w_im);
+}
+
+int csi_mu_link_sim_device(csi_ctx* c, int n_users, const float* const* d_h_re, const float* const* d_h_im, const float* d_w_re, const float* d_w_im,
+                           const float* d_noise_var, uint64_t seed, int64_t first_pkt, int64_t npkt, int ns, int n_sym, int bps,
+                           int32_t* d_bit_errors, float* d_evm_rms, float* d_sinr_db, float* d_g_re, float* d_g_im, float* d_xeq_re,
+                           float* d_xeq_im, float* d_csi, float* d_llr, uint8_t* d_bits) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return mu_link_sim_device(c, n_users, d_h_re, d_h_im, d_w_re, d_w_im, d_noise_var, seed, first_pkt, npkt, ns, n_sym, bps, d_bit_errors,
+                              d_evm_rms, d_sinr_db, d_g_re, d_g_im, d_xeq_re, d_xeq_im, d_csi, d_llr, d_bits);
+}
+
 // ---------------------------------------------------------------- accuracy metric
 int csi_nmse_device(csi_ctx* c, const float* d_ref_re, const float* d_ref_im, const float* d_est_re, const float* d_est_im,
                     int64_t nlinks, int n_bins, float* d_per_link, double* mean_out) {
@@ -1199,6 +1216,7 @@ int csi_get_option(csi_ctx* c, const char* name, int64_t* value) {
     else if (n == "hybrid_launches") *value = c->hybrid_launches;
     else if (n == "link_launches") *value = c->link_launches;
     else if (n == "subspace_launches") *value = c->subspace_launches;
+    else if (n == "mu_launches") *value = c->mu_launches;
     else if (n == "lmmse_blind_fallbacks") {
         // counted on the device behind every launch (lmmse_blind_count_kernel): reading it waits for the stream
         if (c->user_capture) return fail(c, CSI_ERR_INVALID_ARG, "csi_get_option: lmmse_blind_fallbacks cannot be read while a capture is open");

@@ -68,6 +68,7 @@ class DeviceArray:
 HybridWeights = collections.namedtuple('HybridWeights', 'fbb idx n_atoms gain frf_mean')
 LinkResult = collections.namedtuple('LinkResult', 'bit_errors evm_rms dt_snr_db n_info xeq csi llr bits')
 LinkRxResult = collections.namedtuple('LinkRxResult', LinkResult._fields + ('g_nmse', 'gest'))
+MuLinkResult = collections.namedtuple('MuLinkResult', 'bit_errors evm_rms sinr_db n_info g xeq csi llr bits')
 
 
 def frf_from_idx(At, idx):
@@ -774,6 +775,91 @@ class CsiEngine:
         """link_sim with the estimating receiver (link_sim_rx_device).  Returns LinkRxResult: the fields of LinkResult, then g_nmse
         float32 [npkt] and, with details=True, gest complex64 [npkt,234,nr,ns] (None otherwise)."""
         return self._link_sim_host(True, h, fbb, frf_mean, noise_var, seed, first_pkt, n_sym, bps, details)
+
+    # ------------------------------------------------------------------ multi-user downlink (csrc/mu_link.hip.h, DESIGN.md 4.20)
+    @staticmethod
+    def _ptr_array(arrays):
+        """host array of device pointers, as the csi_mu_* entry points read it"""
+        return (ctypes.c_void_p * len(arrays))(*[a.ptr if a is not None else None for a in arrays])
+
+    def mu_precoder_device(self, d_hest_re, d_hest_im, npkt, ns, d_w_re, d_w_im, d_reg=None):
+        """(Regularised) zero-forcing precoder of len(d_hest_re) users from their estimated CSI planes ([npkt,nr,nt,234] each, lists of
+        DeviceArrays) for ns streams per user: d_w_re / d_w_im [npkt, U ns, nt, 234] (csi_mu_precoder_device).  d_reg [npkt] or None
+        (zero forcing).  Asynchronous, on the engine's stream."""
+        self._check(self._lib.csi_mu_precoder_device(self._ctx, len(d_hest_re), self._ptr_array(d_hest_re), self._ptr_array(d_hest_im), int(npkt),
+                                                     int(ns), d_reg.ptr if d_reg is not None else None, d_w_re.ptr, d_w_im.ptr))
+
+    def mu_precoder(self, h_list, ns, reg=None):
+        """The same from numpy arrays: h_list = U complex arrays [npkt,nr,nt,234]; reg None, a scalar or [npkt].  Returns W complex64
+        [npkt, U ns, nt, 234]."""
+        h_list = [np.asarray(h) for h in h_list]
+        npkt = h_list[0].shape[0] if h_list and h_list[0].ndim else 0
+        for h in h_list:
+            if h.shape != (npkt, self.nr, self.nt, N_DATA):
+                raise CsiError(-1, f'every h must be [{npkt},{self.nr},{self.nt},{N_DATA}], got {h.shape}')
+        m = len(h_list) * max(int(ns), 0)
+        dev = [self.to_device(_f32c(h.real)) for h in h_list] + [self.to_device(_f32c(h.imag)) for h in h_list]
+        d_reg = None if reg is None else self.to_device(np.ascontiguousarray(np.broadcast_to(np.asarray(reg, np.float32), (npkt,))))
+        w = [self.empty((npkt, m, self.nt, N_DATA)) for _ in range(2)]
+        try:
+            self.mu_precoder_device(dev[:len(h_list)], dev[len(h_list):], npkt, ns, w[0], w[1], d_reg)
+            self.synchronize()
+            return (w[0].download() + 1j * w[1].download()).astype(np.complex64)
+        finally:
+            for a in dev + w + [d_reg]:
+                if a is not None:
+                    a.free()
+
+    def mu_link_sim_device(self, d_h_re, d_h_im, d_w_re, d_w_im, d_noise_var, seed, first_pkt, npkt, ns, d_bit_errors, d_evm_rms, d_sinr_db,
+                           n_sym=10, bps=2, d_g_re=None, d_g_im=None, d_xeq_re=None, d_xeq_im=None, d_csi=None, d_llr=None, d_bits=None):
+        """Coded QAM for len(d_h_re) users through their TRUE planes (lists of DeviceArrays [npkt,nr,nt,234]) with the precoder planes d_w
+        ([npkt, U ns, nt, 234]) and noise of variance d_noise_var[u][p] (csi_mu_link_sim_device).  Results are [U, npkt]; d_bit_errors holds
+        int32, d_bits U npkt n_info bytes.  Asynchronous, on the engine's stream; the optional arrays may be None."""
+        ptr = lambda a: None if a is None else a.ptr
+        self._check(self._lib.csi_mu_link_sim_device(self._ctx, len(d_h_re), self._ptr_array(d_h_re), self._ptr_array(d_h_im), d_w_re.ptr, d_w_im.ptr,
+                                                     d_noise_var.ptr, int(seed), int(first_pkt), int(npkt), int(ns), int(n_sym), int(bps),
+                                                     d_bit_errors.ptr, d_evm_rms.ptr, d_sinr_db.ptr, ptr(d_g_re), ptr(d_g_im), ptr(d_xeq_re),
+                                                     ptr(d_xeq_im), ptr(d_csi), ptr(d_llr), ptr(d_bits)))
+
+    def mu_link_sim(self, h_list, W, noise_var, seed=0, first_pkt=0, ns=1, n_sym=10, bps=2, details=False):
+        """The same from numpy arrays: h_list = U complex arrays [npkt,nr,nt,234] (the true channels), W complex [npkt, U ns, nt, 234],
+        noise_var a scalar, [U] or [U, npkt].  Returns MuLinkResult(bit_errors int32, evm_rms, sinr_db float32 [U, npkt], n_info, ...); with
+        details=True also g complex64 [U,npkt,ns,M,234], xeq [U,npkt,ns,n_sym,234], csi [U,npkt,ns,234], llr [U,npkt,n_coded] and the decoded
+        bits uint8 [U,npkt,n_info] (None otherwise)."""
+        h_list, W = [np.asarray(h) for h in h_list], np.asarray(W)
+        nu = len(h_list)
+        npkt = W.shape[0] if W.ndim else 0
+        m = nu * int(ns)
+        for h in h_list:
+            if h.shape != (npkt, self.nr, self.nt, N_DATA):
+                raise CsiError(-1, f'every h must be [{npkt},{self.nr},{self.nt},{N_DATA}], got {h.shape}')
+        if W.shape != (npkt, m, self.nt, N_DATA):
+            raise CsiError(-1, f'W must be [{npkt},{m},{self.nt},{N_DATA}], got {W.shape}')
+        nv = np.asarray(noise_var, np.float32)
+        nv = np.ascontiguousarray(np.broadcast_to(nv[:, None] if nv.ndim == 1 else nv, (nu, npkt)))
+        n_info, n_coded = self.link_frame_bits(ns, n_sym, bps)
+        dev = [self.to_device(_f32c(h.real)) for h in h_list] + [self.to_device(_f32c(h.imag)) for h in h_list]
+        dev += [self.to_device(_f32c(W.real)), self.to_device(_f32c(W.imag)), self.to_device(nv)]
+        outs = [self.empty((nu, npkt)) for _ in range(3)]
+        extra = [None] * 7
+        if details:
+            extra = [self.empty((nu, npkt, ns, m, N_DATA)), self.empty((nu, npkt, ns, m, N_DATA)), self.empty((nu, npkt, ns, n_sym, N_DATA)),
+                     self.empty((nu, npkt, ns, n_sym, N_DATA)), self.empty((nu, npkt, ns, N_DATA)), self.empty((nu, npkt, n_coded)),
+                     self.empty(((nu * npkt * n_info + 3) // 4,))]
+        try:
+            self.mu_link_sim_device(dev[:nu], dev[nu:2 * nu], dev[2 * nu], dev[2 * nu + 1], dev[2 * nu + 2], seed, first_pkt, npkt, ns, *outs,
+                                    n_sym=n_sym, bps=bps, d_g_re=extra[0], d_g_im=extra[1], d_xeq_re=extra[2], d_xeq_im=extra[3], d_csi=extra[4],
+                                    d_llr=extra[5], d_bits=extra[6])
+            self.synchronize()
+            c64 = lambda re, im: (re.download() + 1j * im.download()).astype(np.complex64)
+            return MuLinkResult(outs[0].download().view(np.int32), outs[1].download(), outs[2].download(), n_info,
+                                c64(extra[0], extra[1]) if details else None, c64(extra[2], extra[3]) if details else None,
+                                extra[4].download() if details else None, extra[5].download() if details else None,
+                                extra[6].download().view(np.uint8)[:nu * npkt * n_info].reshape(nu, npkt, n_info).copy() if details else None)
+        finally:
+            for a in dev + outs + extra:
+                if a is not None:
+                    a.free()
 
     def viterbi_decode(self, llr):
         """Viterbi decoding of terminated codewords of the rate-1/3 K = 7 code (133, 171, 165): llr float [ncw, 3 n_steps], positive = 0

@@ -4,12 +4,15 @@ true channel with 95 % confidence intervals - the "MSE" curve of snr_loop_testin
 BER_test_maMIMO_LTF.m:408-646 follows per level: the hybrid weights of every estimate (and of the true channel, "perfect") precode
 coded QAM through the true channel, giving the bers_ / EVM_rms_ / dtSNR_ families of metrics.mat.  There the receiver
 knows the effective channel; --rxEstimate runs every source a second time with the receiver of the reference, which estimates it from
-a precoded preamble (csi_link_sim_rx_device), and adds the bersRx_ / EVM_rmsRx_ / gNMSE_ families.
+a precoded preamble (csi_link_sim_rx_device), and adds the bersRx_ / EVM_rmsRx_ / gNMSE_ families.  --users U (U >= 2) serves U users at
+once on the same subcarriers: per source the zero-forcing precoder of the U users' estimates (csi_mu_precoder_device) and
+the data phase through their true channels (csi_mu_link_sim_device) add the bersMU_ / EVM_rmsMU_ / sinrMU_ families, the mean over the users.
 
     python -m dl_channel_estimation_mamimo_amd.sweep -d OUT [--nTX 32 --nRX 4 --nn 1024 1024 --useBN --bs 256 ...]
                                                             [--ber --numSTS 1 --rays 500 --dataSymbols 10 --bps 2 [--rxEstimate]]
                                                             [--channel scattering --scatterers 100 --range 100 --userAz 30 --userEl 0 --randomUsers]
                                                             [--blind] [--delayTaps L [--delayPre P]]
+                                                            [--ber --users U [--muReg zf|rzf] [--userSpacing DEG]]
 
 The module holds no arithmetic of its own: packets with a known channel come from csi_synth_structured (--channel scattering: from
 csi_synth_scattering, whose path delays then feed the LMMSE smoother as the reference's h_tau does), labels from
@@ -37,6 +40,7 @@ ESTIMATORS = ('LS', 'MMSE', 'DNN')
 SOURCES = ESTIMATORS + ('perfect',)      # --ber: whose hybrid weights precode the data phase (perfect = the true channel)
 LINK_FIELDS = ('bers_', 'EVM_rms_', 'dtSNR_')
 RX_FIELDS = ('bersRx_', 'EVM_rmsRx_', 'gNMSE_')     # --rxEstimate: the same data phase equalised with the preamble's estimate of H W
+MU_FIELDS = ('bersMU_', 'EVM_rmsMU_', 'sinrMU_')    # --users: the multi-user data phase, the mean over the users per packet
 DELAY = 'DLY'                            # --delayTaps: the LS rows projected onto a window of delay taps (csi_subspace_smooth_device, w = 1)
 BLIND = 'MMSEb'                          # --blind: the LMMSE smoother on the packet's own statistics (csi_lmmse_blind_device)
 
@@ -95,7 +99,7 @@ def make_dataset(engine, n_train, seed, n_taps=8, amp_scale=True, channel=None):
 
 
 def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=True, keep=False, ber=None, channel=None, blind=False,
-                   rx_estimate=False, delay=None):
+                   rx_estimate=False, delay=None, mu=None):
     """npkt test packets at `snr_db` (packets first_pkt ... of stream `seed`: keep them disjoint from the training packets), LS + DNN
     (estimate_device), the LMMSE smoother on the LS planes, and NMSE_subk of the three estimates against the true channel.
     Returns {'MSE_LS', 'MSE_MMSE', 'MSE_DNN'}: float64 [npkt], the per-link ratios averaged per packet.
@@ -116,7 +120,12 @@ def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=Tr
     rx_estimate=True (with `ber`) adds 'bersRx_X', 'EVM_rmsRx_X' and 'gNMSE_X' per source (link_level).
 
     delay=(L, pre) adds 'MSE_DLY': the LS planes projected onto the channels with taps at delays -pre .. L - pre - 1
-    (subspace.delay_basis, subspace_smooth_device without weights).  It is no source of the data phase.  Nothing else changes."""
+    (subspace.delay_basis, subspace_smooth_device without weights).  It is no source of the data phase.  Nothing else changes.
+
+    mu = dict(users=U, reg='zf' | 'rzf', spacing=degrees) (with `ber`, U >= 2) adds the multi-user data phase (mu_level): user 0 is the
+    user above; user u >= 1 takes its packets from the stream seed + u (scattering channel: at azimuth az_deg + u spacing) and its
+    estimates from the same calls.  Adds 'bersMU_X', 'EVM_rmsMU_X', 'sinrMU_X' float64 [npkt] (the mean over the users) for every source
+    X - here DLY is one too - and 'mu_users' = {X: {'bers', 'EVM_rms', 'sinr': [U][npkt]}}.  Nothing else changes."""
     nr, nt = engine.nr, engine.nt
     d_tau = None
     if channel is None:
@@ -159,12 +168,94 @@ def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=Tr
             planes[BLIND] = b_planes
         out.update(link_level(engine, planes, h_re, h_im, d_std, npkt, seed, first_pkt, amp_scale=amp_scale, rx_estimate=rx_estimate, **ber))
         out['MSE_perfect'] = np.zeros(npkt)
+        if mu:
+            if delay is not None:
+                planes[DELAY] = d_planes
+            others = [user_planes(engine, snr_db, npkt, seed + u, first_pkt, n_taps, amp_scale, channel, blind, delay, u * float(mu.get('spacing', 15.0)))
+                      for u in range(1, int(mu['users']))]
+            nv = np.stack([synth.link_noise_var(d.download(), amp_scale) for d in [d_std] + [o['noise_std'] for o in others]])
+            out.update(mu_level(engine, [planes] + [o['planes'] for o in others], nv, npkt, seed, first_pkt, ns=ber['ns'], n_sym=ber['n_sym'],
+                                bps=ber['bps'], reg=mu.get('reg', 'zf')))
+            for o in others:
+                for a in o['free']:
+                    a.free()
         d_std.free()
     kept = (d_re, d_im, h_re, h_im, ls_re, ls_im)
     for a in (o_re, o_im, m_re, m_im, d_hvec, d_snr, d_link) + b_planes + d_planes + (() if keep else kept):
         a.free()
     if keep:
         out['arrays'] = kept
+    return out
+
+
+def user_planes(engine, snr_db, npkt, seed, first_pkt, n_taps, amp_scale, channel, blind, delay, az_offset):
+    """Test packets of one further user of the multi-user data phase and its estimates, from the calls evaluate_level makes for its own
+    user: {'planes': {X: (re, im)} for LS, MMSE, DNN, perfect (+ MMSEb, DLY), 'noise_std', 'free': every DeviceArray to free}.  The
+    scattering channel places the user az_offset degrees from the channel's az_deg."""
+    nr, nt = engine.nr, engine.nt
+    d_tau = None
+    if channel is None:
+        d_re, d_im, h_re, h_im, d_std = engine.synth_structured(seed, first_pkt, npkt, snr_db=float(snr_db), n_taps=n_taps, amp_scale=amp_scale,
+                                                                want_noise_std=True)
+    else:
+        ch = scattering_args(channel)
+        ch['az_deg'] = ch['az_deg'] + az_offset
+        d_re, d_im, h_re, h_im, d_std, d_tau = engine.synth_scattering(seed, first_pkt, npkt, snr_db=float(snr_db), amp_scale=amp_scale,
+                                                                       want_noise_std=True, want_tau=True, **ch)
+    shape = (npkt, nr, nt, N_DATA)
+    o_re, o_im, ls_re, ls_im, m_re, m_im = (engine.empty(shape) for _ in range(6))
+    engine.estimate_device(d_re, d_im, npkt, o_re, o_im, ls_re, ls_im, checked=True)
+    if d_tau is None:
+        prof = tap_profile(n_taps)
+        d_hvec, L = engine.to_device(np.tile(prof, (npkt, 1))), prof.size
+    else:
+        d_hvec, L = d_tau, scattering_args(channel)['n_scat']
+    d_snr = engine.to_device(np.full((npkt, nr), float(snr_db), np.float32))
+    engine.lmmse_estimate_device(ls_re, ls_im, npkt, d_hvec, L, d_snr, m_re, m_im)
+    planes = dict(LS=(ls_re, ls_im), MMSE=(m_re, m_im), DNN=(o_re, o_im), perfect=(h_re, h_im))
+    free = [d_re, d_im, h_re, h_im, d_std, o_re, o_im, ls_re, ls_im, m_re, m_im, d_hvec, d_snr]
+    if blind:
+        planes[BLIND] = (engine.empty(shape), engine.empty(shape))
+        engine.lmmse_blind_device(d_re, d_im, ls_re, ls_im, npkt, *planes[BLIND])
+        free += list(planes[BLIND])
+    if delay is not None:
+        planes[DELAY] = (engine.empty(shape), engine.empty(shape))
+        engine.subspace_set_basis(subspace.delay_basis(delay[0], delay[1])[0])
+        engine.subspace_smooth_device(ls_re, ls_im, npkt, *planes[DELAY])
+        free += list(planes[DELAY])
+    return dict(planes=planes, noise_std=d_std, free=free)
+
+
+def mu_level(engine, planes, noise_var, npkt, seed, first_pkt, ns=1, n_sym=10, bps=2, reg='zf'):
+    """The multi-user data phase of one level on resident planes.  planes = one dict {X: (re, im)} per user, with the
+    true channel under 'perfect'; noise_var float32 [U, npkt].  For every source X the precoder of the U users' X planes
+    (mu_precoder_device; reg 'zf': none, 'rzf': M noise_var / Nt with the users' mean noise_var of the packet) carries coded QAM through
+    the U TRUE channels (mu_link_sim_device) - the same bits and the same noise for every source.  Returns {'bersMU_X', 'EVM_rmsMU_X',
+    'sinrMU_X'}: float64 [npkt], the mean over the users (of the dB values for sinr), and 'mu_users': {X: {'bers', 'EVM_rms', 'sinr'}}
+    with the [U][npkt] values as lists."""
+    nu, nt = len(planes), engine.nt
+    m = nu * int(ns)
+    if reg not in ('zf', 'rzf'):
+        raise ValueError("reg must be 'zf' or 'rzf', got %r" % (reg,))
+    n_info, _ = engine.link_frame_bits(ns, n_sym, bps)
+    noise_var = np.ascontiguousarray(noise_var, np.float32).reshape(nu, npkt)
+    d_nv = engine.to_device(noise_var)
+    d_reg = engine.to_device((m * noise_var.astype(np.float64).mean(0) / nt).astype(np.float32)) if reg == 'rzf' else None
+    w = [engine.empty((npkt, m, nt, N_DATA)) for _ in range(2)]
+    d_err, d_evm, d_sinr = (engine.empty((nu, npkt)) for _ in range(3))
+    h_re, h_im = [p['perfect'][0] for p in planes], [p['perfect'][1] for p in planes]
+    out, users = {}, {}
+    for name in planes[0]:
+        engine.mu_precoder_device([p[name][0] for p in planes], [p[name][1] for p in planes], npkt, ns, w[0], w[1], d_reg)
+        engine.mu_link_sim_device(h_re, h_im, w[0], w[1], d_nv, seed, first_pkt, npkt, ns, d_err, d_evm, d_sinr, n_sym=n_sym, bps=bps)
+        per = dict(bers=d_err.download().view(np.int32).astype(np.float64) / n_info, EVM_rms=d_evm.download().astype(np.float64),
+                   sinr=d_sinr.download().astype(np.float64))
+        for f, k in zip(MU_FIELDS, ('bers', 'EVM_rms', 'sinr')):
+            out[f + name] = per[k].mean(axis=0)
+        users[name] = {k: v.tolist() for k, v in per.items()}
+    for a in w + [d_err, d_evm, d_sinr, d_nv] + ([d_reg] if d_reg is not None else []):
+        a.free()
+    out['mu_users'] = users
     return out
 
 
@@ -246,6 +337,8 @@ def metric_fields(mse):
         fields += [f + x for x in SOURCES + ((BLIND,) if RX_FIELDS[0] + BLIND in mse else ()) for f in RX_FIELDS]
     if 'MSE_' + DELAY in mse:
         fields += ['MSE_' + DELAY]
+    if MU_FIELDS[0] + 'perfect' in mse:
+        fields += [f + x for x in SOURCES + tuple(e for e in (BLIND, DELAY) if MU_FIELDS[0] + e in mse) for f in MU_FIELDS]
     return fields
 
 
@@ -255,7 +348,7 @@ def write_metrics(path, mse):
     and dtSNR_X for X in SOURCES - with the MSE rows the names of :653 - and MSE_perfect (zeros), which are then written the same way.
     A level evaluated with blind=True carries MSE_MMSEb (and with the data phase bers_MMSEb, EVM_rms_MMSEb, dtSNR_MMSEb): written behind
     those.  A level evaluated with rx_estimate=True carries bersRx_X, EVM_rmsRx_X and gNMSE_X: written behind those, and MSE_DLY of a level evaluated
-    with delay=(L, pre) last (metric_fields)."""
+    with delay=(L, pre) behind those; bersMU_X, EVM_rmsMU_X and sinrMU_X of a level evaluated with mu=... last (metric_fields)."""
     from scipy.io import savemat
     os.makedirs(os.path.dirname(path), exist_ok=True)
     savemat(path, {f: np.asarray(mse[f], np.float64).reshape(1, -1) for f in metric_fields(mse)})
@@ -266,6 +359,7 @@ def format_table(result):
     blind = [BLIND] if result.get('blind') else []
     cols = list(ESTIMATORS) + blind + ([DELAY] if result.get('delay') else []) + (['BER_' + x for x in list(SOURCES) + blind] if result.get('ber') else [])
     cols += [RX_FIELDS[0] + x for x in list(SOURCES) + blind] if result.get('rx_estimate') else []
+    cols += [MU_FIELDS[0] + x for x in list(SOURCES) + blind + ([DELAY] if result.get('delay') else [])] if result.get('mu') else []
     lines = ['%8s' % 'SNR dB' + ''.join('  %-38s' % (e + ': mean [CI low, CI high]') for e in cols)]
     for lv in result['levels']:
         row = '%8g' % lv['snr_db']
@@ -280,7 +374,7 @@ def format_table(result):
 
 def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500, seed=0, modeldir=None, fit_args=None, n_taps=8,
               amp_scale=True, save_dataset=None, verbose=True, ber=None, channel=None, blind=False, rx_estimate=False,
-              delay_taps=None, delay_pre=0):
+              delay_taps=None, delay_pre=0, users=None, mu_reg='zf', user_spacing=15.0):
     """Training set -> models (loaded from `modeldir`, else fitted and saved into `out`) -> every level.  Writes
     <out>/BS<Nt>_SNR<s>/metrics.mat per level and <out>/sweep.json, prints the table, returns the result dict (with the per-packet
     arrays under 'per_packet' = {level: {'MSE_LS', ...}}).  Test packets come from the stream seed + 1, behind the index range of
@@ -294,9 +388,20 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
     sweep.json, which then records 'rx_estimate': true; every other field is what it is without the argument.
     delay_taps=L (with delay_pre=P) adds the estimator DLY per level (evaluate_level(delay=(L, P))): MSE_DLY in metrics.mat, a column of
     the table and an entry per level of sweep.json, which then records 'delay': {taps, pre, rank}; without it every output is what it
-    is without the argument."""
+    is without the argument.
+    users=U (U >= 2, needs `ber`) adds the multi-user data phase per level (evaluate_level(mu=...), mu_reg 'zf' or 'rzf', user_spacing in
+    degrees): bersMU_X, EVM_rmsMU_X and sinrMU_X in metrics.mat behind every other field, the same with confidence intervals and the
+    per-user arrays ('mu_users') per level of sweep.json, which then records 'mu': {users, reg, spacing}; without it every output is
+    what it is without the argument."""
     if rx_estimate and ber is None:
         raise ValueError('rx_estimate needs the data phase (ber)')
+    mu = None
+    if users is not None and int(users) >= 2:
+        if ber is None:
+            raise ValueError('users needs the data phase (ber)')
+        if int(users) > 8 or int(users) * int(ber['ns']) > min(16, engine.nt):
+            raise ValueError('users x ns = %d x %d streams exceed min(16, Nt %d) (or users > 8)' % (int(users), int(ber['ns']), engine.nt))
+        mu = dict(users=int(users), reg=str(mu_reg), spacing=float(user_spacing))
     os.makedirs(out, exist_ok=True)
     result = dict(nt=engine.nt, nr=engine.nr, n_train=int(n_train), n_test=int(n_test), seed=int(seed), n_taps=int(n_taps),
                   amp_scale=bool(amp_scale), levels=[], training=None)
@@ -308,6 +413,8 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
         result['blind'] = True
     if rx_estimate:
         result['rx_estimate'] = True
+    if mu:
+        result['mu'] = dict(mu)
     delay = None
     if delay_taps:
         delay = (int(delay_taps), int(delay_pre))
@@ -330,7 +437,7 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
     for i, snr in enumerate(levels):
         t0 = time.perf_counter()
         mse = evaluate_level(engine, snr, n_test, seed + 1, n_train + i * n_test, n_taps, amp_scale, ber=ber, channel=channel, blind=blind,
-                             rx_estimate=rx_estimate, delay=delay)
+                             rx_estimate=rx_estimate, delay=delay, mu=mu)
         sec = time.perf_counter() - t0
         write_metrics(os.path.join(out, 'BS%d_SNR%g' % (engine.nt, snr), 'metrics.mat'), mse)
         lv = dict(snr_db=float(snr), seconds=sec)
@@ -344,6 +451,12 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
             for f in RX_FIELDS:
                 m, lo, hi = confidence_interval(mse[f + x])
                 lv[f + x] = dict(mean=m, ci_low=lo, ci_high=hi)
+        if mu:
+            for x in SOURCES + ((BLIND,) if blind else ()) + ((DELAY,) if delay else ()):
+                for f in MU_FIELDS:
+                    m, lo, hi = confidence_interval(mse[f + x])
+                    lv[f + x] = dict(mean=m, ci_low=lo, ci_high=hi)
+            lv['mu_users'] = mse['mu_users']
         result['levels'].append(lv)
         per_packet[float(snr)] = mse
     with open(os.path.join(out, 'sweep.json'), 'w') as f:
@@ -381,6 +494,11 @@ def build_parser():
     p.add_argument('--bps', default=2, type=int, help='--ber: bits per QAM symbol (2 or 4)')
     p.add_argument('--rxEstimate', action='store_true',
                    help='--ber: also run the receiver that estimates H W from a precoded preamble (csi_link_sim_rx_device) - bersRx_ / EVM_rmsRx_ / gNMSE_')
+    p.add_argument('--users', default=1, type=int, metavar='U',
+                   help='--ber: serve U users (2 .. 8) at once with a zero-forcing precoder over U x numSTS streams (csi_mu_precoder_device, '
+                        'csi_mu_link_sim_device) - bersMU_ / EVM_rmsMU_ / sinrMU_')
+    p.add_argument('--muReg', default='zf', choices=('zf', 'rzf'), help='--users: zero forcing, or regularised with M link_noise_var / Nt')
+    p.add_argument('--userSpacing', default=15.0, type=float, metavar='DEG', help='--users with --channel scattering: user u sits at azimuth userAz + u DEG')
     p.add_argument('--channel', default='taps', choices=('taps', 'scattering'),
                    help='taps: i.i.d. impulse responses (csi_synth_structured); scattering: the geometric single-bounce channel (csi_synth_scattering)')
     p.add_argument('--scatterers', default=100, type=int, help='--channel scattering: scatterers (N_chan_taps, generate_maMIMO_LTF.m:9)')
@@ -409,6 +527,13 @@ def parse_args(argv=None):
     args = parser.parse_args(argv)
     if args.rxEstimate and not args.ber:
         parser.error('--rxEstimate needs --ber')
+    if args.users != 1:
+        if not 1 <= args.users <= 8:
+            parser.error('--users takes 1 .. 8')
+        if not args.ber:
+            parser.error('--users needs --ber')
+        if args.users * args.numSTS > min(16, args.nTX):
+            parser.error('--users x --numSTS = %d streams exceed min(16, nTX %d)' % (args.users * args.numSTS, args.nTX))
     if args.delayTaps and not (1 <= args.delayTaps <= subspace.MAX_RANK and 0 <= args.delayPre <= args.delayTaps):
         parser.error('--delayTaps takes 1 .. %d and --delayPre 0 .. L' % subspace.MAX_RANK)
     if args.delayPre and not args.delayTaps:
@@ -430,7 +555,8 @@ def main(argv=None):
     run_sweep(eng, args.workdir, levels=args.snr, n_train=args.trainPkts, n_test=args.testPkts, seed=args.seed,
               modeldir=args.modeldir or None, fit_args=fit_args, n_taps=args.taps, save_dataset=args.save_dataset or None,
               verbose=not args.quiet, ber=ber, channel=channel_from_args(args), blind=bool(args.blind),
-              rx_estimate=bool(args.rxEstimate), delay_taps=args.delayTaps or None, delay_pre=args.delayPre)
+              rx_estimate=bool(args.rxEstimate), delay_taps=args.delayTaps or None, delay_pre=args.delayPre,
+              users=args.users if args.users >= 2 else None, mu_reg=args.muReg, user_spacing=args.userSpacing)
     return 0
 
 

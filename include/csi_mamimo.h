@@ -40,10 +40,10 @@
  * context's stream and return without waiting; call csi_synchronize before reading results.
  *
  * Device pointers (csi_predict_device, csi_ls_estimate_device, csi_estimate_device, csi_lmmse_estimate_device, csi_lmmse_blind_device, csi_subspace_smooth_device, csi_nmse_device,
- * csi_hybrid_weights_device, csi_link_sim_device, csi_link_sim_rx_device, csi_viterbi_decode_device, csi_synth_*).  An array of exactly the documented
+ * csi_hybrid_weights_device, csi_link_sim_device, csi_link_sim_rx_device, csi_mu_precoder_device, csi_mu_link_sim_device, csi_viterbi_decode_device, csi_synth_*).  An array of exactly the documented
  * size suffices: it may be a slice of a larger allocation whose neighbours hold live data of any value (NaN and 1e38 included).
  * Nothing outside the arrays is written, nothing outside them reaches a result, and input arrays are not modified.  Every re / im
- * PLANE (the preambles [npkt][Nr][len_ltf], the CSI planes [npkt][Nr][Nt][234 or n_out], fbb, frf_mean, xeq, gest) starts on a 16-byte
+ * PLANE (the preambles [npkt][Nr][len_ltf], the CSI planes [npkt][Nr][Nt][234 or n_out], fbb, frf_mean, xeq, gest, the precoder planes W, g) starts on a 16-byte
  * boundary: the LS and layer-0 kernels move the caller's rows as 16-byte words and by LDS-DMA; hipMalloc, csi_device_malloc and
  * whole torch tensors satisfy that, and so does every packet range of a preamble or CSI plane (Nt is a multiple of 4).  A
  * misaligned plane is refused with CSI_ERR_INVALID_ARG and a text that names the argument, before anything is launched or counted.
@@ -366,6 +366,38 @@ int  csi_link_sim_rx_device(csi_ctx* ctx, const float* d_h_re, const float* d_h_
                             float* d_dt_snr_db, float* d_xeq_re, float* d_xeq_im, float* d_csi, float* d_llr, uint8_t* d_bits,
                             float* d_g_nmse, float* d_gest_re, float* d_gest_im);
 
+/* Multi-user downlink (BER_test_maMIMO_LTF.m:110-112, 238-246, 360-385, 417-484, prm.numUsers; model and deviations: DESIGN.md 4.20,
+ * csrc/mu_link.hip.h).  An addition: the ABI version stays 1.  U = n_users users (1 .. 8), each with CSI planes [npkt][Nr][Nt][234]; ns
+ * streams per user (1 .. min(4, Nr)) addressed to the user's receive antennas 0 .. ns-1; M = U ns <= min(16, Nt); stream m = u ns + s.
+ * csi_mu_precoder_device: per (packet p, subcarrier k)  B[m][j] = hest_u[p][s][j][k],  A = B B^H + reg[p] I (d_reg [npkt], NULL = 0:
+ * zero forcing; the regularised form uses reg = M noise_var / Nt),  Cholesky A = L L^H (a pivot <= 0 or not finite: W = 0 for the item),
+ * V = B^H A^-1,  W[:, m] = sqrt(Nt / M) V[:, m] / |V[:, m]|_2 (a zero or non-finite norm: 0), so that |W|_F^2 = Nt.  d_hest_re / d_hest_im
+ * are HOST arrays of U device pointers (read before the call returns); d_w_re / d_w_im [npkt][M][Nt][234].  One kernel launch.
+ * csi_mu_link_sim_device: the data phase of csi_link_sim_device for every user through the TRUE planes d_h_re / d_h_im (host arrays of
+ * U device pointers) with the precoder planes W.  User seed: seed_0 = seed, seed_u = splitmix64(seed ^ splitmix64(u)); bits, encoder,
+ * mapper and frame sizes of csi_link_sim_device for (ns, n_sym, bps) on the stream seed_u; at user u, antenna i < ns,
+ * y = sum_m G_u[i][m] d_m + w with G_u = H_u[0:ns] W (ns x M) and noise of variance d_noise_var[u][p] (draws of the stream seed_u with
+ * Nr = ns in the index: user 0 with ns = Nr has the bits and the noise of csi_link_sim_device); the single-user equaliser on the user's
+ * own ns x ns block G_uu, the same singular rule; soft bits csi_s / noise_var times the max-log difference - the interference of the other
+ * users' streams is NOT in the scale, the receiver does not know it; Viterbi decoding.
+ * Outputs [U][npkt]: bit_errors int32, evm_rms, sinr_db = 10 log10(sum_k |G_uu|_F^2 / (sum_k |G_u,others|_F^2 + 234 ns noise_var)) (the
+ * IEEE quotient; G_u,others = the columns of the other users).  Optional (may be NULL; planes as pairs): g [U][npkt][ns][M][234],
+ * xeq [U][npkt][ns][n_sym][234], csi [U][npkt][ns][234], llr [U][npkt][n_coded], bits uint8 [U][npkt][n_info].
+ * Both calls are asynchronous on the context's stream and serve fp32 and bf16 contexts alike (every plane is fp32); the data phase runs
+ * in packet chunks against the context's workspace_bytes (the U codewords' coded bits and, when the caller keeps none, their soft bits;
+ * default 1 GiB) with the same bits whatever the chunking.
+ * Refused with text, before anything is launched or counted: n_users outside 1 .. 8, ns outside 1 .. min(4, Nr), M > 16 or M > Nt, bps
+ * not in {2, 4}, n_sym < 1, n_steps > 8190, negative npkt / first_pkt, null required pointers or a null entry of a pointer array, one
+ * plane of a pair without the other, planes off a 16-byte boundary, a single-input context, an LDS image beyond 160 KiB.  npkt == 0
+ * returns 0 and launches nothing; a null context returns -1.  Read-only option "mu_launches"; profile entries "mu_precoder" and
+ * "mu_txrx" (encoders + transmit / receive pass); the decoder is counted under "link_viterbi". */
+int  csi_mu_precoder_device(csi_ctx* ctx, int n_users, const float* const* d_hest_re, const float* const* d_hest_im, int64_t npkt, int ns,
+                            const float* d_reg, float* d_w_re, float* d_w_im);
+int  csi_mu_link_sim_device(csi_ctx* ctx, int n_users, const float* const* d_h_re, const float* const* d_h_im, const float* d_w_re,
+                            const float* d_w_im, const float* d_noise_var, uint64_t seed, int64_t first_pkt, int64_t npkt, int ns,
+                            int n_sym, int bps, int32_t* d_bit_errors, float* d_evm_rms, float* d_sinr_db, float* d_g_re, float* d_g_im,
+                            float* d_xeq_re, float* d_xeq_im, float* d_csi, float* d_llr, uint8_t* d_bits);
+
 /* Accuracy metric of the reference's evaluation, NMSE_subk (BER_test_maMIMO_LTF.m:675-686): per link
  * ||ref - est||^2 / ||ref||^2 over the n_bins bins, mean over the nlinks links ([link][n_bins] planes, e.g.
  * the [npkt][nr][nt][234] outputs of csi_predict / csi_ls_estimate with nlinks = npkt*nr*nt).  Synchronous;
@@ -553,7 +585,7 @@ int  csi_set_option(csi_ctx* ctx, const char* name, int64_t value);
 /* Current value of an option, or of the read-only values: "hs_launches" (split-engine GEMMs launched), "hs_range_fallbacks"
  * (csi_predict calls repeated on the fp32 MFMA kernels), "hs_weight_pins" / "hs_weight_err_e12" (layers pinned to the fp32 kernels
  * at load because their split copies were not fp32-grade; worst relative error x 1e12), "band_available" (the assembly band kernel
- * is embedded in this build), "graph_replays", "subspace_launches" (kernels launched by csi_subspace_smooth[_device]), "lmmse_blind_fallbacks" ((packet, rx) pairs csi_lmmse_blind[_device] handed back unsmoothed), "ls_pilot_fast" (0 generic / 1 Sylvester / 2 permuted pilot), "comm_world",
+ * is embedded in this build), "graph_replays", "subspace_launches" (kernels launched by csi_subspace_smooth[_device]), "mu_launches" (kernels launched by csi_mu_precoder_device / csi_mu_link_sim_device), "lmmse_blind_fallbacks" ((packet, rx) pairs csi_lmmse_blind[_device] handed back unsmoothed), "ls_pilot_fast" (0 generic / 1 Sylvester / 2 permuted pilot), "comm_world",
  * "comm_rank", "comm_blobs", "comm_bytes" (communicator and last broadcast), "hp_direct_out_calls", and where the last pipelined
  * host-buffer call spent its time in microseconds: "hp_total_us", "hp_stage_us", "hp_wait_stage_us", "hp_wait_out_us", "hp_weave_us". */
 int  csi_get_option(csi_ctx* ctx, const char* name, int64_t* value);
