@@ -9,7 +9,7 @@ from ._lib import CsiError, build_library, library_path, load_library   # noqa: 
 from .engine import CsiEngine, DeviceArray, HybridWeights, LinkResult, LinkRxResult, MuLinkResult, frf_from_idx  # noqa: F401
 from .model import CSIModel, load_weight_file, save_weight_file         # noqa: F401
 from .inference import CSIPredictor                                     # noqa: F401
-from . import synth, dist, dataset, trainer, subspace                   # noqa: F401
+from . import synth, dist, dataset, trainer, subspace, beamspace                 # noqa: F401
 
 __all__ = ['CsiEngine', 'DeviceArray', 'HybridWeights', 'LinkResult', 'LinkRxResult', 'MuLinkResult', 'frf_from_idx', 'CSIModel', 'CSIPredictor', 'CsiError', 'build_library',
-           'library_path', 'load_library', 'load_weight_file', 'save_weight_file', 'synth', 'dist', 'dataset', 'trainer', 'subspace']
+           'library_path', 'load_library', 'load_weight_file', 'save_weight_file', 'synth', 'dist', 'dataset', 'trainer', 'subspace', 'beamspace']

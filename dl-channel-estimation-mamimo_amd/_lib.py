@@ -79,6 +79,13 @@ SYMBOLS = {
     'csi_subspace_set_basis': (ctypes.c_int, [_ctx, _fp, _fp, ctypes.c_int]),
     'csi_subspace_smooth': (ctypes.c_int, [_ctx, _fp, _fp, ctypes.c_int64, _fp, _fp, _fp]),
     'csi_subspace_smooth_device': (ctypes.c_int, [_ctx, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp]),
+    'csi_beam_set_basis': (ctypes.c_int, [_ctx, _fp, _fp, ctypes.c_int]),
+    'csi_beam_power_device': (ctypes.c_int, [_ctx, _vp, _vp, ctypes.c_int64, _vp]),
+    'csi_beam_smooth': (ctypes.c_int, [_ctx, _fp, _fp, ctypes.c_int64, _fp, _fp, _fp]),
+    'csi_beam_smooth_device': (ctypes.c_int, [_ctx, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp]),
+    'csi_beam_wiener': (ctypes.c_int, [_ctx, _fp, _fp, ctypes.c_int64, _fp, _fp, _fp, _fp]),
+    'csi_beam_wiener_device': (ctypes.c_int, [_ctx, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp]),
+    'csi_null_noise_device': (ctypes.c_int, [_ctx, _vp, _vp, ctypes.c_int64, _vp]),
     'csi_hybrid_set_dictionary': (ctypes.c_int, [_ctx, _fp, _fp, ctypes.c_int]),
     'csi_hybrid_weights': (ctypes.c_int, [_ctx, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_vp] * 7),
     'csi_hybrid_weights_device': (ctypes.c_int, [_ctx, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_vp] * 7),

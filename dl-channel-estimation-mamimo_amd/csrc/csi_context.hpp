@@ -27,6 +27,7 @@
 #include "synth_scattering.hip.h"
 #include "link_sim.hip.h"
 #include "subspace_smooth.hip.h"
+#include "beam_smooth.hip.h"
 #include "mu_link.hip.h"
 
 using namespace csi;
@@ -64,6 +65,8 @@ enum KernelId {
                          // of the table looks an id up by its name (csi_profile_kernel_name)
     K_MU_PRECODER,       // multi-user downlink: (regularised) zero-forcing precoder per (packet, subcarrier) (mu_link.hip.h); placed like K_SUBSPACE_SMOOTH
     K_MU_TXRX,           // multi-user downlink: encoders + transmit / receive pass per (packet, user)
+    K_BEAM_POWER,        // beam-space smoother (csi_beam_*, beam_smooth.hip.h): beam power E per (packet, rx, beam); placed like K_SUBSPACE_SMOOTH
+    K_BEAM_SMOOTH,       // beam-space smoother: y = A diag(w) A^H x across the Tx antennas
     K_SYNTH_SCATTERING,  // known-channel sounding packets of the scattering channel (synth_scattering.hip.h): the power pass and the packet pass of csi_synth_scattering
     K_LMMSE_NULL_NOISE,  // blind LMMSE smoother (csi_lmmse_blind, lmmse.hip.h): noise variance from the null carriers of the sounding symbols
     K_LMMSE_FREQ_CORR,   // blind LMMSE smoother: sample frequency correlation of the LS rows
@@ -75,7 +78,7 @@ const char* const kKernelNames[K_COUNT] = {
     "ls_estimate", "naive_dense0_gemm", "synth_white", "pilot_table", "cast_bf16", "pair_h1_bf16", "lmmse_levinson",
     "train_gemm", "train_elementwise", "nmse_links", "pair_dense_tail", "input_pool", "conv_frontend",
     "hybrid_svd", "hybrid_corr_argmax", "hybrid_solve", "hybrid_finish", "synth_structured", "link_txrx", "link_viterbi",
-    "subspace_smooth", "mu_precoder", "mu_txrx", "synth_scattering", "lmmse_null_noise", "lmmse_freq_corr", "lmmse_blind"};
+    "subspace_smooth", "mu_precoder", "mu_txrx", "beam_power", "beam_smooth", "synth_scattering", "lmmse_null_noise", "lmmse_freq_corr", "lmmse_blind"};
 
 thread_local std::string g_create_error;
 
@@ -234,6 +237,14 @@ struct csi_ctx {
     int sub_rank = 0, sub_rp = 0;
     size_t sub_lds_attr = 0;
     int64_t subspace_launches = 0;   // "subspace_launches": kernels launched by csi_subspace_smooth_device
+    // beam-space smoother (csi_beam.hpp): the basis as the kernels' two images, a1 re | a1 im [ntp][nbp] then a2 re | a2 im [nbp][ntp], in one
+    // allocation of the largest size (128 x 128) that a second csi_beam_set_basis overwrites; nb 0 = none set.  beam_ws: E and, when the
+    // caller keeps none, w of a csi_beam_wiener_device call ([npkt][nr][nb] each; sized by eager calls)
+    float* beam_a = nullptr;
+    int beam_nb = 0, beam_ntp = 0, beam_nbp = 0;
+    char* beam_ws = nullptr;
+    size_t beam_ws_bytes = 0;
+    int64_t beam_launches = 0;   // "beam_launches": kernels launched by the csi_beam_* entry points
     int64_t mu_launches = 0;     // "mu_launches": kernels launched by csi_mu_precoder_device / csi_mu_link_sim_device
     int64_t link_launches = 0;   // "link_launches": kernels launched by csi_link_sim_device / csi_viterbi_decode_device
     bool user_capture = false;   // between csi_capture_begin and csi_capture_end (csi_hybrid.hpp): device-pointer calls are recorded, not run

@@ -23,6 +23,7 @@
 #include "csi_link.hpp"
 #include "csi_scatter.hpp"
 #include "csi_subspace.hpp"
+#include "csi_beam.hpp"
 #include "csi_mu.hpp"
 #include <initializer_list>
 
@@ -325,6 +326,8 @@ void csi_destroy(csi_ctx* c) {
     if (c->lmb_ws) hipFree(c->lmb_ws);
     if (c->lmb_count) hipFree(c->lmb_count);
     if (c->sub_q) hipFree(c->sub_q);
+    if (c->beam_a) hipFree(c->beam_a);
+    if (c->beam_ws) hipFree(c->beam_ws);
     if (c->hs_peak) hipFree(c->hs_peak);
     if (c->hs_zero) hipFree(c->hs_zero);
     if (c->fuse_ws) hipFree(c->fuse_ws);
@@ -1049,6 +1052,87 @@ int csi_subspace_smooth(csi_ctx* c, const float* h_re, const float* h_im, int64_
     return subspace_smooth_host(c, h_re, h_im, npkt, w, out_re, out_im);
 }
 
+// ---------------------------------------------------------------- beam-space smoother across the Tx antennas (csi_beam.hpp, beam_smooth.hip.h)
+int csi_beam_set_basis(csi_ctx* c, const float* a_re, const float* a_im, int nb) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return beam_set_basis(c, a_re, a_im, nb);
+}
+
+int csi_beam_power_device(csi_ctx* c, const float* d_h_re, const float* d_h_im, int64_t npkt, float* d_power) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    static const char* who = "csi_beam_power_device";
+    if (int rc = beam_check(c, who, d_h_re, d_h_im, npkt, d_power != nullptr, "h, power")) return rc;
+    if (int rc = planes_aligned(c, who, {{"d_h_re", d_h_re}, {"d_h_im", d_h_im}})) return rc;
+    if (reinterpret_cast<uintptr_t>(d_power) & 3) return fail(c, CSI_ERR_INVALID_ARG, "%s: d_power must be aligned for floats (got %p)", who, (const void*)d_power);
+    if (npkt == 0) return CSI_OK;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    return beam_power_launch(c, d_h_re, d_h_im, npkt, d_power);
+}
+
+int csi_beam_smooth_device(csi_ctx* c, const float* d_h_re, const float* d_h_im, int64_t npkt, const float* d_w, float* d_out_re, float* d_out_im) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    static const char* who = "csi_beam_smooth_device";
+    if (int rc = beam_check(c, who, d_h_re, d_h_im, npkt, d_out_re && d_out_im, "h, out")) return rc;
+    if (int rc = planes_aligned(c, who, {{"d_h_re", d_h_re}, {"d_h_im", d_h_im}, {"d_out_re", d_out_re}, {"d_out_im", d_out_im}})) return rc;
+    if (reinterpret_cast<uintptr_t>(d_w) & 3) return fail(c, CSI_ERR_INVALID_ARG, "%s: d_w must be aligned for floats (got %p)", who, (const void*)d_w);
+    if (npkt == 0) return CSI_OK;
+    if (int rc = beam_planes_disjoint(c, who, d_h_re, d_h_im, d_out_re, d_out_im, npkt)) return rc;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    return beam_smooth_launch(c, d_h_re, d_h_im, npkt, d_w, d_out_re, d_out_im);
+}
+
+int csi_beam_smooth(csi_ctx* c, const float* h_re, const float* h_im, int64_t npkt, const float* w, float* out_re, float* out_im) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return beam_host(c, "csi_beam_smooth", false, h_re, h_im, npkt, w, nullptr, out_re, out_im, nullptr);
+}
+
+int csi_beam_wiener_device(csi_ctx* c, const float* d_h_re, const float* d_h_im, int64_t npkt, const float* d_err_var, float* d_out_re, float* d_out_im,
+                           float* d_w_out) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    static const char* who = "csi_beam_wiener_device";
+    if (int rc = beam_check(c, who, d_h_re, d_h_im, npkt, d_err_var && d_out_re && d_out_im, "h, err_var, out")) return rc;
+    if (int rc = planes_aligned(c, who, {{"d_h_re", d_h_re}, {"d_h_im", d_h_im}, {"d_out_re", d_out_re}, {"d_out_im", d_out_im}})) return rc;
+    if ((reinterpret_cast<uintptr_t>(d_err_var) | reinterpret_cast<uintptr_t>(d_w_out)) & 3)
+        return fail(c, CSI_ERR_INVALID_ARG, "%s: d_err_var / d_w_out must be aligned for floats (got %p / %p)", who, (const void*)d_err_var, (void*)d_w_out);
+    if (npkt == 0) return CSI_OK;
+    if (int rc = beam_planes_disjoint(c, who, d_h_re, d_h_im, d_out_re, d_out_im, npkt)) return rc;
+    return beam_wiener_device(c, who, d_h_re, d_h_im, npkt, d_err_var, d_out_re, d_out_im, d_w_out);
+}
+
+int csi_beam_wiener(csi_ctx* c, const float* h_re, const float* h_im, int64_t npkt, const float* err_var, float* out_re, float* out_im, float* w_out) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return beam_host(c, "csi_beam_wiener", true, h_re, h_im, npkt, nullptr, err_var, out_re, out_im, w_out);
+}
+
+// the null-carrier statistic of csi_lmmse_blind_device on its own: the same kernel, the same launch shape, the same bits
+int csi_null_noise_device(csi_ctx* c, const float* d_ltf_re, const float* d_ltf_im, int64_t npkt, double* d_noise_var) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    static const char* who = "csi_null_noise_device";
+    const csi_config& cf = c->cfg;
+    if (cf.nt == 0) return fail(c, CSI_ERR_INVALID_ARG, "single-input context (nt=0): no sounding symbols");
+    if (npkt < 0) return fail(c, CSI_ERR_INVALID_ARG, "%s: npkt %lld must not be negative", who, (long long)npkt);
+    if (!d_ltf_re || !d_ltf_im || !d_noise_var) return fail(c, CSI_ERR_INVALID_ARG, "%s: null required pointer (ltf, noise_var)", who);
+    if (cf.len_ltf < LMB_SYM * cf.nt || cf.len_ltf % 4 != 0)
+        return fail(c, CSI_ERR_INVALID_ARG, "%s: len_ltf %d does not hold %d sounding symbols of 320 samples in 16-byte words", who, cf.len_ltf, cf.nt);
+    if (int rc = planes_aligned(c, who, {{"d_ltf_re", d_ltf_re}, {"d_ltf_im", d_ltf_im}})) return rc;
+    if (reinterpret_cast<uintptr_t>(d_noise_var) & 7)
+        return fail(c, CSI_ERR_INVALID_ARG, "%s: d_noise_var must be aligned for doubles (got %p)", who, (void*)d_noise_var);
+    if (npkt == 0) return CSI_OK;
+    HIP_TRY(c, hipSetDevice(cf.device));
+    const int64_t nblk = npkt * cf.nr;
+    const int64_t max_items = ((int64_t)1 << 30) / cf.nr * cf.nr;      // whole packets per launch
+    for (int64_t b0 = 0; b0 < nblk; b0 += max_items) {
+        const int64_t nb = std::min(max_items, nblk - b0);
+        LmmseNoiseArgs a{};
+        a.ltf_re = d_ltf_re + (size_t)b0 * cf.len_ltf; a.ltf_im = d_ltf_im + (size_t)b0 * cf.len_ltf;
+        a.tw = c->lmb_tw; a.nv = d_noise_var + b0; a.nt = cf.nt; a.len_ltf = cf.len_ltf;
+        ProfScope ps(c, K_LMMSE_NULL_NOISE, (double)nb * cf.nt * LMB_NULLS * LMB_FFT * 44.0, (double)nb * cf.nt * LMB_FFT * 8.0);
+        hipLaunchKernelGGL(lmmse_null_noise_kernel, dim3((unsigned)nb), dim3(LMB_THREADS), 0, c->stream, a);
+        HIP_TRY(c, hipGetLastError());
+    }
+    return CSI_OK;
+}
+
 // ---------------------------------------------------------------- hybrid beamforming weights (csi_hybrid.hpp, hybrid_weights.hip.h)
 int csi_hybrid_set_dictionary(csi_ctx* c, const float* at_re, const float* at_im, int n_rays) {
     if (!c) return CSI_ERR_INVALID_ARG;
@@ -1216,6 +1300,7 @@ int csi_get_option(csi_ctx* c, const char* name, int64_t* value) {
     else if (n == "hybrid_launches") *value = c->hybrid_launches;
     else if (n == "link_launches") *value = c->link_launches;
     else if (n == "subspace_launches") *value = c->subspace_launches;
+    else if (n == "beam_launches") *value = c->beam_launches;
     else if (n == "mu_launches") *value = c->mu_launches;
     else if (n == "lmmse_blind_fallbacks") {
         // counted on the device behind every launch (lmmse_blind_count_kernel): reading it waits for the stream

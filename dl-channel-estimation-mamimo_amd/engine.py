@@ -633,6 +633,92 @@ class CsiEngine:
         out.imag = o_im
         return out
 
+    # ------------------------------------------------------------------ beam-space smoother across the Tx antennas
+    def beam_set_basis(self, A):
+        """Basis of the beam-space smoother: complex [nt][nb] with orthonormal columns, nb = 1 .. nt <= 128 (for instance
+        beamspace.dft_basis(nt)), kept on the device in float32; a second call replaces it."""
+        A = np.asarray(A)
+        if A.ndim != 2 or A.shape[0] != self.nt:
+            raise CsiError(-1, f'basis must be [{self.nt}][nb], got {A.shape}')
+        re, im = _f32c(A.real), _f32c(A.imag)
+        self._check(self._lib.csi_beam_set_basis(self._ctx, _fp(re), _fp(im), A.shape[1]))
+        self.beam_nb = int(A.shape[1])
+
+    def _beam_planes(self, h):
+        h = np.asarray(h)
+        re, im = _f32c(h.real), _f32c(h.imag)
+        npkt = re.shape[0] if re.ndim else 0
+        if re.shape != (npkt, self.nr, self.nt, N_DATA):
+            raise CsiError(-1, f'h must be [npkt,{self.nr},{self.nt},{N_DATA}], got {re.shape}')
+        return re, im, npkt
+
+    @staticmethod
+    def _c64(o_re, o_im):
+        out = np.empty(o_re.shape, dtype=np.complex64)
+        out.real = o_re
+        out.imag = o_im
+        return out
+
+    def beam_power(self, h):
+        """E[p][r][b] = mean over the 234 carriers of |sum_j conj(A[j][b]) h[p][r][j][k]|^2 (csi_beam_power_device; A from
+        beam_set_basis).  h complex [npkt,nr,nt,234]; returns float32 [npkt,nr,nb]."""
+        re, im, npkt = self._beam_planes(h)
+        nb = getattr(self, 'beam_nb', 0)
+        if npkt == 0:
+            return np.empty((0, self.nr, nb), np.float32)
+        d_re, d_im, d_e = self.to_device(re), self.to_device(im), self.empty((npkt, self.nr, max(nb, 1)))      # no basis: the call refuses
+        try:
+            self.beam_power_device(d_re, d_im, npkt, d_e)
+            return d_e.download()
+        finally:
+            for a in (d_re, d_im, d_e):
+                a.free()
+
+    def beam_smooth(self, h, weights=None):
+        """y = A diag(w) A^H x along the antenna axis of h complex [npkt,nr,nt,234] (csi_beam_smooth; A from beam_set_basis).
+        weights float [npkt,nr,nb], or None for the plain projection.  Returns complex64 [npkt,nr,nt,234]."""
+        re, im, npkt = self._beam_planes(h)
+        w = None
+        if weights is not None:
+            w = _f32c(weights)
+            nb = getattr(self, 'beam_nb', 0)
+            if w.shape != (npkt, self.nr, nb):
+                raise CsiError(-1, f'weights must be [{npkt},{self.nr},{nb}], got {w.shape}')
+        o_re, o_im = np.empty_like(re), np.empty_like(re)
+        self._check(self._lib.csi_beam_smooth(self._ctx, _fp(re), _fp(im), npkt, _fp(w) if w is not None else None, _fp(o_re), _fp(o_im)))
+        return self._c64(o_re, o_im)
+
+    def beam_wiener(self, h, err_var, details=False):
+        """The beam-space Wiener smoother (csi_beam_wiener): beam power of every (packet, rx), w = 1 - v / E where E > v and 0 elsewhere
+        (beamspace.wiener_weights), then beam_smooth with these weights.  err_var float [npkt,nr]: the error variance of one element
+        of h (for an LS estimate: null_noise(ltf) / nt).  Returns complex64 [npkt,nr,nt,234]; with ``details`` also w float32
+        [npkt,nr,nb]."""
+        re, im, npkt = self._beam_planes(h)
+        v = _f32c(err_var)
+        if v.shape != (npkt, self.nr):
+            raise CsiError(-1, f'err_var must be [{npkt},{self.nr}], got {v.shape}')
+        o_re, o_im = np.empty_like(re), np.empty_like(re)
+        w = np.empty((npkt, self.nr, getattr(self, 'beam_nb', 0)), np.float32) if details else None
+        self._check(self._lib.csi_beam_wiener(self._ctx, _fp(re), _fp(im), npkt, _fp(v), _fp(o_re), _fp(o_im), _fp(w) if details else None))
+        out = self._c64(o_re, o_im)
+        return (out, w) if details else out
+
+    def null_noise(self, ltf):
+        """The noise level of every (packet, rx) from the null carriers of the sounding symbols (csi_null_noise_device): the statistic
+        csi_lmmse_blind takes, on its own.  ltf complex [npkt,nr,len_ltf]; returns float64 [npkt,nr].  The error variance of one
+        element of the LS estimate of these preambles is the result / nt."""
+        re, im = self._split(ltf, None)
+        npkt = re.shape[0]
+        if npkt == 0:
+            return np.empty((0, self.nr), np.float64)
+        d_re, d_im, d_nv = self.to_device(re), self.to_device(im), self.empty((npkt, self.nr, 2))
+        try:
+            self.null_noise_device(d_re, d_im, npkt, d_nv)
+            return d_nv.download().view(np.float64)[..., 0]
+        finally:
+            for a in (d_re, d_im, d_nv):
+                a.free()
+
     # ------------------------------------------------------------------ hybrid beamforming weights
     def set_dictionary(self, At):
         """Dictionary of array responses for hybrid_weights: complex [Nt][rays] (for instance synth.steering_ula), kept on the
@@ -1065,6 +1151,27 @@ class CsiEngine:
         themselves), d_w [npkt][nr][rank] or None for the plain projection; one launch, asynchronous."""
         self._check(self._lib.csi_subspace_smooth_device(self._ctx, d_h_re.ptr, d_h_im.ptr, int(npkt), d_w.ptr if d_w is not None else None,
                                                          d_out_re.ptr, d_out_im.ptr))
+
+    def beam_power_device(self, d_h_re, d_h_im, npkt, d_power):
+        """Beam power on device-resident planes (csi_beam_power_device): d_power [npkt][nr][nb]; one launch, asynchronous."""
+        self._check(self._lib.csi_beam_power_device(self._ctx, d_h_re.ptr, d_h_im.ptr, int(npkt), d_power.ptr))
+
+    def beam_smooth_device(self, d_h_re, d_h_im, npkt, d_out_re, d_out_im, d_w=None):
+        """Beam-space smoother on device-resident planes (csi_beam_smooth_device): out planes like h (they may be the h planes
+        themselves), d_w [npkt][nr][nb] or None for the plain projection; one launch, asynchronous."""
+        self._check(self._lib.csi_beam_smooth_device(self._ctx, d_h_re.ptr, d_h_im.ptr, int(npkt), d_w.ptr if d_w is not None else None,
+                                                     d_out_re.ptr, d_out_im.ptr))
+
+    def beam_wiener_device(self, d_h_re, d_h_im, npkt, d_err_var, d_out_re, d_out_im, d_w=None):
+        """Beam-space Wiener smoother on device-resident planes (csi_beam_wiener_device): d_err_var [npkt][nr], out planes like h (they
+        may be the h planes themselves), optional d_w [npkt][nr][nb] receives the weights; three launches, asynchronous."""
+        self._check(self._lib.csi_beam_wiener_device(self._ctx, d_h_re.ptr, d_h_im.ptr, int(npkt), d_err_var.ptr, d_out_re.ptr, d_out_im.ptr,
+                                                     d_w.ptr if d_w is not None else None))
+
+    def null_noise_device(self, d_ltf_re, d_ltf_im, npkt, d_noise_var):
+        """The null-carrier noise level of device-resident preambles (csi_null_noise_device): d_noise_var [npkt][nr] as float64 (an
+        array of 2 float32 words per (packet, rx)); asynchronous."""
+        self._check(self._lib.csi_null_noise_device(self._ctx, d_ltf_re.ptr, d_ltf_im.ptr, int(npkt), d_noise_var.ptr))
 
     # ------------------------------------------------------------------ profiling
     def profile_enable(self, on=True):

@@ -11,7 +11,7 @@ the data phase through their true channels (csi_mu_link_sim_device) add the bers
     python -m dl_channel_estimation_mamimo_amd.sweep -d OUT [--nTX 32 --nRX 4 --nn 1024 1024 --useBN --bs 256 ...]
                                                             [--ber --numSTS 1 --rays 500 --dataSymbols 10 --bps 2 [--rxEstimate]]
                                                             [--channel scattering --scatterers 100 --range 100 --userAz 30 --userEl 0 --randomUsers]
-                                                            [--blind] [--delayTaps L [--delayPre P]]
+                                                            [--blind] [--delayTaps L [--delayPre P]] [--beams]
                                                             [--ber --users U [--muReg zf|rzf] [--userSpacing DEG]]
 
 The module holds no arithmetic of its own: packets with a known channel come from csi_synth_structured (--channel scattering: from
@@ -20,7 +20,9 @@ csi_ls_estimate_device, the fit from trainer.fit, the estimates from csi_estimat
 NMSE from csi_nmse_device (--blind adds the estimator MMSEb: csi_lmmse_blind_device, the smoother that takes its noise level and its
 frequency correlation from the packet itself instead of from the generator; --delayTaps L adds the estimator DLY:
 csi_subspace_smooth_device with w = 1, the projection of the LS rows onto the channels of at most L delay taps, which uses nothing
-from the generator either - the basis comes from subspace.delay_basis); the hybrid weights from csi_hybrid_weights_device and bit errors, EVM and beamforming gain from
+from the generator either - the basis comes from subspace.delay_basis; --beams adds the estimator ANG: csi_beam_wiener_device on the
+LS planes with the DFT beams of beamspace.dft_basis and the error level csi_null_noise_device finds in the preambles' null carriers,
+and with --delayTaps the estimator DLYANG, the same step on the DLY planes); the hybrid weights from csi_hybrid_weights_device and bit errors, EVM and beamforming gain from
 csi_link_sim_device, with the noise level of a data symbol from synth.link_noise_var.  Only the per-packet mean of the per-link
 ratios (NMSE_subk, BER_test_maMIMO_LTF.m:675-686), errors / n_info and the confidence interval are taken on the host."""
 import argparse
@@ -33,7 +35,7 @@ import time
 import numpy as np
 
 from . import dataset as ds
-from . import subspace, synth, trainer
+from . import beamspace, subspace, synth, trainer
 from .engine import N_DATA
 
 ESTIMATORS = ('LS', 'MMSE', 'DNN')
@@ -42,6 +44,8 @@ LINK_FIELDS = ('bers_', 'EVM_rms_', 'dtSNR_')
 RX_FIELDS = ('bersRx_', 'EVM_rmsRx_', 'gNMSE_')     # --rxEstimate: the same data phase equalised with the preamble's estimate of H W
 MU_FIELDS = ('bersMU_', 'EVM_rmsMU_', 'sinrMU_')    # --users: the multi-user data phase, the mean over the users per packet
 DELAY = 'DLY'                            # --delayTaps: the LS rows projected onto a window of delay taps (csi_subspace_smooth_device, w = 1)
+BEAMS = 'ANG'                            # --beams: the beam-space Wiener smoother across the Tx antennas on the LS planes (csi_beam_wiener_device)
+DELAY_BEAMS = 'DLYANG'                   # --beams with --delayTaps: the same step on the DLY planes
 BLIND = 'MMSEb'                          # --blind: the LMMSE smoother on the packet's own statistics (csi_lmmse_blind_device)
 
 
@@ -99,7 +103,7 @@ def make_dataset(engine, n_train, seed, n_taps=8, amp_scale=True, channel=None):
 
 
 def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=True, keep=False, ber=None, channel=None, blind=False,
-                   rx_estimate=False, delay=None, mu=None):
+                   rx_estimate=False, delay=None, mu=None, beams=False):
     """npkt test packets at `snr_db` (packets first_pkt ... of stream `seed`: keep them disjoint from the training packets), LS + DNN
     (estimate_device), the LMMSE smoother on the LS planes, and NMSE_subk of the three estimates against the true channel.
     Returns {'MSE_LS', 'MSE_MMSE', 'MSE_DNN'}: float64 [npkt], the per-link ratios averaged per packet.
@@ -125,7 +129,10 @@ def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=Tr
     mu = dict(users=U, reg='zf' | 'rzf', spacing=degrees) (with `ber`, U >= 2) adds the multi-user data phase (mu_level): user 0 is the
     user above; user u >= 1 takes its packets from the stream seed + u (scattering channel: at azimuth az_deg + u spacing) and its
     estimates from the same calls.  Adds 'bersMU_X', 'EVM_rmsMU_X', 'sinrMU_X' float64 [npkt] (the mean over the users) for every source
-    X - here DLY is one too - and 'mu_users' = {X: {'bers', 'EVM_rms', 'sinr': [U][npkt]}}.  Nothing else changes."""
+    X - here DLY is one too - and 'mu_users' = {X: {'bers', 'EVM_rms', 'sinr': [U][npkt]}}.  Nothing else changes.
+
+    beams=True adds 'MSE_ANG' (beam_planes: the beam-space Wiener smoother on the LS planes) and, with `delay`, 'MSE_DLYANG' (the same
+    step on the DLY planes).  ANG is a source of the multi-user data phase as DLY is, and of no other.  Nothing else changes."""
     nr, nt = engine.nr, engine.nt
     d_tau = None
     if channel is None:
@@ -159,6 +166,10 @@ def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=Tr
         engine.subspace_set_basis(subspace.delay_basis(delay[0], delay[1])[0])
         engine.subspace_smooth_device(ls_re, ls_im, npkt, d_planes[0], d_planes[1])
         estimates.append((DELAY, d_planes))
+    a_planes = {}
+    if beams:
+        a_planes = beam_planes(engine, d_re, d_im, (ls_re, ls_im), d_planes or None, npkt, delay)
+        estimates += list(a_planes.items())
     for name, (e_re, e_im) in estimates:
         engine.nmse_device(h_re, h_im, e_re, e_im, npkt * nr * nt, N_DATA, d_per_link=d_link)
         out['MSE_' + name] = d_link.download().astype(np.float64).reshape(npkt, nr * nt).mean(axis=1)
@@ -171,7 +182,10 @@ def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=Tr
         if mu:
             if delay is not None:
                 planes[DELAY] = d_planes
-            others = [user_planes(engine, snr_db, npkt, seed + u, first_pkt, n_taps, amp_scale, channel, blind, delay, u * float(mu.get('spacing', 15.0)))
+            if beams:
+                planes[BEAMS] = a_planes[BEAMS]
+            others = [user_planes(engine, snr_db, npkt, seed + u, first_pkt, n_taps, amp_scale, channel, blind, delay, u * float(mu.get('spacing', 15.0)),
+                                  beams=beams)
                       for u in range(1, int(mu['users']))]
             nv = np.stack([synth.link_noise_var(d.download(), amp_scale) for d in [d_std] + [o['noise_std'] for o in others]])
             out.update(mu_level(engine, [planes] + [o['planes'] for o in others], nv, npkt, seed, first_pkt, ns=ber['ns'], n_sym=ber['n_sym'],
@@ -181,16 +195,41 @@ def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=Tr
                     a.free()
         d_std.free()
     kept = (d_re, d_im, h_re, h_im, ls_re, ls_im)
-    for a in (o_re, o_im, m_re, m_im, d_hvec, d_snr, d_link) + b_planes + d_planes + (() if keep else kept):
+    for a in (o_re, o_im, m_re, m_im, d_hvec, d_snr, d_link) + b_planes + d_planes + tuple(a for p in a_planes.values() for a in p) + (() if keep else kept):
         a.free()
     if keep:
         out['arrays'] = kept
     return out
 
 
-def user_planes(engine, snr_db, npkt, seed, first_pkt, n_taps, amp_scale, channel, blind, delay, az_offset):
+def beam_planes(engine, d_ltf_re, d_ltf_im, ls, dly, npkt, delay):
+    """The estimators of --beams on resident planes: the noise level nv of every (packet, rx) from the null carriers of the preambles
+    (null_noise_device), the error variance of one LS element nv / Nt, and the beam-space Wiener smoother with the DFT beams
+    (beam_wiener_device) on the LS planes `ls` -> 'ANG'.  With the DLY planes `dly` of the window `delay` the same step with the error
+    variance (nv / Nt) rank / 234 - a delay projection leaves the error white across the antennas - -> 'DLYANG'.  Returns
+    {name: (re, im)} of new DeviceArrays."""
+    nr, nt = engine.nr, engine.nt
+    d_nv = engine.empty((npkt, nr, 2))
+    engine.null_noise_device(d_ltf_re, d_ltf_im, npkt, d_nv)
+    err_var = d_nv.download().view(np.float64)[..., 0] / nt
+    d_nv.free()
+    engine.beam_set_basis(beamspace.dft_basis(nt))
+    out = {}
+    jobs = [(BEAMS, ls, err_var)]
+    if dly is not None:
+        jobs.append((DELAY_BEAMS, dly, err_var * subspace.delay_basis(*delay)[0].shape[1] / N_DATA))
+    for name, (x_re, x_im), v in jobs:
+        d_v = engine.to_device(v.astype(np.float32))
+        out[name] = (engine.empty((npkt, nr, nt, N_DATA)), engine.empty((npkt, nr, nt, N_DATA)))
+        engine.beam_wiener_device(x_re, x_im, npkt, d_v, out[name][0], out[name][1])
+        engine.synchronize()
+        d_v.free()
+    return out
+
+
+def user_planes(engine, snr_db, npkt, seed, first_pkt, n_taps, amp_scale, channel, blind, delay, az_offset, beams=False):
     """Test packets of one further user of the multi-user data phase and its estimates, from the calls evaluate_level makes for its own
-    user: {'planes': {X: (re, im)} for LS, MMSE, DNN, perfect (+ MMSEb, DLY), 'noise_std', 'free': every DeviceArray to free}.  The
+    user: {'planes': {X: (re, im)} for LS, MMSE, DNN, perfect (+ MMSEb, DLY, ANG), 'noise_std', 'free': every DeviceArray to free}.  The
     scattering channel places the user az_offset degrees from the channel's az_deg."""
     nr, nt = engine.nr, engine.nt
     d_tau = None
@@ -223,6 +262,9 @@ def user_planes(engine, snr_db, npkt, seed, first_pkt, n_taps, amp_scale, channe
         engine.subspace_set_basis(subspace.delay_basis(delay[0], delay[1])[0])
         engine.subspace_smooth_device(ls_re, ls_im, npkt, *planes[DELAY])
         free += list(planes[DELAY])
+    if beams:
+        planes[BEAMS] = beam_planes(engine, d_re, d_im, (ls_re, ls_im), None, npkt, None)[BEAMS]
+        free += list(planes[BEAMS])
     return dict(planes=planes, noise_std=d_std, free=free)
 
 
@@ -339,6 +381,9 @@ def metric_fields(mse):
         fields += ['MSE_' + DELAY]
     if MU_FIELDS[0] + 'perfect' in mse:
         fields += [f + x for x in SOURCES + tuple(e for e in (BLIND, DELAY) if MU_FIELDS[0] + e in mse) for f in MU_FIELDS]
+    fields += ['MSE_' + e for e in (BEAMS, DELAY_BEAMS) if 'MSE_' + e in mse]
+    if MU_FIELDS[0] + BEAMS in mse:
+        fields += [f + BEAMS for f in MU_FIELDS]
     return fields
 
 
@@ -348,7 +393,8 @@ def write_metrics(path, mse):
     and dtSNR_X for X in SOURCES - with the MSE rows the names of :653 - and MSE_perfect (zeros), which are then written the same way.
     A level evaluated with blind=True carries MSE_MMSEb (and with the data phase bers_MMSEb, EVM_rms_MMSEb, dtSNR_MMSEb): written behind
     those.  A level evaluated with rx_estimate=True carries bersRx_X, EVM_rmsRx_X and gNMSE_X: written behind those, and MSE_DLY of a level evaluated
-    with delay=(L, pre) behind those; bersMU_X, EVM_rmsMU_X and sinrMU_X of a level evaluated with mu=... last (metric_fields)."""
+    with delay=(L, pre) behind those; bersMU_X, EVM_rmsMU_X and sinrMU_X of a level evaluated with mu=... behind those; MSE_ANG, MSE_DLYANG and
+    bersMU_ANG, EVM_rmsMU_ANG, sinrMU_ANG of a level evaluated with beams=True last (metric_fields)."""
     from scipy.io import savemat
     os.makedirs(os.path.dirname(path), exist_ok=True)
     savemat(path, {f: np.asarray(mse[f], np.float64).reshape(1, -1) for f in metric_fields(mse)})
@@ -360,6 +406,8 @@ def format_table(result):
     cols = list(ESTIMATORS) + blind + ([DELAY] if result.get('delay') else []) + (['BER_' + x for x in list(SOURCES) + blind] if result.get('ber') else [])
     cols += [RX_FIELDS[0] + x for x in list(SOURCES) + blind] if result.get('rx_estimate') else []
     cols += [MU_FIELDS[0] + x for x in list(SOURCES) + blind + ([DELAY] if result.get('delay') else [])] if result.get('mu') else []
+    if result.get('beams'):
+        cols += [BEAMS] + ([DELAY_BEAMS] if result.get('delay') else []) + ([MU_FIELDS[0] + BEAMS] if result.get('mu') else [])
     lines = ['%8s' % 'SNR dB' + ''.join('  %-38s' % (e + ': mean [CI low, CI high]') for e in cols)]
     for lv in result['levels']:
         row = '%8g' % lv['snr_db']
@@ -374,7 +422,7 @@ def format_table(result):
 
 def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500, seed=0, modeldir=None, fit_args=None, n_taps=8,
               amp_scale=True, save_dataset=None, verbose=True, ber=None, channel=None, blind=False, rx_estimate=False,
-              delay_taps=None, delay_pre=0, users=None, mu_reg='zf', user_spacing=15.0):
+              delay_taps=None, delay_pre=0, users=None, mu_reg='zf', user_spacing=15.0, beams=False):
     """Training set -> models (loaded from `modeldir`, else fitted and saved into `out`) -> every level.  Writes
     <out>/BS<Nt>_SNR<s>/metrics.mat per level and <out>/sweep.json, prints the table, returns the result dict (with the per-packet
     arrays under 'per_packet' = {level: {'MSE_LS', ...}}).  Test packets come from the stream seed + 1, behind the index range of
@@ -392,7 +440,11 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
     users=U (U >= 2, needs `ber`) adds the multi-user data phase per level (evaluate_level(mu=...), mu_reg 'zf' or 'rzf', user_spacing in
     degrees): bersMU_X, EVM_rmsMU_X and sinrMU_X in metrics.mat behind every other field, the same with confidence intervals and the
     per-user arrays ('mu_users') per level of sweep.json, which then records 'mu': {users, reg, spacing}; without it every output is
-    what it is without the argument."""
+    what it is without the argument.
+    beams=True adds the estimator ANG per level (evaluate_level(beams=True)) and, with delay_taps, DLYANG: MSE_ANG / MSE_DLYANG in
+    metrics.mat behind every other field, columns of the table and entries per level of sweep.json, which then records 'beams': true;
+    with users also the source ANG of the multi-user data phase (bersMU_ANG, EVM_rmsMU_ANG, sinrMU_ANG and its per-user arrays).
+    Without it every output is what it is without the argument."""
     if rx_estimate and ber is None:
         raise ValueError('rx_estimate needs the data phase (ber)')
     mu = None
@@ -419,6 +471,8 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
     if delay_taps:
         delay = (int(delay_taps), int(delay_pre))
         result['delay'] = dict(taps=delay[0], pre=delay[1], rank=int(subspace.delay_basis(*delay)[0].shape[1]))
+    if beams:
+        result['beams'] = True
     if modeldir:
         load_models(engine, modeldir)
         if save_dataset:
@@ -437,7 +491,7 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
     for i, snr in enumerate(levels):
         t0 = time.perf_counter()
         mse = evaluate_level(engine, snr, n_test, seed + 1, n_train + i * n_test, n_taps, amp_scale, ber=ber, channel=channel, blind=blind,
-                             rx_estimate=rx_estimate, delay=delay, mu=mu)
+                             rx_estimate=rx_estimate, delay=delay, mu=mu, beams=beams)
         sec = time.perf_counter() - t0
         write_metrics(os.path.join(out, 'BS%d_SNR%g' % (engine.nt, snr), 'metrics.mat'), mse)
         lv = dict(snr_db=float(snr), seconds=sec)
@@ -457,6 +511,12 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
                     m, lo, hi = confidence_interval(mse[f + x])
                     lv[f + x] = dict(mean=m, ci_low=lo, ci_high=hi)
             lv['mu_users'] = mse['mu_users']
+        for e in ((BEAMS,) + ((DELAY_BEAMS,) if delay else ())) if beams else ():
+            m, lo, hi = confidence_interval(mse['MSE_' + e])
+            lv[e] = dict(mean=m, ci_low=lo, ci_high=hi)
+        for f in MU_FIELDS if (beams and mu) else ():
+            m, lo, hi = confidence_interval(mse[f + BEAMS])
+            lv[f + BEAMS] = dict(mean=m, ci_low=lo, ci_high=hi)
         result['levels'].append(lv)
         per_packet[float(snr)] = mse
     with open(os.path.join(out, 'sweep.json'), 'w') as f:
@@ -510,6 +570,9 @@ def build_parser():
                    help='add the estimator MMSEb: LMMSE smoothing from the packet\'s own statistics (csi_lmmse_blind_device) - MSE_MMSEb, and with --ber its link metrics')
     p.add_argument('--delayTaps', default=0, type=int, metavar='L',
                    help='add the estimator DLY: the LS rows projected onto the channels of at most L delay taps (csi_subspace_smooth_device, 1 .. 128) - MSE_DLY')
+    p.add_argument('--beams', action='store_true',
+                   help='add the estimator ANG: the beam-space Wiener smoother of the LS planes across the Tx antennas (csi_null_noise_device, '
+                        'csi_beam_wiener_device, nTX <= %d) - MSE_ANG; with --delayTaps also DLYANG (MSE_DLYANG), with --users the source ANG' % beamspace.MAX_NT)
     p.add_argument('--delayPre', default=0, type=int, metavar='P', help='--delayTaps: taps of the window in front of delay 0 (0 .. L)')
     return p
 
@@ -538,6 +601,8 @@ def parse_args(argv=None):
         parser.error('--delayTaps takes 1 .. %d and --delayPre 0 .. L' % subspace.MAX_RANK)
     if args.delayPre and not args.delayTaps:
         parser.error('--delayPre needs --delayTaps')
+    if args.beams and args.nTX > beamspace.MAX_NT:
+        parser.error('--beams takes nTX up to %d' % beamspace.MAX_NT)
     return args
 
 
@@ -556,7 +621,7 @@ def main(argv=None):
               modeldir=args.modeldir or None, fit_args=fit_args, n_taps=args.taps, save_dataset=args.save_dataset or None,
               verbose=not args.quiet, ber=ber, channel=channel_from_args(args), blind=bool(args.blind),
               rx_estimate=bool(args.rxEstimate), delay_taps=args.delayTaps or None, delay_pre=args.delayPre,
-              users=args.users if args.users >= 2 else None, mu_reg=args.muReg, user_spacing=args.userSpacing)
+              users=args.users if args.users >= 2 else None, mu_reg=args.muReg, user_spacing=args.userSpacing, beams=bool(args.beams))
     return 0
 
 

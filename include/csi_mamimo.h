@@ -24,6 +24,9 @@
  *        neither the impulse response nor the SNR                   csi_lmmse_blind[_device]
  *   (an addition, no reference counterpart: the delay-subspace
  *        smoother of an LS estimate, same place in the chain)       csi_subspace_set_basis, csi_subspace_smooth[_device]
+ *   (an addition, no reference counterpart: the beam-space Wiener
+ *        smoother of an LS estimate across the Tx antennas, same
+ *        place in the chain, and the null-carrier noise level)       csi_beam_set_basis, csi_beam_power_device, csi_beam_smooth[_device], csi_beam_wiener[_device], csi_null_noise_device
  *   NMSE_subk           BER_test_maMIMO_LTF.m:675-686                csi_nmse[_device]
  *   known-channel sounding packets  generate_maMIMO_LTF.m:197-342   csi_synth_structured
  *   phased.ScatteringMIMOChannel    helperApplyMUChannel.m:44-143   csi_synth_scattering
@@ -39,7 +42,7 @@
  * has pinned (hipHostMalloc / hipHostRegister).  *_device entry points take device pointers, enqueue on the
  * context's stream and return without waiting; call csi_synchronize before reading results.
  *
- * Device pointers (csi_predict_device, csi_ls_estimate_device, csi_estimate_device, csi_lmmse_estimate_device, csi_lmmse_blind_device, csi_subspace_smooth_device, csi_nmse_device,
+ * Device pointers (csi_predict_device, csi_ls_estimate_device, csi_estimate_device, csi_lmmse_estimate_device, csi_lmmse_blind_device, csi_subspace_smooth_device, csi_beam_power_device, csi_beam_smooth_device, csi_beam_wiener_device, csi_null_noise_device, csi_nmse_device,
  * csi_hybrid_weights_device, csi_link_sim_device, csi_link_sim_rx_device, csi_mu_precoder_device, csi_mu_link_sim_device, csi_viterbi_decode_device, csi_synth_*).  An array of exactly the documented
  * size suffices: it may be a slice of a larger allocation whose neighbours hold live data of any value (NaN and 1e38 included).
  * Nothing outside the arrays is written, nothing outside them reaches a result, and input arrays are not modified.  Every re / im
@@ -47,7 +50,7 @@
  * boundary: the LS and layer-0 kernels move the caller's rows as 16-byte words and by LDS-DMA; hipMalloc, csi_device_malloc and
  * whole torch tensors satisfy that, and so does every packet range of a preamble or CSI plane (Nt is a multiple of 4).  A
  * misaligned plane is refused with CSI_ERR_INVALID_ARG and a text that names the argument, before anything is launched or counted.
- * The remaining arrays - hvec, snr_db, the weights w of csi_subspace_smooth_device, noise_var, noise_std, tau, the per-packet and per-link results, idx, n_atoms, gain, csi,
+ * The remaining arrays - hvec, snr_db, the weights w of csi_subspace_smooth_device, power, w and err_var of the csi_beam_* entry points, noise_var, noise_std, tau, the per-packet and per-link results, idx, n_atoms, gain, csi,
  * llr, bits - and the four planes of csi_nmse_device ([nlinks][n_bins] for ANY n_bins) are read and written element by element and
  * need the alignment of their element type only.
  *
@@ -279,6 +282,58 @@ int  csi_subspace_set_basis(csi_ctx* ctx, const float* q_re, const float* q_im, 
 int  csi_subspace_smooth(csi_ctx* ctx, const float* h_re, const float* h_im, int64_t npkt, const float* w, float* out_re, float* out_im);
 int  csi_subspace_smooth_device(csi_ctx* ctx, const float* d_h_re, const float* d_h_im, int64_t npkt, const float* d_w,
                                 float* d_out_re, float* d_out_im);
+
+/* Beam-space Wiener smoother of a CSI tensor across the Tx antennas (csrc/beam_smooth.hip.h, csrc/csi_beam.hpp).  An
+ * addition: the reference has no such estimator.  It stands where LMMSE_ce stands (helperMIMOChannelEstimate.m:37-39) and is the
+ * antenna-domain counterpart of the delay-subspace smoother above: the paths that reach a user leave a half-wavelength ULA inside a
+ * narrow cone, so across the antennas h[p][rx][:][k] is a sum of a few steering vectors.  It needs no direction, no angular spread, no
+ * SNR from a simulator and no training.
+ * The planes are [npkt][Nr][Nt][234], re and im separate, as everywhere.  For an orthonormal basis A [Nt][nb] with
+ * 1 <= nb <= Nt <= 128, for every (packet p, rx r):
+ *     t_b[k]  = sum_j conj(A[j][b]) h[p][r][j][k]              b < nb, k < 234
+ *     E[p][r][b] = (1 / 234) sum_k |t_b[k]|^2                  (beam power)
+ *     y_j[k]  = sum_b A[j][b] w[p][r][b] t_b[k]
+ * w float32 [npkt][Nr][nb]; NULL means all ones (the projection onto the span of A).  The Wiener entry makes its own weights from
+ * v float32 [npkt][Nr], the error variance of ONE element of the input planes:  w = 1 - v / E  where E > v,  w = 0  everywhere else
+ * (E = 0 falls under this case).  Non-finite inputs are not screened.
+ * The Python package builds the DFT beams of the half-wavelength ULA (beamspace.dft_basis):  A[j][b] = exp(-2 pi i y_j u_b) / sqrt(Nt),
+ * y_j = (j - (Nt - 1) / 2) / 2,  u_b = 2 (b - Nt / 2) / Nt  - the sign of the transmit factor exp(-2 pi i y_j v_s) of
+ * csrc/synth_scattering.hip.h.  The library accepts ANY orthonormal A, as csi_subspace_set_basis does.
+ * csi_beam_set_basis: host planes a_re / a_im [Nt][nb], kept on the context as device images padded to whole tiles of 32; a second
+ * call replaces them (it waits for the stream; graphs captured with the earlier basis must be captured again).  Refused with text: nb
+ * outside 1 .. Nt, null planes, a non-finite entry, an A^H A further than 1e-4 from the identity in any entry (checked in double on
+ * the host), an open capture, a single-input context, Nt > 128.
+ * csi_beam_power_device: d_power [npkt][Nr][nb] = E.  One launch.
+ * csi_beam_smooth_device: d_w [npkt][Nr][nb] or NULL, d_out like d_h.  One launch, no workspace.  out may be the input planes
+ * themselves, re with re and im with im; any other overlap of an output plane with an input plane or with the other output plane is
+ * refused.
+ * csi_beam_wiener_device: d_err_var [npkt][Nr], d_w_out [npkt][Nr][nb] or NULL.  Three launches: the power pass, the weight pass, the
+ * smoothing pass (h is read twice).  E, and w when the caller keeps none, live in a context workspace sized by eager calls: inside
+ * csi_capture_begin / _end the call is usable after one eager call of the same shape, as csi_lmmse_blind_device is.  The output is
+ * bit for bit what csi_beam_smooth_device gives with the w it reports, and E bit for bit what csi_beam_power_device writes.
+ * All products are exact fp32 products with fp32 accumulation (v_mfma_f32_32x32x2_f32) and every sum, the 234-carrier sum of E
+ * included, runs in an order that depends on Nt, nb and the carrier index only (no atomics): the bits of a (packet, rx) do not depend
+ * on the call, the chunk or its position in the batch.  The *_device entries enqueue on the context's stream and do not wait.
+ * csi_beam_smooth / csi_beam_wiener: host buffers, in the packet chunks of csi_subspace_smooth (256 MiB of staging; the context's
+ * workspace_bytes when that is smaller); same bits as the device entries.  w_out of csi_beam_wiener may be NULL.
+ * csi_null_noise_device: d_noise_var double [npkt][Nr] = the null-carrier statistic of csi_lmmse_blind_device on its own, from the
+ * preambles d_ltf [npkt][Nr][len_ltf]: same kernel, same definition, same bits as that entry's noise_var output.  The error variance
+ * of one element of the LS estimate of these preambles is noise_var / Nt.
+ * Every entry returns -1 on a null context, and refuses with text, before anything is launched or counted: npkt < 0, null required
+ * pointers, planes off a 16-byte boundary, and (the csi_beam_* entries) no basis set (CSI_ERR_NOT_READY).  npkt == 0 returns 0 and
+ * launches nothing.  Read-only option "beam_launches"; profile entries "beam_power" (planes * 234 * nb * (8 Nt + 3) flop,
+ * planes * (8 * 234 Nt + 4 nb) + 8 Nt nb bytes) and "beam_smooth" (16 * planes * 234 * Nt * nb flop, planes * (16 * 234 Nt + 4 nb)
+ * + 16 Nt nb bytes); planes = npkt * Nr. */
+int  csi_beam_set_basis(csi_ctx* ctx, const float* a_re, const float* a_im, int nb);
+int  csi_beam_power_device(csi_ctx* ctx, const float* d_h_re, const float* d_h_im, int64_t npkt, float* d_power);
+int  csi_beam_smooth(csi_ctx* ctx, const float* h_re, const float* h_im, int64_t npkt, const float* w, float* out_re, float* out_im);
+int  csi_beam_smooth_device(csi_ctx* ctx, const float* d_h_re, const float* d_h_im, int64_t npkt, const float* d_w,
+                            float* d_out_re, float* d_out_im);
+int  csi_beam_wiener(csi_ctx* ctx, const float* h_re, const float* h_im, int64_t npkt, const float* err_var, float* out_re, float* out_im,
+                     float* w_out);
+int  csi_beam_wiener_device(csi_ctx* ctx, const float* d_h_re, const float* d_h_im, int64_t npkt, const float* d_err_var,
+                            float* d_out_re, float* d_out_im, float* d_w_out);
+int  csi_null_noise_device(csi_ctx* ctx, const float* d_ltf_re, const float* d_ltf_im, int64_t npkt, double* d_noise_var);
 
 /* Hybrid beamforming weights from a CSI tensor (BER_test_maMIMO_LTF.m:347-376, generate_maMIMO_LTF.m:414-425: the toolbox's
  * SVD + orthogonal-matching-pursuit split of the optimal precoder into an analog and a digital part).  One item = one
@@ -585,7 +640,7 @@ int  csi_set_option(csi_ctx* ctx, const char* name, int64_t value);
 /* Current value of an option, or of the read-only values: "hs_launches" (split-engine GEMMs launched), "hs_range_fallbacks"
  * (csi_predict calls repeated on the fp32 MFMA kernels), "hs_weight_pins" / "hs_weight_err_e12" (layers pinned to the fp32 kernels
  * at load because their split copies were not fp32-grade; worst relative error x 1e12), "band_available" (the assembly band kernel
- * is embedded in this build), "graph_replays", "subspace_launches" (kernels launched by csi_subspace_smooth[_device]), "mu_launches" (kernels launched by csi_mu_precoder_device / csi_mu_link_sim_device), "lmmse_blind_fallbacks" ((packet, rx) pairs csi_lmmse_blind[_device] handed back unsmoothed), "ls_pilot_fast" (0 generic / 1 Sylvester / 2 permuted pilot), "comm_world",
+ * is embedded in this build), "graph_replays", "subspace_launches" (kernels launched by csi_subspace_smooth[_device]), "beam_launches" (kernels launched by the csi_beam_* entry points), "mu_launches" (kernels launched by csi_mu_precoder_device / csi_mu_link_sim_device), "lmmse_blind_fallbacks" ((packet, rx) pairs csi_lmmse_blind[_device] handed back unsmoothed), "ls_pilot_fast" (0 generic / 1 Sylvester / 2 permuted pilot), "comm_world",
  * "comm_rank", "comm_blobs", "comm_bytes" (communicator and last broadcast), "hp_direct_out_calls", and where the last pipelined
  * host-buffer call spent its time in microseconds: "hp_total_us", "hp_stage_us", "hp_wait_stage_us", "hp_wait_out_us", "hp_weave_us". */
 int  csi_get_option(csi_ctx* ctx, const char* name, int64_t* value);
