@@ -1,8 +1,10 @@
-// csi_beam.hpp - host side of the beam-space smoother (kernels: beam_smooth.hip.h): the basis check and its two device
-// images, the argument checks, the launches of csi_beam_power_device / csi_beam_smooth_device / csi_beam_wiener_device and the chunked
-// host entry points.
+// csi_beam.hpp - host side of the beam-space smoother (kernels: beam_smooth.hip.h): the basis and its two device images,
+// the argument checks, the launches of csi_beam_power_device / csi_beam_smooth_device / csi_beam_wiener_device and the two host entry
+// points as one staged call.  The orthonormality check of the basis and the overlap rule of the planes are csi_stage.hpp's, shared
+// with csi_subspace.hpp.
 #pragma once
 #include "csi_context.hpp"
+#include "csi_stage.hpp"
 #include "beam_smooth.hip.h"
 
 namespace {
@@ -21,27 +23,7 @@ int beam_set_basis(csi_ctx* c, const float* a_re, const float* a_im, int nb) {
     if (!a_re || !a_im) return fail(c, CSI_ERR_INVALID_ARG, "%s: null basis planes", who);
     if (c->user_capture) return fail(c, CSI_ERR_INVALID_ARG, "%s: the basis cannot be replaced while a capture is open", who);
     const int nt = cf.nt;
-    const size_t na = (size_t)nt * nb;
-    for (size_t i = 0; i < na; ++i)
-        if (!std::isfinite(a_re[i]) || !std::isfinite(a_im[i]))
-            return fail(c, CSI_ERR_INVALID_ARG, "%s: non-finite basis entry at [%zu][%zu]", who, i / nb, i % nb);
-    // A^H A against the identity, in double on the host (nt nb^2 complex products once per basis)
-    double worst = 0.0;
-    int wi = 0, wj = 0;
-    for (int i = 0; i < nb; ++i)
-        for (int j = i; j < nb; ++j) {
-            double sr = 0.0, si = 0.0;
-            for (int k = 0; k < nt; ++k) {
-                const double ar = a_re[(size_t)k * nb + i], ai = a_im[(size_t)k * nb + i];
-                const double br = a_re[(size_t)k * nb + j], bi = a_im[(size_t)k * nb + j];
-                sr += ar * br + ai * bi;          // conj(a) b
-                si += ar * bi - ai * br;
-            }
-            const double d = std::hypot(sr - (i == j ? 1.0 : 0.0), si);
-            if (d > worst) { worst = d; wi = i; wj = j; }
-        }
-    if (!(worst <= BM_ORTHO_TOL))
-        return fail(c, CSI_ERR_INVALID_ARG, "%s: basis is not orthonormal: |A^H A - I| = %.3g at [%d][%d] (at most %g)", who, worst, wi, wj, BM_ORTHO_TOL);
+    if (int rc = basis_orthonormal(c, who, a_re, a_im, nt, nb, BM_ORTHO_TOL, 'A')) return rc;
     const int ntp = bm_pad(nt), nbp = bm_pad(nb);
     const size_t plane = (size_t)ntp * nbp;
     std::vector<float> img(4 * plane, 0.0f);
@@ -69,12 +51,6 @@ int beam_set_basis(csi_ctx* c, const float* a_re, const float* a_im, int nb) {
     return CSI_OK;
 }
 
-// [p, p + bytes) and [q, q + bytes) share a byte
-inline bool bm_overlap(const void* p, const void* q, size_t bytes) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-    return a < b + bytes && b < a + bytes;
-}
-
 // what every entry refuses except the alignment of the planes (the caller's: planes_aligned).  `rest`: the other required pointers are
 // all there
 int beam_check(csi_ctx* c, const char* who, const float* h_re, const float* h_im, int64_t npkt, bool rest, const char* names) {
@@ -86,13 +62,9 @@ int beam_check(csi_ctx* c, const char* who, const float* h_re, const float* h_im
     return CSI_OK;
 }
 
-// out may be the input planes themselves, re with re and im with im; every other shared byte is refused
+// the overlap rule of the in / out planes (csi_stage.hpp: inout_planes_disjoint) over npkt packets
 int beam_planes_disjoint(csi_ctx* c, const char* who, const float* h_re, const float* h_im, const float* out_re, const float* out_im, int64_t npkt) {
-    const size_t bytes = (size_t)npkt * c->cfg.nr * c->cfg.nt * BM_N * sizeof(float);
-    if ((out_re != h_re && bm_overlap(out_re, h_re, bytes)) || (out_im != h_im && bm_overlap(out_im, h_im, bytes)) ||
-        bm_overlap(out_re, h_im, bytes) || bm_overlap(out_im, h_re, bytes) || bm_overlap(out_re, out_im, bytes))
-        return fail(c, CSI_ERR_INVALID_ARG, "%s: an output plane may be its own input plane (re with re, im with im); any other overlap of the planes is refused", who);
-    return CSI_OK;
+    return inout_planes_disjoint(c, who, h_re, h_im, out_re, out_im, (size_t)npkt * c->cfg.nr * c->cfg.nt * BM_N * sizeof(float));
 }
 
 BeamArgs beam_args(const csi_ctx* c, const float* d_h_re, const float* d_h_im, int64_t npkt) {
@@ -189,55 +161,21 @@ int beam_wiener_device(csi_ctx* c, const char* who, const float* d_h_re, const f
     return beam_smooth_launch(c, d_h_re, d_h_im, npkt, d_w, d_out_re, d_out_im);
 }
 
-// the packet chunk of the host entry points: that of csi_subspace_smooth (256 MiB of staging for four planes, or what the context's
-// workspace_bytes allows when that is less)
-int64_t beam_host_chunk(const csi_ctx* c, int64_t npkt) {
-    const csi_config& cf = c->cfg;
-    const size_t pkt_f = (size_t)cf.nr * cf.nt * BM_N;
-    const int64_t budget = cf.workspace_bytes > 0 ? std::min<int64_t>(cf.workspace_bytes, (int64_t)256 << 20) : ((int64_t)256 << 20);
-    const int64_t chunk = std::max<int64_t>(1, budget / (int64_t)(4 * pkt_f * sizeof(float)));
-    return std::min(chunk, npkt);
-}
-
-// both host forms.  wiener: v (err_var, [npkt][Nr]) makes the weights, which go back to w_out when that is given; otherwise w
-// ([npkt][Nr][nb] or null) is the smoother's input
+// both host forms, as one staged call (csi_stage.hpp) whose chunk is sized by the four CSI planes.  wiener: v (err_var, [npkt][Nr]) makes
+// the weights, which go back to w_out when that is given; otherwise w ([npkt][Nr][nb] or null) is the smoother's input
 int beam_host(csi_ctx* c, const char* who, bool wiener, const float* h_re, const float* h_im, int64_t npkt, const float* w, const float* v,
               float* out_re, float* out_im, float* w_out) {
     if (int rc = beam_check(c, who, h_re, h_im, npkt, out_re && out_im && (!wiener || v), wiener ? "h, err_var, out" : "h, out")) return rc;
     if (npkt == 0) return CSI_OK;
     const csi_config& cf = c->cfg;
     HIP_TRY(c, hipSetDevice(cf.device));
-    const int nb = c->beam_nb;
-    const size_t pkt_f = (size_t)cf.nr * cf.nt * BM_N;                    // floats per packet and plane
-    const size_t w_f = (w || v) ? (size_t)cf.nr * nb : 0;
-    const size_t v_f = v ? (size_t)cf.nr : 0;
-    const int64_t chunk = beam_host_chunk(c, npkt);
-    int rc = ensure_bytes(c, &c->stage, &c->stage_bytes, (4 * pkt_f + w_f + v_f) * sizeof(float) * (size_t)chunk);
-    if (rc) return rc;
-    float* d_re = reinterpret_cast<float*>(c->stage);      // planes of whole packets: pkt_f is a multiple of 4 floats (nt % 4 == 0)
-    float* d_im = d_re + pkt_f * chunk;
-    float* d_ore = d_im + pkt_f * chunk;
-    float* d_oim = d_ore + pkt_f * chunk;
-    float* d_w = w_f ? d_oim + pkt_f * chunk : nullptr;
-    float* d_v = v ? d_w + w_f * chunk : nullptr;
-    for (int64_t p0 = 0; p0 < npkt; p0 += chunk) {
-        const int64_t np = std::min(chunk, npkt - p0);
-        HIP_TRY(c, hipMemcpyAsync(d_re, h_re + p0 * pkt_f, pkt_f * np * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(d_im, h_im + p0 * pkt_f, pkt_f * np * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        if (v) {
-            HIP_TRY(c, hipMemcpyAsync(d_v, v + p0 * v_f, v_f * np * sizeof(float), hipMemcpyHostToDevice, c->stream));
-            rc = beam_wiener_device(c, who, d_re, d_im, np, d_v, d_ore, d_oim, d_w);
-        } else {
-            if (w) HIP_TRY(c, hipMemcpyAsync(d_w, w + p0 * w_f, w_f * np * sizeof(float), hipMemcpyHostToDevice, c->stream));
-            rc = beam_smooth_launch(c, d_re, d_im, np, d_w, d_ore, d_oim);
-        }
-        if (rc) return rc;
-        HIP_TRY(c, hipMemcpyAsync(out_re + p0 * pkt_f, d_ore, pkt_f * np * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(out_im + p0 * pkt_f, d_oim, pkt_f * np * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        if (w_out) HIP_TRY(c, hipMemcpyAsync(w_out + p0 * w_f, d_w, w_f * np * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    return CSI_OK;
+    const size_t pkt = (size_t)cf.nr * cf.nt * BM_N * sizeof(float);      // bytes per packet and plane: a multiple of 16 (nt % 4 == 0)
+    StagePlane p[] = {{pkt, h_re, nullptr}, {pkt, h_im, nullptr}, {pkt, nullptr, out_re}, {pkt, nullptr, out_im},
+                      {(w || v) ? (size_t)cf.nr * c->beam_nb * sizeof(float) : 0, w, w_out}, {v ? (size_t)cf.nr * sizeof(float) : 0, v, nullptr}};
+    return staged_call(c, npkt, stage_budget(c), 4 * pkt, 0, true, p, [&](int64_t, int64_t np) {
+        if (v) return beam_wiener_device(c, who, p[0].as<float>(), p[1].as<float>(), np, p[5].as<float>(), p[2].as<float>(), p[3].as<float>(), p[4].as<float>());
+        return beam_smooth_launch(c, p[0].as<float>(), p[1].as<float>(), np, w ? p[4].as<float>() : nullptr, p[2].as<float>(), p[3].as<float>());
+    });
 }
 
 }  // namespace

@@ -1,8 +1,9 @@
 // csi_hybrid.hpp - host side of the hybrid beamforming weights (kernels: hybrid_weights.hip.h): the dictionary on
-// the context, the chunked launch sequence of csi_hybrid_weights_device, the host-pointer form, and the caller-driven graph
+// the context, the chunked launch sequence of csi_hybrid_weights_device, the host-pointer form (a staged call, csi_stage.hpp), and the caller-driven graph
 // capture that puts several device-pointer calls (csi_estimate_device + csi_hybrid_weights_device) into one hipGraph.
 #pragma once
 #include "csi_context.hpp"
+#include "csi_stage.hpp"
 
 namespace {
 
@@ -155,7 +156,8 @@ int hybrid_weights_device(csi_ctx* c, const float* d_h_re, const float* d_h_im, 
     return CSI_OK;
 }
 
-// host pointers: upload / compute / download per packet chunk through the staging buffer csi_lmmse_estimate and csi_nmse use
+// host pointers: a staged call (csi_stage.hpp) whose chunk is sized by everything it stages.  The optional planes keep their room when the
+// caller leaves them out; the device form then gets a null pointer in their place
 int hybrid_weights_host(csi_ctx* c, const float* h_re, const float* h_im, const float* eval_re, const float* eval_im, int64_t npkt,
                         int ns, int ntrf, float stop_tol, float* fbb_re, float* fbb_im, int32_t* idx, int32_t* n_atoms, float* gain,
                         float* frf_mean_re, float* frf_mean_im) {
@@ -169,49 +171,19 @@ int hybrid_weights_host(csi_ctx* c, const float* h_re, const float* h_im, const 
     if (npkt == 0) return CSI_OK;
     const csi_config& cf = c->cfg;
     HIP_TRY(c, hipSetDevice(cf.device));
-    const size_t pkt_f = (size_t)cf.nr * cf.nt * HY_N;                                     // floats per packet and CSI plane
-    const size_t out_f = (size_t)HY_N * (2 * ns * ntrf + ntrf + 2) + (size_t)2 * ntrf * cf.nt;   // result words per packet
-    const size_t per_pkt = (4 * pkt_f + out_f) * sizeof(float);
-    int64_t chunk = std::max<int64_t>(1, ((int64_t)256 << 20) / (int64_t)per_pkt);
-    chunk = std::min(chunk, npkt);
-    rc = ensure_bytes(c, &c->stage, &c->stage_bytes, per_pkt * (size_t)chunk);
-    if (rc) return rc;
-    float* d_re = reinterpret_cast<float*>(c->stage);
-    float* d_im = d_re + pkt_f * chunk;
-    float* d_ere = d_im + pkt_f * chunk;
-    float* d_eim = d_ere + pkt_f * chunk;
-    float* d_fre = d_eim + pkt_f * chunk;
-    float* d_fim = d_fre + (size_t)HY_N * ns * ntrf * chunk;
-    int32_t* d_idx = reinterpret_cast<int32_t*>(d_fim + (size_t)HY_N * ns * ntrf * chunk);
-    int32_t* d_na = d_idx + (size_t)HY_N * ntrf * chunk;
-    float* d_gain = reinterpret_cast<float*>(d_na + (size_t)HY_N * chunk);
-    float* d_mre = d_gain + (size_t)HY_N * chunk;
-    float* d_mim = d_mre + (size_t)ntrf * cf.nt * chunk;
-    for (int64_t p0 = 0; p0 < npkt; p0 += chunk) {
-        const int64_t np = std::min(chunk, npkt - p0);
-        const size_t items = (size_t)np * HY_N, i0 = (size_t)p0 * HY_N;
-        HIP_TRY(c, hipMemcpyAsync(d_re, h_re + p0 * pkt_f, pkt_f * np * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(d_im, h_im + p0 * pkt_f, pkt_f * np * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        if (eval_re) {
-            HIP_TRY(c, hipMemcpyAsync(d_ere, eval_re + p0 * pkt_f, pkt_f * np * sizeof(float), hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(c, hipMemcpyAsync(d_eim, eval_im + p0 * pkt_f, pkt_f * np * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        }
-        rc = hybrid_weights_device(c, d_re, d_im, eval_re ? d_ere : nullptr, eval_re ? d_eim : nullptr, np, ns, ntrf, stop_tol, d_fre, d_fim,
-                                   d_idx, n_atoms ? d_na : nullptr, gain ? d_gain : nullptr, frf_mean_re ? d_mre : nullptr, frf_mean_re ? d_mim : nullptr);
-        if (rc) return rc;
-        HIP_TRY(c, hipMemcpyAsync(fbb_re + i0 * ns * ntrf, d_fre, items * ns * ntrf * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(fbb_im + i0 * ns * ntrf, d_fim, items * ns * ntrf * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(idx + i0 * ntrf, d_idx, items * ntrf * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        if (n_atoms) HIP_TRY(c, hipMemcpyAsync(n_atoms + i0, d_na, items * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        if (gain) HIP_TRY(c, hipMemcpyAsync(gain + i0, d_gain, items * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        if (frf_mean_re) {
-            const size_t mf = (size_t)np * ntrf * cf.nt;
-            HIP_TRY(c, hipMemcpyAsync(frf_mean_re + (size_t)p0 * ntrf * cf.nt, d_mre, mf * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(c, hipMemcpyAsync(frf_mean_im + (size_t)p0 * ntrf * cf.nt, d_mim, mf * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        }
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    return CSI_OK;
+    const size_t pkt = (size_t)cf.nr * cf.nt * HY_N * sizeof(float);      // bytes per packet and CSI plane
+    const size_t item = (size_t)HY_N * 4;                                 // ... and per 4-byte word of a carrier's result
+    const size_t mean = (size_t)ntrf * cf.nt * sizeof(float);
+    StagePlane p[] = {{pkt, h_re, nullptr}, {pkt, h_im, nullptr}, {pkt, eval_re, nullptr}, {pkt, eval_im, nullptr},
+                      {item * ns * ntrf, nullptr, fbb_re}, {item * ns * ntrf, nullptr, fbb_im}, {item * ntrf, nullptr, idx},
+                      {item, nullptr, n_atoms}, {item, nullptr, gain}, {mean, nullptr, frf_mean_re}, {mean, nullptr, frf_mean_im}};
+    size_t per_pkt = 0;
+    for (const StagePlane& q : p) per_pkt += q.bytes;
+    return staged_call(c, npkt, STAGE_BUDGET, per_pkt, 0, true, p, [&](int64_t, int64_t np) {
+        return hybrid_weights_device(c, p[0].as<float>(), p[1].as<float>(), eval_re ? p[2].as<float>() : nullptr, eval_re ? p[3].as<float>() : nullptr, np,
+                                     ns, ntrf, stop_tol, p[4].as<float>(), p[5].as<float>(), p[6].as<int32_t>(), n_atoms ? p[7].as<int32_t>() : nullptr,
+                                     gain ? p[8].as<float>() : nullptr, frf_mean_re ? p[9].as<float>() : nullptr, frf_mean_re ? p[10].as<float>() : nullptr);
+    });
 }
 
 // ---------------------------------------------------------------- caller-driven capture of several device-pointer calls

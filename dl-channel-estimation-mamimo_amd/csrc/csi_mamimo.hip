@@ -14,6 +14,7 @@
 #include "csi_dnn_hs.hpp"
 #include "csi_dnn_f32.hpp"
 #include "csi_ls.hpp"
+#include "csi_lmmse.hpp"
 #include "csi_dnn_small.hpp"
 #include "csi_dnn_bf16.hpp"
 #include "csi_train.hpp"
@@ -865,171 +866,49 @@ int csi_ls_estimate_device(csi_ctx* c, const float* d_ltf_re, const float* d_ltf
     return ls_run(c, d_ltf_re, d_ltf_im, npkt, d_h_re, d_h_im);
 }
 
+// ---------------------------------------------------------------- LMMSE smoothers (csi_lmmse.hpp, lmmse.hip.h)
 int csi_lmmse_estimate_device(csi_ctx* c, const float* d_h_re, const float* d_h_im, int64_t npkt, const float* d_hvec, int L,
                               const float* d_snr_db, float* d_out_re, float* d_out_im) {
     if (!c) return CSI_ERR_INVALID_ARG;
-    if (c->cfg.nt == 0) return fail(c, CSI_ERR_INVALID_ARG, "single-input context (nt=0): no LMMSE estimate");
-    if (npkt < 0 || L < 1 || (npkt > 0 && (!d_h_re || !d_h_im || !d_hvec || !d_snr_db || !d_out_re || !d_out_im)))
-        return fail(c, CSI_ERR_INVALID_ARG, "csi_lmmse_estimate_device: bad argument");
+    if (int rc = lmmse_estimate_check(c, d_h_re, d_h_im, npkt, d_hvec, L, d_snr_db, d_out_re, d_out_im)) return rc;
     if (npkt == 0) return CSI_OK;
     if (int rc = planes_aligned(c, "csi_lmmse_estimate_device", {{"d_h_re", d_h_re}, {"d_h_im", d_h_im}, {"d_out_re", d_out_re}, {"d_out_im", d_out_im}})) return rc;
-    const csi_config& cf = c->cfg;
-    HIP_TRY(c, hipSetDevice(cf.device));
-    const int n_jc = (cf.nt + LM_RHS - 1) / LM_RHS;
-    const int64_t nblk = npkt * cf.nr;
-    const int64_t max_items = ((int64_t)1 << 30) / n_jc / cf.nr * cf.nr;      // whole packets per launch
-    for (int64_t b0 = 0; b0 < nblk; b0 += max_items) {
-        const int64_t nb = std::min(max_items, nblk - b0);
-        LmmseArgs a{};
-        a.h_re = d_h_re + (size_t)b0 * cf.nt * LM_N;
-        a.h_im = d_h_im + (size_t)b0 * cf.nt * LM_N;
-        a.hvec = d_hvec + (size_t)(b0 / cf.nr) * L;
-        a.snr_db = d_snr_db + b0;
-        a.o_re = d_out_re + (size_t)b0 * cf.nt * LM_N;
-        a.o_im = d_out_im + (size_t)b0 * cf.nt * LM_N;
-        a.nt = cf.nt; a.nr = cf.nr; a.L = L;
-        // per right-hand side: 2 * n^2 complex multiply-adds = 16 n^2 flop (fp64)
-        ProfScope ps(c, K_LMMSE, (double)nb * (cf.nt + n_jc) * 16.0 * LM_N * LM_N, (double)nb * cf.nt * LM_N * 16.0);
-        hipLaunchKernelGGL(lmmse_levinson_kernel, dim3((unsigned)(nb * n_jc)), dim3(LM_THREADS), 0, c->stream, a, n_jc);
-        HIP_TRY(c, hipGetLastError());
-    }
-    return CSI_OK;
+    return lmmse_estimate_launch(c, d_h_re, d_h_im, npkt, d_hvec, L, d_snr_db, d_out_re, d_out_im);
 }
 
 int csi_lmmse_estimate(csi_ctx* c, const float* h_re, const float* h_im, int64_t npkt, const float* hvec, int L,
                        const float* snr_db, float* out_re, float* out_im) {
     if (!c) return CSI_ERR_INVALID_ARG;
-    if (npkt < 0 || L < 1 || (npkt > 0 && (!h_re || !h_im || !hvec || !snr_db || !out_re || !out_im)))
-        return fail(c, CSI_ERR_INVALID_ARG, "csi_lmmse_estimate: bad argument");
-    if (npkt == 0) return CSI_OK;
-    const csi_config& cf = c->cfg;
-    HIP_TRY(c, hipSetDevice(cf.device));
-    const size_t pkt_f = (size_t)cf.nr * cf.nt * LM_N;                     // floats per packet and plane
-    int64_t chunk = std::max<int64_t>(1, ((int64_t)256 << 20) / (int64_t)(4 * pkt_f * sizeof(float)));
-    chunk = std::min(chunk, npkt);
-    const size_t need = (4 * pkt_f + (size_t)L + cf.nr) * sizeof(float) * (size_t)chunk;
-    int rc = ensure_bytes(c, &c->stage, &c->stage_bytes, need);
-    if (rc) return rc;
-    float* d_re = reinterpret_cast<float*>(c->stage);
-    float* d_im = d_re + pkt_f * chunk;
-    float* d_ore = d_im + pkt_f * chunk;
-    float* d_oim = d_ore + pkt_f * chunk;
-    float* d_hv = d_oim + pkt_f * chunk;
-    float* d_snr = d_hv + (size_t)L * chunk;
-    for (int64_t p0 = 0; p0 < npkt; p0 += chunk) {
-        const int64_t np = std::min(chunk, npkt - p0);
-        HIP_TRY(c, hipMemcpyAsync(d_re, h_re + p0 * pkt_f, pkt_f * np * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(d_im, h_im + p0 * pkt_f, pkt_f * np * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(d_hv, hvec + p0 * L, (size_t)L * np * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(d_snr, snr_db + p0 * cf.nr, (size_t)cf.nr * np * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        rc = csi_lmmse_estimate_device(c, d_re, d_im, np, d_hv, L, d_snr, d_ore, d_oim);
-        if (rc) return rc;
-        HIP_TRY(c, hipMemcpyAsync(out_re + p0 * pkt_f, d_ore, pkt_f * np * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(out_im + p0 * pkt_f, d_oim, pkt_f * np * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    return CSI_OK;
+    return lmmse_estimate_host(c, h_re, h_im, npkt, hvec, L, snr_db, out_re, out_im);
 }
 
-// ---------------------------------------------------------------- LMMSE smoothing from the packet's own statistics (lmmse.hip.h, second half)
 int csi_lmmse_blind_device(csi_ctx* c, const float* d_ltf_re, const float* d_ltf_im, const float* d_h_re, const float* d_h_im, int64_t npkt,
                            float* d_out_re, float* d_out_im, double* d_noise_var, double* d_corr) {
     if (!c) return CSI_ERR_INVALID_ARG;
     static const char* who = "csi_lmmse_blind_device";
-    const csi_config& cf = c->cfg;
-    if (cf.nt == 0) return fail(c, CSI_ERR_INVALID_ARG, "single-input context (nt=0): no LMMSE estimate");
-    if (npkt <= 0) return fail(c, CSI_ERR_INVALID_ARG, "%s: npkt %lld must be positive", who, (long long)npkt);
-    if (!d_ltf_re || !d_ltf_im || !d_h_re || !d_h_im || !d_out_re || !d_out_im)
-        return fail(c, CSI_ERR_INVALID_ARG, "%s: null required pointer (ltf, h, out)", who);
-    if (cf.len_ltf < LMB_SYM * cf.nt || cf.len_ltf % 4 != 0)
-        return fail(c, CSI_ERR_INVALID_ARG, "%s: len_ltf %d does not hold %d sounding symbols of 320 samples in 16-byte words", who, cf.len_ltf, cf.nt);
+    if (int rc = lmmse_blind_check(c, who, d_ltf_re, d_ltf_im, d_h_re, d_h_im, npkt, d_out_re, d_out_im)) return rc;
     if (int rc = planes_aligned(c, who, {{"d_ltf_re", d_ltf_re}, {"d_ltf_im", d_ltf_im}, {"d_h_re", d_h_re}, {"d_h_im", d_h_im},
                                          {"d_out_re", d_out_re}, {"d_out_im", d_out_im}})) return rc;
     if ((reinterpret_cast<uintptr_t>(d_noise_var) | reinterpret_cast<uintptr_t>(d_corr)) & 7)
         return fail(c, CSI_ERR_INVALID_ARG, "%s: d_noise_var / d_corr must be aligned for doubles (got %p / %p)", who, (void*)d_noise_var, (void*)d_corr);
-    HIP_TRY(c, hipSetDevice(cf.device));
-    const int n_jc = (cf.nt + LM_RHS - 1) / LM_RHS;
-    const int64_t nblk = npkt * cf.nr;
-    // the statistics the caller does not keep, and the fallback flags, live in the context ([nblk] nv | [nblk][234] c | [nblk] flags)
-    const size_t ws_need = (size_t)nblk * (sizeof(double) + LM_N * sizeof(cd) + sizeof(int));
-    if (int rc = ensure_bytes(c, &c->lmb_ws, &c->lmb_ws_bytes, ws_need)) return rc;
-    double* nv = d_noise_var ? d_noise_var : reinterpret_cast<double*>(c->lmb_ws);
-    cd* corr = d_corr ? reinterpret_cast<cd*>(d_corr) : reinterpret_cast<cd*>(c->lmb_ws + (size_t)nblk * sizeof(double));
-    int* flags = reinterpret_cast<int*>(c->lmb_ws + (size_t)nblk * (sizeof(double) + LM_N * sizeof(cd)));
-    const int64_t max_items = ((int64_t)1 << 30) / n_jc / cf.nr * cf.nr;      // whole packets per launch
-    for (int64_t b0 = 0; b0 < nblk; b0 += max_items) {
-        const int64_t nb = std::min(max_items, nblk - b0);
-        const size_t ho = (size_t)b0 * cf.nt * LM_N;
-        {
-            LmmseNoiseArgs a{};
-            a.ltf_re = d_ltf_re + (size_t)b0 * cf.len_ltf; a.ltf_im = d_ltf_im + (size_t)b0 * cf.len_ltf;
-            a.tw = c->lmb_tw; a.nv = nv + b0; a.nt = cf.nt; a.len_ltf = cf.len_ltf;
-            // per (symbol, null bin): 256 complex multiply-adds in fp64 pairs = 4 x 11 flop each
-            ProfScope ps(c, K_LMMSE_NULL_NOISE, (double)nb * cf.nt * LMB_NULLS * LMB_FFT * 44.0, (double)nb * cf.nt * LMB_FFT * 8.0);
-            hipLaunchKernelGGL(lmmse_null_noise_kernel, dim3((unsigned)nb), dim3(LMB_THREADS), 0, c->stream, a);
-            HIP_TRY(c, hipGetLastError());
-        }
-        {
-            LmmseCorrArgs a{};
-            a.h_re = d_h_re + ho; a.h_im = d_h_im + ho; a.corr = corr + (size_t)b0 * LM_N; a.nt = cf.nt;
-            ProfScope ps(c, K_LMMSE_FREQ_CORR, (double)nb * cf.nt * (LM_N * (LM_N + 1) / 2) * 8.0, (double)nb * cf.nt * LM_N * 8.0);
-            hipLaunchKernelGGL(lmmse_freq_corr_kernel, dim3((unsigned)nb), dim3(LMB_THREADS), 0, c->stream, a);
-            HIP_TRY(c, hipGetLastError());
-        }
-        {
-            LmmseBlindArgs a{};
-            a.h_re = d_h_re + ho; a.h_im = d_h_im + ho; a.nv = nv + b0; a.corr = corr + (size_t)b0 * LM_N;
-            a.o_re = d_out_re + ho; a.o_im = d_out_im + ho; a.fallback = flags + b0; a.nt = cf.nt; a.nr = cf.nr;
-            ProfScope ps(c, K_LMMSE_BLIND, (double)nb * (cf.nt + n_jc) * 16.0 * LM_N * LM_N, (double)nb * cf.nt * LM_N * 16.0);
-            hipLaunchKernelGGL(lmmse_blind_kernel, dim3((unsigned)(nb * n_jc)), dim3(LM_THREADS), 0, c->stream, a, n_jc);
-            HIP_TRY(c, hipGetLastError());
-            hipLaunchKernelGGL(lmmse_blind_count_kernel, dim3(1), dim3(LMB_THREADS), 0, c->stream, flags + b0, (long long)nb, c->lmb_count);
-            HIP_TRY(c, hipGetLastError());
-        }
-    }
-    return CSI_OK;
+    return lmmse_blind_launch(c, d_ltf_re, d_ltf_im, d_h_re, d_h_im, npkt, d_out_re, d_out_im, d_noise_var, d_corr);
 }
 
 int csi_lmmse_blind(csi_ctx* c, const float* ltf_re, const float* ltf_im, const float* h_re, const float* h_im, int64_t npkt,
                     float* out_re, float* out_im, double* noise_var, double* corr) {
     if (!c) return CSI_ERR_INVALID_ARG;
-    if (npkt <= 0) return fail(c, CSI_ERR_INVALID_ARG, "csi_lmmse_blind: npkt %lld must be positive", (long long)npkt);
-    if (!ltf_re || !ltf_im || !h_re || !h_im || !out_re || !out_im)
-        return fail(c, CSI_ERR_INVALID_ARG, "csi_lmmse_blind: null required pointer (ltf, h, out)");
-    const csi_config& cf = c->cfg;
-    if (cf.nt == 0) return fail(c, CSI_ERR_INVALID_ARG, "single-input context (nt=0): no LMMSE estimate");
-    HIP_TRY(c, hipSetDevice(cf.device));
-    const size_t pkt_f = (size_t)cf.nr * cf.nt * LM_N;                     // floats per packet and CSI plane
-    const size_t ltf_f = (size_t)cf.nr * cf.len_ltf;                       // floats per packet and preamble plane
-    int64_t chunk = std::max<int64_t>(1, ((int64_t)256 << 20) / (int64_t)(4 * pkt_f * sizeof(float)));      // the chunk of csi_lmmse_estimate
-    chunk = std::min(chunk, npkt);
-    const size_t stat_d = (size_t)cf.nr * (1 + 2 * LM_N);                  // doubles per packet: nv and c
-    const size_t need = ((4 * pkt_f + 2 * ltf_f) * sizeof(float) + stat_d * sizeof(double)) * (size_t)chunk;
-    int rc = ensure_bytes(c, &c->stage, &c->stage_bytes, need);
-    if (rc) return rc;
-    float* d_lre = reinterpret_cast<float*>(c->stage);
-    float* d_lim = d_lre + ltf_f * chunk;
-    float* d_re = d_lim + ltf_f * chunk;
-    float* d_im = d_re + pkt_f * chunk;
-    float* d_ore = d_im + pkt_f * chunk;
-    float* d_oim = d_ore + pkt_f * chunk;
-    double* d_nv = reinterpret_cast<double*>(d_oim + pkt_f * chunk);       // behind float planes of whole packets: a multiple of 8 bytes
-    double* d_c = d_nv + (size_t)cf.nr * chunk;
-    for (int64_t p0 = 0; p0 < npkt; p0 += chunk) {
-        const int64_t np = std::min(chunk, npkt - p0);
-        HIP_TRY(c, hipMemcpyAsync(d_lre, ltf_re + p0 * ltf_f, ltf_f * np * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(d_lim, ltf_im + p0 * ltf_f, ltf_f * np * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(d_re, h_re + p0 * pkt_f, pkt_f * np * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(d_im, h_im + p0 * pkt_f, pkt_f * np * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        rc = csi_lmmse_blind_device(c, d_lre, d_lim, d_re, d_im, np, d_ore, d_oim, d_nv, d_c);
-        if (rc) return rc;
-        HIP_TRY(c, hipMemcpyAsync(out_re + p0 * pkt_f, d_ore, pkt_f * np * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(out_im + p0 * pkt_f, d_oim, pkt_f * np * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        if (noise_var) HIP_TRY(c, hipMemcpyAsync(noise_var + p0 * cf.nr, d_nv, (size_t)cf.nr * np * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        if (corr) HIP_TRY(c, hipMemcpyAsync(corr + p0 * cf.nr * 2 * LM_N, d_c, (size_t)cf.nr * np * 2 * LM_N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    return CSI_OK;
+    return lmmse_blind_host(c, ltf_re, ltf_im, h_re, h_im, npkt, out_re, out_im, noise_var, corr);
+}
+
+int csi_null_noise_device(csi_ctx* c, const float* d_ltf_re, const float* d_ltf_im, int64_t npkt, double* d_noise_var) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    static const char* who = "csi_null_noise_device";
+    if (int rc = null_noise_check(c, who, d_ltf_re, d_ltf_im, npkt, d_noise_var)) return rc;
+    if (int rc = planes_aligned(c, who, {{"d_ltf_re", d_ltf_re}, {"d_ltf_im", d_ltf_im}})) return rc;
+    if (reinterpret_cast<uintptr_t>(d_noise_var) & 7)
+        return fail(c, CSI_ERR_INVALID_ARG, "%s: d_noise_var must be aligned for doubles (got %p)", who, (void*)d_noise_var);
+    if (npkt == 0) return CSI_OK;
+    return null_noise_launch(c, d_ltf_re, d_ltf_im, npkt, d_noise_var);
 }
 
 // ---------------------------------------------------------------- delay-subspace smoother (csi_subspace.hpp, subspace_smooth.hip.h)
@@ -1102,35 +981,6 @@ int csi_beam_wiener_device(csi_ctx* c, const float* d_h_re, const float* d_h_im,
 int csi_beam_wiener(csi_ctx* c, const float* h_re, const float* h_im, int64_t npkt, const float* err_var, float* out_re, float* out_im, float* w_out) {
     if (!c) return CSI_ERR_INVALID_ARG;
     return beam_host(c, "csi_beam_wiener", true, h_re, h_im, npkt, nullptr, err_var, out_re, out_im, w_out);
-}
-
-// the null-carrier statistic of csi_lmmse_blind_device on its own: the same kernel, the same launch shape, the same bits
-int csi_null_noise_device(csi_ctx* c, const float* d_ltf_re, const float* d_ltf_im, int64_t npkt, double* d_noise_var) {
-    if (!c) return CSI_ERR_INVALID_ARG;
-    static const char* who = "csi_null_noise_device";
-    const csi_config& cf = c->cfg;
-    if (cf.nt == 0) return fail(c, CSI_ERR_INVALID_ARG, "single-input context (nt=0): no sounding symbols");
-    if (npkt < 0) return fail(c, CSI_ERR_INVALID_ARG, "%s: npkt %lld must not be negative", who, (long long)npkt);
-    if (!d_ltf_re || !d_ltf_im || !d_noise_var) return fail(c, CSI_ERR_INVALID_ARG, "%s: null required pointer (ltf, noise_var)", who);
-    if (cf.len_ltf < LMB_SYM * cf.nt || cf.len_ltf % 4 != 0)
-        return fail(c, CSI_ERR_INVALID_ARG, "%s: len_ltf %d does not hold %d sounding symbols of 320 samples in 16-byte words", who, cf.len_ltf, cf.nt);
-    if (int rc = planes_aligned(c, who, {{"d_ltf_re", d_ltf_re}, {"d_ltf_im", d_ltf_im}})) return rc;
-    if (reinterpret_cast<uintptr_t>(d_noise_var) & 7)
-        return fail(c, CSI_ERR_INVALID_ARG, "%s: d_noise_var must be aligned for doubles (got %p)", who, (void*)d_noise_var);
-    if (npkt == 0) return CSI_OK;
-    HIP_TRY(c, hipSetDevice(cf.device));
-    const int64_t nblk = npkt * cf.nr;
-    const int64_t max_items = ((int64_t)1 << 30) / cf.nr * cf.nr;      // whole packets per launch
-    for (int64_t b0 = 0; b0 < nblk; b0 += max_items) {
-        const int64_t nb = std::min(max_items, nblk - b0);
-        LmmseNoiseArgs a{};
-        a.ltf_re = d_ltf_re + (size_t)b0 * cf.len_ltf; a.ltf_im = d_ltf_im + (size_t)b0 * cf.len_ltf;
-        a.tw = c->lmb_tw; a.nv = d_noise_var + b0; a.nt = cf.nt; a.len_ltf = cf.len_ltf;
-        ProfScope ps(c, K_LMMSE_NULL_NOISE, (double)nb * cf.nt * LMB_NULLS * LMB_FFT * 44.0, (double)nb * cf.nt * LMB_FFT * 8.0);
-        hipLaunchKernelGGL(lmmse_null_noise_kernel, dim3((unsigned)nb), dim3(LMB_THREADS), 0, c->stream, a);
-        HIP_TRY(c, hipGetLastError());
-    }
-    return CSI_OK;
 }
 
 // ---------------------------------------------------------------- hybrid beamforming weights (csi_hybrid.hpp, hybrid_weights.hip.h)
@@ -1260,23 +1110,17 @@ int csi_nmse(csi_ctx* c, const float* ref_re, const float* ref_im, const float* 
     if (nlinks <= 0 || n_bins <= 0 || !ref_re || !ref_im || !est_re || !est_im || !mean_out)
         return fail(c, CSI_ERR_INVALID_ARG, "csi_nmse: bad argument");
     HIP_TRY(c, hipSetDevice(c->cfg.device));
+    // four planes of whole links and 256 bytes of room behind them; csi_nmse_device synchronizes, and every chunk's mean is weighed with its links
     const size_t row = (size_t)n_bins * sizeof(float);
-    const int64_t chunk = std::min<int64_t>(nlinks, std::max<int64_t>(1, ((int64_t)256 << 20) / (int64_t)(4 * row)));
-    int rc = ensure_bytes(c, &c->stage, &c->stage_bytes, 4 * row * (size_t)chunk + 256);
-    if (rc) return rc;
-    float* d[4];
-    for (int i = 0; i < 4; ++i) d[i] = reinterpret_cast<float*>(c->stage) + (size_t)i * chunk * n_bins;
-    const float* h[4] = {ref_re, ref_im, est_re, est_im};
+    StagePlane p[] = {{row, ref_re, nullptr}, {row, ref_im, nullptr}, {row, est_re, nullptr}, {row, est_im, nullptr}};
     double total = 0.0;
-    for (int64_t l0 = 0; l0 < nlinks; l0 += chunk) {
-        const int64_t nl = std::min(chunk, nlinks - l0);
-        for (int i = 0; i < 4; ++i)
-            HIP_TRY(c, hipMemcpyAsync(d[i], h[i] + (size_t)l0 * n_bins, row * (size_t)nl, hipMemcpyHostToDevice, c->stream));
+    int rc = staged_call(c, nlinks, STAGE_BUDGET, 4 * row, 256, false, p, [&](int64_t, int64_t nl) {
         double mean = 0.0;
-        rc = csi_nmse_device(c, d[0], d[1], d[2], d[3], nl, n_bins, nullptr, &mean);
-        if (rc) return rc;
+        const int r = csi_nmse_device(c, p[0].as<float>(), p[1].as<float>(), p[2].as<float>(), p[3].as<float>(), nl, n_bins, nullptr, &mean);
         total += mean * (double)nl;
-    }
+        return r;
+    });
+    if (rc) return rc;
     *mean_out = total / (double)nlinks;
     return CSI_OK;
 }

@@ -1,7 +1,9 @@
-// csi_subspace.hpp - host side of the delay-subspace smoother (kernel: subspace_smooth.hip.h): the basis check and its
-// two device images, the argument checks, the one launch of csi_subspace_smooth_device and the chunked host entry point.
+// csi_subspace.hpp - host side of the delay-subspace smoother (kernel: subspace_smooth.hip.h): the basis and its two
+// device images, the argument checks, the one launch of csi_subspace_smooth_device and the host entry point as a staged call.  The
+// orthonormality check of the basis and the overlap rule of the planes are csi_stage.hpp's, shared with csi_beam.hpp.
 #pragma once
 #include "csi_context.hpp"
+#include "csi_stage.hpp"
 #include "subspace_smooth.hip.h"
 
 namespace {
@@ -16,27 +18,7 @@ int subspace_set_basis(csi_ctx* c, const float* q_re, const float* q_im, int ran
     if (rank < 1 || rank > SB_MAX_RANK) return fail(c, CSI_ERR_INVALID_ARG, "%s: rank %d outside 1 .. %d", who, rank, SB_MAX_RANK);
     if (!q_re || !q_im) return fail(c, CSI_ERR_INVALID_ARG, "%s: null basis planes", who);
     if (c->user_capture) return fail(c, CSI_ERR_INVALID_ARG, "%s: the basis cannot be replaced while a capture is open", who);
-    const size_t nq = (size_t)SB_N * rank;
-    for (size_t i = 0; i < nq; ++i)
-        if (!std::isfinite(q_re[i]) || !std::isfinite(q_im[i]))
-            return fail(c, CSI_ERR_INVALID_ARG, "%s: non-finite basis entry at [%zu][%zu]", who, i / rank, i % rank);
-    // Q^H Q against the identity, in double on the host (234 r^2 complex products once per basis)
-    double worst = 0.0;
-    int wi = 0, wj = 0;
-    for (int i = 0; i < rank; ++i)
-        for (int j = i; j < rank; ++j) {
-            double sr = 0.0, si = 0.0;
-            for (int k = 0; k < SB_N; ++k) {
-                const double ar = q_re[(size_t)k * rank + i], ai = q_im[(size_t)k * rank + i];
-                const double br = q_re[(size_t)k * rank + j], bi = q_im[(size_t)k * rank + j];
-                sr += ar * br + ai * bi;          // conj(a) b
-                si += ar * bi - ai * br;
-            }
-            const double d = std::hypot(sr - (i == j ? 1.0 : 0.0), si);
-            if (d > worst) { worst = d; wi = i; wj = j; }
-        }
-    if (!(worst <= SB_ORTHO_TOL))
-        return fail(c, CSI_ERR_INVALID_ARG, "%s: basis is not orthonormal: |Q^H Q - I| = %.3g at [%d][%d] (at most %g)", who, worst, wi, wj, SB_ORTHO_TOL);
+    if (int rc = basis_orthonormal(c, who, q_re, q_im, SB_N, rank, SB_ORTHO_TOL, 'Q')) return rc;
     const int rp = (rank + 31) / 32 * 32;
     std::vector<float> img((size_t)2 * SB_N * rp + (size_t)2 * rp * SB_NP, 0.0f);
     float* qa_re = img.data();
@@ -67,12 +49,6 @@ int subspace_set_basis(csi_ctx* c, const float* q_re, const float* q_im, int ran
     return CSI_OK;
 }
 
-// [p, p + bytes) and [q, q + bytes) share a byte
-inline bool sb_overlap(const void* p, const void* q, size_t bytes) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-    return a < b + bytes && b < a + bytes;
-}
-
 // everything csi_subspace_smooth_device refuses except the alignment of the planes (the caller's: planes_aligned)
 int subspace_check(csi_ctx* c, const char* who, const float* h_re, const float* h_im, int64_t npkt, const float* out_re, const float* out_im) {
     const csi_config& cf = c->cfg;
@@ -89,10 +65,7 @@ int subspace_smooth_device(csi_ctx* c, const char* who, const float* d_h_re, con
     if (npkt == 0) return CSI_OK;
     const int64_t rows = npkt * cf.nr * cf.nt;
     const size_t bytes = (size_t)rows * SB_N * sizeof(float);
-    // out may be the input planes themselves, re with re and im with im; every other shared byte is refused
-    if ((d_out_re != d_h_re && sb_overlap(d_out_re, d_h_re, bytes)) || (d_out_im != d_h_im && sb_overlap(d_out_im, d_h_im, bytes)) ||
-        sb_overlap(d_out_re, d_h_im, bytes) || sb_overlap(d_out_im, d_h_re, bytes) || sb_overlap(d_out_re, d_out_im, bytes))
-        return fail(c, CSI_ERR_INVALID_ARG, "%s: an output plane may be its own input plane (re with re, im with im); any other overlap of the planes is refused", who);
+    if (int rc = inout_planes_disjoint(c, who, d_h_re, d_h_im, d_out_re, d_out_im, bytes)) return rc;
     const int64_t tiles = (rows + SB_ROWS - 1) / SB_ROWS;
     if (tiles > 0x7fffffff) return fail(c, CSI_ERR_INVALID_ARG, "%s: %lld rows exceed one launch (2^31 - 1 tiles of %d rows)", who, (long long)rows, SB_ROWS);
     HIP_TRY(c, hipSetDevice(cf.device));
@@ -119,32 +92,13 @@ int subspace_smooth_host(csi_ctx* c, const float* h_re, const float* h_im, int64
     if (npkt == 0) return CSI_OK;
     const csi_config& cf = c->cfg;
     HIP_TRY(c, hipSetDevice(cf.device));
-    const int rank = c->sub_rank;
-    const size_t pkt_f = (size_t)cf.nr * cf.nt * SB_N;                    // floats per packet and plane
-    const size_t w_f = w ? (size_t)cf.nr * rank : 0;
-    // the chunk of csi_lmmse_estimate (256 MiB of staging), or what the context's workspace_bytes allows when that is less
-    const int64_t budget = cf.workspace_bytes > 0 ? std::min<int64_t>(cf.workspace_bytes, (int64_t)256 << 20) : ((int64_t)256 << 20);
-    int64_t chunk = std::max<int64_t>(1, budget / (int64_t)(4 * pkt_f * sizeof(float)));
-    chunk = std::min(chunk, npkt);
-    int rc = ensure_bytes(c, &c->stage, &c->stage_bytes, (4 * pkt_f + w_f) * sizeof(float) * (size_t)chunk);
-    if (rc) return rc;
-    float* d_re = reinterpret_cast<float*>(c->stage);      // planes of whole packets: pkt_f is a multiple of 4 floats (nt % 4 == 0)
-    float* d_im = d_re + pkt_f * chunk;
-    float* d_ore = d_im + pkt_f * chunk;
-    float* d_oim = d_ore + pkt_f * chunk;
-    float* d_w = w ? d_oim + pkt_f * chunk : nullptr;
-    for (int64_t p0 = 0; p0 < npkt; p0 += chunk) {
-        const int64_t np = std::min(chunk, npkt - p0);
-        HIP_TRY(c, hipMemcpyAsync(d_re, h_re + p0 * pkt_f, pkt_f * np * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(d_im, h_im + p0 * pkt_f, pkt_f * np * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        if (w) HIP_TRY(c, hipMemcpyAsync(d_w, w + p0 * w_f, w_f * np * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        rc = subspace_smooth_device(c, who, d_re, d_im, np, d_w, d_ore, d_oim);
-        if (rc) return rc;
-        HIP_TRY(c, hipMemcpyAsync(out_re + p0 * pkt_f, d_ore, pkt_f * np * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(out_im + p0 * pkt_f, d_oim, pkt_f * np * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    return CSI_OK;
+    const size_t pkt = (size_t)cf.nr * cf.nt * SB_N * sizeof(float);      // bytes per packet and plane: a multiple of 16 (nt % 4 == 0)
+    // a staged call (csi_stage.hpp): the chunk is sized by the four CSI planes, the weights ride behind them
+    StagePlane p[] = {{pkt, h_re, nullptr}, {pkt, h_im, nullptr}, {pkt, nullptr, out_re}, {pkt, nullptr, out_im},
+                      {w ? (size_t)cf.nr * c->sub_rank * sizeof(float) : 0, w, nullptr}};
+    return staged_call(c, npkt, stage_budget(c), 4 * pkt, 0, true, p, [&](int64_t, int64_t np) {
+        return subspace_smooth_device(c, who, p[0].as<float>(), p[1].as<float>(), np, w ? p[4].as<float>() : nullptr, p[2].as<float>(), p[3].as<float>());
+    });
 }
 
 }  // namespace

@@ -11,6 +11,8 @@
 //     which gets the NAME the function was looked up by and the HIP_LAUNCH_PARAM argument record) and are otherwise counted and
 //     dropped - a harness of host logic does not need what the kernels compute; mock::launch_shape_hook sees every hipLaunchKernel with
 //     its grid, workgroup size and dynamic LDS bytes, mock::func_attribute_hook every hipFuncSetAttribute;
+//   * mock::alloc_hook sees every hipMalloc (the size requested), mock::copy_hook every hipMemcpyAsync / hipMemcpy (destination, source,
+//     bytes, kind) and mock::sync_hook every hipStreamSynchronize, on the calling thread and in front of the work itself;
 //   * with MOCK_HIP_FAIL_MODULE_LOAD set in the environment hipModuleLoad / hipModuleLoadData fail, and - as in the real runtime - the
 //     error stays the thread's last error until hipGetLastError reads it;
 //   * one "node" of mock::n_devices gfx950 devices.
@@ -101,6 +103,9 @@ inline thread_local long fail_alloc_in = -1;        // > 0: the n-th hipMalloc o
 inline std::function<hipError_t(const void* fn, void** args, hipStream_t st)> launch_hook;
 inline std::function<void(const void* fn, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st)> launch_shape_hook;      // called in front of launch_hook
 inline std::function<void(const void* fn, hipFuncAttribute attr, int value)> func_attribute_hook;
+inline std::function<void(size_t bytes)> alloc_hook;
+inline std::function<void(const void* dst, const void* src, size_t bytes, hipMemcpyKind kind)> copy_hook;
+inline std::function<void(hipStream_t st)> sync_hook;
 struct Function { std::string name; };              // what hipModuleGetFunction hands out: the symbol name it was asked for
 // a module launch: kernel name, grid x / y, block x, the HIP_LAUNCH_PARAM buffer (null / 0 when the launch passed none), stream
 inline std::function<void(const char* name, unsigned gx, unsigned gy, unsigned bx, const void* params, size_t bytes, hipStream_t st)> module_launch_hook;
@@ -156,6 +161,7 @@ hipError_t hipStreamDestroy(hipStream_t s) {
     return hipSuccess;
 }
 hipError_t hipStreamSynchronize(hipStream_t s) {
+    if (mock::sync_hook) mock::sync_hook(s);
     mock::S(s)->sync();
     return hipSuccess;
 }
@@ -215,6 +221,7 @@ hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) {
     return hipSuccess;
 }
 hipError_t hipMalloc(void** p, size_t n) {
+    if (mock::alloc_hook) mock::alloc_hook(n);
     if (mock::fail_alloc_in > 0 && --mock::fail_alloc_in == 0) { mock::fail_alloc_in = -1; *p = nullptr; return hipErrorOutOfMemory; }
     const size_t bytes = (n + 255) / 256 * 256;
     *p = std::aligned_alloc(256, bytes ? bytes : 256);
@@ -252,6 +259,7 @@ hipError_t hipPointerGetAttributes(hipPointerAttribute_t* a, const void* p) {
 }
 hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind k, hipStream_t st) {
     ++mock::g_copies;
+    if (mock::copy_hook) mock::copy_hook(d, s, n, k);
     bool pageable_src = false;
     if (k == hipMemcpyHostToDevice || k == hipMemcpyHostToHost) {
         std::lock_guard<std::mutex> lk(mock::g_mu);
@@ -273,7 +281,8 @@ hipError_t hipMemcpyPeerAsync(void* d, int, const void* s, int, size_t n, hipStr
     mock::S(st)->push([d, s, n] { std::memcpy(d, s, n); });
     return hipSuccess;
 }
-hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) {
+hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind k) {
+    if (mock::copy_hook) mock::copy_hook(d, s, n, k);
     mock::null_stream()->sync();
     std::memcpy(d, s, n);
     return hipSuccess;

@@ -12,7 +12,7 @@
 // Band8Args (128 bytes) or a Band8ArgsCs (144 bytes) -
 //   <kernel name> grid=<x>,<y> block=<x> bytes=<record> M=<> N1=<> nt=<> tiled=<1 tiled copy | 0 plain weights | ?> [part=<0 | 1>]
 // The record's W1 is kept and named when the log is read: a model's tiled copy (Model::Wt1) is allocated once and stays.
-// Test-only entry points of THIS translation unit; the product header does not know them.  (Further down: the log of the LS kernels.)
+// Test-only entry points of THIS translation unit; the product header does not know them.  (Further down: the log of the LS kernels and the log of the staged host calls.)
 #if !defined(__HIP_DEVICE_COMPILE__)
 namespace {
 struct BandLaunch { std::string name; unsigned gx, gy, bx; size_t bytes; Band8ArgsCs rec; };
@@ -39,7 +39,7 @@ std::mutex ls_log_mu;
 std::vector<std::string> ls_log;
 const void* ls_attr_fn = nullptr;
 int ls_attr_value = -1;
-std::string ls_kernel_name(const void* fn) {
+std::string kernel_name(const void* fn) {
     Dl_info info{};
     if (!dladdr(fn, &info) || !info.dli_sname || info.dli_saddr != fn) return "";
     int status = 0;
@@ -48,8 +48,58 @@ std::string ls_kernel_name(const void* fn) {
     std::free(d);
     for (const char* prefix : {"void ", "csi::"})
         if (s.compare(0, std::strlen(prefix), prefix) == 0) s.erase(0, std::strlen(prefix));
+    return s;
+}
+std::string ls_kernel_name(const void* fn) {
+    const std::string s = kernel_name(fn);
     return s.compare(0, 3, "ls_") == 0 || s.compare(0, 18, "small_l0_ls_kernel") == 0 ? s : "";
 }
+
+// ---- what a staged host call does (tests/test_staged_calls_host.py).  While a context is named (csi_mock_stage_log_clear), one text line
+// per hipMalloc, hipMemcpyAsync / hipMemcpy, hipLaunchKernel and hipStreamSynchronize of the process -
+//   malloc bytes=<requested>
+//   copy <H2D | D2H | ...> bytes=<> dev=<buffer>+<offset> host=<array>+<offset>
+//   launch grid=<x>,<y>,<z> block=<x>,<y>,<z> lds=<dynamic bytes> kernel=<name as in the LS log, every kernel>
+//   sync
+// <buffer> is the context's buffer that holds the device address (stage, skbuf, ...: stage_log_where), <array> the host array the test
+// named (csi_mock_stage_log_name) that holds the host address; "local" is an address none of them holds (a variable of the library's).
+std::mutex stage_log_mu;
+std::vector<std::string> stage_log;
+csi_ctx* stage_log_ctx = nullptr;
+struct NamedRange { std::string name; const char* base; size_t bytes; };
+std::vector<NamedRange> stage_log_arrays;
+std::string stage_log_where(const void* p, bool device) {
+    const char* a = static_cast<const char*>(p);
+    const csi_ctx* c = stage_log_ctx;
+    const size_t slack = G_SLACK_FLOATS * sizeof(float);      // ensure_bytes allocates it behind the bytes it was asked for
+    std::vector<NamedRange> dev = {{"stage", c->stage, c->stage_bytes + slack}, {"skbuf", c->skbuf, c->skbuf_bytes + slack},
+                                   {"lmb_ws", c->lmb_ws, c->lmb_ws_bytes + slack}, {"hyb_ws", c->hyb_ws, c->hyb_ws_bytes + slack},
+                                   {"beam_ws", c->beam_ws, c->beam_ws_bytes + slack},
+                                   {"sub_q", reinterpret_cast<const char*>(c->sub_q), SB_IMAGE_FLOATS * sizeof(float)},
+                                   {"beam_a", reinterpret_cast<const char*>(c->beam_a), BM_IMAGE_FLOATS * sizeof(float)}};
+    for (const NamedRange& r : device ? dev : stage_log_arrays)
+        if (r.base && a >= r.base && a < r.base + r.bytes) return r.name + "+" + std::to_string(a - r.base);
+    return "local";
+}
+const bool stage_log_hooked = [] {
+    mock::alloc_hook = [](size_t bytes) {
+        std::lock_guard<std::mutex> lk(stage_log_mu);
+        if (stage_log_ctx) stage_log.push_back("malloc bytes=" + std::to_string(bytes));
+    };
+    mock::copy_hook = [](const void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+        std::lock_guard<std::mutex> lk(stage_log_mu);
+        if (!stage_log_ctx) return;
+        const bool up = kind == hipMemcpyHostToDevice, down = kind == hipMemcpyDeviceToHost;
+        if (!up && !down) { stage_log.push_back("copy kind=" + std::to_string((int)kind) + " bytes=" + std::to_string(bytes)); return; }
+        stage_log.push_back(std::string("copy ") + (up ? "H2D" : "D2H") + " bytes=" + std::to_string(bytes) + " dev=" + stage_log_where(up ? dst : src, true) +
+                      " host=" + stage_log_where(up ? src : dst, false));
+    };
+    mock::sync_hook = [](hipStream_t) {
+        std::lock_guard<std::mutex> lk(stage_log_mu);
+        if (stage_log_ctx) stage_log.push_back("sync");
+    };
+    return true;
+}();
 const bool ls_log_hooked = [] {
     mock::func_attribute_hook = [](const void* fn, hipFuncAttribute attr, int value) {
         const std::string name = ls_kernel_name(fn);
@@ -60,6 +110,14 @@ const bool ls_log_hooked = [] {
         ls_log.push_back("attr value=" + std::to_string(value) + " kernel=" + name);
     };
     mock::launch_shape_hook = [](const void* fn, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t) {
+        {
+            std::lock_guard<std::mutex> lk(stage_log_mu);
+            if (stage_log_ctx) {
+                char line[160];
+                std::snprintf(line, sizeof line, "launch grid=%u,%u,%u block=%u,%u,%u lds=%zu kernel=", grid.x, grid.y, grid.z, block.x, block.y, block.z, lds_bytes);
+                stage_log.push_back(line + kernel_name(fn));
+            }
+        }
         const std::string name = ls_kernel_name(fn);
         if (name.empty()) return;
         std::lock_guard<std::mutex> lk(ls_log_mu);
@@ -91,6 +149,24 @@ int64_t csi_mock_ls_log_read(char* buf, int64_t cap) {
 void csi_mock_ls_log_clear(void) {
     std::lock_guard<std::mutex> lk(ls_log_mu);
     ls_log.clear();
+}
+// the staged-call log: csi_mock_stage_log_clear empties it and names the context whose calls are kept from now on (null: none - before the
+// context goes); csi_mock_stage_log_name names a host array (null name: forgets them all); csi_mock_stage_log_read as csi_mock_ls_log_read
+void csi_mock_stage_log_clear(csi_ctx* c) {
+    std::lock_guard<std::mutex> lk(stage_log_mu);
+    stage_log.clear();
+    stage_log_ctx = c;
+}
+void csi_mock_stage_log_name(const char* name, const void* base, int64_t bytes) {
+    std::lock_guard<std::mutex> lk(stage_log_mu);
+    if (!name) stage_log_arrays.clear();
+    else stage_log_arrays.push_back({name, static_cast<const char*>(base), (size_t)bytes});
+}
+int64_t csi_mock_stage_log_read(char* buf, int64_t cap) {
+    std::string text;
+    std::lock_guard<std::mutex> lk(stage_log_mu);
+    for (const std::string& l : stage_log) text += l + '\n';
+    return text_out(text, buf, cap);
 }
 // what csi_set_pilot left on the "device" (host memory here): which = 0 P, 1 Ppad, 2 Pbf, 3 p_tables; returns the payload bytes (without the
 // slack behind them; 0: the context has no such buffer) and the address in *ptr.  The sizes are written out here, not taken from the library.
