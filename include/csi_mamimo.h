@@ -346,6 +346,8 @@ int  csi_null_noise_device(csi_ctx* ctx, const float* d_ltf_re, const float* d_l
  * is frf[m][:] = At[:, idx[m]] and is not written out), n_atoms int32 [npkt][234], gain [npkt][234] = |H_eval frf^T fbb^T|_F^2
  * with H_eval = the eval planes (same shape as h) or h itself when they are NULL, frf_mean [npkt][ntrf][Nt] = mean of frf over a
  * packet's subcarriers.  Slots behind an early stop hold index -1 and zero coefficients (and add nothing to frf_mean).
+ * An all-zero item has Fopt = 0 and every metric 0: its first step takes column 0 (the lowest index of the tie), fits it with zero
+ * coefficients and stops there - n_atoms 1, idx (0, -1, ..), fbb 0, gain 0, every output finite; other items are not affected.
  * stop_tol <= 0 selects 1e-5.  eval, n_atoms, gain and frf_mean may be NULL.
  * csi_hybrid_set_dictionary: host planes [Nt][n_rays], n_rays <= 4096, kept on the context; columns are used as given (no
  * normalisation); a second call replaces the dictionary.

@@ -20,7 +20,9 @@ N = 234
 ORDER = 4.0      # the kernels sum in another order than numpy's complex64 products: the factor tests/test_gpu_subspace.py grants for that
 # (Nt, Nr, npkt, basis).  The shapes are the smallest at which the tiling can go wrong: everything padded; odd nb < Nt; Nt no multiple of
 # 8; exactly one 32-tile each way; both dimensions one past a 32-tile (two tiles each way, the second nearly empty); two full tiles; four
-# tiles (a plane that would not fit LDS whole); several workgroups of the smoother (74 planes x 8 carrier tiles in workgroups of 4)
+# tiles (a plane that would not fit LDS whole); several workgroups of the smoother (74 planes x 8 carrier tiles in workgroups of 4);
+# unequal tile counts, where the kernel's width (1, 2 or 4 tiles: the larger count, rounded up) exceeds one or both of them and the
+# skips of the missing tiles run: 3 / 1 and 3 / 3 antenna / beam tiles in the 4-wide kernel, 4 / 1, and 2 / 1 in the 2-wide one
 CASES = {
     'nt4_dft': (4, 1, 1, 'dft'),
     'nt4_random3': (4, 2, 3, ('random', 3)),
@@ -30,8 +32,12 @@ CASES = {
     'nt64_dft': (64, 2, 2, 'dft'),
     'nt128_dft': (128, 1, 2, 'dft'),
     'nt8_37pkt': (8, 2, 37, 'dft'),
+    'nt72_random20': (72, 2, 2, ('random', 20)),
+    'nt96_dft': (96, 1, 2, 'dft'),
+    'nt128_random5': (128, 2, 1, ('random', 5)),
+    'nt40_random8': (40, 1, 3, ('random', 8)),
 }
-GUARD_CASES = ['nt4_random3', 'nt36_random33', 'nt128_dft', 'nt8_37pkt']
+GUARD_CASES = ['nt4_random3', 'nt36_random33', 'nt128_dft', 'nt8_37pkt', 'nt72_random20', 'nt128_random5']
 
 
 def _planes(rng, shape):

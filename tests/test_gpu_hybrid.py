@@ -23,6 +23,9 @@ RAY_SEED = 5
 # (Nt, Nr, Ns, NtRF, rays, SNR dB, packets)
 SHAPES = [(8, 4, 1, 1, 500, 10, 8), (8, 2, 1, 2, 64, -10, 8), (32, 4, 2, 4, 500, 0, 4), (32, 4, 4, 8, 500, -10, 3),
           (16, 4, 3, 5, 333, 0, 6), (64, 8, 4, 16, 256, 10, 2), (128, 16, 2, 4, 500, 10, 1)]
+# the widths, antenna counts and caps beyond powers of two (hybrid_ref.NEW_SHAPES says what each row is for).  The context and the
+# 64 KiB LDS request of the correlation kernel are accepted at Nt = 256, the stage's own limit, so the row at the cap stands as it is
+SHAPES += R.NEW_SHAPES
 
 
 def dictionary(pkg, nt, rays):
@@ -30,15 +33,7 @@ def dictionary(pkg, nt, rays):
     return pkg.synth.steering_ula(nt, az, el).astype(np.complex64)
 
 
-def ls_csi(oracle, nt, nr, snr, npkt, seed=11, block=250):
-    """fp64 LS estimates of make_structured_packets(default_rng(seed), ...), rounded to the complex64 the library receives"""
-    rng = np.random.default_rng(seed)
-    P = oracle.hadamard(nt)
-    out = []
-    for p0 in range(0, npkt, block):
-        ltf, _ = oracle.make_structured_packets(rng, min(block, npkt - p0), nr, P, snr_db=snr)
-        out.append(oracle.ls_estimate(ltf, P).astype(np.complex64))
-    return np.concatenate(out)
+ls_csi = R.ls_csi           # the Hadamard pilot where Nt is a power of two, a seeded +-1 pilot elsewhere
 
 
 def engine(pkg, nt, nr, At=None, **kw):

@@ -18,7 +18,9 @@ pytestmark = pytest.mark.gpu
 N = 234
 ORDER = 4.0      # the kernel sums in another order than numpy's complex64 products: the factor test_d_ml_shortfall_on_real_llrs uses for that
 # (Nt, Nr, npkt, basis): 4 rows, the smallest call; odd rank, 24 rows, less than any tile; 592 rows: several workgroups and a partial
-# last tile (two rank tiles, carriers in halves); top rank (four rank tiles); 1152 rows; a basis without delay structure
+# last tile (two rank tiles, carriers in halves); top rank (four rank tiles); 1152 rows; a basis without delay structure; ranks that
+# fill no whole number of tiles: 33 (two rank tiles, carriers in halves, the second tile one column), 65 and 96 (three rank tiles:
+# the fourth wave idles through stage 1; 65 leaves the third tile one column)
 CASES = {
     'rows4_rank1': (4, 1, 1, ('delay', 1, 0)),
     'rows24_rank13': (4, 2, 3, ('delay', 13, 0)),
@@ -26,6 +28,9 @@ CASES = {
     'rows20_rank128': (4, 1, 5, ('delay', 128, 16)),
     'rows1152_rank16': (32, 4, 9, ('delay', 16, 0)),
     'rows24_random13': (4, 2, 3, ('random', 13)),
+    'rows24_rank33': (4, 2, 3, ('delay', 33, 4)),
+    'rows40_random65': (4, 2, 5, ('random', 65)),
+    'rows36_rank96': (4, 3, 3, ('delay', 96, 12)),
 }
 
 
@@ -119,7 +124,7 @@ def test_b_projection(pkg, name):
 
 
 # ---------------------------------------------------------------------------------------------------------------- weights
-@pytest.mark.parametrize('name', ['rows24_rank13', 'rows592_rank64'])
+@pytest.mark.parametrize('name', ['rows24_rank13', 'rows592_rank64', 'rows24_rank33'])
 def test_c_weights(pkg, name):
     k = _case(pkg, name)
     e, Q, x = k['e'], k['Q'], k['x']
@@ -196,7 +201,7 @@ def test_d_second_basis_replaces_the_first(pkg):
 
 
 # ---------------------------------------------------------------------------------------------------------------- guard bands
-@pytest.mark.parametrize('name', ['rows24_rank13', 'rows592_rank64'])
+@pytest.mark.parametrize('name', ['rows24_rank13', 'rows592_rank64', 'rows36_rank96'])
 def test_e_guard_bands(pkg, name):
     """Every plane and w as exact-size slices between NaN / 3e38 guards: no guard word damaged, every output word written, nothing of
     an input guard in a result, inputs unchanged, and the bits of the call on plain arrays."""

@@ -1,5 +1,6 @@
 """CPU tests of the hybrid beamforming weights: the C-ABI surface (header, ctypes table, exported symbols, refusals that need no
-device), the fp64 restatement tests/hybrid_ref.py against a literal per-item loop, and the dictionary helpers of synth."""
+device), the fp64 restatement tests/hybrid_ref.py against a literal per-item loop, the dictionary helpers of synth, and the designs of
+the input builders behind tests/test_gpu_hybrid_regimes.py (atom counts per stop_tol, gap shares, where the equal columns sit)."""
 import ctypes
 import os
 import re
@@ -124,3 +125,122 @@ def test_frf_from_idx(pkg):
     assert frf.shape == (2, 1, 2, 4)
     assert np.array_equal(frf[0, 0, 0], At[:, 2]) and (frf[0, 0, 1] == 0).all() and np.array_equal(frf[1, 0, 1], At[:, 4])
     assert np.array_equal(frf, R.frf_from_idx(At, idx))
+
+
+# ---------------------------------------------------------------------------------------------- the builders of the regime tests
+GAP_MIN = 3e-3              # tests/test_gpu_hybrid.py
+
+
+def test_new_shape_rows_leave_no_item_out(pkg, oracle):
+    """The rows added to the replay grid, on their own inputs: no item falls under the gap rule (the replay allows 1 %), the +-1
+    pilots are non-singular, the widths are the ones the rows are there for, and the dictionary of every row has ntrf columns."""
+    assert [R.svd_lanes(nr) for nr in (1, 3, 5, 6, 7, 12)] == [64, 64, 64, 56, 41, 14]
+    assert {R.svd_lanes(row[1]) for row in R.NEW_SHAPES} >= {56, 41, 14}
+    for nt, nr, ns, ntrf, rays, snr, npkt in R.NEW_SHAPES:
+        assert nt % 4 == 0 and nt <= 256 and nr <= min(nt, 16) and 1 <= ns <= min(nr, ntrf) and ntrf <= min(nt, rays, 16) and rays <= 4096
+        if nt & (nt - 1):
+            P = R.pm1_pilot(nt)
+            assert set(np.unique(P)) == {-1.0, 1.0} and np.linalg.matrix_rank(P) == nt and np.array_equal(P, R.pm1_pilot(nt))
+        h = R.ls_csi(oracle, nt, nr, snr, npkt)
+        assert h.shape == (npkt, nr, nt, 234) and h.dtype == np.complex64 and np.isfinite(h).all()
+        share, g_min = R.left_out_share(R.csi_to_items(h), ns, GAP_MIN)
+        print('Nt %d Nr %d Ns %d: left out %.4f, smallest gap %.3g' % (nt, nr, ns, share, g_min))
+        assert share == 0.0, (nt, nr, ns, share, g_min)
+    # a power of two keeps the Hadamard pilot: the inputs of the older rows are what they were
+    rng = np.random.default_rng(11)
+    ltf, _ = oracle.make_structured_packets(rng, 1, 2, oracle.hadamard(8), snr_db=10)
+    assert np.array_equal(R.ls_csi(oracle, 8, 2, 10, 1), oracle.ls_estimate(ltf, oracle.hadamard(8)).astype(np.complex64))
+
+
+def test_full_span_cases_in_fp64(pkg, oracle):
+    """The pursuit over the unitary DFT dictionary with NtRF = Nt in the fp64 definition: every item takes Nt atoms, frf^T fbb^T
+    is Fopt (the gain is the sum of the ns largest sigma^2 to 1e-12) and at most 1 % of the items fall under the gap rule."""
+    assert len(R.FULL_SPAN_CASES) == 14 and all(nr <= nt for nt, nr, _ in R.FULL_SPAN_CASES)
+    for nt, nr, ns in R.FULL_SPAN_CASES:
+        At = R.dft_dictionary(nt)
+        A = At.astype(np.complex128)
+        assert np.abs(np.conj(A).T @ A - np.eye(nt)).max() < 1e-6
+        H = R.csi_to_items(R.ls_csi(oracle, nt, nr, R.FULL_SPAN_SNR, R.FULL_SPAN_PACKETS))
+        share, g_min = R.left_out_share(H, ns, GAP_MIN)
+        print('Nt %d Nr %d Ns %d: left out %.4f, smallest gap %.3g' % (nt, nr, ns, share, g_min))
+        assert share <= 0.01, (nt, nr, ns, share)
+        if (nt, nr) in ((8, 7), (12, 12), (16, 5)):
+            fbb, idx, n_atoms = R.omp(H, At, ns, nt)
+            assert (n_atoms == nt).all()
+            _, sv = R.fopt_of(H, ns)
+            g = R.gain(H, R.weights_matrix(At, idx, fbb))
+            assert np.abs(g / (sv[:, :ns] ** 2).sum(axis=1) - 1.0).max() < 1e-12
+
+
+def test_mixed_stop_design(pkg):
+    """The fp64 definition on the rounded inputs returns the designed atom counts at the three stop_tol values and the designed
+    columns in descending-magnitude order; every residual is at least 3 % from either threshold (an exact fit: under 1e-6), and
+    every choice the definition makes is at least 1e-3 from a tie, so a correct fp32 run has the same indices."""
+    h, At, kind, cols = R.mixed_stop_inputs()
+    assert h.shape == (2, 4, 32, 234) and h.dtype == np.complex64 and At.shape == (32, 32)
+    assert np.array_equal(kind[:8], [1, 2, 3, 4, 1, 2, 3, 4]) and np.array_equal(kind[234:238], [1, 2, 3, 4])
+    H = R.csi_to_items(h)
+    for t in (1, 2, 3):
+        c = cols[kind == t]
+        assert (c[:, :t] >= 0).all() and (c[:, t:] == -1).all() and all(len(set(r[:t])) == t for r in c)
+    idx, margin, resid = R.omp_margins(H, At, 1, R.MIXED_NTRF)
+    print('smallest distance from a tie %.3g' % margin.min())
+    assert margin.min() >= 1e-3
+    for t in (1, 2, 3):
+        sel = kind == t
+        assert np.array_equal(idx[sel, :t], cols[sel, :t]) and (idx[sel, t:] == -1).all()
+        assert np.nanmax(resid[sel, t - 1]) < 1e-6
+    early = [resid[kind == 2, 0], resid[kind == 3, 0], resid[kind == 3, 1]]
+    print('residuals one step early: %s; white after three atoms: min %.3f' % (
+        ', '.join('%.3f' % r.mean() for r in early), resid[kind == 4, 2].min()))
+    for r, want in zip(early, (0.514, 0.570, 0.287)):
+        assert np.abs(r - want).max() < 1e-3
+    for stop_tol, counts in R.MIXED_STOP_TABLE.items():
+        tol = R.DEFAULT_STOP_TOL if stop_tol is None else stop_tol
+        _, idx_t, n_atoms = R.omp(H, At, 1, R.MIXED_NTRF, tol)
+        assert np.array_equal(n_atoms, R.mixed_stop_counts(kind, stop_tol)), stop_tol
+        assert np.array_equal(np.unique(n_atoms[kind == 4]), [4]) and counts[3] == 4
+        near = np.abs(resid[np.isfinite(resid)] / tol - 1.0).min()
+        assert stop_tol is None or near >= 0.03, (stop_tol, near)
+    share, _ = R.left_out_share(H, 1, GAP_MIN)
+    assert share <= 0.01
+
+
+def test_tie_and_span_stop_design(pkg):
+    """The copies sit where the correlation kernel's order decides - another register of the same lane, the other half wave, another
+    tile, the partial last tile - and every item's best metric belongs to its pair alone."""
+    lane = R.corr_lane_of
+    assert lane(0) == (0, 0, 0) and lane(3) == (0, 0, 3) and lane(4) == (0, 1, 0) and lane(8) == (0, 0, 4) and lane(31) == (0, 1, 15) and lane(32) == (1, 0, 0)
+    (c0, o0), (c1, o1), (c2, o2), (c3, o3) = R.TIE_COPIES
+    assert lane(c0)[:2] == lane(o0)[:2] and lane(c0)[2] != lane(o0)[2]
+    assert lane(c1)[0] == lane(o1)[0] and lane(c1)[1] != lane(o1)[1]
+    assert lane(c2)[0] != lane(o2)[0]
+    assert lane(c3)[0] == (R.TIE_RAYS - 1) // 32 != lane(o3)[0] and R.TIE_RAYS % 32 != 0
+    h, At, want = R.tie_inputs()
+    assert At.shape == (16, 70) and h.shape == (2, 2, 16, 234) and np.abs(np.abs(At) - 1.0).max() < 1e-6
+    for copy, orig in R.TIE_COPIES:
+        assert copy > orig and np.array_equal(At[:, copy], At[:, orig])
+    A = At.astype(np.complex128)
+    gram = np.abs(np.conj(A).T @ A) / 16.0
+    twins = {frozenset(p) for p in R.TIE_COPIES}
+    for a in range(70):
+        for b in range(a + 1, 70):
+            assert (gram[a, b] > 0.999) == (frozenset((b, a)) in twins), (a, b)
+    assert np.array_equal(np.unique(want), [1, 2, 3, 10]) and np.array_equal(want[:4], [1, 2, 3, 10])
+    fopt, _ = R.fopt_of(R.csi_to_items(h), 1)
+    met = R.metric(A, fopt)
+    rows = np.arange(met.shape[0])
+    best = met[rows, want]
+    assert np.abs(best / 16.0 - 1.0).max() < 1e-6
+    copy_of = dict((o, c) for c, o in R.TIE_COPIES)
+    met[rows, want] = 0.0
+    met[rows, [copy_of[k] for k in want]] = 0.0
+    assert (met.max(axis=1) / best).max() < 0.9
+    # the span stop: two identical unit-modulus columns
+    h2, At2 = R.span_stop_inputs()
+    assert At2.shape == (16, 2) and np.array_equal(At2[:, 0], At2[:, 1]) and np.abs(np.abs(At2) - 1.0).max() < 1e-6
+    assert h2.shape == (2, 4, 16, 234) and h2.dtype == np.complex64
+    # zero items
+    hz, zero = R.with_zero_items(np.ones((3, 2, 4, 234), np.complex64))
+    assert zero.sum() == 235 and zero[117] and zero[234:468].all() and not zero[468:].any()
+    assert not R.csi_to_items(hz)[zero].any() and (R.csi_to_items(hz)[~zero] == 1).all()
