@@ -99,6 +99,8 @@ SYMBOLS = {
     'csi_mu_precoder_device': (ctypes.c_int, [_ctx, ctypes.c_int, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.c_int64, ctypes.c_int, _vp, _vp, _vp]),
     'csi_mu_link_sim_device': (ctypes.c_int, [_ctx, ctypes.c_int, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_int64,
                                               ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [_vp] * 10),
+    'csi_mu_hybrid_precoder_device': (ctypes.c_int, [_ctx, ctypes.c_int, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.c_int64, ctypes.c_int, ctypes.c_int]
+                                      + [_vp] * 7),
     'csi_capture_begin': (ctypes.c_int, [_ctx]),
     'csi_capture_end': (ctypes.c_int, [_ctx, ctypes.POINTER(ctypes.c_void_p)]),
     'csi_capture_launch': (ctypes.c_int, [_ctx, _vp]),

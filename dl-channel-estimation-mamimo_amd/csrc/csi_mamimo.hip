@@ -26,6 +26,7 @@
 #include "csi_subspace.hpp"
 #include "csi_beam.hpp"
 #include "csi_mu.hpp"
+#include "csi_mu_hybrid.hpp"
 #include <initializer_list>
 
 namespace {
@@ -323,6 +324,7 @@ void csi_destroy(csi_ctx* c) {
     if (c->hyb_at_re) hipFree(c->hyb_at_re);
     if (c->hyb_ws) hipFree(c->hyb_ws);
     if (c->link_ws) hipFree(c->link_ws);
+    if (c->muh_ws) hipFree(c->muh_ws);
     if (c->lmb_tw) hipFree(c->lmb_tw);
     if (c->lmb_ws) hipFree(c->lmb_ws);
     if (c->lmb_count) hipFree(c->lmb_count);
@@ -1073,6 +1075,14 @@ int csi_mu_link_sim_device(csi_ctx* c, int n_users, const float* const* d_h_re, 
     if (!c) return CSI_ERR_INVALID_ARG;
     return mu_link_sim_device(c, n_users, d_h_re, d_h_im, d_w_re, d_w_im, d_noise_var, seed, first_pkt, npkt, ns, n_sym, bps, d_bit_errors,
                               d_evm_rms, d_sinr_db, d_g_re, d_g_im, d_xeq_re, d_xeq_im, d_csi, d_llr, d_bits);
+}
+
+// ---------------------------------------------------------------- multi-user hybrid precoder (csi_mu_hybrid.hpp, mu_hybrid.hip.h)
+int csi_mu_hybrid_precoder_device(csi_ctx* c, int n_users, const float* const* d_hest_re, const float* const* d_hest_im, int64_t npkt, int ns,
+                                  int n_rf, const float* d_reg, float* d_w_re, float* d_w_im, int32_t* d_idx, float* d_fbb_re, float* d_fbb_im,
+                                  float* d_score) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return mu_hybrid_precoder_device(c, n_users, d_hest_re, d_hest_im, npkt, ns, n_rf, d_reg, d_w_re, d_w_im, d_idx, d_fbb_re, d_fbb_im, d_score);
 }
 
 // ---------------------------------------------------------------- accuracy metric

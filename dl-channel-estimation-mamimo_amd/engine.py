@@ -947,6 +947,51 @@ class CsiEngine:
                 if a is not None:
                     a.free()
 
+    # ------------------------------------------------------------------ multi-user hybrid precoder (csrc/mu_hybrid.hip.h)
+    def mu_hybrid_precoder_device(self, d_hest_re, d_hest_im, npkt, ns, n_rf, d_w_re, d_w_im, d_idx, d_reg=None, d_fbb_re=None, d_fbb_im=None,
+                                  d_score=None):
+        """Hybrid precoder of len(d_hest_re) users (lists of DeviceArrays [npkt,nr,nt,234]) with n_rf RF chains on the dictionary of
+        set_dictionary: per packet n_rf beams chosen greedily by their wideband score, behind them (regularised) zero forcing on the effective
+        channel per subcarrier (csi_mu_hybrid_precoder_device).  d_w_re / d_w_im [npkt, U ns, nt, 234] as mu_link_sim_device reads them; d_idx
+        [npkt, n_rf] holds int32 (``download().view(np.int32)``); optional: d_reg [npkt], the pair d_fbb_re / d_fbb_im [npkt, 234, n_rf, U ns],
+        d_score [npkt, U ns, rays].  Asynchronous, on the engine's stream."""
+        ptr = lambda a: None if a is None else a.ptr
+        self._check(self._lib.csi_mu_hybrid_precoder_device(self._ctx, len(d_hest_re), self._ptr_array(d_hest_re), self._ptr_array(d_hest_im),
+                                                            int(npkt), int(ns), int(n_rf), ptr(d_reg), d_w_re.ptr, d_w_im.ptr, d_idx.ptr,
+                                                            ptr(d_fbb_re), ptr(d_fbb_im), ptr(d_score)))
+
+    def mu_hybrid_precoder(self, hests, ns, n_rf, reg=None, keep_fbb=False, keep_score=False):
+        """The same from numpy arrays: hests = U complex arrays [npkt,nr,nt,234]; reg None, a scalar or [npkt].  Returns (w_re, w_im float32
+        [npkt, U ns, nt, 234], idx int32 [npkt, n_rf]), then with keep_fbb the baseband part fbb complex64 [npkt, 234, n_rf, U ns] and with
+        keep_score the beam scores float32 [npkt, U ns, rays]; the analog part of packet p is dictionary[:, idx[p]]."""
+        hests = [np.asarray(h) for h in hests]
+        npkt = hests[0].shape[0] if hests and hests[0].ndim else 0
+        for h in hests:
+            if h.shape != (npkt, self.nr, self.nt, N_DATA):
+                raise CsiError(-1, f'every h must be [{npkt},{self.nr},{self.nt},{N_DATA}], got {h.shape}')
+        nu, m, q = len(hests), len(hests) * max(int(ns), 0), max(int(n_rf), 0)
+        if getattr(self, 'dictionary', None) is None:
+            raise CsiError(-2, 'mu_hybrid_precoder: no dictionary set (set_dictionary)')
+        rays = self.dictionary.shape[1]
+        dev = [self.to_device(_f32c(h.real)) for h in hests] + [self.to_device(_f32c(h.imag)) for h in hests]
+        d_reg = None if reg is None else self.to_device(np.ascontiguousarray(np.broadcast_to(np.asarray(reg, np.float32), (npkt,))))
+        outs = [self.empty((npkt, m, self.nt, N_DATA)), self.empty((npkt, m, self.nt, N_DATA)), self.empty((npkt, q))]
+        fbb = [self.empty((npkt, N_DATA, q, m)) for _ in range(2)] if keep_fbb else [None, None]
+        score = self.empty((npkt, m, rays)) if keep_score else None
+        try:
+            self.mu_hybrid_precoder_device(dev[:nu], dev[nu:], npkt, ns, n_rf, outs[0], outs[1], outs[2], d_reg, fbb[0], fbb[1], score)
+            self.synchronize()
+            res = [outs[0].download(), outs[1].download(), outs[2].download().view(np.int32)]
+            if keep_fbb:
+                res.append((fbb[0].download() + 1j * fbb[1].download()).astype(np.complex64))
+            if keep_score:
+                res.append(score.download())
+            return tuple(res)
+        finally:
+            for a in dev + outs + fbb + [d_reg, score]:
+                if a is not None:
+                    a.free()
+
     def viterbi_decode(self, llr):
         """Viterbi decoding of terminated codewords of the rate-1/3 K = 7 code (133, 171, 165): llr float [ncw, 3 n_steps], positive = 0
         -> uint8 [ncw, n_steps - 6] (csi_viterbi_decode_device; fp32 metrics, ties to the predecessor with the lower state number)."""

@@ -7,12 +7,14 @@ knows the effective channel; --rxEstimate runs every source a second time with t
 a precoded preamble (csi_link_sim_rx_device), and adds the bersRx_ / EVM_rmsRx_ / gNMSE_ families.  --users U (U >= 2) serves U users at
 once on the same subcarriers: per source the zero-forcing precoder of the U users' estimates (csi_mu_precoder_device) and
 the data phase through their true channels (csi_mu_link_sim_device) add the bersMU_ / EVM_rmsMU_ / sinrMU_ families, the mean over the users.
+--muHybrid NRF runs that phase a second time behind the hybrid precoder of NRF RF chains (csi_mu_hybrid_precoder_device:
+beams from the --ber dictionary, zero forcing on the effective channel) and adds the bersMUH_ / EVM_rmsMUH_ / sinrMUH_ families.
 
     python -m dl_channel_estimation_mamimo_amd.sweep -d OUT [--nTX 32 --nRX 4 --nn 1024 1024 --useBN --bs 256 ...]
                                                             [--ber --numSTS 1 --rays 500 --dataSymbols 10 --bps 2 [--rxEstimate]]
                                                             [--channel scattering --scatterers 100 --range 100 --userAz 30 --userEl 0 --randomUsers]
                                                             [--blind] [--delayTaps L [--delayPre P]] [--beams]
-                                                            [--ber --users U [--muReg zf|rzf] [--userSpacing DEG]]
+                                                            [--ber --users U [--muReg zf|rzf] [--userSpacing DEG] [--muHybrid NRF]]
 
 The module holds no arithmetic of its own: packets with a known channel come from csi_synth_structured (--channel scattering: from
 csi_synth_scattering, whose path delays then feed the LMMSE smoother as the reference's h_tau does), labels from
@@ -42,6 +44,7 @@ ESTIMATORS = ('LS', 'MMSE', 'DNN')
 SOURCES = ESTIMATORS + ('perfect',)      # --ber: whose hybrid weights precode the data phase (perfect = the true channel)
 LINK_FIELDS = ('bers_', 'EVM_rms_', 'dtSNR_')
 RX_FIELDS = ('bersRx_', 'EVM_rmsRx_', 'gNMSE_')     # --rxEstimate: the same data phase equalised with the preamble's estimate of H W
+MUH_FIELDS = ('bersMUH_', 'EVM_rmsMUH_', 'sinrMUH_')  # --muHybrid: the same data phase behind the hybrid precoder of n_rf RF chains
 MU_FIELDS = ('bersMU_', 'EVM_rmsMU_', 'sinrMU_')    # --users: the multi-user data phase, the mean over the users per packet
 DELAY = 'DLY'                            # --delayTaps: the LS rows projected onto a window of delay taps (csi_subspace_smooth_device, w = 1)
 BEAMS = 'ANG'                            # --beams: the beam-space Wiener smoother across the Tx antennas on the LS planes (csi_beam_wiener_device)
@@ -103,7 +106,7 @@ def make_dataset(engine, n_train, seed, n_taps=8, amp_scale=True, channel=None):
 
 
 def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=True, keep=False, ber=None, channel=None, blind=False,
-                   rx_estimate=False, delay=None, mu=None, beams=False):
+                   rx_estimate=False, delay=None, mu=None, beams=False, mu_hybrid=None):
     """npkt test packets at `snr_db` (packets first_pkt ... of stream `seed`: keep them disjoint from the training packets), LS + DNN
     (estimate_device), the LMMSE smoother on the LS planes, and NMSE_subk of the three estimates against the true channel.
     Returns {'MSE_LS', 'MSE_MMSE', 'MSE_DNN'}: float64 [npkt], the per-link ratios averaged per packet.
@@ -132,7 +135,11 @@ def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=Tr
     X - here DLY is one too - and 'mu_users' = {X: {'bers', 'EVM_rms', 'sinr': [U][npkt]}}.  Nothing else changes.
 
     beams=True adds 'MSE_ANG' (beam_planes: the beam-space Wiener smoother on the LS planes) and, with `delay`, 'MSE_DLYANG' (the same
-    step on the DLY planes).  ANG is a source of the multi-user data phase as DLY is, and of no other.  Nothing else changes."""
+    step on the DLY planes).  ANG is a source of the multi-user data phase as DLY is, and of no other.  Nothing else changes.
+
+    mu_hybrid=n_rf (with `mu`) runs the multi-user data phase a second time per source behind the hybrid precoder of n_rf RF chains on the
+    engine's dictionary (mu_level): 'bersMUH_X', 'EVM_rmsMUH_X', 'sinrMUH_X' and 'muh_users' (the per-user arrays and the chosen beams).
+    Nothing else changes."""
     nr, nt = engine.nr, engine.nt
     d_tau = None
     if channel is None:
@@ -189,7 +196,7 @@ def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=Tr
                       for u in range(1, int(mu['users']))]
             nv = np.stack([synth.link_noise_var(d.download(), amp_scale) for d in [d_std] + [o['noise_std'] for o in others]])
             out.update(mu_level(engine, [planes] + [o['planes'] for o in others], nv, npkt, seed, first_pkt, ns=ber['ns'], n_sym=ber['n_sym'],
-                                bps=ber['bps'], reg=mu.get('reg', 'zf')))
+                                bps=ber['bps'], reg=mu.get('reg', 'zf'), n_rf=mu_hybrid))
             for o in others:
                 for a in o['free']:
                     a.free()
@@ -268,13 +275,16 @@ def user_planes(engine, snr_db, npkt, seed, first_pkt, n_taps, amp_scale, channe
     return dict(planes=planes, noise_std=d_std, free=free)
 
 
-def mu_level(engine, planes, noise_var, npkt, seed, first_pkt, ns=1, n_sym=10, bps=2, reg='zf'):
+def mu_level(engine, planes, noise_var, npkt, seed, first_pkt, ns=1, n_sym=10, bps=2, reg='zf', n_rf=None):
     """The multi-user data phase of one level on resident planes.  planes = one dict {X: (re, im)} per user, with the
     true channel under 'perfect'; noise_var float32 [U, npkt].  For every source X the precoder of the U users' X planes
     (mu_precoder_device; reg 'zf': none, 'rzf': M noise_var / Nt with the users' mean noise_var of the packet) carries coded QAM through
     the U TRUE channels (mu_link_sim_device) - the same bits and the same noise for every source.  Returns {'bersMU_X', 'EVM_rmsMU_X',
     'sinrMU_X'}: float64 [npkt], the mean over the users (of the dB values for sinr), and 'mu_users': {X: {'bers', 'EVM_rms', 'sinr'}}
-    with the [U][npkt] values as lists."""
+    with the [U][npkt] values as lists.
+    n_rf adds, per source, the same data phase - the same user seeds and the same noise, a paired comparison - behind the hybrid precoder of
+    n_rf RF chains on the engine's dictionary (mu_hybrid_precoder_device) with the same reg: 'bersMUH_X', 'EVM_rmsMUH_X',
+    'sinrMUH_X' and 'muh_users': {X: {'bers', 'EVM_rms', 'sinr', 'beams': [npkt][n_rf] dictionary columns}}."""
     nu, nt = len(planes), engine.nt
     m = nu * int(ns)
     if reg not in ('zf', 'rzf'):
@@ -286,18 +296,28 @@ def mu_level(engine, planes, noise_var, npkt, seed, first_pkt, ns=1, n_sym=10, b
     w = [engine.empty((npkt, m, nt, N_DATA)) for _ in range(2)]
     d_err, d_evm, d_sinr = (engine.empty((nu, npkt)) for _ in range(3))
     h_re, h_im = [p['perfect'][0] for p in planes], [p['perfect'][1] for p in planes]
-    out, users = {}, {}
-    for name in planes[0]:
-        engine.mu_precoder_device([p[name][0] for p in planes], [p[name][1] for p in planes], npkt, ns, w[0], w[1], d_reg)
+    d_idx = engine.empty((npkt, int(n_rf))) if n_rf else None
+    out, users, users_h = {}, {}, {}
+
+    def data_phase(fields):
         engine.mu_link_sim_device(h_re, h_im, w[0], w[1], d_nv, seed, first_pkt, npkt, ns, d_err, d_evm, d_sinr, n_sym=n_sym, bps=bps)
         per = dict(bers=d_err.download().view(np.int32).astype(np.float64) / n_info, EVM_rms=d_evm.download().astype(np.float64),
                    sinr=d_sinr.download().astype(np.float64))
-        for f, k in zip(MU_FIELDS, ('bers', 'EVM_rms', 'sinr')):
+        for f, k in zip(fields, ('bers', 'EVM_rms', 'sinr')):
             out[f + name] = per[k].mean(axis=0)
-        users[name] = {k: v.tolist() for k, v in per.items()}
-    for a in w + [d_err, d_evm, d_sinr, d_nv] + ([d_reg] if d_reg is not None else []):
+        return {k: v.tolist() for k, v in per.items()}
+
+    for name in planes[0]:
+        engine.mu_precoder_device([p[name][0] for p in planes], [p[name][1] for p in planes], npkt, ns, w[0], w[1], d_reg)
+        users[name] = data_phase(MU_FIELDS)
+    for name in planes[0] if n_rf else ():
+        engine.mu_hybrid_precoder_device([p[name][0] for p in planes], [p[name][1] for p in planes], npkt, ns, int(n_rf), w[0], w[1], d_idx, d_reg)
+        users_h[name] = dict(data_phase(MUH_FIELDS), beams=d_idx.download().view(np.int32).tolist())
+    for a in w + [d_err, d_evm, d_sinr, d_nv] + ([d_reg] if d_reg is not None else []) + ([d_idx] if d_idx is not None else []):
         a.free()
     out['mu_users'] = users
+    if n_rf:
+        out['muh_users'] = users_h
     return out
 
 
@@ -384,6 +404,8 @@ def metric_fields(mse):
     fields += ['MSE_' + e for e in (BEAMS, DELAY_BEAMS) if 'MSE_' + e in mse]
     if MU_FIELDS[0] + BEAMS in mse:
         fields += [f + BEAMS for f in MU_FIELDS]
+    if MUH_FIELDS[0] + 'perfect' in mse:
+        fields += [f + x for x in SOURCES + tuple(e for e in (BLIND, DELAY, BEAMS) if MUH_FIELDS[0] + e in mse) for f in MUH_FIELDS]
     return fields
 
 
@@ -394,7 +416,8 @@ def write_metrics(path, mse):
     A level evaluated with blind=True carries MSE_MMSEb (and with the data phase bers_MMSEb, EVM_rms_MMSEb, dtSNR_MMSEb): written behind
     those.  A level evaluated with rx_estimate=True carries bersRx_X, EVM_rmsRx_X and gNMSE_X: written behind those, and MSE_DLY of a level evaluated
     with delay=(L, pre) behind those; bersMU_X, EVM_rmsMU_X and sinrMU_X of a level evaluated with mu=... behind those; MSE_ANG, MSE_DLYANG and
-    bersMU_ANG, EVM_rmsMU_ANG, sinrMU_ANG of a level evaluated with beams=True last (metric_fields)."""
+    bersMU_ANG, EVM_rmsMU_ANG, sinrMU_ANG of a level evaluated with beams=True behind those; bersMUH_X, EVM_rmsMUH_X and sinrMUH_X of a level
+    evaluated with mu_hybrid=... last (metric_fields)."""
     from scipy.io import savemat
     os.makedirs(os.path.dirname(path), exist_ok=True)
     savemat(path, {f: np.asarray(mse[f], np.float64).reshape(1, -1) for f in metric_fields(mse)})
@@ -408,6 +431,8 @@ def format_table(result):
     cols += [MU_FIELDS[0] + x for x in list(SOURCES) + blind + ([DELAY] if result.get('delay') else [])] if result.get('mu') else []
     if result.get('beams'):
         cols += [BEAMS] + ([DELAY_BEAMS] if result.get('delay') else []) + ([MU_FIELDS[0] + BEAMS] if result.get('mu') else [])
+    if result.get('mu_hybrid'):
+        cols += [MUH_FIELDS[0] + x for x in list(SOURCES) + blind + ([DELAY] if result.get('delay') else []) + ([BEAMS] if result.get('beams') else [])]
     lines = ['%8s' % 'SNR dB' + ''.join('  %-38s' % (e + ': mean [CI low, CI high]') for e in cols)]
     for lv in result['levels']:
         row = '%8g' % lv['snr_db']
@@ -422,7 +447,7 @@ def format_table(result):
 
 def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500, seed=0, modeldir=None, fit_args=None, n_taps=8,
               amp_scale=True, save_dataset=None, verbose=True, ber=None, channel=None, blind=False, rx_estimate=False,
-              delay_taps=None, delay_pre=0, users=None, mu_reg='zf', user_spacing=15.0, beams=False):
+              delay_taps=None, delay_pre=0, users=None, mu_reg='zf', user_spacing=15.0, beams=False, mu_hybrid=None):
     """Training set -> models (loaded from `modeldir`, else fitted and saved into `out`) -> every level.  Writes
     <out>/BS<Nt>_SNR<s>/metrics.mat per level and <out>/sweep.json, prints the table, returns the result dict (with the per-packet
     arrays under 'per_packet' = {level: {'MSE_LS', ...}}).  Test packets come from the stream seed + 1, behind the index range of
@@ -444,7 +469,11 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
     beams=True adds the estimator ANG per level (evaluate_level(beams=True)) and, with delay_taps, DLYANG: MSE_ANG / MSE_DLYANG in
     metrics.mat behind every other field, columns of the table and entries per level of sweep.json, which then records 'beams': true;
     with users also the source ANG of the multi-user data phase (bersMU_ANG, EVM_rmsMU_ANG, sinrMU_ANG and its per-user arrays).
-    Without it every output is what it is without the argument."""
+    Without it every output is what it is without the argument.
+    mu_hybrid=n_rf (needs `users`, U ns <= n_rf <= min(16, Nt, rays)) adds the multi-user data phase behind the hybrid precoder of n_rf RF
+    chains per source (evaluate_level(mu_hybrid=...)): bersMUH_X, EVM_rmsMUH_X and sinrMUH_X in metrics.mat behind every other field, the
+    same with confidence intervals and 'muh_users' (per-user arrays and chosen beams) per level of sweep.json, which then records
+    'mu_hybrid': {n_rf}; without it every output is what it is without the argument."""
     if rx_estimate and ber is None:
         raise ValueError('rx_estimate needs the data phase (ber)')
     mu = None
@@ -454,6 +483,13 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
         if int(users) > 8 or int(users) * int(ber['ns']) > min(16, engine.nt):
             raise ValueError('users x ns = %d x %d streams exceed min(16, Nt %d) (or users > 8)' % (int(users), int(ber['ns']), engine.nt))
         mu = dict(users=int(users), reg=str(mu_reg), spacing=float(user_spacing))
+    if mu_hybrid is not None:
+        if mu is None:
+            raise ValueError('mu_hybrid needs the multi-user data phase (users >= 2)')
+        rays = engine.dictionary.shape[1]
+        if not mu['users'] * int(ber['ns']) <= int(mu_hybrid) <= min(16, engine.nt, rays):
+            raise ValueError('mu_hybrid n_rf %d outside users x ns = %d .. min(16, Nt %d, rays %d)' % (int(mu_hybrid), mu['users'] * int(ber['ns']), engine.nt, rays))
+        mu_hybrid = int(mu_hybrid)
     os.makedirs(out, exist_ok=True)
     result = dict(nt=engine.nt, nr=engine.nr, n_train=int(n_train), n_test=int(n_test), seed=int(seed), n_taps=int(n_taps),
                   amp_scale=bool(amp_scale), levels=[], training=None)
@@ -467,6 +503,8 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
         result['rx_estimate'] = True
     if mu:
         result['mu'] = dict(mu)
+    if mu_hybrid:
+        result['mu_hybrid'] = dict(n_rf=mu_hybrid)
     delay = None
     if delay_taps:
         delay = (int(delay_taps), int(delay_pre))
@@ -491,7 +529,7 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
     for i, snr in enumerate(levels):
         t0 = time.perf_counter()
         mse = evaluate_level(engine, snr, n_test, seed + 1, n_train + i * n_test, n_taps, amp_scale, ber=ber, channel=channel, blind=blind,
-                             rx_estimate=rx_estimate, delay=delay, mu=mu, beams=beams)
+                             rx_estimate=rx_estimate, delay=delay, mu=mu, beams=beams, mu_hybrid=mu_hybrid)
         sec = time.perf_counter() - t0
         write_metrics(os.path.join(out, 'BS%d_SNR%g' % (engine.nt, snr), 'metrics.mat'), mse)
         lv = dict(snr_db=float(snr), seconds=sec)
@@ -517,6 +555,12 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
         for f in MU_FIELDS if (beams and mu) else ():
             m, lo, hi = confidence_interval(mse[f + BEAMS])
             lv[f + BEAMS] = dict(mean=m, ci_low=lo, ci_high=hi)
+        if mu_hybrid:
+            for x in SOURCES + ((BLIND,) if blind else ()) + ((DELAY,) if delay else ()) + ((BEAMS,) if beams else ()):
+                for f in MUH_FIELDS:
+                    m, lo, hi = confidence_interval(mse[f + x])
+                    lv[f + x] = dict(mean=m, ci_low=lo, ci_high=hi)
+            lv['muh_users'] = mse['muh_users']
         result['levels'].append(lv)
         per_packet[float(snr)] = mse
     with open(os.path.join(out, 'sweep.json'), 'w') as f:
@@ -558,6 +602,9 @@ def build_parser():
                    help='--ber: serve U users (2 .. 8) at once with a zero-forcing precoder over U x numSTS streams (csi_mu_precoder_device, '
                         'csi_mu_link_sim_device) - bersMU_ / EVM_rmsMU_ / sinrMU_')
     p.add_argument('--muReg', default='zf', choices=('zf', 'rzf'), help='--users: zero forcing, or regularised with M link_noise_var / Nt')
+    p.add_argument('--muHybrid', default=0, type=int, metavar='NRF',
+                   help='--users: also precode with NRF RF chains - beams chosen from the --ber dictionary, zero forcing on the effective channel '
+                        '(csi_mu_hybrid_precoder_device, U x numSTS <= NRF <= min(16, nTX, rays)) - bersMUH_ / EVM_rmsMUH_ / sinrMUH_')
     p.add_argument('--userSpacing', default=15.0, type=float, metavar='DEG', help='--users with --channel scattering: user u sits at azimuth userAz + u DEG')
     p.add_argument('--channel', default='taps', choices=('taps', 'scattering'),
                    help='taps: i.i.d. impulse responses (csi_synth_structured); scattering: the geometric single-bounce channel (csi_synth_scattering)')
@@ -597,6 +644,11 @@ def parse_args(argv=None):
             parser.error('--users needs --ber')
         if args.users * args.numSTS > min(16, args.nTX):
             parser.error('--users x --numSTS = %d streams exceed min(16, nTX %d)' % (args.users * args.numSTS, args.nTX))
+    if args.muHybrid:
+        if args.users < 2 or not args.ber:
+            parser.error('--muHybrid needs --ber --users U (U >= 2)')
+        if not args.users * args.numSTS <= args.muHybrid <= min(16, args.nTX, args.rays):
+            parser.error('--muHybrid %d outside --users x --numSTS = %d .. min(16, nTX %d, rays %d)' % (args.muHybrid, args.users * args.numSTS, args.nTX, args.rays))
     if args.delayTaps and not (1 <= args.delayTaps <= subspace.MAX_RANK and 0 <= args.delayPre <= args.delayTaps):
         parser.error('--delayTaps takes 1 .. %d and --delayPre 0 .. L' % subspace.MAX_RANK)
     if args.delayPre and not args.delayTaps:
@@ -621,7 +673,8 @@ def main(argv=None):
               modeldir=args.modeldir or None, fit_args=fit_args, n_taps=args.taps, save_dataset=args.save_dataset or None,
               verbose=not args.quiet, ber=ber, channel=channel_from_args(args), blind=bool(args.blind),
               rx_estimate=bool(args.rxEstimate), delay_taps=args.delayTaps or None, delay_pre=args.delayPre,
-              users=args.users if args.users >= 2 else None, mu_reg=args.muReg, user_spacing=args.userSpacing, beams=bool(args.beams))
+              users=args.users if args.users >= 2 else None, mu_reg=args.muReg, user_spacing=args.userSpacing, beams=bool(args.beams),
+              mu_hybrid=args.muHybrid or None)
     return 0
 
 

@@ -43,7 +43,7 @@
  * context's stream and return without waiting; call csi_synchronize before reading results.
  *
  * Device pointers (csi_predict_device, csi_ls_estimate_device, csi_estimate_device, csi_lmmse_estimate_device, csi_lmmse_blind_device, csi_subspace_smooth_device, csi_beam_power_device, csi_beam_smooth_device, csi_beam_wiener_device, csi_null_noise_device, csi_nmse_device,
- * csi_hybrid_weights_device, csi_link_sim_device, csi_link_sim_rx_device, csi_mu_precoder_device, csi_mu_link_sim_device, csi_viterbi_decode_device, csi_synth_*).  An array of exactly the documented
+ * csi_hybrid_weights_device, csi_link_sim_device, csi_link_sim_rx_device, csi_mu_precoder_device, csi_mu_link_sim_device, csi_mu_hybrid_precoder_device, csi_viterbi_decode_device, csi_synth_*).  An array of exactly the documented
  * size suffices: it may be a slice of a larger allocation whose neighbours hold live data of any value (NaN and 1e38 included).
  * Nothing outside the arrays is written, nothing outside them reaches a result, and input arrays are not modified.  Every re / im
  * PLANE (the preambles [npkt][Nr][len_ltf], the CSI planes [npkt][Nr][Nt][234 or n_out], fbb, frf_mean, xeq, gest, the precoder planes W, g) starts on a 16-byte
@@ -455,6 +455,32 @@ int  csi_mu_link_sim_device(csi_ctx* ctx, int n_users, const float* const* d_h_r
                             int n_sym, int bps, int32_t* d_bit_errors, float* d_evm_rms, float* d_sinr_db, float* d_g_re, float* d_g_im,
                             float* d_xeq_re, float* d_xeq_im, float* d_csi, float* d_llr, uint8_t* d_bits);
 
+/* Multi-user hybrid precoder (generate_maMIMO_LTF_SINR.m:357-369, helperJSDMTransmitWeights - a toolbox helper outside the reference tree;
+ * model, deviation from JSDM and kernel plans: DESIGN.md 4.22, csrc/mu_hybrid.hip.h).  An addition: the ABI version stays 1.  The shapes of
+ * csi_mu_precoder_device (U users, ns streams per user, M = U ns, B_k[m][j] = hest_u[p][s][j][k]), the dictionary At [Nt][R] of
+ * csi_hybrid_set_dictionary (columns as given) and n_rf RF chains, M <= n_rf <= min(16, Nt, R):
+ *   score     S[p][m][r] = sum_k | sum_j B_k[m][j] At[j][r] |^2  (fp32 MFMA; every sum in an order that depends on Nt, R and the subcarrier
+ *             index alone, no atomics)
+ *   select    per packet, q = 0 .. n_rf-1: stream m = q mod M; idx[p][q] = argmax over the rays not yet taken in this packet of S[p][m][r],
+ *             the lowest r on a tie, a non-finite score compares as -inf;  Frf[:, q] = At[:, idx[p][q]] (Nt x n_rf, flat over the subcarriers)
+ *   baseband  per (packet, subcarrier): G = B_k Frf,  A = G G^H + reg[p] I (d_reg [npkt], NULL = 0),  Cholesky A = L L^H (a pivot <= 0 or
+ *             not finite: W = 0 and Fbb = 0 for the item),  Vbb = G^H A^-1,  V = Frf Vbb,  c_m = sqrt(Nt / M) / |V[:, m]|_2 (a zero or
+ *             non-finite norm: 0),  W[:, m] = c_m V[:, m],  Fbb[:, m] = c_m Vbb[:, m]:  W = Frf Fbb and |W|_F^2 = Nt, the normalisation of
+ *             csi_mu_precoder_device.
+ * Outputs: d_w_re / d_w_im [npkt][M][Nt][234] (what csi_mu_link_sim_device reads), d_idx int32 [npkt][n_rf]; optional (may be NULL): the pair
+ * d_fbb_re / d_fbb_im [npkt][234][n_rf][M], d_score [npkt][M][R].  d_hest_re / d_hest_im are HOST arrays of U device pointers.
+ * Asynchronous on the context's stream; serves fp32 and bf16 contexts alike; usable inside csi_capture_begin / _end after one eager call
+ * of the same shape.  Runs in packet chunks against the context's workspace_bytes when d_score is NULL (the score planes of a chunk live
+ * in the workspace; default 1 GiB), three kernel launches per chunk, with the same bits whatever the chunking, the call or the packet's
+ * position in it.
+ * Refused with text, before anything is launched or counted: everything csi_mu_precoder_device refuses, no dictionary set
+ * (CSI_ERR_NOT_READY), n_rf outside M .. min(16, Nt, R), one fbb plane without the other, planes off a 16-byte boundary, an LDS image beyond
+ * 160 KiB (the score kernel stages four dictionary tiles, 1 KiB per antenna: Nt > 160), an open capture that would have to grow the workspace.  npkt == 0 returns 0 and launches nothing; a null context returns -1.
+ * The launches count under "mu_launches"; profile entries "mu_beam_score", "mu_beam_select" and "mu_hybrid_precoder". */
+int  csi_mu_hybrid_precoder_device(csi_ctx* ctx, int n_users, const float* const* d_hest_re, const float* const* d_hest_im, int64_t npkt,
+                                   int ns, int n_rf, const float* d_reg, float* d_w_re, float* d_w_im, int32_t* d_idx, float* d_fbb_re,
+                                   float* d_fbb_im, float* d_score);
+
 /* Accuracy metric of the reference's evaluation, NMSE_subk (BER_test_maMIMO_LTF.m:675-686): per link
  * ||ref - est||^2 / ||ref||^2 over the n_bins bins, mean over the nlinks links ([link][n_bins] planes, e.g.
  * the [npkt][nr][nt][234] outputs of csi_predict / csi_ls_estimate with nlinks = npkt*nr*nt).  Synchronous;
@@ -642,7 +668,7 @@ int  csi_set_option(csi_ctx* ctx, const char* name, int64_t value);
 /* Current value of an option, or of the read-only values: "hs_launches" (split-engine GEMMs launched), "hs_range_fallbacks"
  * (csi_predict calls repeated on the fp32 MFMA kernels), "hs_weight_pins" / "hs_weight_err_e12" (layers pinned to the fp32 kernels
  * at load because their split copies were not fp32-grade; worst relative error x 1e12), "band_available" (the assembly band kernel
- * is embedded in this build), "graph_replays", "subspace_launches" (kernels launched by csi_subspace_smooth[_device]), "beam_launches" (kernels launched by the csi_beam_* entry points), "mu_launches" (kernels launched by csi_mu_precoder_device / csi_mu_link_sim_device), "lmmse_blind_fallbacks" ((packet, rx) pairs csi_lmmse_blind[_device] handed back unsmoothed), "ls_pilot_fast" (0 generic / 1 Sylvester / 2 permuted pilot), "comm_world",
+ * is embedded in this build), "graph_replays", "subspace_launches" (kernels launched by csi_subspace_smooth[_device]), "beam_launches" (kernels launched by the csi_beam_* entry points), "mu_launches" (kernels launched by csi_mu_precoder_device / csi_mu_link_sim_device / csi_mu_hybrid_precoder_device), "lmmse_blind_fallbacks" ((packet, rx) pairs csi_lmmse_blind[_device] handed back unsmoothed), "ls_pilot_fast" (0 generic / 1 Sylvester / 2 permuted pilot), "comm_world",
  * "comm_rank", "comm_blobs", "comm_bytes" (communicator and last broadcast), "hp_direct_out_calls", and where the last pipelined
  * host-buffer call spent its time in microseconds: "hp_total_us", "hp_stage_us", "hp_wait_stage_us", "hp_wait_out_us", "hp_weave_us". */
 int  csi_get_option(csi_ctx* ctx, const char* name, int64_t* value);
