@@ -30,6 +30,7 @@
 #include "beam_smooth.hip.h"
 #include "mu_link.hip.h"
 #include "mu_hybrid.hip.h"
+#include "mu_jsdm.hip.h"
 
 using namespace csi;
 
@@ -69,6 +70,9 @@ enum KernelId {
     K_MU_BEAM_SCORE,     // multi-user hybrid precoder (mu_hybrid.hip.h): wideband beam score per (packet, stream, ray) (fp32 MFMA); placed like K_SUBSPACE_SMOOTH
     K_MU_BEAM_SELECT,    // multi-user hybrid precoder: greedy choice of the n_rf beams of a packet
     K_MU_HYBRID_PRECODER,// multi-user hybrid precoder: zero forcing on the effective channel B Frf per (packet, subcarrier)
+    K_MU_COV,            // multi-user JSDM precoder (mu_jsdm.hip.h): transmit covariance per (packet, user) (fp32 MFMA); placed like K_SUBSPACE_SMOOTH
+    K_MU_JSDM_EIG,       // multi-user JSDM precoder: Jacobi eigenvectors per (packet, group), both stages (covariance; nulled covariance -> beams)
+    K_MU_JSDM_BASEBAND,  // multi-user JSDM precoder: zero forcing on the effective channel B Frf per (packet, subcarrier), per group or jointly
     K_BEAM_POWER,        // beam-space smoother (csi_beam_*, beam_smooth.hip.h): beam power E per (packet, rx, beam); placed like K_SUBSPACE_SMOOTH
     K_BEAM_SMOOTH,       // beam-space smoother: y = A diag(w) A^H x across the Tx antennas
     K_SYNTH_SCATTERING,  // known-channel sounding packets of the scattering channel (synth_scattering.hip.h): the power pass and the packet pass of csi_synth_scattering
@@ -82,7 +86,7 @@ const char* const kKernelNames[K_COUNT] = {
     "ls_estimate", "naive_dense0_gemm", "synth_white", "pilot_table", "cast_bf16", "pair_h1_bf16", "lmmse_levinson",
     "train_gemm", "train_elementwise", "nmse_links", "pair_dense_tail", "input_pool", "conv_frontend",
     "hybrid_svd", "hybrid_corr_argmax", "hybrid_solve", "hybrid_finish", "synth_structured", "link_txrx", "link_viterbi",
-    "subspace_smooth", "mu_precoder", "mu_txrx", "mu_beam_score", "mu_beam_select", "mu_hybrid_precoder", "beam_power", "beam_smooth", "synth_scattering", "lmmse_null_noise", "lmmse_freq_corr", "lmmse_blind"};
+    "subspace_smooth", "mu_precoder", "mu_txrx", "mu_beam_score", "mu_beam_select", "mu_hybrid_precoder", "mu_cov", "mu_jsdm_eig", "mu_jsdm_baseband", "beam_power", "beam_smooth", "synth_scattering", "lmmse_null_noise", "lmmse_freq_corr", "lmmse_blind"};
 
 thread_local std::string g_create_error;
 
@@ -249,10 +253,13 @@ struct csi_ctx {
     char* beam_ws = nullptr;
     size_t beam_ws_bytes = 0;
     int64_t beam_launches = 0;   // "beam_launches": kernels launched by the csi_beam_* entry points
-    int64_t mu_launches = 0;     // "mu_launches": kernels launched by csi_mu_precoder_device / csi_mu_link_sim_device / csi_mu_hybrid_precoder_device
+    int64_t mu_launches = 0;     // "mu_launches": kernels launched by csi_mu_precoder_device / csi_mu_link_sim_device / csi_mu_hybrid_precoder_device / csi_mu_covariance_device / csi_mu_jsdm_precoder_device
     char* muh_ws = nullptr;      // multi-user hybrid precoder (csi_mu_hybrid.hpp): the score planes of a packet chunk when the caller keeps none (sized by eager calls)
     size_t muh_ws_bytes = 0;
     size_t muh_lds_attr[3] = {}; // dynamic-LDS limit already raised for its score kernel / baseband kernel of 64 lanes / of 32 lanes
+    char* muj_ws = nullptr;      // multi-user JSDM precoder (csi_mu_jsdm.hpp): covariance, eigenvalue, U*, rank and Frf planes of a packet chunk (sized by eager calls)
+    size_t muj_ws_bytes = 0;
+    size_t muj_lds_attr[3] = {}; // dynamic-LDS limit already raised for its eigen kernel / baseband kernel of 64 lanes / of 32 lanes
     int64_t link_launches = 0;   // "link_launches": kernels launched by csi_link_sim_device / csi_viterbi_decode_device
     bool user_capture = false;   // between csi_capture_begin and csi_capture_end (csi_hybrid.hpp): device-pointer calls are recorded, not run
     bool user_capture_use_graph = false;

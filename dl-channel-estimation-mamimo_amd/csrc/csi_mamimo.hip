@@ -27,6 +27,7 @@
 #include "csi_beam.hpp"
 #include "csi_mu.hpp"
 #include "csi_mu_hybrid.hpp"
+#include "csi_mu_jsdm.hpp"
 #include <initializer_list>
 
 namespace {
@@ -325,6 +326,7 @@ void csi_destroy(csi_ctx* c) {
     if (c->hyb_ws) hipFree(c->hyb_ws);
     if (c->link_ws) hipFree(c->link_ws);
     if (c->muh_ws) hipFree(c->muh_ws);
+    if (c->muj_ws) hipFree(c->muj_ws);
     if (c->lmb_tw) hipFree(c->lmb_tw);
     if (c->lmb_ws) hipFree(c->lmb_ws);
     if (c->lmb_count) hipFree(c->lmb_count);
@@ -1083,6 +1085,22 @@ int csi_mu_hybrid_precoder_device(csi_ctx* c, int n_users, const float* const* d
                                   float* d_score) {
     if (!c) return CSI_ERR_INVALID_ARG;
     return mu_hybrid_precoder_device(c, n_users, d_hest_re, d_hest_im, npkt, ns, n_rf, d_reg, d_w_re, d_w_im, d_idx, d_fbb_re, d_fbb_im, d_score);
+}
+
+// ---------------------------------------------------------------- multi-user JSDM precoder (csi_mu_jsdm.hpp, mu_jsdm.hip.h)
+int csi_mu_covariance_device(csi_ctx* c, int n_users, const float* const* d_hest_re, const float* const* d_hest_im, int64_t npkt,
+                             float* d_cov_re, float* d_cov_im) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return mu_covariance_device(c, n_users, d_hest_re, d_hest_im, npkt, d_cov_re, d_cov_im);
+}
+
+int csi_mu_jsdm_precoder_device(csi_ctx* c, int n_users, const float* const* d_hest_re, const float* const* d_hest_im, int64_t npkt, int ns,
+                                const int32_t* group, int r_star, int n_beams, float rank_tol, int flags, const float* d_reg,
+                                const float* d_cov_re, const float* d_cov_im, float* d_w_re, float* d_w_im, float* d_frf_re, float* d_frf_im,
+                                float* d_fbb_re, float* d_fbb_im, float* d_eig, float* d_ustar_re, float* d_ustar_im, int32_t* d_rank) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return mu_jsdm_precoder_device(c, n_users, d_hest_re, d_hest_im, npkt, ns, group, r_star, n_beams, rank_tol, flags, d_reg, d_cov_re, d_cov_im,
+                                   d_w_re, d_w_im, d_frf_re, d_frf_im, d_fbb_re, d_fbb_im, d_eig, d_ustar_re, d_ustar_im, d_rank);
 }
 
 // ---------------------------------------------------------------- accuracy metric

@@ -992,6 +992,101 @@ class CsiEngine:
                 if a is not None:
                     a.free()
 
+    # ------------------------------------------------------------------ multi-user JSDM precoder (csrc/mu_jsdm.hip.h)
+    JSDM_PGP, JSDM_UNIT_MODULUS = 1, 2
+
+    def mu_covariance_device(self, d_hest_re, d_hest_im, npkt, d_cov_re, d_cov_im):
+        """Transmit covariances of len(d_hest_re) users (lists of DeviceArrays [npkt,nr,nt,234]) over the carriers and all receive antennas
+        into d_cov_re / d_cov_im [npkt, U, nt, nt] (csi_mu_covariance_device).  Asynchronous, on the engine's stream."""
+        self._check(self._lib.csi_mu_covariance_device(self._ctx, len(d_hest_re), self._ptr_array(d_hest_re), self._ptr_array(d_hest_im), int(npkt),
+                                                       d_cov_re.ptr, d_cov_im.ptr))
+
+    def mu_covariance(self, hests):
+        """The same from numpy arrays: hests = U complex arrays [npkt,nr,nt,234] -> complex64 [npkt, U, nt, nt]."""
+        hests = [np.asarray(h) for h in hests]
+        npkt = hests[0].shape[0] if hests and hests[0].ndim else 0
+        for h in hests:
+            if h.shape != (npkt, self.nr, self.nt, N_DATA):
+                raise CsiError(-1, f'every h must be [{npkt},{self.nr},{self.nt},{N_DATA}], got {h.shape}')
+        nu = len(hests)
+        dev = [self.to_device(_f32c(h.real)) for h in hests] + [self.to_device(_f32c(h.imag)) for h in hests]
+        outs = [self.empty((npkt, nu, self.nt, self.nt)) for _ in range(2)]
+        try:
+            self.mu_covariance_device(dev[:nu], dev[nu:], npkt, outs[0], outs[1])
+            self.synchronize()
+            return (outs[0].download() + 1j * outs[1].download()).astype(np.complex64)
+        finally:
+            for a in dev + outs:
+                a.free()
+
+    def mu_jsdm_precoder_device(self, d_hest_re, d_hest_im, npkt, ns, r_star, n_beams, d_w_re, d_w_im, groups=None, rank_tol=0.05, flags=1,
+                                d_reg=None, d_cov_re=None, d_cov_im=None, d_frf_re=None, d_frf_im=None, d_fbb_re=None, d_fbb_im=None, d_eig=None,
+                                d_ustar_re=None, d_ustar_im=None, d_rank=None):
+        """JSDM precoder of len(d_hest_re) users (lists of DeviceArrays [npkt,nr,nt,234]): per packet the analog matrix from the eigenvectors
+        of the group covariances after nulling r_star directions of every other group, n_beams RF chains per group, and behind it
+        (regularised) zero forcing on the effective channel per subcarrier (csi_mu_jsdm_precoder_device).  groups: None (every user its own
+        group) or U ints 0 .. G-1; flags: JSDM_PGP (per-group processing) | JSDM_UNIT_MODULUS.  d_w_re / d_w_im [npkt, U ns, nt, 234] as
+        mu_link_sim_device reads them; optional: d_reg [npkt], the pair d_cov_* [npkt, U, nt, nt] IN (replaces the covariance step), the
+        pairs d_frf_* [npkt, nt, G n_beams], d_fbb_* [npkt, 234, G n_beams, U ns], d_eig [npkt, G, nt], the pair d_ustar_* [npkt, G, nt,
+        r_star], d_rank [npkt, G, 2] holding int32 (``download().view(np.int32)``).  Asynchronous, on the engine's stream."""
+        ptr = lambda a: None if a is None else a.ptr
+        grp = None if groups is None else (ctypes.c_int32 * len(groups))(*[int(g) for g in groups])
+        self._check(self._lib.csi_mu_jsdm_precoder_device(self._ctx, len(d_hest_re), self._ptr_array(d_hest_re), self._ptr_array(d_hest_im),
+                                                          int(npkt), int(ns), grp, int(r_star), int(n_beams), float(rank_tol), int(flags),
+                                                          ptr(d_reg), ptr(d_cov_re), ptr(d_cov_im), d_w_re.ptr, d_w_im.ptr, ptr(d_frf_re),
+                                                          ptr(d_frf_im), ptr(d_fbb_re), ptr(d_fbb_im), ptr(d_eig), ptr(d_ustar_re),
+                                                          ptr(d_ustar_im), ptr(d_rank)))
+
+    def mu_jsdm_precoder(self, hests, ns, r_star, n_beams, groups=None, rank_tol=0.05, mode='pgp', unit_modulus=False, reg=None, cov=None,
+                         keep_frf=False, keep_fbb=False, keep_eig=False):
+        """The same from numpy arrays: hests = U complex arrays [npkt,nr,nt,234]; mode 'pgp' or 'jgp'; reg None, a scalar or [npkt]; cov None
+        or complex [npkt, U, nt, nt] (a long-term covariance in place of the packet's own).  Returns (w_re, w_im float32 [npkt, U ns, nt,
+        234]), then with keep_frf the analog part frf complex64 [npkt, nt, G n_beams], with keep_fbb the baseband part fbb complex64 [npkt,
+        234, G n_beams, U ns], and with keep_eig the three of the first stage: eig float32 [npkt, G, nt], ustar complex64 [npkt, G, nt,
+        r_star], rank int32 [npkt, G, 2] = (r_g, q_g)."""
+        if mode not in ('pgp', 'jgp'):
+            raise CsiError(-1, f"mu_jsdm_precoder: mode {mode!r} is not 'pgp' or 'jgp'")
+        hests = [np.asarray(h) for h in hests]
+        npkt = hests[0].shape[0] if hests and hests[0].ndim else 0
+        for h in hests:
+            if h.shape != (npkt, self.nr, self.nt, N_DATA):
+                raise CsiError(-1, f'every h must be [{npkt},{self.nr},{self.nt},{N_DATA}], got {h.shape}')
+        nu, m = len(hests), len(hests) * max(int(ns), 0)
+        ng = nu if groups is None else (max([int(g) for g in groups] + [0]) + 1)
+        q, rs = max(ng * int(n_beams), 0), max(int(r_star), 0)
+        flags = (self.JSDM_PGP if mode == 'pgp' else 0) | (self.JSDM_UNIT_MODULUS if unit_modulus else 0)
+        dev = [self.to_device(_f32c(h.real)) for h in hests] + [self.to_device(_f32c(h.imag)) for h in hests]
+        d_reg = None if reg is None else self.to_device(np.ascontiguousarray(np.broadcast_to(np.asarray(reg, np.float32), (npkt,))))
+        d_cov = [None, None]
+        if cov is not None:
+            cov = np.asarray(cov)
+            if cov.shape != (npkt, nu, self.nt, self.nt):
+                raise CsiError(-1, f'cov must be [{npkt},{nu},{self.nt},{self.nt}], got {cov.shape}')
+            d_cov = [self.to_device(_f32c(cov.real)), self.to_device(_f32c(cov.imag))]
+        outs = [self.empty((npkt, m, self.nt, N_DATA)) for _ in range(2)]
+        frf = [self.empty((npkt, self.nt, q)) for _ in range(2)] if keep_frf else [None, None]
+        fbb = [self.empty((npkt, N_DATA, q, m)) for _ in range(2)] if keep_fbb else [None, None]
+        first = [None] * 4
+        if keep_eig:
+            first = [self.empty((npkt, ng, self.nt))] + [self.empty((npkt, ng, self.nt, rs)) if rs else None for _ in range(2)] + [self.empty((npkt, ng, 2))]
+        try:
+            self.mu_jsdm_precoder_device(dev[:nu], dev[nu:], npkt, ns, r_star, n_beams, outs[0], outs[1], groups, rank_tol, flags, d_reg,
+                                         d_cov[0], d_cov[1], frf[0], frf[1], fbb[0], fbb[1], first[0], first[1], first[2], first[3])
+            self.synchronize()
+            res = [outs[0].download(), outs[1].download()]
+            if keep_frf:
+                res.append((frf[0].download() + 1j * frf[1].download()).astype(np.complex64))
+            if keep_fbb:
+                res.append((fbb[0].download() + 1j * fbb[1].download()).astype(np.complex64))
+            if keep_eig:
+                ustar = (first[1].download() + 1j * first[2].download()) if rs else np.zeros((npkt, ng, self.nt, 0))
+                res += [first[0].download(), ustar.astype(np.complex64), first[3].download().view(np.int32)]
+            return tuple(res)
+        finally:
+            for a in dev + outs + frf + fbb + first + d_cov + [d_reg]:
+                if a is not None:
+                    a.free()
+
     def viterbi_decode(self, llr):
         """Viterbi decoding of terminated codewords of the rate-1/3 K = 7 code (133, 171, 165): llr float [ncw, 3 n_steps], positive = 0
         -> uint8 [ncw, n_steps - 6] (csi_viterbi_decode_device; fp32 metrics, ties to the predecessor with the lower state number)."""

@@ -9,12 +9,16 @@ once on the same subcarriers: per source the zero-forcing preco
 the data phase through their true channels (csi_mu_link_sim_device) add the bersMU_ / EVM_rmsMU_ / sinrMU_ families, the mean over the users.
 --muHybrid NRF runs that phase a second time behind the hybrid precoder of NRF RF chains (csi_mu_hybrid_precoder_device:
 beams from the --ber dictionary, zero forcing on the effective channel) and adds the bersMUH_ / EVM_rmsMUH_ / sinrMUH_ families.
+--muJSDM B runs it once more behind the JSDM precoder of B RF chains per user (csi_mu_jsdm_precoder_device: every user its
+own group, beams from the covariance eigenvectors after nulling --jsdmRank directions of every other user) and adds the bersMUJ_ /
+EVM_rmsMUJ_ / sinrMUJ_ families.
 
     python -m dl_channel_estimation_mamimo_amd.sweep -d OUT [--nTX 32 --nRX 4 --nn 1024 1024 --useBN --bs 256 ...]
                                                             [--ber --numSTS 1 --rays 500 --dataSymbols 10 --bps 2 [--rxEstimate]]
                                                             [--channel scattering --scatterers 100 --range 100 --userAz 30 --userEl 0 --randomUsers]
                                                             [--blind] [--delayTaps L [--delayPre P]] [--beams]
-                                                            [--ber --users U [--muReg zf|rzf] [--userSpacing DEG] [--muHybrid NRF]]
+                                                            [--ber --users U [--muReg zf|rzf] [--userSpacing DEG] [--muHybrid NRF]
+                                                             [--muJSDM B [--jsdmRank R] [--jsdmTol T] [--jsdmMode pgp|jgp]]]
 
 The module holds no arithmetic of its own: packets with a known channel come from csi_synth_structured (--channel scattering: from
 csi_synth_scattering, whose path delays then feed the LMMSE smoother as the reference's h_tau does), labels from
@@ -45,6 +49,7 @@ SOURCES = ESTIMATORS + ('perfect',)      # --ber: whose hybrid weights precode t
 LINK_FIELDS = ('bers_', 'EVM_rms_', 'dtSNR_')
 RX_FIELDS = ('bersRx_', 'EVM_rmsRx_', 'gNMSE_')     # --rxEstimate: the same data phase equalised with the preamble's estimate of H W
 MUH_FIELDS = ('bersMUH_', 'EVM_rmsMUH_', 'sinrMUH_')  # --muHybrid: the same data phase behind the hybrid precoder of n_rf RF chains
+MUJ_FIELDS = ('bersMUJ_', 'EVM_rmsMUJ_', 'sinrMUJ_')  # --muJSDM: the same data phase behind the JSDM precoder of b RF chains per user
 MU_FIELDS = ('bersMU_', 'EVM_rmsMU_', 'sinrMU_')    # --users: the multi-user data phase, the mean over the users per packet
 DELAY = 'DLY'                            # --delayTaps: the LS rows projected onto a window of delay taps (csi_subspace_smooth_device, w = 1)
 BEAMS = 'ANG'                            # --beams: the beam-space Wiener smoother across the Tx antennas on the LS planes (csi_beam_wiener_device)
@@ -106,7 +111,7 @@ def make_dataset(engine, n_train, seed, n_taps=8, amp_scale=True, channel=None):
 
 
 def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=True, keep=False, ber=None, channel=None, blind=False,
-                   rx_estimate=False, delay=None, mu=None, beams=False, mu_hybrid=None):
+                   rx_estimate=False, delay=None, mu=None, beams=False, mu_hybrid=None, mu_jsdm=None):
     """npkt test packets at `snr_db` (packets first_pkt ... of stream `seed`: keep them disjoint from the training packets), LS + DNN
     (estimate_device), the LMMSE smoother on the LS planes, and NMSE_subk of the three estimates against the true channel.
     Returns {'MSE_LS', 'MSE_MMSE', 'MSE_DNN'}: float64 [npkt], the per-link ratios averaged per packet.
@@ -139,6 +144,8 @@ def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=Tr
 
     mu_hybrid=n_rf (with `mu`) runs the multi-user data phase a second time per source behind the hybrid precoder of n_rf RF chains on the
     engine's dictionary (mu_level): 'bersMUH_X', 'EVM_rmsMUH_X', 'sinrMUH_X' and 'muh_users' (the per-user arrays and the chosen beams).
+    mu_jsdm={b, r_star, tol, mode} (with `mu`) runs it once more per source behind the JSDM precoder (mu_level): 'bersMUJ_X', 'EVM_rmsMUJ_X',
+    'sinrMUJ_X' and 'muj_users' (the per-user arrays and the mean ranks).
     Nothing else changes."""
     nr, nt = engine.nr, engine.nt
     d_tau = None
@@ -196,7 +203,7 @@ def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=Tr
                       for u in range(1, int(mu['users']))]
             nv = np.stack([synth.link_noise_var(d.download(), amp_scale) for d in [d_std] + [o['noise_std'] for o in others]])
             out.update(mu_level(engine, [planes] + [o['planes'] for o in others], nv, npkt, seed, first_pkt, ns=ber['ns'], n_sym=ber['n_sym'],
-                                bps=ber['bps'], reg=mu.get('reg', 'zf'), n_rf=mu_hybrid))
+                                bps=ber['bps'], reg=mu.get('reg', 'zf'), n_rf=mu_hybrid, jsdm=mu_jsdm))
             for o in others:
                 for a in o['free']:
                     a.free()
@@ -275,7 +282,7 @@ def user_planes(engine, snr_db, npkt, seed, first_pkt, n_taps, amp_scale, channe
     return dict(planes=planes, noise_std=d_std, free=free)
 
 
-def mu_level(engine, planes, noise_var, npkt, seed, first_pkt, ns=1, n_sym=10, bps=2, reg='zf', n_rf=None):
+def mu_level(engine, planes, noise_var, npkt, seed, first_pkt, ns=1, n_sym=10, bps=2, reg='zf', n_rf=None, jsdm=None):
     """The multi-user data phase of one level on resident planes.  planes = one dict {X: (re, im)} per user, with the
     true channel under 'perfect'; noise_var float32 [U, npkt].  For every source X the precoder of the U users' X planes
     (mu_precoder_device; reg 'zf': none, 'rzf': M noise_var / Nt with the users' mean noise_var of the packet) carries coded QAM through
@@ -284,7 +291,10 @@ def mu_level(engine, planes, noise_var, npkt, seed, first_pkt, ns=1, n_sym=10, b
     with the [U][npkt] values as lists.
     n_rf adds, per source, the same data phase - the same user seeds and the same noise, a paired comparison - behind the hybrid precoder of
     n_rf RF chains on the engine's dictionary (mu_hybrid_precoder_device) with the same reg: 'bersMUH_X', 'EVM_rmsMUH_X',
-    'sinrMUH_X' and 'muh_users': {X: {'bers', 'EVM_rms', 'sinr', 'beams': [npkt][n_rf] dictionary columns}}."""
+    'sinrMUH_X' and 'muh_users': {X: {'bers', 'EVM_rms', 'sinr', 'beams': [npkt][n_rf] dictionary columns}}.
+    jsdm = {b, r_star, tol, mode} adds, per source and in the same way, the data phase behind the JSDM precoder with every user its own group
+    (mu_jsdm_precoder_device): 'bersMUJ_X', 'EVM_rmsMUJ_X', 'sinrMUJ_X' and 'muj_users': {X: {'bers', 'EVM_rms', 'sinr',
+    'r_g', 'q_g': the mean kept rank and the mean number of nulled directions over packets and users}}."""
     nu, nt = len(planes), engine.nt
     m = nu * int(ns)
     if reg not in ('zf', 'rzf'):
@@ -297,7 +307,8 @@ def mu_level(engine, planes, noise_var, npkt, seed, first_pkt, ns=1, n_sym=10, b
     d_err, d_evm, d_sinr = (engine.empty((nu, npkt)) for _ in range(3))
     h_re, h_im = [p['perfect'][0] for p in planes], [p['perfect'][1] for p in planes]
     d_idx = engine.empty((npkt, int(n_rf))) if n_rf else None
-    out, users, users_h = {}, {}, {}
+    d_rank = engine.empty((npkt, nu, 2)) if jsdm else None
+    out, users, users_h, users_j = {}, {}, {}, {}
 
     def data_phase(fields):
         engine.mu_link_sim_device(h_re, h_im, w[0], w[1], d_nv, seed, first_pkt, npkt, ns, d_err, d_evm, d_sinr, n_sym=n_sym, bps=bps)
@@ -313,11 +324,19 @@ def mu_level(engine, planes, noise_var, npkt, seed, first_pkt, ns=1, n_sym=10, b
     for name in planes[0] if n_rf else ():
         engine.mu_hybrid_precoder_device([p[name][0] for p in planes], [p[name][1] for p in planes], npkt, ns, int(n_rf), w[0], w[1], d_idx, d_reg)
         users_h[name] = dict(data_phase(MUH_FIELDS), beams=d_idx.download().view(np.int32).tolist())
-    for a in w + [d_err, d_evm, d_sinr, d_nv] + ([d_reg] if d_reg is not None else []) + ([d_idx] if d_idx is not None else []):
+    for name in planes[0] if jsdm else ():
+        engine.mu_jsdm_precoder_device([p[name][0] for p in planes], [p[name][1] for p in planes], npkt, ns, int(jsdm['r_star']), int(jsdm['b']), w[0], w[1],
+                                       rank_tol=float(jsdm['tol']), flags=engine.JSDM_PGP if jsdm['mode'] == 'pgp' else 0, d_reg=d_reg, d_rank=d_rank)
+        per = data_phase(MUJ_FIELDS)
+        rank = d_rank.download().view(np.int32).astype(np.float64)
+        users_j[name] = dict(per, r_g=float(rank[..., 0].mean()), q_g=float(rank[..., 1].mean()))
+    for a in w + [d_err, d_evm, d_sinr, d_nv] + [x for x in (d_reg, d_idx, d_rank) if x is not None]:
         a.free()
     out['mu_users'] = users
     if n_rf:
         out['muh_users'] = users_h
+    if jsdm:
+        out['muj_users'] = users_j
     return out
 
 
@@ -406,6 +425,8 @@ def metric_fields(mse):
         fields += [f + BEAMS for f in MU_FIELDS]
     if MUH_FIELDS[0] + 'perfect' in mse:
         fields += [f + x for x in SOURCES + tuple(e for e in (BLIND, DELAY, BEAMS) if MUH_FIELDS[0] + e in mse) for f in MUH_FIELDS]
+    if MUJ_FIELDS[0] + 'perfect' in mse:
+        fields += [f + x for x in SOURCES + tuple(e for e in (BLIND, DELAY, BEAMS) if MUJ_FIELDS[0] + e in mse) for f in MUJ_FIELDS]
     return fields
 
 
@@ -417,7 +438,7 @@ def write_metrics(path, mse):
     those.  A level evaluated with rx_estimate=True carries bersRx_X, EVM_rmsRx_X and gNMSE_X: written behind those, and MSE_DLY of a level evaluated
     with delay=(L, pre) behind those; bersMU_X, EVM_rmsMU_X and sinrMU_X of a level evaluated with mu=... behind those; MSE_ANG, MSE_DLYANG and
     bersMU_ANG, EVM_rmsMU_ANG, sinrMU_ANG of a level evaluated with beams=True behind those; bersMUH_X, EVM_rmsMUH_X and sinrMUH_X of a level
-    evaluated with mu_hybrid=... last (metric_fields)."""
+    evaluated with mu_hybrid=... behind those; bersMUJ_X, EVM_rmsMUJ_X and sinrMUJ_X of a level evaluated with mu_jsdm=... last (metric_fields)."""
     from scipy.io import savemat
     os.makedirs(os.path.dirname(path), exist_ok=True)
     savemat(path, {f: np.asarray(mse[f], np.float64).reshape(1, -1) for f in metric_fields(mse)})
@@ -433,6 +454,8 @@ def format_table(result):
         cols += [BEAMS] + ([DELAY_BEAMS] if result.get('delay') else []) + ([MU_FIELDS[0] + BEAMS] if result.get('mu') else [])
     if result.get('mu_hybrid'):
         cols += [MUH_FIELDS[0] + x for x in list(SOURCES) + blind + ([DELAY] if result.get('delay') else []) + ([BEAMS] if result.get('beams') else [])]
+    if result.get('mu_jsdm'):
+        cols += [MUJ_FIELDS[0] + x for x in list(SOURCES) + blind + ([DELAY] if result.get('delay') else []) + ([BEAMS] if result.get('beams') else [])]
     lines = ['%8s' % 'SNR dB' + ''.join('  %-38s' % (e + ': mean [CI low, CI high]') for e in cols)]
     for lv in result['levels']:
         row = '%8g' % lv['snr_db']
@@ -445,9 +468,26 @@ def format_table(result):
     return '\n'.join(lines)
 
 
+def jsdm_problem(users, ns, nt, b, r_star=4, tol=0.05, mode='pgp'):
+    """What csi_mu_jsdm_precoder_device would refuse of a JSDM run with every user its own group, as text; None when it is served."""
+    if b < 1 or ns > b:
+        return 'numSTS %d streams per user exceed B = %d RF chains per user' % (ns, b)
+    if users * b > 16:
+        return 'U x B = %d x %d RF chains exceed 16' % (users, b)
+    if r_star < 0 or (users - 1) * r_star > nt - b:
+        return '(U - 1) x R = %d x %d directions to null exceed nTX - B = %d' % (users - 1, r_star, nt - b)
+    if nt > 64:
+        return 'nTX %d exceeds 64' % nt
+    if not (tol >= 0.0 and tol < float('inf')):
+        return 'the threshold %r must be finite and not negative' % (tol,)
+    if mode not in ('pgp', 'jgp'):
+        return "the mode %r is not 'pgp' or 'jgp'" % (mode,)
+    return None
+
+
 def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500, seed=0, modeldir=None, fit_args=None, n_taps=8,
               amp_scale=True, save_dataset=None, verbose=True, ber=None, channel=None, blind=False, rx_estimate=False,
-              delay_taps=None, delay_pre=0, users=None, mu_reg='zf', user_spacing=15.0, beams=False, mu_hybrid=None):
+              delay_taps=None, delay_pre=0, users=None, mu_reg='zf', user_spacing=15.0, beams=False, mu_hybrid=None, mu_jsdm=None):
     """Training set -> models (loaded from `modeldir`, else fitted and saved into `out`) -> every level.  Writes
     <out>/BS<Nt>_SNR<s>/metrics.mat per level and <out>/sweep.json, prints the table, returns the result dict (with the per-packet
     arrays under 'per_packet' = {level: {'MSE_LS', ...}}).  Test packets come from the stream seed + 1, behind the index range of
@@ -473,7 +513,12 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
     mu_hybrid=n_rf (needs `users`, U ns <= n_rf <= min(16, Nt, rays)) adds the multi-user data phase behind the hybrid precoder of n_rf RF
     chains per source (evaluate_level(mu_hybrid=...)): bersMUH_X, EVM_rmsMUH_X and sinrMUH_X in metrics.mat behind every other field, the
     same with confidence intervals and 'muh_users' (per-user arrays and chosen beams) per level of sweep.json, which then records
-    'mu_hybrid': {n_rf}; without it every output is what it is without the argument."""
+    'mu_hybrid': {n_rf}; without it every output is what it is without the argument.
+    mu_jsdm={b[, r_star = 4, tol = 0.05, mode = 'pgp']} (needs `users`; ns <= b, U b <= 16, (U - 1) r_star <= Nt - b, Nt <= 64) adds the
+    multi-user data phase behind the JSDM precoder per source, every user its own group (evaluate_level(mu_jsdm=...)): bersMUJ_X,
+    EVM_rmsMUJ_X and sinrMUJ_X in metrics.mat behind every other field, the same with confidence intervals and 'muj_users' (per-user arrays,
+    mean r_g / q_g) per level of sweep.json, which then records 'mu_jsdm': {b, r_star, tol, mode}; without it every output is what it is
+    without the argument."""
     if rx_estimate and ber is None:
         raise ValueError('rx_estimate needs the data phase (ber)')
     mu = None
@@ -490,6 +535,13 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
         if not mu['users'] * int(ber['ns']) <= int(mu_hybrid) <= min(16, engine.nt, rays):
             raise ValueError('mu_hybrid n_rf %d outside users x ns = %d .. min(16, Nt %d, rays %d)' % (int(mu_hybrid), mu['users'] * int(ber['ns']), engine.nt, rays))
         mu_hybrid = int(mu_hybrid)
+    if mu_jsdm is not None:
+        if mu is None:
+            raise ValueError('mu_jsdm needs the multi-user data phase (users >= 2)')
+        mu_jsdm = dict(b=int(mu_jsdm['b']), r_star=int(mu_jsdm.get('r_star', 4)), tol=float(mu_jsdm.get('tol', 0.05)), mode=str(mu_jsdm.get('mode', 'pgp')))
+        problem = jsdm_problem(mu['users'], int(ber['ns']), engine.nt, **mu_jsdm)
+        if problem:
+            raise ValueError('mu_jsdm: ' + problem)
     os.makedirs(out, exist_ok=True)
     result = dict(nt=engine.nt, nr=engine.nr, n_train=int(n_train), n_test=int(n_test), seed=int(seed), n_taps=int(n_taps),
                   amp_scale=bool(amp_scale), levels=[], training=None)
@@ -505,6 +557,8 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
         result['mu'] = dict(mu)
     if mu_hybrid:
         result['mu_hybrid'] = dict(n_rf=mu_hybrid)
+    if mu_jsdm:
+        result['mu_jsdm'] = dict(mu_jsdm)
     delay = None
     if delay_taps:
         delay = (int(delay_taps), int(delay_pre))
@@ -529,7 +583,7 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
     for i, snr in enumerate(levels):
         t0 = time.perf_counter()
         mse = evaluate_level(engine, snr, n_test, seed + 1, n_train + i * n_test, n_taps, amp_scale, ber=ber, channel=channel, blind=blind,
-                             rx_estimate=rx_estimate, delay=delay, mu=mu, beams=beams, mu_hybrid=mu_hybrid)
+                             rx_estimate=rx_estimate, delay=delay, mu=mu, beams=beams, mu_hybrid=mu_hybrid, mu_jsdm=mu_jsdm)
         sec = time.perf_counter() - t0
         write_metrics(os.path.join(out, 'BS%d_SNR%g' % (engine.nt, snr), 'metrics.mat'), mse)
         lv = dict(snr_db=float(snr), seconds=sec)
@@ -561,6 +615,12 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
                     m, lo, hi = confidence_interval(mse[f + x])
                     lv[f + x] = dict(mean=m, ci_low=lo, ci_high=hi)
             lv['muh_users'] = mse['muh_users']
+        if mu_jsdm:
+            for x in SOURCES + ((BLIND,) if blind else ()) + ((DELAY,) if delay else ()) + ((BEAMS,) if beams else ()):
+                for f in MUJ_FIELDS:
+                    m, lo, hi = confidence_interval(mse[f + x])
+                    lv[f + x] = dict(mean=m, ci_low=lo, ci_high=hi)
+            lv['muj_users'] = mse['muj_users']
         result['levels'].append(lv)
         per_packet[float(snr)] = mse
     with open(os.path.join(out, 'sweep.json'), 'w') as f:
@@ -605,6 +665,12 @@ def build_parser():
     p.add_argument('--muHybrid', default=0, type=int, metavar='NRF',
                    help='--users: also precode with NRF RF chains - beams chosen from the --ber dictionary, zero forcing on the effective channel '
                         '(csi_mu_hybrid_precoder_device, U x numSTS <= NRF <= min(16, nTX, rays)) - bersMUH_ / EVM_rmsMUH_ / sinrMUH_')
+    p.add_argument('--muJSDM', default=0, type=int, metavar='B',
+                   help='--users: also precode with B RF chains per user behind covariance eigenbeams that null the other users '
+                        '(csi_mu_jsdm_precoder_device, every user its own group; numSTS <= B, U x B <= 16, nTX <= 64) - bersMUJ_ / EVM_rmsMUJ_ / sinrMUJ_')
+    p.add_argument('--jsdmRank', default=4, type=int, metavar='R', help='--muJSDM: directions of a user that the others null ((U - 1) R <= nTX - B)')
+    p.add_argument('--jsdmTol', default=0.05, type=float, metavar='T', help='--muJSDM: a direction is nulled while its eigenvalue exceeds T of the largest')
+    p.add_argument('--jsdmMode', default='pgp', choices=('pgp', 'jgp'), help='--muJSDM: per-group (block-diagonal, the reference) or joint baseband processing')
     p.add_argument('--userSpacing', default=15.0, type=float, metavar='DEG', help='--users with --channel scattering: user u sits at azimuth userAz + u DEG')
     p.add_argument('--channel', default='taps', choices=('taps', 'scattering'),
                    help='taps: i.i.d. impulse responses (csi_synth_structured); scattering: the geometric single-bounce channel (csi_synth_scattering)')
@@ -649,6 +715,12 @@ def parse_args(argv=None):
             parser.error('--muHybrid needs --ber --users U (U >= 2)')
         if not args.users * args.numSTS <= args.muHybrid <= min(16, args.nTX, args.rays):
             parser.error('--muHybrid %d outside --users x --numSTS = %d .. min(16, nTX %d, rays %d)' % (args.muHybrid, args.users * args.numSTS, args.nTX, args.rays))
+    if args.muJSDM:
+        if args.users < 2 or not args.ber:
+            parser.error('--muJSDM needs --ber --users U (U >= 2)')
+        problem = jsdm_problem(args.users, args.numSTS, args.nTX, args.muJSDM, args.jsdmRank, args.jsdmTol, args.jsdmMode)
+        if problem:
+            parser.error('--muJSDM: ' + problem)
     if args.delayTaps and not (1 <= args.delayTaps <= subspace.MAX_RANK and 0 <= args.delayPre <= args.delayTaps):
         parser.error('--delayTaps takes 1 .. %d and --delayPre 0 .. L' % subspace.MAX_RANK)
     if args.delayPre and not args.delayTaps:
@@ -674,7 +746,8 @@ def main(argv=None):
               verbose=not args.quiet, ber=ber, channel=channel_from_args(args), blind=bool(args.blind),
               rx_estimate=bool(args.rxEstimate), delay_taps=args.delayTaps or None, delay_pre=args.delayPre,
               users=args.users if args.users >= 2 else None, mu_reg=args.muReg, user_spacing=args.userSpacing, beams=bool(args.beams),
-              mu_hybrid=args.muHybrid or None)
+              mu_hybrid=args.muHybrid or None,
+              mu_jsdm=dict(b=args.muJSDM, r_star=args.jsdmRank, tol=args.jsdmTol, mode=args.jsdmMode) if args.muJSDM else None)
     return 0
 
 

@@ -43,7 +43,7 @@
  * context's stream and return without waiting; call csi_synchronize before reading results.
  *
  * Device pointers (csi_predict_device, csi_ls_estimate_device, csi_estimate_device, csi_lmmse_estimate_device, csi_lmmse_blind_device, csi_subspace_smooth_device, csi_beam_power_device, csi_beam_smooth_device, csi_beam_wiener_device, csi_null_noise_device, csi_nmse_device,
- * csi_hybrid_weights_device, csi_link_sim_device, csi_link_sim_rx_device, csi_mu_precoder_device, csi_mu_link_sim_device, csi_mu_hybrid_precoder_device, csi_viterbi_decode_device, csi_synth_*).  An array of exactly the documented
+ * csi_hybrid_weights_device, csi_link_sim_device, csi_link_sim_rx_device, csi_mu_precoder_device, csi_mu_link_sim_device, csi_mu_hybrid_precoder_device, csi_mu_covariance_device, csi_mu_jsdm_precoder_device, csi_viterbi_decode_device, csi_synth_*).  An array of exactly the documented
  * size suffices: it may be a slice of a larger allocation whose neighbours hold live data of any value (NaN and 1e38 included).
  * Nothing outside the arrays is written, nothing outside them reaches a result, and input arrays are not modified.  Every re / im
  * PLANE (the preambles [npkt][Nr][len_ltf], the CSI planes [npkt][Nr][Nt][234 or n_out], fbb, frf_mean, xeq, gest, the precoder planes W, g) starts on a 16-byte
@@ -481,6 +481,54 @@ int  csi_mu_hybrid_precoder_device(csi_ctx* ctx, int n_users, const float* const
                                    int ns, int n_rf, const float* d_reg, float* d_w_re, float* d_w_im, int32_t* d_idx, float* d_fbb_re,
                                    float* d_fbb_im, float* d_score);
 
+/* Multi-user JSDM precoder (BER_test_maMIMO_LTF.m:355-389: joint spatial division multiplexing - the users grouped by their transmit
+ * covariance, an analog matrix from the covariance eigenvectors after a block diagonalisation that nulls the other groups, a precoder per
+ * group behind it; model, deviation from the toolbox helper and kernel plans: DESIGN.md 4.23, csrc/mu_jsdm.hip.h).  An addition: the ABI
+ * version stays 1.  The shapes of csi_mu_precoder_device (U users, ns streams per user, M = U ns <= 16, B_k[m][j] = hest_u[p][s][j][k]) and
+ *   group[u]   a HOST array of U ints with values 0 .. G-1, every group non-empty; NULL: every user is its own group
+ *   r_star     >= 0, directions of a group that the others null;  n_beams = b >= 1 RF chains per group, n_rf = G b <= 16;  rank_tol >= 0
+ *   flags      bit 0: per-group processing (PGP, the reference's block-diagonal form), otherwise joint processing (JGP); bit 1: analog
+ *              weights of unit modulus
+ *   conditions ns |group g| <= b for every group, (G-1) r_star <= Nt - b, Nt <= 64
+ *   cov        per (packet, user): R_u[j][j'] = (1 / (Nr 234)) sum_{i < Nr} sum_k conj(h_u[i][j][k]) h_u[i][j'][k]  (all Nr receive
+ *              antennas; Nt x Nt Hermitian, to the bit; a beam w has mean gain w^H R w; fp32 MFMA, every sum in an order fixed by the shape,
+ *              no atomics).  R_g = the mean over the users of group g in ascending user order
+ *   eig        R_g = U_g L_g U_g^H, eigenvalues descending; in each eigenvector the entry of largest modulus is real and positive, the
+ *              lowest j on a tie.  r_g = the number of i < r_star with l_i > rank_tol l_0 (l_0 <= 0 or not finite: 0); U*_g = the first r_g
+ *              columns.  (Hermitian Jacobi in fp32, parallel round-robin ordering; with s = max_j |R[j][j]| a rotation is applied where
+ *              |R[p][q]| > 2^-23 s, the first sweep without one ends the iteration, 24 sweeps at the most)
+ *   null       Xi_g = [U*_g' : g' != g, ascending]; Q_g = modified Gram-Schmidt of Xi_g in column order, two passes, a column whose
+ *              residual is <= 1e-3 of its norm is dropped, q_g columns kept; Rt_g = P R_g P - l_0(R_g) Q_g Q_g^H with P = I - Q_g Q_g^H,
+ *              symmetrised: span(Q_g) goes to the bottom of the spectrum, so the leading eigenvectors of Rt_g lie in the null space even
+ *              where P R_g P has rank below b
+ *   beams      F_g = the first b eigenvectors of Rt_g, same convention; with bit 1 F_g[j][q] = exp(i arg F_g[j][q]) / sqrt(Nt) (arg of an
+ *              exact 0 is 0).  Frf[p] = [F_0 ... F_{G-1}], Nt x n_rf, flat over the subcarriers
+ *   baseband   per (packet, subcarrier), the stage of csi_mu_hybrid_precoder_device with the packet's own Frf: Gm = B_k Frf, with PGP the
+ *              entries whose chain's group differs from the stream's group set to 0; A = Gm Gm^H + reg[p] I; Cholesky (a pivot <= 0 or not
+ *              finite: W = 0 and Fbb = 0 for the item); Vbb = Gm^H A^-1; V = Frf Vbb; c_m = sqrt(Nt / M) / |V[:, m]|_2; W[:, m] = c_m V[:, m],
+ *              Fbb[:, m] = c_m Vbb[:, m]: W = Frf Fbb, |W|_F^2 = Nt, and with PGP Fbb is block diagonal with exact zeros elsewhere.
+ * csi_mu_covariance_device writes the covariances alone, d_cov_re / d_cov_im [npkt][U][Nt][Nt] (one launch).  csi_mu_jsdm_precoder_device:
+ * the optional pair d_cov_re / d_cov_im IN replaces the covariance step (a caller's long-term covariance); outputs d_w_re / d_w_im
+ * [npkt][M][Nt][234] (what csi_mu_link_sim_device reads); optional (may be NULL): the pairs d_frf_re / d_frf_im [npkt][Nt][n_rf],
+ * d_fbb_re / d_fbb_im [npkt][234][n_rf][M], d_eig [npkt][G][Nt] (descending), the pair d_ustar_re / d_ustar_im [npkt][G][Nt][r_star] (zero
+ * past r_g), d_rank int32 [npkt][G][2] = (r_g, q_g).  d_hest_re / d_hest_im are HOST arrays of U device pointers.
+ * Both are asynchronous on the context's stream, serve fp32 and bf16 contexts alike and are usable inside csi_capture_begin / _end after
+ * one eager call of the same shape.  The precoder runs in packet chunks against the context's workspace_bytes (the covariance, eigenvalue,
+ * U*, rank and Frf planes of a chunk live in the workspace; default 1 GiB), four kernel launches per chunk (three with the covariances
+ * handed in), with the same bits whatever the chunking, the call or the packet's position in it.
+ * Refused with text, before anything is launched or counted: everything csi_mu_precoder_device refuses, a group entry outside 0 .. G-1 or
+ * an empty group, n_rf > 16, ns |group g| > b, r_star < 0 or > Nt, (G-1) r_star > Nt - b, rank_tol negative or not finite, unknown flag
+ * bits, Nt > 64 (the eigen kernel holds the matrix and the vectors in LDS), one plane of a pair without the other, planes off a 16-byte
+ * boundary, an open capture that would have to grow the workspace.  npkt == 0 returns 0 and launches nothing; a null context returns -1.
+ * The launches count under "mu_launches"; profile entries "mu_cov", "mu_jsdm_eig" and "mu_jsdm_baseband". */
+int  csi_mu_covariance_device(csi_ctx* ctx, int n_users, const float* const* d_hest_re, const float* const* d_hest_im, int64_t npkt,
+                              float* d_cov_re, float* d_cov_im);
+int  csi_mu_jsdm_precoder_device(csi_ctx* ctx, int n_users, const float* const* d_hest_re, const float* const* d_hest_im, int64_t npkt,
+                                 int ns, const int32_t* group, int r_star, int n_beams, float rank_tol, int flags, const float* d_reg,
+                                 const float* d_cov_re, const float* d_cov_im, float* d_w_re, float* d_w_im, float* d_frf_re,
+                                 float* d_frf_im, float* d_fbb_re, float* d_fbb_im, float* d_eig, float* d_ustar_re, float* d_ustar_im,
+                                 int32_t* d_rank);
+
 /* Accuracy metric of the reference's evaluation, NMSE_subk (BER_test_maMIMO_LTF.m:675-686): per link
  * ||ref - est||^2 / ||ref||^2 over the n_bins bins, mean over the nlinks links ([link][n_bins] planes, e.g.
  * the [npkt][nr][nt][234] outputs of csi_predict / csi_ls_estimate with nlinks = npkt*nr*nt).  Synchronous;
@@ -668,7 +716,7 @@ int  csi_set_option(csi_ctx* ctx, const char* name, int64_t value);
 /* Current value of an option, or of the read-only values: "hs_launches" (split-engine GEMMs launched), "hs_range_fallbacks"
  * (csi_predict calls repeated on the fp32 MFMA kernels), "hs_weight_pins" / "hs_weight_err_e12" (layers pinned to the fp32 kernels
  * at load because their split copies were not fp32-grade; worst relative error x 1e12), "band_available" (the assembly band kernel
- * is embedded in this build), "graph_replays", "subspace_launches" (kernels launched by csi_subspace_smooth[_device]), "beam_launches" (kernels launched by the csi_beam_* entry points), "mu_launches" (kernels launched by csi_mu_precoder_device / csi_mu_link_sim_device / csi_mu_hybrid_precoder_device), "lmmse_blind_fallbacks" ((packet, rx) pairs csi_lmmse_blind[_device] handed back unsmoothed), "ls_pilot_fast" (0 generic / 1 Sylvester / 2 permuted pilot), "comm_world",
+ * is embedded in this build), "graph_replays", "subspace_launches" (kernels launched by csi_subspace_smooth[_device]), "beam_launches" (kernels launched by the csi_beam_* entry points), "mu_launches" (kernels launched by csi_mu_precoder_device / csi_mu_link_sim_device / csi_mu_hybrid_precoder_device / csi_mu_covariance_device / csi_mu_jsdm_precoder_device), "lmmse_blind_fallbacks" ((packet, rx) pairs csi_lmmse_blind[_device] handed back unsmoothed), "ls_pilot_fast" (0 generic / 1 Sylvester / 2 permuted pilot), "comm_world",
  * "comm_rank", "comm_blobs", "comm_bytes" (communicator and last broadcast), "hp_direct_out_calls", and where the last pipelined
  * host-buffer call spent its time in microseconds: "hp_total_us", "hp_stage_us", "hp_wait_stage_us", "hp_wait_out_us", "hp_weave_us". */
 int  csi_get_option(csi_ctx* ctx, const char* name, int64_t* value);
