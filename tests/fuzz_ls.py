@@ -4,7 +4,8 @@ cases is part of the gpu test suite (tests/test_gpu_ls.py::test_fuzz_ls_cases).
 
 Every case: antenna count, rx count and packet count at random (item counts below, at and far above the resident grid of
 the persistent kernels), the Sylvester Hadamard pilot matrix or a generic one, the automatic kernel and every kernel
-that can serve the shape ('ls_kernel' 1-6, 'ls_v2' 0 / 1); checked on the first, two middle and the last packets."""
+that can serve the shape ('ls_kernel' 1-7; 'ls_v2' 0 ... 3 for the ring kernels 5 and 6, 0 / 1 for the bf16-split kernel 7 at
+16 <= Nt <= 128); checked on the first, two middle and the last packets."""
 import os
 import sys
 
@@ -36,10 +37,10 @@ def run_case(rng, c=0, log=print):
     sel = np.unique(np.r_[0, npkt // 3, npkt // 2, npkt - 1])
     ref = oracle.ls_estimate(np.asarray(ltf)[sel].astype(np.complex64), P)
     refc = np.concatenate([ref.real, ref.imag], -1)
-    kernels = [0] + ([4, 5] if had and nt >= 16 else []) + ([1] if nt <= 64 else []) + ([2, 6] if 16 <= nt <= 128 else []) + [3]
+    kernels = [0] + ([4, 5] if had and nt >= 16 else []) + ([1] if nt <= 64 else []) + ([2, 6, 7] if 16 <= nt <= 128 else []) + [3]
     worst = 0.0
     for k in kernels:
-        for v in ((0, 1) if k in (5, 6) else (0,)):
+        for v in ((0, 1, 2, 3) if k in (5, 6) else ((0, 1) if k == 7 else (0,))):
             e.set_option('ls_kernel', k)
             e.set_option('ls_v2', v)
             h = e.ls_estimate(ltf)

@@ -80,13 +80,23 @@ def test_ls_bf16_split_despread(pkg, oracle, pieces):
         assert e.get_option('ls_pilot_pieces') == pieces
         assert e.get_option('ls_mode') == (6 if nt <= 32 else 7), (nt, pieces)   # the automatic choice (round 4: the bf16-split kernel from Nt = 33)
         if nt <= 32 and npkt * nr > 256:
-            # the one-antenna-tile form of kernel 7 with TWO workgroups per CU is not selected any more (rare wrong first items of a CU's
-            # second workgroup on one box of the pool, open: DESIGN.md 4.2) - what the library runs for this shape is checked instead
+            # the one-antenna-tile form of kernel 7 with TWO workgroups per CU is not built any more (its wrong items were the packed +-i
+            # rotations beside another workgroup's MFMAs, root-caused and removed: DESIGN.md 4.12) - what the library runs for this shape
+            # is checked first, then the one-workgroup-per-CU rows of kernel 7 themselves, forced, on the same persistent walk
             h = e.ls_estimate(ltf)
             ref = oracle.ls_estimate(np.asarray(ltf).astype(np.complex64), P)
             assert rel_rows(np.concatenate([h.real, h.imag], -1), np.concatenate([ref.real, ref.imag], -1)) < TOL, (nt, nr, npkt)
             for _ in range(4):
                 assert np.array_equal(h, e.ls_estimate(ltf))
+            e.set_option('ls_kernel', 7)
+            assert e.get_option('ls_mode') == 7 and e.get_option('ls_per_cu') == 1
+            h7 = e.ls_estimate(ltf)                                                     # EVERY item against the oracle
+            assert rel_rows(np.concatenate([h7.real, h7.imag], -1), np.concatenate([ref.real, ref.imag], -1)) < TOL, (nt, nr, npkt, 'ls_kernel 7')
+            assert not np.array_equal(h, h7)                                            # really another kernel than the automatic choice
+            e.set_option('ls_v2', 1)                                                    # the other ring depth: the same arithmetic per (bin, antenna)
+            assert np.array_equal(h7, e.ls_estimate(ltf))
+            e.set_option('ls_v2', 0)
+            assert np.array_equal(h7, e.ls_estimate(ltf))
             continue
         e.set_option('ls_kernel', 7)
         h = e.ls_estimate(ltf)
