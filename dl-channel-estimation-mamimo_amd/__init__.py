@@ -6,10 +6,10 @@ the hand-written HIP kernels of ``csrc/`` (gfx950).  There is no CPU fallback: e
 entry point raises if ``libcsi_mamimo.so`` is missing or no gfx950 device is visible.
 """
 from ._lib import CsiError, build_library, library_path, load_library   # noqa: F401
-from .engine import CsiEngine, DeviceArray, HybridWeights, LinkResult, LinkRxResult, MuLinkResult, frf_from_idx  # noqa: F401
+from .engine import CsiEngine, DeviceArray, HybridWeights, LinkResult, LinkRxResult, MuLinkResult, FeedbackReport, frf_from_idx  # noqa: F401
 from .model import CSIModel, load_weight_file, save_weight_file         # noqa: F401
 from .inference import CSIPredictor                                     # noqa: F401
-from . import synth, dist, dataset, trainer, subspace, beamspace                 # noqa: F401
+from . import synth, dist, dataset, trainer, subspace, beamspace, feedback       # noqa: F401
 
-__all__ = ['CsiEngine', 'DeviceArray', 'HybridWeights', 'LinkResult', 'LinkRxResult', 'MuLinkResult', 'frf_from_idx', 'CSIModel', 'CSIPredictor', 'CsiError', 'build_library',
-           'library_path', 'load_library', 'load_weight_file', 'save_weight_file', 'synth', 'dist', 'dataset', 'trainer', 'subspace', 'beamspace']
+__all__ = ['CsiEngine', 'DeviceArray', 'HybridWeights', 'LinkResult', 'LinkRxResult', 'MuLinkResult', 'FeedbackReport', 'frf_from_idx', 'CSIModel', 'CSIPredictor', 'CsiError', 'build_library',
+           'library_path', 'load_library', 'load_weight_file', 'save_weight_file', 'synth', 'dist', 'dataset', 'trainer', 'subspace', 'beamspace', 'feedback']

@@ -31,6 +31,7 @@
 #include "mu_link.hip.h"
 #include "mu_hybrid.hip.h"
 #include "mu_jsdm.hip.h"
+#include "feedback.hip.h"
 
 using namespace csi;
 
@@ -73,6 +74,8 @@ enum KernelId {
     K_MU_COV,            // multi-user JSDM precoder (mu_jsdm.hip.h): transmit covariance per (packet, user) (fp32 MFMA); placed like K_SUBSPACE_SMOOTH
     K_MU_JSDM_EIG,       // multi-user JSDM precoder: Jacobi eigenvectors per (packet, group), both stages (covariance; nulled covariance -> beams)
     K_MU_JSDM_BASEBAND,  // multi-user JSDM precoder: zero forcing on the effective channel B Frf per (packet, subcarrier), per group or jointly
+    K_FB_COMPRESS,       // quantised CSI feedback (feedback.hip.h): singular vectors, Givens angles and codes per (packet, reported carrier)
+    K_FB_EXPAND,         // quantised CSI feedback: the report expanded into precoder or CSI planes per (packet, carrier)
     K_BEAM_POWER,        // beam-space smoother (csi_beam_*, beam_smooth.hip.h): beam power E per (packet, rx, beam); placed like K_SUBSPACE_SMOOTH
     K_BEAM_SMOOTH,       // beam-space smoother: y = A diag(w) A^H x across the Tx antennas
     K_SYNTH_SCATTERING,  // known-channel sounding packets of the scattering channel (synth_scattering.hip.h): the power pass and the packet pass of csi_synth_scattering
@@ -86,7 +89,7 @@ const char* const kKernelNames[K_COUNT] = {
     "ls_estimate", "naive_dense0_gemm", "synth_white", "pilot_table", "cast_bf16", "pair_h1_bf16", "lmmse_levinson",
     "train_gemm", "train_elementwise", "nmse_links", "pair_dense_tail", "input_pool", "conv_frontend",
     "hybrid_svd", "hybrid_corr_argmax", "hybrid_solve", "hybrid_finish", "synth_structured", "link_txrx", "link_viterbi",
-    "subspace_smooth", "mu_precoder", "mu_txrx", "mu_beam_score", "mu_beam_select", "mu_hybrid_precoder", "mu_cov", "mu_jsdm_eig", "mu_jsdm_baseband", "beam_power", "beam_smooth", "synth_scattering", "lmmse_null_noise", "lmmse_freq_corr", "lmmse_blind"};
+    "subspace_smooth", "mu_precoder", "mu_txrx", "mu_beam_score", "mu_beam_select", "mu_hybrid_precoder", "mu_cov", "mu_jsdm_eig", "mu_jsdm_baseband", "fb_compress", "fb_expand", "beam_power", "beam_smooth", "synth_scattering", "lmmse_null_noise", "lmmse_freq_corr", "lmmse_blind"};
 
 thread_local std::string g_create_error;
 
@@ -260,6 +263,12 @@ struct csi_ctx {
     char* muj_ws = nullptr;      // multi-user JSDM precoder (csi_mu_jsdm.hpp): covariance, eigenvalue, U*, rank and Frf planes of a packet chunk (sized by eager calls)
     size_t muj_ws_bytes = 0;
     size_t muj_lds_attr[3] = {}; // dynamic-LDS limit already raised for its eigen kernel / baseband kernel of 64 lanes / of 32 lanes
+    char* fb_ws = nullptr;       // quantised CSI feedback (csi_feedback.hpp): the singular vectors of a packet chunk (sized by eager calls)
+    size_t fb_ws_bytes = 0;
+    float* fb_tab = nullptr;     // ... and the cos / sin tables of the bin centres of (fb_tab_bphi, fb_tab_bpsi)
+    int fb_tab_bphi = 0, fb_tab_bpsi = 0;
+    size_t fb_lds_attr[2] = {};  // dynamic-LDS limit already raised for its compress / expand kernel
+    int64_t feedback_launches = 0;   // "feedback_launches": kernels launched by csi_feedback_compress_device / csi_feedback_expand_device
     int64_t link_launches = 0;   // "link_launches": kernels launched by csi_link_sim_device / csi_viterbi_decode_device
     bool user_capture = false;   // between csi_capture_begin and csi_capture_end (csi_hybrid.hpp): device-pointer calls are recorded, not run
     bool user_capture_use_graph = false;

@@ -28,6 +28,7 @@
 #include "csi_mu.hpp"
 #include "csi_mu_hybrid.hpp"
 #include "csi_mu_jsdm.hpp"
+#include "csi_feedback.hpp"
 #include <initializer_list>
 
 namespace {
@@ -327,6 +328,8 @@ void csi_destroy(csi_ctx* c) {
     if (c->link_ws) hipFree(c->link_ws);
     if (c->muh_ws) hipFree(c->muh_ws);
     if (c->muj_ws) hipFree(c->muj_ws);
+    if (c->fb_ws) hipFree(c->fb_ws);
+    if (c->fb_tab) hipFree(c->fb_tab);
     if (c->lmb_tw) hipFree(c->lmb_tw);
     if (c->lmb_ws) hipFree(c->lmb_ws);
     if (c->lmb_count) hipFree(c->lmb_count);
@@ -1103,6 +1106,21 @@ int csi_mu_jsdm_precoder_device(csi_ctx* c, int n_users, const float* const* d_h
                                    d_w_re, d_w_im, d_frf_re, d_frf_im, d_fbb_re, d_fbb_im, d_eig, d_ustar_re, d_ustar_im, d_rank);
 }
 
+// ---------------------------------------------------------------- quantised CSI feedback (csi_feedback.hpp, feedback.hip.h)
+int csi_feedback_compress_device(csi_ctx* c, const float* d_h_re, const float* d_h_im, int64_t npkt, int nc, int b_phi, int b_psi, int ng,
+                                 uint16_t* d_phi_code, uint16_t* d_psi_code, float* d_phi, float* d_psi, float* d_sigma, float* d_v_re,
+                                 float* d_v_im) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return feedback_compress_device(c, d_h_re, d_h_im, npkt, nc, b_phi, b_psi, ng, d_phi_code, d_psi_code, d_phi, d_psi, d_sigma, d_v_re, d_v_im);
+}
+
+int csi_feedback_expand_device(csi_ctx* c, const uint16_t* d_phi_code, const uint16_t* d_psi_code, const float* d_phi, const float* d_psi,
+                               const float* d_sigma, int64_t npkt, int nc, int b_phi, int b_psi, int ng, int layout, float* d_out_re,
+                               float* d_out_im) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return feedback_expand_device(c, d_phi_code, d_psi_code, d_phi, d_psi, d_sigma, npkt, nc, b_phi, b_psi, ng, layout, d_out_re, d_out_im);
+}
+
 // ---------------------------------------------------------------- accuracy metric
 int csi_nmse_device(csi_ctx* c, const float* d_ref_re, const float* d_ref_im, const float* d_est_re, const float* d_est_im,
                     int64_t nlinks, int n_bins, float* d_per_link, double* mean_out) {
@@ -1174,6 +1192,7 @@ int csi_get_option(csi_ctx* c, const char* name, int64_t* value) {
     else if (n == "subspace_launches") *value = c->subspace_launches;
     else if (n == "beam_launches") *value = c->beam_launches;
     else if (n == "mu_launches") *value = c->mu_launches;
+    else if (n == "feedback_launches") *value = c->feedback_launches;
     else if (n == "lmmse_blind_fallbacks") {
         // counted on the device behind every launch (lmmse_blind_count_kernel): reading it waits for the stream
         if (c->user_capture) return fail(c, CSI_ERR_INVALID_ARG, "csi_get_option: lmmse_blind_fallbacks cannot be read while a capture is open");

@@ -69,6 +69,7 @@ HybridWeights = collections.namedtuple('HybridWeights', 'fbb idx n_atoms gain fr
 LinkResult = collections.namedtuple('LinkResult', 'bit_errors evm_rms dt_snr_db n_info xeq csi llr bits')
 LinkRxResult = collections.namedtuple('LinkRxResult', LinkResult._fields + ('g_nmse', 'gest'))
 MuLinkResult = collections.namedtuple('MuLinkResult', 'bit_errors evm_rms sinr_db n_info g xeq csi llr bits')
+FeedbackReport = collections.namedtuple('FeedbackReport', 'phi_code psi_code phi psi sigma v nc b_phi b_psi ng')
 
 
 def frf_from_idx(At, idx):
@@ -1084,6 +1085,91 @@ class CsiEngine:
             return tuple(res)
         finally:
             for a in dev + outs + frf + fbb + first + d_cov + [d_reg]:
+                if a is not None:
+                    a.free()
+
+    # ------------------------------------------------------------------ quantised CSI feedback (csrc/feedback.hip.h)
+    FB_LAYOUT_W, FB_LAYOUT_CSI = 0, 1
+
+    def feedback_compress_device(self, d_h_re, d_h_im, npkt, nc, b_phi, b_psi, ng=1, d_phi_code=None, d_psi_code=None, d_phi=None, d_psi=None,
+                                 d_sigma=None, d_v_re=None, d_v_im=None):
+        """Givens-angle report of the nc dominant right singular vectors of every (packet, reported carrier) of the planes d_h_re /
+        d_h_im [npkt,nr,nt,234] (csi_feedback_compress_device): d_phi_code / d_psi_code hold uint16 [npkt, n_ang, n_rep] (arrays of
+        (npkt n_ang n_rep + 1) // 2 floats serve), optional d_phi / d_psi float32 of the same shape, d_sigma [npkt, nc, n_rep], the pair
+        d_v_re / d_v_im [npkt, nc, nt, n_rep]; n_ang = feedback.n_angles(nt, nc), n_rep = feedback.n_reports(ng).  b_phi = b_psi = 0: the
+        continuous angles only.  Asynchronous, on the engine's stream."""
+        ptr = lambda a: None if a is None else a.ptr
+        self._check(self._lib.csi_feedback_compress_device(self._ctx, d_h_re.ptr, d_h_im.ptr, int(npkt), int(nc), int(b_phi), int(b_psi), int(ng),
+                                                           ptr(d_phi_code), ptr(d_psi_code), ptr(d_phi), ptr(d_psi), ptr(d_sigma), ptr(d_v_re),
+                                                           ptr(d_v_im)))
+
+    def feedback_expand_device(self, npkt, nc, b_phi, b_psi, ng, layout, d_out_re, d_out_im, d_phi_code=None, d_psi_code=None, d_phi=None,
+                               d_psi=None, d_sigma=None):
+        """A report expanded at the base station (csi_feedback_expand_device) from the codes or from the continuous angles (exactly one
+        pair): layout FB_LAYOUT_W - d_out_re / d_out_im [npkt, nc, nt, 234], sqrt(nt / nc) Vhat, what mu_link_sim_device reads with one
+        user and ns = nc; FB_LAYOUT_CSI - [npkt, nr, nt, 234], row s < nc = sigma_s conj(Vhat[:, s]) (d_sigma None: 1), the other rows
+        zero.  Asynchronous, on the engine's stream."""
+        ptr = lambda a: None if a is None else a.ptr
+        self._check(self._lib.csi_feedback_expand_device(self._ctx, ptr(d_phi_code), ptr(d_psi_code), ptr(d_phi), ptr(d_psi), ptr(d_sigma),
+                                                         int(npkt), int(nc), int(b_phi), int(b_psi), int(ng), int(layout), d_out_re.ptr, d_out_im.ptr))
+
+    def _u16_download(self, d, shape):
+        n = int(np.prod(shape, dtype=np.int64))
+        return d.download().view(np.uint16)[:n].reshape(shape).copy()
+
+    def feedback_compress(self, h, nc, b_phi=0, b_psi=0, ng=1, keep_angles=False, keep_v=False):
+        """The same from a complex array h [npkt,nr,nt,234] -> FeedbackReport: phi_code / psi_code uint16 [npkt, n_ang, n_rep] (None with
+        b_phi = b_psi = 0), phi / psi float32 (with keep_angles, and always without bits), sigma float32 [npkt, nc, n_rep], v complex64
+        [npkt, nc, nt, n_rep] with keep_v (the vectors that were decomposed)."""
+        from . import feedback as fb
+        h = np.asarray(h)
+        if h.ndim != 4 or h.shape[1:] != (self.nr, self.nt, N_DATA):
+            raise CsiError(-1, f'h must be [npkt,{self.nr},{self.nt},{N_DATA}], got {h.shape}')
+        npkt, coded = h.shape[0], (int(b_phi), int(b_psi)) != (0, 0)
+        ang = (npkt, max(fb.n_angles(self.nt, nc), 0), fb.n_reports(ng if ng in (1, 2, 4) else 1))
+        words = ((int(np.prod(ang, dtype=np.int64)) + 1) // 2,)
+        dev = [self.to_device(_f32c(h.real)), self.to_device(_f32c(h.imag))]
+        codes = [self.empty(words) for _ in range(2)] if coded else [None, None]
+        angles = [self.empty(ang) for _ in range(2)] if keep_angles or not coded else [None, None]
+        sigma = self.empty((npkt, max(int(nc), 0), ang[2]))
+        v = [self.empty((npkt, max(int(nc), 0), self.nt, ang[2])) for _ in range(2)] if keep_v else [None, None]
+        try:
+            self.feedback_compress_device(dev[0], dev[1], npkt, nc, b_phi, b_psi, ng, codes[0], codes[1], angles[0], angles[1], sigma, v[0], v[1])
+            self.synchronize()
+            return FeedbackReport(*[self._u16_download(c, ang) if c is not None else None for c in codes],
+                                  *[a.download() if a is not None else None for a in angles], sigma.download(),
+                                  (v[0].download() + 1j * v[1].download()).astype(np.complex64) if keep_v else None,
+                                  int(nc), int(b_phi), int(b_psi), int(ng))
+        finally:
+            for a in dev + codes + angles + [sigma] + v:
+                if a is not None:
+                    a.free()
+
+    def feedback_expand(self, report, layout='w', use_sigma=True, continuous=False):
+        """A FeedbackReport expanded into complex64 planes: layout 'w' [npkt, nc, nt, 234] or 'csi' [npkt, nr, nt, 234] (use_sigma False:
+        unit singular values).  The codes are used where the report has them, unless `continuous` asks for its angles."""
+        if layout not in ('w', 'csi'):
+            raise CsiError(-1, f"feedback_expand: layout {layout!r} is not 'w' or 'csi'")
+        coded = report.phi_code is not None and not continuous
+        src = (report.phi_code, report.psi_code) if coded else (report.phi, report.psi)
+        if src[0] is None or src[1] is None:
+            raise CsiError(-1, 'feedback_expand: the report holds neither codes nor angles to expand')
+        npkt = src[0].shape[0]
+        if coded:
+            pad = [np.concatenate([np.ascontiguousarray(c, np.uint16).reshape(-1), np.zeros(c.size & 1, np.uint16)]).view(np.float32) for c in src]
+            dev = [self.to_device(x) for x in pad]
+        else:
+            dev = [self.to_device(_f32c(x)) for x in src]
+        d_sigma = self.to_device(_f32c(report.sigma)) if (use_sigma and layout == 'csi' and report.sigma is not None) else None
+        outs = [self.empty((npkt, report.nc if layout == 'w' else self.nr, self.nt, N_DATA)) for _ in range(2)]
+        try:
+            kw = dict(d_phi_code=dev[0], d_psi_code=dev[1]) if coded else dict(d_phi=dev[0], d_psi=dev[1])
+            self.feedback_expand_device(npkt, report.nc, report.b_phi, report.b_psi, report.ng, self.FB_LAYOUT_W if layout == 'w' else self.FB_LAYOUT_CSI,
+                                        outs[0], outs[1], d_sigma=d_sigma, **kw)
+            self.synchronize()
+            return (outs[0].download() + 1j * outs[1].download()).astype(np.complex64)
+        finally:
+            for a in dev + outs + [d_sigma]:
                 if a is not None:
                     a.free()
 

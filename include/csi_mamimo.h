@@ -43,7 +43,7 @@
  * context's stream and return without waiting; call csi_synchronize before reading results.
  *
  * Device pointers (csi_predict_device, csi_ls_estimate_device, csi_estimate_device, csi_lmmse_estimate_device, csi_lmmse_blind_device, csi_subspace_smooth_device, csi_beam_power_device, csi_beam_smooth_device, csi_beam_wiener_device, csi_null_noise_device, csi_nmse_device,
- * csi_hybrid_weights_device, csi_link_sim_device, csi_link_sim_rx_device, csi_mu_precoder_device, csi_mu_link_sim_device, csi_mu_hybrid_precoder_device, csi_mu_covariance_device, csi_mu_jsdm_precoder_device, csi_viterbi_decode_device, csi_synth_*).  An array of exactly the documented
+ * csi_hybrid_weights_device, csi_link_sim_device, csi_link_sim_rx_device, csi_mu_precoder_device, csi_mu_link_sim_device, csi_mu_hybrid_precoder_device, csi_mu_covariance_device, csi_mu_jsdm_precoder_device, csi_feedback_compress_device, csi_feedback_expand_device, csi_viterbi_decode_device, csi_synth_*).  An array of exactly the documented
  * size suffices: it may be a slice of a larger allocation whose neighbours hold live data of any value (NaN and 1e38 included).
  * Nothing outside the arrays is written, nothing outside them reaches a result, and input arrays are not modified.  Every re / im
  * PLANE (the preambles [npkt][Nr][len_ltf], the CSI planes [npkt][Nr][Nt][234 or n_out], fbb, frf_mean, xeq, gest, the precoder planes W, g) starts on a 16-byte
@@ -529,6 +529,47 @@ int  csi_mu_jsdm_precoder_device(csi_ctx* ctx, int n_users, const float* const* 
                                  float* d_frf_im, float* d_fbb_re, float* d_fbb_im, float* d_eig, float* d_ustar_re, float* d_ustar_im,
                                  int32_t* d_rank);
 
+/* Quantised CSI feedback: the compressed beamforming report of IEEE 802.11-2016 19.3.12.3.6 with Nt rows, and its expansion at the
+ * base station (model, plan and what is not modelled: DESIGN.md 4.24, csrc/feedback.hip.h).  An addition: the ABI version stays 1.
+ *   reports    carriers k_r = r ng, r < n_rep = ceil(234 / ng), ng in {1, 2, 4}; carrier k is served by report k / ng (hold, no interpolation)
+ *   V          per (packet, reported carrier) the nc <= min(4, Nr, Nt) dominant right singular vectors of H[i][j] = h[p][i][j][k_r], exactly
+ *              the Fopt of csi_hybrid_weights_device (fp64 Jacobi on H H^H, largest first, lowest index on a tie, a zero column where
+ *              sigma_s = 0); sigma[s] the singular value in fp32.  Column s is multiplied by exp(-j arg V[Nt-1][s]): the last row real and >= 0
+ *   angles     for i = 0 .. min(nc, Nt-1) - 1:  phi[l][i] = arg V[l][i] in [0, 2 pi), l = i .. Nt-2, row l multiplied by exp(-j phi[l][i]);
+ *              then for l = i+1 .. Nt-1 in this order psi[l][i] = atan2(Re V[l][i], Re V[i][i]) in [0, pi/2], rows (i, l) <- (c x_i + s x_l,
+ *              -s x_i + c x_l) with c, s from the unquantised values (hypot 0: c = 1, s = 0).  n_ang = sum_i (Nt-1-i) angles of each kind,
+ *              stored in this loop order
+ *   codes      k_phi = floor(phi 2^(b_phi-1) / pi) mod 2^b_phi, k_psi = min(floor(psi 2^(b_psi+1) / pi), 2^b_psi - 1); the expansion uses
+ *              the bin centres phi = pi (2^-b_phi + k 2^(1-b_phi)), psi = pi (2^-(b_psi+2) + k 2^-(b_psi+1)), their cos / sin computed on the
+ *              host in double and rounded to fp32.  b_phi 2 .. 10, b_psi 1 .. 8 (the standard's pairs: SU (4,2) / (6,4), MU (7,5) / (9,7))
+ *   expansion  the steps backwards on the first nc columns of the identity: Vhat has orthonormal columns whatever the codes
+ * csi_feedback_compress_device: d_h_re / d_h_im [npkt][Nr][Nt][234] IN; d_phi_code / d_psi_code uint16 [npkt][n_ang][n_rep]; optional (may
+ * be NULL): the continuous angles d_phi / d_psi fp32 [npkt][n_ang][n_rep], d_sigma [npkt][nc][n_rep], the pair d_v_re / d_v_im
+ * [npkt][nc][Nt][n_rep] (the vectors after the column phases: what was decomposed).  b_phi = b_psi = 0 asks for the continuous angles only;
+ * the code pointers may then be NULL.
+ * csi_feedback_expand_device: exactly one of the pairs (d_phi_code, d_psi_code) and (d_phi, d_psi) is non-NULL; d_sigma [npkt][nc][n_rep]
+ * or NULL; layout CSI_FB_LAYOUT_W: d_out_re / d_out_im [npkt][nc][Nt][234], the columns scaled by sqrt(Nt / nc), so |W|_F^2 = Nt - what
+ * csi_mu_link_sim_device reads with n_users = 1, ns = nc; CSI_FB_LAYOUT_CSI: [npkt][Nr][Nt][234], row s < nc = sigma_s conj(Vhat[:, s])
+ * (conj(Vhat[:, s]) when d_sigma is NULL), rows >= nc zero: the base station's rebuilt S V^H in the layout csi_mu_precoder_device and
+ * every other estimate consumer reads.  sigma travels UNQUANTISED: the report's per-stream SNR fields are not modelled.
+ * Both are asynchronous on the context's stream and serve fp32 and bf16 contexts alike (all planes are fp32).  The compression runs in
+ * packet chunks against the context's workspace_bytes (the singular vectors of a chunk live in the workspace; default 1 GiB), one launch
+ * per chunk; the expansion is one launch; the same bits whatever the chunking, the call or the packet's position in it.
+ * Refused with text, before anything is launched or counted: nc outside 1 .. min(4, Nr, Nt), Nr > 16, ng not 1, 2 or 4, b_phi outside
+ * 2 .. 10 or b_psi outside 1 .. 8 or only one of them 0, an unknown layout, null required pointers, one array of a pair without the other,
+ * both or neither of the expansion's input pairs, re / im planes off a 16-byte boundary, a single-input context, a per-workgroup LDS image
+ * beyond 160 KiB (Nt nc beyond 2560), negative npkt, an open capture that would have to grow the workspace or change the tables.
+ * npkt == 0 returns 0 and launches nothing; a null context returns -1.  The launches count under "feedback_launches"; profile entries
+ * "fb_compress" and "fb_expand". */
+#define CSI_FB_LAYOUT_W 0
+#define CSI_FB_LAYOUT_CSI 1
+int  csi_feedback_compress_device(csi_ctx* ctx, const float* d_h_re, const float* d_h_im, int64_t npkt, int nc, int b_phi, int b_psi,
+                                  int ng, uint16_t* d_phi_code, uint16_t* d_psi_code, float* d_phi, float* d_psi, float* d_sigma,
+                                  float* d_v_re, float* d_v_im);
+int  csi_feedback_expand_device(csi_ctx* ctx, const uint16_t* d_phi_code, const uint16_t* d_psi_code, const float* d_phi,
+                                const float* d_psi, const float* d_sigma, int64_t npkt, int nc, int b_phi, int b_psi, int ng, int layout,
+                                float* d_out_re, float* d_out_im);
+
 /* Accuracy metric of the reference's evaluation, NMSE_subk (BER_test_maMIMO_LTF.m:675-686): per link
  * ||ref - est||^2 / ||ref||^2 over the n_bins bins, mean over the nlinks links ([link][n_bins] planes, e.g.
  * the [npkt][nr][nt][234] outputs of csi_predict / csi_ls_estimate with nlinks = npkt*nr*nt).  Synchronous;
@@ -716,7 +757,7 @@ int  csi_set_option(csi_ctx* ctx, const char* name, int64_t value);
 /* Current value of an option, or of the read-only values: "hs_launches" (split-engine GEMMs launched), "hs_range_fallbacks"
  * (csi_predict calls repeated on the fp32 MFMA kernels), "hs_weight_pins" / "hs_weight_err_e12" (layers pinned to the fp32 kernels
  * at load because their split copies were not fp32-grade; worst relative error x 1e12), "band_available" (the assembly band kernel
- * is embedded in this build), "graph_replays", "subspace_launches" (kernels launched by csi_subspace_smooth[_device]), "beam_launches" (kernels launched by the csi_beam_* entry points), "mu_launches" (kernels launched by csi_mu_precoder_device / csi_mu_link_sim_device / csi_mu_hybrid_precoder_device / csi_mu_covariance_device / csi_mu_jsdm_precoder_device), "lmmse_blind_fallbacks" ((packet, rx) pairs csi_lmmse_blind[_device] handed back unsmoothed), "ls_pilot_fast" (0 generic / 1 Sylvester / 2 permuted pilot), "comm_world",
+ * is embedded in this build), "graph_replays", "subspace_launches" (kernels launched by csi_subspace_smooth[_device]), "beam_launches" (kernels launched by the csi_beam_* entry points), "mu_launches" (kernels launched by csi_mu_precoder_device / csi_mu_link_sim_device / csi_mu_hybrid_precoder_device / csi_mu_covariance_device / csi_mu_jsdm_precoder_device), "feedback_launches" (kernels launched by csi_feedback_compress_device / csi_feedback_expand_device), "lmmse_blind_fallbacks" ((packet, rx) pairs csi_lmmse_blind[_device] handed back unsmoothed), "ls_pilot_fast" (0 generic / 1 Sylvester / 2 permuted pilot), "comm_world",
  * "comm_rank", "comm_blobs", "comm_bytes" (communicator and last broadcast), "hp_direct_out_calls", and where the last pipelined
  * host-buffer call spent its time in microseconds: "hp_total_us", "hp_stage_us", "hp_wait_stage_us", "hp_wait_out_us", "hp_weave_us". */
 int  csi_get_option(csi_ctx* ctx, const char* name, int64_t* value);
