@@ -1,21 +1,34 @@
 """The evaluation the reference exists for, in the order its pipeline runs it (full_pipeline_maMIMO_DNNEst.sh:40-58): a noise-free
 training set, a fit of both component models, and per SNR level the NMSE of the LS, the LMMSE and the DNN estimate against the
-true channel with 95 % confidence intervals - the "MSE" curve of snr_loop_testing.m:33-64,88-94.  With --ber the data phase of
-BER_test_maMIMO_LTF.m:408-646 follows per level: the hybrid weights of every estimate (and of the true channel, "perfect") precode
-coded QAM through the true channel, giving the bers_ / EVM_rms_ / dtSNR_ families of metrics.mat.  There the receiver
-knows the effective channel; --rxEstimate runs every source a second time with the receiver of the reference, which estimates it from
-a precoded preamble (csi_link_sim_rx_device), and adds the bersRx_ / EVM_rmsRx_ / gNMSE_ families.  --users U (U >= 2) serves U users at
-once on the same subcarriers: per source the zero-forcing precoder of the U users' estimates (csi_mu_precoder_device) and
-the data phase through their true channels (csi_mu_link_sim_device) add the bersMU_ / EVM_rmsMU_ / sinrMU_ families, the mean over the users.
---muHybrid NRF runs that phase a second time behind the hybrid precoder of NRF RF chains (csi_mu_hybrid_precoder_device:
-beams from the --ber dictionary, zero forcing on the effective channel) and adds the bersMUH_ / EVM_rmsMUH_ / sinrMUH_ families.
---muJSDM B runs it once more behind the JSDM precoder of B RF chains per user (csi_mu_jsdm_precoder_device: every user its
-own group, beams from the covariance eigenvectors after nulling --jsdmRank directions of every other user) and adds the bersMUJ_ /
-EVM_rmsMUJ_ / sinrMUJ_ families.
---feedback BPHI BPSI puts the quantised CSI feedback of DESIGN.md 4.24 between every source's estimate and the transmitter: the estimate
-goes through the Givens-angle report (csi_feedback_compress_device) and its expansion (csi_feedback_expand_device), and W = sqrt(Nt / ns)
-Vhat carries the data phase of one user (bersFB_ / EVM_rmsFB_ / sinrFB_); with --users every user's estimate goes through its own report
-and the rebuilt S V^H planes through the zero-forcing precoder (bersMUFB_ / EVM_rmsMUFB_ / sinrMUFB_, paired with the MU fields).
+true channel with 95 % confidence intervals - the "MSE" curve of snr_loop_testing.m:33-64,88-94.  Every option adds estimators or
+data phases to a level and nothing else: without an option every output is what it is without the argument.
+
+    flag (argument of run_sweep)          needs     adds per level, X = every source the family carries            DESIGN.md
+    --ber (ber)                           -         bers_X, EVM_rms_X, dtSNR_X, MSE_perfect: the data phase of       4.17
+                                                    BER_test_maMIMO_LTF.m:408-646, the receiver knows H W
+    --rxEstimate (rx_estimate)            --ber     bersRx_X, EVM_rmsRx_X, gNMSE_X: the receiver estimates H W       4.17
+                                                    from a precoded preamble
+    --channel scattering (channel)        -         nothing; packets from csi_synth_scattering, whose path delays   4.18
+                                                    feed the LMMSE smoother as the reference's h_tau does
+    --blind (blind)                       -         MSE_MMSEb and the source MMSEb: the LMMSE smoother on the        4.3
+                                                    packet's own statistics
+    --delayTaps L --delayPre P            -         MSE_DLY: the LS rows projected onto at most L delay taps; a     4.19
+      (delay_taps, delay_pre)                       source of the multi-user families only
+    --beams (beams)                       -         MSE_ANG: the beam-space Wiener smoother on the LS planes, a      4.21
+                                                    source of the multi-user families only; with --delayTaps
+                                                    MSE_DLYANG, the same step on the DLY planes, no source
+    --users U --muReg --userSpacing       --ber     bersMU_X, EVM_rmsMU_X, sinrMU_X (the mean over the users)        4.20
+      (users, mu_reg, user_spacing)                 and mu_users: U users behind a zero-forcing precoder
+    --muHybrid NRF (mu_hybrid)            --users   bersMUH_X, EVM_rmsMUH_X, sinrMUH_X, muh_users (+ beams):         4.22
+                                                    the same behind the hybrid precoder of NRF RF chains
+    --muJSDM B --jsdmRank --jsdmTol       --users   bersMUJ_X, EVM_rmsMUJ_X, sinrMUJ_X, muj_users (+ r_g, q_g):      4.23
+      --jsdmMode (mu_jsdm)                          the same behind the JSDM precoder, every user its own group
+    --feedback BPHI BPSI --feedbackNg     --ber     bersFB_X, EVM_rmsFB_X, sinrFB_X: one user's data phase behind    4.24
+      (feedback)                                    the expanded Givens-angle report of X; with --users also
+                                                    bersMUFB_X, EVM_rmsMUFB_X, sinrMUFB_X and mufb_users
+
+FAMILIES below states this as data - fields, sources, switches, the per-user record - and MAT_ORDER / JSON_ORDER the two orders
+the rows are written in; metric_fields, format_table and the per-level summary of run_sweep are read off them.
 
     python -m dl_channel_estimation_mamimo_amd.sweep -d OUT [--nTX 32 --nRX 4 --nn 1024 1024 --useBN --bs 256 ...]
                                                             [--ber --numSTS 1 --rays 500 --dataSymbols 10 --bps 2 [--rxEstimate]]
@@ -25,18 +38,17 @@ and the rebuilt S V^H planes through the zero-forcing precoder (bersMUFB_ / EVM_
                                                              [--muJSDM B [--jsdmRank R] [--jsdmTol T] [--jsdmMode pgp|jgp]]]
                                                             [--feedback BPHI BPSI [--feedbackNg G]]
 
-The module holds no arithmetic of its own: packets with a known channel come from csi_synth_structured (--channel scattering: from
-csi_synth_scattering, whose path delays then feed the LMMSE smoother as the reference's h_tau does), labels from
-csi_ls_estimate_device, the fit from trainer.fit, the estimates from csi_estimate_device / csi_lmmse_estimate_device and every
-NMSE from csi_nmse_device (--blind adds the estimator MMSEb: csi_lmmse_blind_device, the smoother that takes its noise level and its
-frequency correlation from the packet itself instead of from the generator; --delayTaps L adds the estimator DLY:
-csi_subspace_smooth_device with w = 1, the projection of the LS rows onto the channels of at most L delay taps, which uses nothing
-from the generator either - the basis comes from subspace.delay_basis; --beams adds the estimator ANG: csi_beam_wiener_device on the
-LS planes with the DFT beams of beamspace.dft_basis and the error level csi_null_noise_device finds in the preambles' null carriers,
-and with --delayTaps the estimator DLYANG, the same step on the DLY planes); the hybrid weights from csi_hybrid_weights_device and bit errors, EVM and beamforming gain from
-csi_link_sim_device, with the noise level of a data symbol from synth.link_noise_var.  Only the per-packet mean of the per-link
-ratios (NMSE_subk, BER_test_maMIMO_LTF.m:675-686), errors / n_info and the confidence interval are taken on the host."""
+The module holds no arithmetic of its own: packets come from csi_synth_structured / csi_synth_scattering, labels from
+csi_ls_estimate_device, the fit from trainer.fit, the estimates from csi_estimate_device, csi_lmmse_estimate_device,
+csi_lmmse_blind_device, csi_subspace_smooth_device (basis: subspace.delay_basis) and csi_beam_wiener_device (beams:
+beamspace.dft_basis, error level: csi_null_noise_device), every NMSE from csi_nmse_device, the precoders from
+csi_hybrid_weights_device, csi_mu_precoder_device, csi_mu_hybrid_precoder_device, csi_mu_jsdm_precoder_device and
+csi_feedback_compress_device / csi_feedback_expand_device, bit errors, EVM and gains from csi_link_sim_device,
+csi_link_sim_rx_device and csi_mu_link_sim_device, with the noise level of a data symbol from synth.link_noise_var.  Only the
+per-packet mean of the per-link ratios (NMSE_subk, BER_test_maMIMO_LTF.m:675-686), errors / n_info, the mean over the users and the
+confidence interval are taken on the host."""
 import argparse
+import collections
 import json
 import os
 import pickle
@@ -63,6 +75,33 @@ BEAMS = 'ANG'                            # --beams: the beam-space Wiener smooth
 DELAY_BEAMS = 'DLYANG'                   # --beams with --delayTaps: the same step on the DLY planes
 BLIND = 'MMSEb'                          # --blind: the LMMSE smoother on the packet's own statistics (csi_lmmse_blind_device)
 
+SINGLE = SOURCES + (BLIND,)              # the sources of a single-user data phase
+EVERY = SINGLE + (DELAY, BEAMS)          # the sources of a multi-user one
+# An estimator exists when all of these keys of the result dict (sweep.json) are set; the others always do.
+SOURCE_NEEDS = {BLIND: ('blind',), DELAY: ('delay',), BEAMS: ('beams',), DELAY_BEAMS: ('beams', 'delay')}
+# fields: the prefixes of evaluate_level's dict and of metrics.mat; json: their prefixes in a level of sweep.json (None: not listed
+# there) - the table shows the first; sources: who may carry the family; needs: the keys of the result dict that switch it on;
+# users: the key of its per-user record in evaluate_level's dict and in sweep.json.
+Family = collections.namedtuple('Family', 'fields json sources needs users')
+FAMILIES = dict(
+    MSE=Family(('MSE_',), ('',), ESTIMATORS + ('perfect', BLIND, DELAY, BEAMS, DELAY_BEAMS), (), None),
+    LINK=Family(LINK_FIELDS, ('BER_', None, None), SINGLE, ('ber',), None),
+    RX=Family(RX_FIELDS, RX_FIELDS, SINGLE, ('rx_estimate',), None),
+    MU=Family(MU_FIELDS, MU_FIELDS, EVERY, ('mu',), 'mu_users'),
+    MUH=Family(MUH_FIELDS, MUH_FIELDS, EVERY, ('mu_hybrid',), 'muh_users'),
+    MUJ=Family(MUJ_FIELDS, MUJ_FIELDS, EVERY, ('mu_jsdm',), 'muj_users'),
+    FB=Family(FB_FIELDS, FB_FIELDS, SINGLE, ('feedback',), None),
+    MUFB=Family(MUFB_FIELDS, MUFB_FIELDS, EVERY, ('feedback', 'mu'), 'mufb_users'))
+# The two orders the rows (family, source) are written in, as blocks (family, sources) - source-major within a block - and
+# (family, USERS) for the per-user record.  Both are contracts with whoever reads the files.  They differ in their heads, which grew
+# option by option; every family behind MU stands whole, in the order of the table, at the end of both.
+USERS = ()
+_WHOLE = tuple(b for k in FAMILIES if k not in ('MSE', 'LINK', 'RX', 'MU') for b in ((k, FAMILIES[k].sources), (k, USERS)))
+MAT_ORDER = (('MSE', ESTIMATORS), ('LINK', SOURCES), ('MSE', ('perfect',)), ('MSE', (BLIND,)), ('LINK', (BLIND,)), ('RX', SINGLE),
+             ('MSE', (DELAY,)), ('MU', SINGLE + (DELAY,)), ('MSE', (BEAMS, DELAY_BEAMS)), ('MU', (BEAMS,))) + _WHOLE      # metrics.mat
+JSON_ORDER = (('MSE', ESTIMATORS + (BLIND, DELAY)), ('LINK', SINGLE), ('RX', SINGLE), ('MU', SINGLE + (DELAY,)), ('MU', USERS),
+              ('MSE', (BEAMS, DELAY_BEAMS)), ('MU', (BEAMS,))) + _WHOLE                             # a level of sweep.json, the table
+
 
 def tap_profile(n_taps=8):
     """The generator's tap profile exp(-0.5 t) / sqrt(2), t < n_taps (csrc/synth_structured.hip.h)."""
@@ -80,6 +119,11 @@ def confidence_interval(x):
     m, sem = float(x.mean()), float(x.std(ddof=1) / np.sqrt(n))
     q = float(t.ppf(0.975, n - 1))
     return m, m - q * sem, m + q * sem
+
+
+def _interval(x):
+    m, lo, hi = confidence_interval(x)
+    return dict(mean=m, ci_low=lo, ci_high=hi)
 
 
 def scattering_args(channel):
@@ -117,113 +161,92 @@ def make_dataset(engine, n_train, seed, n_taps=8, amp_scale=True, channel=None):
     return ds.dataset_from_packets(ltf, labels, engine.pilot)
 
 
-def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=True, keep=False, ber=None, channel=None, blind=False,
-                   rx_estimate=False, delay=None, mu=None, beams=False, mu_hybrid=None, mu_jsdm=None, feedback=None):
-    """npkt test packets at `snr_db` (packets first_pkt ... of stream `seed`: keep them disjoint from the training packets), LS + DNN
-    (estimate_device), the LMMSE smoother on the LS planes, and NMSE_subk of the three estimates against the true channel.
-    Returns {'MSE_LS', 'MSE_MMSE', 'MSE_DNN'}: float64 [npkt], the per-link ratios averaged per packet.
+def user_estimates(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=True, channel=None, blind=False, delay=None, beams=False,
+                   az_offset=0.0, want_noise_std=True, delay_beams=False):
+    """npkt test packets of one user at `snr_db` (packets first_pkt ... of stream `seed`) and every estimate of their channel: LS + DNN
+    (estimate_device), the LMMSE smoother on the LS planes, with blind MMSEb (lmmse_blind_device on the preambles and the LS planes),
+    with delay = (L, pre) DLY (the LS planes projected onto the taps at delays -pre .. L - pre - 1: subspace.delay_basis,
+    subspace_smooth_device without weights), with beams ANG and, with delay_beams and delay, DLYANG (beam_planes).
 
-    LMMSE inputs: hvec is the generator's tap profile exp(-0.5 t) / sqrt(2), the impulse response LMMSE_ce.m's `h` stands for (the
-    reference hands it the scatterer delays h_tau, generate_maMIMO_LTF.m:342, which a synthetic channel does not have); snr_db[p][r]
-    is the level.  keep=True adds 'arrays': the DeviceArrays ltf_re, ltf_im, h_re, h_im, ls_re, ls_im (the caller frees them).
+    LMMSE inputs: hvec is the generator's tap profile exp(-0.5 t) / sqrt(2), the impulse response LMMSE_ce.m's `h` stands for;
+    with the scattering channel (channel: scattering_args, the user az_offset degrees from its az_deg) the generator's path delays tau
+    (L = n_scat), the input the reference gives LMMSE_ce (h_tau, generate_maMIMO_LTF.m:342); snr_db[p][r] is the level.
 
-    ber = dict(ns, ntrf, n_sym, bps) adds the data phase (link_level): 'bers_X', 'EVM_rms_X', 'dtSNR_X' float64 [npkt] for X in SOURCES
-    and 'MSE_perfect' (zeros).  The engine needs a dictionary (set_dictionary).
-
-    channel (scattering_args) takes the packets from csi_synth_scattering instead; hvec is then the generator's path delays tau
-    (L = n_scat), the input the reference gives LMMSE_ce.
-
-    blind=True adds 'MSE_MMSEb': the smoother that needs neither hvec nor the level (lmmse_blind_device on the preambles and the LS
-    planes), and with `ber` the source MMSEb of the data phase.  Nothing else changes.
-
-    rx_estimate=True (with `ber`) adds 'bersRx_X', 'EVM_rmsRx_X' and 'gNMSE_X' per source (link_level).
-
-    delay=(L, pre) adds 'MSE_DLY': the LS planes projected onto the channels with taps at delays -pre .. L - pre - 1
-    (subspace.delay_basis, subspace_smooth_device without weights).  It is no source of the data phase.  Nothing else changes.
-
-    mu = dict(users=U, reg='zf' | 'rzf', spacing=degrees) (with `ber`, U >= 2) adds the multi-user data phase (mu_level): user 0 is the
-    user above; user u >= 1 takes its packets from the stream seed + u (scattering channel: at azimuth az_deg + u spacing) and its
-    estimates from the same calls.  Adds 'bersMU_X', 'EVM_rmsMU_X', 'sinrMU_X' float64 [npkt] (the mean over the users) for every source
-    X - here DLY is one too - and 'mu_users' = {X: {'bers', 'EVM_rms', 'sinr': [U][npkt]}}.  Nothing else changes.
-
-    beams=True adds 'MSE_ANG' (beam_planes: the beam-space Wiener smoother on the LS planes) and, with `delay`, 'MSE_DLYANG' (the same
-    step on the DLY planes).  ANG is a source of the multi-user data phase as DLY is, and of no other.  Nothing else changes.
-
-    mu_hybrid=n_rf (with `mu`) runs the multi-user data phase a second time per source behind the hybrid precoder of n_rf RF chains on the
-    engine's dictionary (mu_level): 'bersMUH_X', 'EVM_rmsMUH_X', 'sinrMUH_X' and 'muh_users' (the per-user arrays and the chosen beams).
-    mu_jsdm={b, r_star, tol, mode} (with `mu`) runs it once more per source behind the JSDM precoder (mu_level): 'bersMUJ_X', 'EVM_rmsMUJ_X',
-    'sinrMUJ_X' and 'muj_users' (the per-user arrays and the mean ranks).
-    feedback={b_phi, b_psi, ng} (with `ber`) adds the data phase behind the quantised feedback of every source of the single-user data
-    phase (feedback_level): 'bersFB_X', 'EVM_rmsFB_X', 'sinrFB_X'; with `mu` also 'bersMUFB_X', 'EVM_rmsMUFB_X', 'sinrMUFB_X' and
-    'mufb_users' for every source of the multi-user one (mu_level).
-    Nothing else changes."""
+    Returns {'planes': {X: (re, im)} with the true channel under 'perfect', 'ltf': (re, im), 'noise_std' (None unless wanted),
+    'free': every DeviceArray allocated here, for the caller to free}."""
     nr, nt = engine.nr, engine.nt
-    d_tau = None
-    if channel is None:
+    ch = scattering_args(channel)
+    if ch is None:
         d_re, d_im, h_re, h_im, d_std = engine.synth_structured(seed, first_pkt, npkt, snr_db=float(snr_db), n_taps=n_taps, amp_scale=amp_scale,
-                                                                want_noise_std=ber is not None)
+                                                                want_noise_std=want_noise_std)
     else:
+        ch['az_deg'] = ch['az_deg'] + az_offset
         d_re, d_im, h_re, h_im, d_std, d_tau = engine.synth_scattering(seed, first_pkt, npkt, snr_db=float(snr_db), amp_scale=amp_scale,
-                                                                       want_noise_std=ber is not None, want_tau=True,
-                                                                       **scattering_args(channel))
+                                                                       want_noise_std=want_noise_std, want_tau=True, **ch)
     shape = (npkt, nr, nt, N_DATA)
     o_re, o_im, ls_re, ls_im, m_re, m_im = (engine.empty(shape) for _ in range(6))
     engine.estimate_device(d_re, d_im, npkt, o_re, o_im, ls_re, ls_im, checked=True)
-    if d_tau is None:
+    if ch is None:
         prof = tap_profile(n_taps)
         d_hvec, L = engine.to_device(np.tile(prof, (npkt, 1))), prof.size
     else:
-        d_hvec, L = d_tau, scattering_args(channel)['n_scat']
+        d_hvec, L = d_tau, ch['n_scat']
     d_snr = engine.to_device(np.full((npkt, nr), float(snr_db), np.float32))
     engine.lmmse_estimate_device(ls_re, ls_im, npkt, d_hvec, L, d_snr, m_re, m_im)
+    planes = dict(LS=(ls_re, ls_im), MMSE=(m_re, m_im), DNN=(o_re, o_im), perfect=(h_re, h_im))
+    if blind:
+        planes[BLIND] = (engine.empty(shape), engine.empty(shape))
+        engine.lmmse_blind_device(d_re, d_im, ls_re, ls_im, npkt, *planes[BLIND])
+    if delay is not None:
+        planes[DELAY] = (engine.empty(shape), engine.empty(shape))
+        engine.subspace_set_basis(subspace.delay_basis(delay[0], delay[1])[0])
+        engine.subspace_smooth_device(ls_re, ls_im, npkt, *planes[DELAY])
+    if beams:
+        planes.update(beam_planes(engine, d_re, d_im, planes['LS'], planes[DELAY] if delay_beams and delay is not None else None, npkt, delay))
+    free = [d_re, d_im, d_hvec, d_snr] + [a for p in planes.values() for a in p] + ([d_std] if d_std is not None else [])
+    return dict(planes=planes, ltf=(d_re, d_im), noise_std=d_std, free=free)
+
+
+def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=True, keep=False, ber=None, channel=None, blind=False,
+                   rx_estimate=False, delay=None, mu=None, beams=False, mu_hybrid=None, mu_jsdm=None, feedback=None):
+    """One level: the estimates of npkt test packets at `snr_db` (user_estimates: packets first_pkt ... of stream `seed`, keep them
+    disjoint from the training packets) and NMSE_subk of each against the true channel, then the data phases the options ask for (the
+    table of the module).  Returns {'MSE_X': float64 [npkt], the per-link ratios averaged per packet} for X = LS, MMSE, DNN and every
+    estimator switched on, the families of link_level (ber = dict(ns, ntrf, n_sym, bps), rx_estimate; the engine needs a dictionary,
+    set_dictionary) with 'MSE_perfect' (zeros), of feedback_level (feedback = {b_phi, b_psi, ng}) and of mu_level (mu = dict(users=U,
+    reg='zf' | 'rzf', spacing=degrees), mu_hybrid = n_rf, mu_jsdm = {b, r_star, tol, mode}, feedback) with their per-user records.
+    In the multi-user phase user 0 is the user above; user u >= 1 takes its packets from the stream seed + u (scattering channel: at
+    azimuth az_deg + u spacing) and its estimates from the same calls, DLYANG left out.
+    keep=True adds 'arrays': the DeviceArrays ltf_re, ltf_im, h_re, h_im, ls_re, ls_im (the caller frees them)."""
+    nr, nt = engine.nr, engine.nt
+    users = [user_estimates(engine, snr_db, npkt, seed, first_pkt, n_taps, amp_scale, channel, blind, delay, beams,
+                            want_noise_std=ber is not None, delay_beams=True)]
+    planes, d_std = users[0]['planes'], users[0]['noise_std']
+    h_re, h_im = planes['perfect']
     d_link = engine.empty((npkt * nr * nt,))
     out = {}
-    estimates = list(zip(ESTIMATORS, ((ls_re, ls_im), (m_re, m_im), (o_re, o_im))))
-    b_planes = ()
-    if blind:
-        b_planes = (engine.empty(shape), engine.empty(shape))
-        engine.lmmse_blind_device(d_re, d_im, ls_re, ls_im, npkt, b_planes[0], b_planes[1])
-        estimates.append((BLIND, b_planes))
-    d_planes = ()
-    if delay is not None:
-        d_planes = (engine.empty(shape), engine.empty(shape))
-        engine.subspace_set_basis(subspace.delay_basis(delay[0], delay[1])[0])
-        engine.subspace_smooth_device(ls_re, ls_im, npkt, d_planes[0], d_planes[1])
-        estimates.append((DELAY, d_planes))
-    a_planes = {}
-    if beams:
-        a_planes = beam_planes(engine, d_re, d_im, (ls_re, ls_im), d_planes or None, npkt, delay)
-        estimates += list(a_planes.items())
-    for name, (e_re, e_im) in estimates:
-        engine.nmse_device(h_re, h_im, e_re, e_im, npkt * nr * nt, N_DATA, d_per_link=d_link)
-        out['MSE_' + name] = d_link.download().astype(np.float64).reshape(npkt, nr * nt).mean(axis=1)
+    for name, (e_re, e_im) in planes.items():
+        if name != 'perfect':
+            engine.nmse_device(h_re, h_im, e_re, e_im, npkt * nr * nt, N_DATA, d_per_link=d_link)
+            out['MSE_' + name] = d_link.download().astype(np.float64).reshape(npkt, nr * nt).mean(axis=1)
+    d_link.free()
     if ber is not None:
-        planes = dict(LS=(ls_re, ls_im), MMSE=(m_re, m_im), DNN=(o_re, o_im), perfect=(h_re, h_im))
-        if blind:
-            planes[BLIND] = b_planes
-        out.update(link_level(engine, planes, h_re, h_im, d_std, npkt, seed, first_pkt, amp_scale=amp_scale, rx_estimate=rx_estimate, **ber))
+        single = {x: planes[x] for x in SINGLE if x in planes}
+        out.update(link_level(engine, single, h_re, h_im, d_std, npkt, seed, first_pkt, amp_scale=amp_scale, rx_estimate=rx_estimate, **ber))
         out['MSE_perfect'] = np.zeros(npkt)
         if feedback:
-            out.update(feedback_level(engine, planes, h_re, h_im, synth.link_noise_var(d_std.download(), amp_scale), npkt, seed, first_pkt,
+            out.update(feedback_level(engine, single, h_re, h_im, synth.link_noise_var(d_std.download(), amp_scale), npkt, seed, first_pkt,
                                       ns=ber['ns'], n_sym=ber['n_sym'], bps=ber['bps'], **feedback))
         if mu:
-            if delay is not None:
-                planes[DELAY] = d_planes
-            if beams:
-                planes[BEAMS] = a_planes[BEAMS]
-            others = [user_planes(engine, snr_db, npkt, seed + u, first_pkt, n_taps, amp_scale, channel, blind, delay, u * float(mu.get('spacing', 15.0)),
-                                  beams=beams)
-                      for u in range(1, int(mu['users']))]
-            nv = np.stack([synth.link_noise_var(d.download(), amp_scale) for d in [d_std] + [o['noise_std'] for o in others]])
-            out.update(mu_level(engine, [planes] + [o['planes'] for o in others], nv, npkt, seed, first_pkt, ns=ber['ns'], n_sym=ber['n_sym'],
-                                bps=ber['bps'], reg=mu.get('reg', 'zf'), n_rf=mu_hybrid, jsdm=mu_jsdm, fb=feedback))
-            for o in others:
-                for a in o['free']:
-                    a.free()
-        d_std.free()
-    kept = (d_re, d_im, h_re, h_im, ls_re, ls_im)
-    for a in (o_re, o_im, m_re, m_im, d_hvec, d_snr, d_link) + b_planes + d_planes + tuple(a for p in a_planes.values() for a in p) + (() if keep else kept):
-        a.free()
+            users += [user_estimates(engine, snr_db, npkt, seed + u, first_pkt, n_taps, amp_scale, channel, blind, delay, beams,
+                                     az_offset=u * float(mu.get('spacing', 15.0))) for u in range(1, int(mu['users']))]
+            nv = np.stack([synth.link_noise_var(u['noise_std'].download(), amp_scale) for u in users])
+            out.update(mu_level(engine, [{x: u['planes'][x] for x in EVERY if x in u['planes']} for u in users], nv, npkt, seed, first_pkt,
+                                ns=ber['ns'], n_sym=ber['n_sym'], bps=ber['bps'], reg=mu.get('reg', 'zf'), n_rf=mu_hybrid, jsdm=mu_jsdm, fb=feedback))
+    kept = users[0]['ltf'] + planes['perfect'] + planes['LS']
+    for a in (a for u in users for a in u['free']):
+        if not keep or all(a is not k for k in kept):
+            a.free()
     if keep:
         out['arrays'] = kept
     return out
@@ -254,45 +277,9 @@ def beam_planes(engine, d_ltf_re, d_ltf_im, ls, dly, npkt, delay):
     return out
 
 
-def user_planes(engine, snr_db, npkt, seed, first_pkt, n_taps, amp_scale, channel, blind, delay, az_offset, beams=False):
-    """Test packets of one further user of the multi-user data phase and its estimates, from the calls evaluate_level makes for its own
-    user: {'planes': {X: (re, im)} for LS, MMSE, DNN, perfect (+ MMSEb, DLY, ANG), 'noise_std', 'free': every DeviceArray to free}.  The
-    scattering channel places the user az_offset degrees from the channel's az_deg."""
-    nr, nt = engine.nr, engine.nt
-    d_tau = None
-    if channel is None:
-        d_re, d_im, h_re, h_im, d_std = engine.synth_structured(seed, first_pkt, npkt, snr_db=float(snr_db), n_taps=n_taps, amp_scale=amp_scale,
-                                                                want_noise_std=True)
-    else:
-        ch = scattering_args(channel)
-        ch['az_deg'] = ch['az_deg'] + az_offset
-        d_re, d_im, h_re, h_im, d_std, d_tau = engine.synth_scattering(seed, first_pkt, npkt, snr_db=float(snr_db), amp_scale=amp_scale,
-                                                                       want_noise_std=True, want_tau=True, **ch)
-    shape = (npkt, nr, nt, N_DATA)
-    o_re, o_im, ls_re, ls_im, m_re, m_im = (engine.empty(shape) for _ in range(6))
-    engine.estimate_device(d_re, d_im, npkt, o_re, o_im, ls_re, ls_im, checked=True)
-    if d_tau is None:
-        prof = tap_profile(n_taps)
-        d_hvec, L = engine.to_device(np.tile(prof, (npkt, 1))), prof.size
-    else:
-        d_hvec, L = d_tau, scattering_args(channel)['n_scat']
-    d_snr = engine.to_device(np.full((npkt, nr), float(snr_db), np.float32))
-    engine.lmmse_estimate_device(ls_re, ls_im, npkt, d_hvec, L, d_snr, m_re, m_im)
-    planes = dict(LS=(ls_re, ls_im), MMSE=(m_re, m_im), DNN=(o_re, o_im), perfect=(h_re, h_im))
-    free = [d_re, d_im, h_re, h_im, d_std, o_re, o_im, ls_re, ls_im, m_re, m_im, d_hvec, d_snr]
-    if blind:
-        planes[BLIND] = (engine.empty(shape), engine.empty(shape))
-        engine.lmmse_blind_device(d_re, d_im, ls_re, ls_im, npkt, *planes[BLIND])
-        free += list(planes[BLIND])
-    if delay is not None:
-        planes[DELAY] = (engine.empty(shape), engine.empty(shape))
-        engine.subspace_set_basis(subspace.delay_basis(delay[0], delay[1])[0])
-        engine.subspace_smooth_device(ls_re, ls_im, npkt, *planes[DELAY])
-        free += list(planes[DELAY])
-    if beams:
-        planes[BEAMS] = beam_planes(engine, d_re, d_im, (ls_re, ls_im), None, npkt, None)[BEAMS]
-        free += list(planes[BEAMS])
-    return dict(planes=planes, noise_std=d_std, free=free)
+def _download_metrics(d_errors, d_evm, d_third, n_info):
+    """What a data phase leaves on the device, as float64 in the shape of the arrays: (bit errors / n_info, EVM, the third metric)."""
+    return d_errors.download().view(np.int32).astype(np.float64) / n_info, d_evm.download().astype(np.float64), d_third.download().astype(np.float64)
 
 
 class _Report:
@@ -333,12 +320,9 @@ def feedback_level(engine, planes, h_re, h_im, noise_var, npkt, seed, first_pkt,
     for name, (e_re, e_im) in planes.items():
         report.through(e_re, e_im, engine.FB_LAYOUT_W, w[0], w[1])
         engine.mu_link_sim_device([h_re], [h_im], w[0], w[1], d_nv, seed, first_pkt, npkt, ns, d_err, d_evm, d_sinr, n_sym=n_sym, bps=bps)
-        out[FB_FIELDS[0] + name] = d_err.download().view(np.int32).astype(np.float64)[0] / n_info
-        out[FB_FIELDS[1] + name] = d_evm.download().astype(np.float64)[0]
-        out[FB_FIELDS[2] + name] = d_sinr.download().astype(np.float64)[0]
-    for a in w + [d_err, d_evm, d_sinr, d_nv]:
+        out.update(zip((f + name for f in FAMILIES['FB'].fields), (v[0] for v in _download_metrics(d_err, d_evm, d_sinr, n_info))))
+    for a in w + [d_err, d_evm, d_sinr, d_nv, report]:
         a.free()
-    report.free()
     return out
 
 
@@ -369,49 +353,52 @@ def mu_level(engine, planes, noise_var, npkt, seed, first_pkt, ns=1, n_sym=10, b
     w = [engine.empty((npkt, m, nt, N_DATA)) for _ in range(2)]
     d_err, d_evm, d_sinr = (engine.empty((nu, npkt)) for _ in range(3))
     h_re, h_im = [p['perfect'][0] for p in planes], [p['perfect'][1] for p in planes]
-    d_idx = engine.empty((npkt, int(n_rf))) if n_rf else None
-    d_rank = engine.empty((npkt, nu, 2)) if jsdm else None
-    out, users, users_h, users_j, users_fb = {}, {}, {}, {}, {}
+    scratch = w + [d_err, d_evm, d_sinr, d_nv] + ([d_reg] if d_reg is not None else [])
 
-    def data_phase(fields):
-        engine.mu_link_sim_device(h_re, h_im, w[0], w[1], d_nv, seed, first_pkt, npkt, ns, d_err, d_evm, d_sinr, n_sym=n_sym, bps=bps)
-        per = dict(bers=d_err.download().view(np.int32).astype(np.float64) / n_info, EVM_rms=d_evm.download().astype(np.float64),
-                   sinr=d_sinr.download().astype(np.float64))
-        for f, k in zip(fields, ('bers', 'EVM_rms', 'sinr')):
-            out[f + name] = per[k].mean(axis=0)
-        return {k: v.tolist() for k, v in per.items()}
+    # The precoder variants in the order they run: (family, the step that leaves the precoder of the users' planes e_re[u], e_im[u] in
+    # w, what the step adds to a source's per-user record - read after the data phase).
+    def zero_forcing(e_re, e_im):
+        engine.mu_precoder_device(e_re, e_im, npkt, ns, w[0], w[1], d_reg)
+    variants = [('MU', zero_forcing, dict)]
+    if n_rf:
+        d_idx = engine.empty((npkt, int(n_rf)))
+        scratch.append(d_idx)
+        variants.append(('MUH', lambda e_re, e_im: engine.mu_hybrid_precoder_device(e_re, e_im, npkt, ns, int(n_rf), w[0], w[1], d_idx, d_reg),
+                         lambda: dict(beams=d_idx.download().view(np.int32).tolist())))
+    if jsdm:
+        d_rank = engine.empty((npkt, nu, 2))
+        scratch.append(d_rank)
 
-    for name in planes[0]:
-        engine.mu_precoder_device([p[name][0] for p in planes], [p[name][1] for p in planes], npkt, ns, w[0], w[1], d_reg)
-        users[name] = data_phase(MU_FIELDS)
-    for name in planes[0] if n_rf else ():
-        engine.mu_hybrid_precoder_device([p[name][0] for p in planes], [p[name][1] for p in planes], npkt, ns, int(n_rf), w[0], w[1], d_idx, d_reg)
-        users_h[name] = dict(data_phase(MUH_FIELDS), beams=d_idx.download().view(np.int32).tolist())
-    for name in planes[0] if jsdm else ():
-        engine.mu_jsdm_precoder_device([p[name][0] for p in planes], [p[name][1] for p in planes], npkt, ns, int(jsdm['r_star']), int(jsdm['b']), w[0], w[1],
-                                       rank_tol=float(jsdm['tol']), flags=engine.JSDM_PGP if jsdm['mode'] == 'pgp' else 0, d_reg=d_reg, d_rank=d_rank)
-        per = data_phase(MUJ_FIELDS)
-        rank = d_rank.download().view(np.int32).astype(np.float64)
-        users_j[name] = dict(per, r_g=float(rank[..., 0].mean()), q_g=float(rank[..., 1].mean()))
+        def mean_ranks():
+            rank = d_rank.download().view(np.int32).astype(np.float64)
+            return dict(r_g=float(rank[..., 0].mean()), q_g=float(rank[..., 1].mean()))
+        variants.append(('MUJ', lambda e_re, e_im: engine.mu_jsdm_precoder_device(
+            e_re, e_im, npkt, ns, int(jsdm['r_star']), int(jsdm['b']), w[0], w[1], rank_tol=float(jsdm['tol']),
+            flags=engine.JSDM_PGP if jsdm['mode'] == 'pgp' else 0, d_reg=d_reg, d_rank=d_rank), mean_ranks))
     if fb:
         report = _Report(engine, npkt, ns, fb['b_phi'], fb['b_psi'], fb['ng'])
         rebuilt = [[engine.empty((npkt, engine.nr, nt, N_DATA)) for _ in range(2)] for _ in range(nu)]
-        for name in planes[0]:
+        scratch += [report] + [x for r in rebuilt for x in r]
+
+        def through_the_reports(e_re, e_im):
             for u in range(nu):
-                report.through(planes[u][name][0], planes[u][name][1], engine.FB_LAYOUT_CSI, rebuilt[u][0], rebuilt[u][1])
-            engine.mu_precoder_device([r[0] for r in rebuilt], [r[1] for r in rebuilt], npkt, ns, w[0], w[1], d_reg)
-            users_fb[name] = data_phase(MUFB_FIELDS)
-        report.free()
-        for a in (x for r in rebuilt for x in r):
-            a.free()
-        out['mufb_users'] = users_fb
-    for a in w + [d_err, d_evm, d_sinr, d_nv] + [x for x in (d_reg, d_idx, d_rank) if x is not None]:
+                report.through(e_re[u], e_im[u], engine.FB_LAYOUT_CSI, rebuilt[u][0], rebuilt[u][1])
+            zero_forcing([r[0] for r in rebuilt], [r[1] for r in rebuilt])
+        variants.append(('MUFB', through_the_reports, dict))
+
+    out, users = {}, {}
+    for family, precode, extras in variants:
+        fields, per_user = FAMILIES[family].fields, users.setdefault(FAMILIES[family].users, {})
+        for name in planes[0]:
+            precode([p[name][0] for p in planes], [p[name][1] for p in planes])
+            engine.mu_link_sim_device(h_re, h_im, w[0], w[1], d_nv, seed, first_pkt, npkt, ns, d_err, d_evm, d_sinr, n_sym=n_sym, bps=bps)
+            per = _download_metrics(d_err, d_evm, d_sinr, n_info)
+            out.update(zip((f + name for f in fields), (v.mean(axis=0) for v in per)))
+            per_user[name] = dict(zip(('bers', 'EVM_rms', 'sinr'), (v.tolist() for v in per)), **extras())
+    for a in scratch:
         a.free()
-    out['mu_users'] = users
-    if n_rf:
-        out['muh_users'] = users_h
-    if jsdm:
-        out['muj_users'] = users_j
+    # the per-user records stand behind every field, the feedback's first: the order this dict has always had
+    out.update((k, users[k]) for k in sorted(users, key=lambda k: k != FAMILIES['MUFB'].users))
     return out
 
 
@@ -437,14 +424,10 @@ def link_level(engine, planes, h_re, h_im, d_noise_std, npkt, seed, first_pkt, n
         engine.hybrid_weights_device(e_re, e_im, npkt, ns, ntrf, fbb[0], fbb[1], d_idx, d_frf_mean_re=frf[0], d_frf_mean_im=frf[1])
         engine.link_sim_device(h_re, h_im, fbb[0], fbb[1], frf[0], frf[1], d_nv, seed, first_pkt, npkt, ns, ntrf, d_err, d_evm, d_gain,
                                n_sym=n_sym, bps=bps)
-        out['bers_' + name] = d_err.download().view(np.int32).astype(np.float64) / n_info
-        out['EVM_rms_' + name] = d_evm.download().astype(np.float64)
-        out['dtSNR_' + name] = d_gain.download().astype(np.float64)
+        out.update(zip((f + name for f in LINK_FIELDS), _download_metrics(d_err, d_evm, d_gain, n_info)))
         if rx_estimate:
             engine.link_sim_rx_device(h_re, h_im, fbb[0], fbb[1], frf[0], frf[1], d_nv, seed, first_pkt, npkt, ns, ntrf, *d_rx, n_sym=n_sym, bps=bps)
-            out_rx['bersRx_' + name] = d_rx[0].download().view(np.int32).astype(np.float64) / n_info
-            out_rx['EVM_rmsRx_' + name] = d_rx[1].download().astype(np.float64)
-            out_rx['gNMSE_' + name] = d_rx[3].download().astype(np.float64)
+            out_rx.update(zip((f + name for f in RX_FIELDS), _download_metrics(d_rx[0], d_rx[1], d_rx[3], n_info)))
     for a in fbb + frf + [d_idx, d_err, d_evm, d_gain, d_nv] + d_rx:
         a.free()
     out.update(out_rx)
@@ -482,63 +465,41 @@ def load_models(engine, modeldir):
 
 
 def metric_fields(mse):
-    """The fields of metrics.mat that the level `mse` (evaluate_level) carries, in the order they are written: a family that an
-    option adds stands behind every field that exists without it."""
-    fields = ['MSE_' + e for e in ESTIMATORS]
-    if 'bers_perfect' in mse:
-        fields += [f + x for x in SOURCES for f in LINK_FIELDS] + ['MSE_perfect']
-    if 'MSE_' + BLIND in mse:
-        fields += ['MSE_' + BLIND] + ([f + BLIND for f in LINK_FIELDS] if 'bers_' + BLIND in mse else [])
-    if RX_FIELDS[0] + 'perfect' in mse:
-        fields += [f + x for x in SOURCES + ((BLIND,) if RX_FIELDS[0] + BLIND in mse else ()) for f in RX_FIELDS]
-    if 'MSE_' + DELAY in mse:
-        fields += ['MSE_' + DELAY]
-    if MU_FIELDS[0] + 'perfect' in mse:
-        fields += [f + x for x in SOURCES + tuple(e for e in (BLIND, DELAY) if MU_FIELDS[0] + e in mse) for f in MU_FIELDS]
-    fields += ['MSE_' + e for e in (BEAMS, DELAY_BEAMS) if 'MSE_' + e in mse]
-    if MU_FIELDS[0] + BEAMS in mse:
-        fields += [f + BEAMS for f in MU_FIELDS]
-    if MUH_FIELDS[0] + 'perfect' in mse:
-        fields += [f + x for x in SOURCES + tuple(e for e in (BLIND, DELAY, BEAMS) if MUH_FIELDS[0] + e in mse) for f in MUH_FIELDS]
-    if MUJ_FIELDS[0] + 'perfect' in mse:
-        fields += [f + x for x in SOURCES + tuple(e for e in (BLIND, DELAY, BEAMS) if MUJ_FIELDS[0] + e in mse) for f in MUJ_FIELDS]
-    for fam in (FB_FIELDS, MUFB_FIELDS):
-        if fam[0] + 'perfect' in mse:
-            fields += [f + x for x in SOURCES + tuple(e for e in (BLIND, DELAY, BEAMS) if fam[0] + e in mse) for f in fam]
-    return fields
+    """The fields of metrics.mat that the level `mse` (evaluate_level) carries, in the order they are written (MAT_ORDER): a family
+    that an option adds stands behind every field that exists without it."""
+    return [f + x for family, sources in MAT_ORDER for x in sources for f in FAMILIES[family].fields if f + x in mse]
 
 
 def write_metrics(path, mse):
-    """metrics.mat with MSE_LS, MSE_MMSE, MSE_DNN as 1 x npkt rows: the names BER_test_maMIMO_LTF.m:653 saves and
-    snr_loop_testing.m:37-58 loads.  A level evaluated with the data phase (evaluate_level(ber=...)) also carries bers_X, EVM_rms_X
-    and dtSNR_X for X in SOURCES - with the MSE rows the names of :653 - and MSE_perfect (zeros), which are then written the same way.
-    A level evaluated with blind=True carries MSE_MMSEb (and with the data phase bers_MMSEb, EVM_rms_MMSEb, dtSNR_MMSEb): written behind
-    those.  A level evaluated with rx_estimate=True carries bersRx_X, EVM_rmsRx_X and gNMSE_X: written behind those, and MSE_DLY of a level evaluated
-    with delay=(L, pre) behind those; bersMU_X, EVM_rmsMU_X and sinrMU_X of a level evaluated with mu=... behind those; MSE_ANG, MSE_DLYANG and
-    bersMU_ANG, EVM_rmsMU_ANG, sinrMU_ANG of a level evaluated with beams=True behind those; bersMUH_X, EVM_rmsMUH_X and sinrMUH_X of a level
-    evaluated with mu_hybrid=... behind those; bersMUJ_X, EVM_rmsMUJ_X and sinrMUJ_X of a level evaluated with mu_jsdm=... behind those; bersFB_X, EVM_rmsFB_X, sinrFB_X and then
-    bersMUFB_X, EVM_rmsMUFB_X, sinrMUFB_X of a level evaluated with feedback=... last (metric_fields)."""
+    """metrics.mat with the fields of the level `mse` (metric_fields) as 1 x npkt float64 rows.  MSE_LS, MSE_MMSE, MSE_DNN and, of a
+    level evaluated with the data phase, bers_X, EVM_rms_X, dtSNR_X and MSE_perfect are the names BER_test_maMIMO_LTF.m:653 saves and
+    snr_loop_testing.m:37-58 loads; the fields of every other option follow them."""
     from scipy.io import savemat
     os.makedirs(os.path.dirname(path), exist_ok=True)
     savemat(path, {f: np.asarray(mse[f], np.float64).reshape(1, -1) for f in metric_fields(mse)})
     return path
 
 
+def _columns(result):
+    """(key of a level of sweep.json, key of evaluate_level's dict, whether the table shows it) of every row that the options recorded
+    in `result` switch on, in JSON_ORDER; a per-user record has the same key in both, is copied as it is and comes with None."""
+    def on(needs):
+        return all(result.get(k) for k in needs)
+    for name, sources in JSON_ORDER:
+        family = FAMILIES[name]
+        if not on(family.needs):
+            continue
+        if sources == USERS and family.users:
+            yield family.users, None, False
+        for x in sources:
+            if on(SOURCE_NEEDS.get(x, ())):
+                for i, (f, j) in enumerate(zip(family.fields, family.json)):
+                    if j is not None:
+                        yield j + x, f + x, i == 0
+
+
 def format_table(result):
-    blind = [BLIND] if result.get('blind') else []
-    cols = list(ESTIMATORS) + blind + ([DELAY] if result.get('delay') else []) + (['BER_' + x for x in list(SOURCES) + blind] if result.get('ber') else [])
-    cols += [RX_FIELDS[0] + x for x in list(SOURCES) + blind] if result.get('rx_estimate') else []
-    cols += [MU_FIELDS[0] + x for x in list(SOURCES) + blind + ([DELAY] if result.get('delay') else [])] if result.get('mu') else []
-    if result.get('beams'):
-        cols += [BEAMS] + ([DELAY_BEAMS] if result.get('delay') else []) + ([MU_FIELDS[0] + BEAMS] if result.get('mu') else [])
-    if result.get('mu_hybrid'):
-        cols += [MUH_FIELDS[0] + x for x in list(SOURCES) + blind + ([DELAY] if result.get('delay') else []) + ([BEAMS] if result.get('beams') else [])]
-    if result.get('mu_jsdm'):
-        cols += [MUJ_FIELDS[0] + x for x in list(SOURCES) + blind + ([DELAY] if result.get('delay') else []) + ([BEAMS] if result.get('beams') else [])]
-    if result.get('feedback'):
-        cols += [FB_FIELDS[0] + x for x in list(SOURCES) + blind]
-        if result.get('mu'):
-            cols += [MUFB_FIELDS[0] + x for x in list(SOURCES) + blind + ([DELAY] if result.get('delay') else []) + ([BEAMS] if result.get('beams') else [])]
+    cols = [key for key, _, shown in _columns(result) if shown]
     lines = ['%8s' % 'SNR dB' + ''.join('  %-38s' % (e + ': mean [CI low, CI high]') for e in cols)]
     for lv in result['levels']:
         row = '%8g' % lv['snr_db']
@@ -586,42 +547,16 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
               amp_scale=True, save_dataset=None, verbose=True, ber=None, channel=None, blind=False, rx_estimate=False,
               delay_taps=None, delay_pre=0, users=None, mu_reg='zf', user_spacing=15.0, beams=False, mu_hybrid=None, mu_jsdm=None,
               feedback=None):
-    """Training set -> models (loaded from `modeldir`, else fitted and saved into `out`) -> every level.  Writes
+    """Training set -> models (loaded from `modeldir`, else fitted and saved into `out`) -> every level (evaluate_level).  Writes
     <out>/BS<Nt>_SNR<s>/metrics.mat per level and <out>/sweep.json, prints the table, returns the result dict (with the per-packet
     arrays under 'per_packet' = {level: {'MSE_LS', ...}}).  Test packets come from the stream seed + 1, behind the index range of
-    the training packets, so no test packet repeats a training packet.  ber = dict(ns, ntrf, n_sym, bps) adds the data phase per level
-    (evaluate_level): the BER / EVM / dtSNR fields in metrics.mat and 'BER_X' columns with the same confidence interval.
-    channel (scattering_args) takes training and test packets from csi_synth_scattering; sweep.json then records its parameters under
-    'channel'.  blind=True adds the estimator MMSEb per level (evaluate_level): MSE_MMSEb in metrics.mat, a column of the table and an
-    entry per level of sweep.json, which then records 'blind': true; with `ber` also the source MMSEb.  Without it every output is
-    what it is without the argument.  rx_estimate=True (needs `ber`) adds the receiver that estimates the effective channel
-    (link_level): bersRx_X, EVM_rmsRx_X and gNMSE_X in metrics.mat and, with the same confidence interval, as the last entries per level of
-    sweep.json, which then records 'rx_estimate': true; every other field is what it is without the argument.
-    delay_taps=L (with delay_pre=P) adds the estimator DLY per level (evaluate_level(delay=(L, P))): MSE_DLY in metrics.mat, a column of
-    the table and an entry per level of sweep.json, which then records 'delay': {taps, pre, rank}; without it every output is what it
-    is without the argument.
-    users=U (U >= 2, needs `ber`) adds the multi-user data phase per level (evaluate_level(mu=...), mu_reg 'zf' or 'rzf', user_spacing in
-    degrees): bersMU_X, EVM_rmsMU_X and sinrMU_X in metrics.mat behind every other field, the same with confidence intervals and the
-    per-user arrays ('mu_users') per level of sweep.json, which then records 'mu': {users, reg, spacing}; without it every output is
-    what it is without the argument.
-    beams=True adds the estimator ANG per level (evaluate_level(beams=True)) and, with delay_taps, DLYANG: MSE_ANG / MSE_DLYANG in
-    metrics.mat behind every other field, columns of the table and entries per level of sweep.json, which then records 'beams': true;
-    with users also the source ANG of the multi-user data phase (bersMU_ANG, EVM_rmsMU_ANG, sinrMU_ANG and its per-user arrays).
-    Without it every output is what it is without the argument.
-    mu_hybrid=n_rf (needs `users`, U ns <= n_rf <= min(16, Nt, rays)) adds the multi-user data phase behind the hybrid precoder of n_rf RF
-    chains per source (evaluate_level(mu_hybrid=...)): bersMUH_X, EVM_rmsMUH_X and sinrMUH_X in metrics.mat behind every other field, the
-    same with confidence intervals and 'muh_users' (per-user arrays and chosen beams) per level of sweep.json, which then records
-    'mu_hybrid': {n_rf}; without it every output is what it is without the argument.
-    mu_jsdm={b[, r_star = 4, tol = 0.05, mode = 'pgp']} (needs `users`; ns <= b, U b <= 16, (U - 1) r_star <= Nt - b, Nt <= 64) adds the
-    multi-user data phase behind the JSDM precoder per source, every user its own group (evaluate_level(mu_jsdm=...)): bersMUJ_X,
-    EVM_rmsMUJ_X and sinrMUJ_X in metrics.mat behind every other field, the same with confidence intervals and 'muj_users' (per-user arrays,
-    mean r_g / q_g) per level of sweep.json, which then records 'mu_jsdm': {b, r_star, tol, mode}; without it every output is what it is
-    without the argument.
-    feedback={b_phi, b_psi[, ng = 1]} (needs `ber`; ns <= min(4, Nr, Nt)) puts the quantised CSI feedback between every source's estimate
-    and the transmitter (evaluate_level(feedback=...)): bersFB_X, EVM_rmsFB_X, sinrFB_X and, with `users`, bersMUFB_X, EVM_rmsMUFB_X,
-    sinrMUFB_X in metrics.mat behind every other field, the same with confidence intervals (and 'mufb_users') per level of sweep.json,
-    which then records 'feedback': {b_phi, b_psi, ng, report_bits: the bits of one packet's report}; without it every output is what it
-    is without the argument."""
+    the training packets, so no test packet repeats a training packet.  The options are those of the module's table; each is checked
+    here against what its device calls serve (U >= 2, U ns <= min(16, Nt), U <= 8; U ns <= n_rf <= min(16, Nt, rays); jsdm_problem
+    with r_star = 4, tol = 0.05, mode = 'pgp' unless given; feedback_problem with ng = 1 unless given) and recorded in sweep.json under
+    the key the table's `needs` name ('ber', 'channel': its parameters, 'blind', 'rx_estimate', 'mu': {users, reg, spacing},
+    'mu_hybrid': {n_rf}, 'mu_jsdm': {b, r_star, tol, mode}, 'feedback': {b_phi, b_psi, ng, report_bits: the bits of one packet's
+    report}, 'delay': {taps, pre, rank}, 'beams'); a level of sweep.json then holds mean and confidence interval of every field the
+    option adds, and the per-user records, in JSON_ORDER."""
     if feedback is not None:
         if ber is None:
             raise ValueError('feedback needs the data phase (ber)')
@@ -652,32 +587,19 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
         problem = jsdm_problem(mu['users'], int(ber['ns']), engine.nt, **mu_jsdm)
         if problem:
             raise ValueError('mu_jsdm: ' + problem)
+    delay = (int(delay_taps), int(delay_pre)) if delay_taps else None
     os.makedirs(out, exist_ok=True)
     result = dict(nt=engine.nt, nr=engine.nr, n_train=int(n_train), n_test=int(n_test), seed=int(seed), n_taps=int(n_taps),
                   amp_scale=bool(amp_scale), levels=[], training=None)
-    if ber is not None:
-        result['ber'] = {k: (None if v is None else int(v)) for k, v in ber.items()}
-    if channel is not None:
-        result['channel'] = dict(scattering_args(channel), model='scattering')
-    if blind:
-        result['blind'] = True
-    if rx_estimate:
-        result['rx_estimate'] = True
-    if mu:
-        result['mu'] = dict(mu)
-    if mu_hybrid:
-        result['mu_hybrid'] = dict(n_rf=mu_hybrid)
-    if mu_jsdm:
-        result['mu_jsdm'] = dict(mu_jsdm)
     if feedback:
         from . import feedback as fbm
-        result['feedback'] = dict(feedback, report_bits=fbm.report_bits(engine.nt, int(ber['ns']), feedback['b_phi'], feedback['b_psi'], feedback['ng']))
-    delay = None
-    if delay_taps:
-        delay = (int(delay_taps), int(delay_pre))
-        result['delay'] = dict(taps=delay[0], pre=delay[1], rank=int(subspace.delay_basis(*delay)[0].shape[1]))
-    if beams:
-        result['beams'] = True
+        report_bits = fbm.report_bits(engine.nt, int(ber['ns']), feedback['b_phi'], feedback['b_psi'], feedback['ng'])
+    options = dict(ber=ber and {k: (None if v is None else int(v)) for k, v in ber.items()},
+                   channel=channel is not None and dict(scattering_args(channel), model='scattering'), blind=bool(blind),
+                   rx_estimate=bool(rx_estimate), mu=mu and dict(mu), mu_hybrid=mu_hybrid and dict(n_rf=mu_hybrid), mu_jsdm=mu_jsdm and dict(mu_jsdm),
+                   feedback=feedback and dict(feedback, report_bits=report_bits),
+                   delay=delay and dict(taps=delay[0], pre=delay[1], rank=int(subspace.delay_basis(*delay)[0].shape[1])), beams=bool(beams))
+    result.update((k, v) for k, v in options.items() if v)          # an option that is off leaves no key
     if modeldir:
         load_models(engine, modeldir)
         if save_dataset:
@@ -698,54 +620,10 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
         mse = evaluate_level(engine, snr, n_test, seed + 1, n_train + i * n_test, n_taps, amp_scale, ber=ber, channel=channel, blind=blind,
                              rx_estimate=rx_estimate, delay=delay, mu=mu, beams=beams, mu_hybrid=mu_hybrid, mu_jsdm=mu_jsdm,
                              feedback=feedback)
-        sec = time.perf_counter() - t0
+        lv = dict(snr_db=float(snr), seconds=time.perf_counter() - t0)
         write_metrics(os.path.join(out, 'BS%d_SNR%g' % (engine.nt, snr), 'metrics.mat'), mse)
-        lv = dict(snr_db=float(snr), seconds=sec)
-        for e in ESTIMATORS + ((BLIND,) if blind else ()) + ((DELAY,) if delay else ()):
-            m, lo, hi = confidence_interval(mse['MSE_' + e])
-            lv[e] = dict(mean=m, ci_low=lo, ci_high=hi)
-        for x in (SOURCES + ((BLIND,) if blind else ())) if ber is not None else ():
-            m, lo, hi = confidence_interval(mse['bers_' + x])
-            lv['BER_' + x] = dict(mean=m, ci_low=lo, ci_high=hi)
-        for x in (SOURCES + ((BLIND,) if blind else ())) if rx_estimate else ():
-            for f in RX_FIELDS:
-                m, lo, hi = confidence_interval(mse[f + x])
-                lv[f + x] = dict(mean=m, ci_low=lo, ci_high=hi)
-        if mu:
-            for x in SOURCES + ((BLIND,) if blind else ()) + ((DELAY,) if delay else ()):
-                for f in MU_FIELDS:
-                    m, lo, hi = confidence_interval(mse[f + x])
-                    lv[f + x] = dict(mean=m, ci_low=lo, ci_high=hi)
-            lv['mu_users'] = mse['mu_users']
-        for e in ((BEAMS,) + ((DELAY_BEAMS,) if delay else ())) if beams else ():
-            m, lo, hi = confidence_interval(mse['MSE_' + e])
-            lv[e] = dict(mean=m, ci_low=lo, ci_high=hi)
-        for f in MU_FIELDS if (beams and mu) else ():
-            m, lo, hi = confidence_interval(mse[f + BEAMS])
-            lv[f + BEAMS] = dict(mean=m, ci_low=lo, ci_high=hi)
-        if mu_hybrid:
-            for x in SOURCES + ((BLIND,) if blind else ()) + ((DELAY,) if delay else ()) + ((BEAMS,) if beams else ()):
-                for f in MUH_FIELDS:
-                    m, lo, hi = confidence_interval(mse[f + x])
-                    lv[f + x] = dict(mean=m, ci_low=lo, ci_high=hi)
-            lv['muh_users'] = mse['muh_users']
-        if mu_jsdm:
-            for x in SOURCES + ((BLIND,) if blind else ()) + ((DELAY,) if delay else ()) + ((BEAMS,) if beams else ()):
-                for f in MUJ_FIELDS:
-                    m, lo, hi = confidence_interval(mse[f + x])
-                    lv[f + x] = dict(mean=m, ci_low=lo, ci_high=hi)
-            lv['muj_users'] = mse['muj_users']
-        if feedback:
-            for x in SOURCES + ((BLIND,) if blind else ()):
-                for f in FB_FIELDS:
-                    m, lo, hi = confidence_interval(mse[f + x])
-                    lv[f + x] = dict(mean=m, ci_low=lo, ci_high=hi)
-            if mu:
-                for x in SOURCES + ((BLIND,) if blind else ()) + ((DELAY,) if delay else ()) + ((BEAMS,) if beams else ()):
-                    for f in MUFB_FIELDS:
-                        m, lo, hi = confidence_interval(mse[f + x])
-                        lv[f + x] = dict(mean=m, ci_low=lo, ci_high=hi)
-                lv['mufb_users'] = mse['mufb_users']
+        for key, field, _ in _columns(result):
+            lv[key] = mse[key] if field is None else _interval(mse[field])
         result['levels'].append(lv)
         per_packet[float(snr)] = mse
     with open(os.path.join(out, 'sweep.json'), 'w') as f:
