@@ -84,7 +84,7 @@ RcclApi& rccl() {
 // host-side scalars of the device blobs, one record for both component models
 struct WireLayer {
     int32_t in, out, ldw, ldwb, ldwh, wshift, wshift_f, ashift, ashift_pre;
-    int32_t has_Wt, has_Wb, has_Wb_p, has_Wh, has_Wh_f, has_Wh_p, has_bias, has_bias_hs, has_scale, has_shift;
+    int32_t has[LAYER_BUFS];      // which rows of kLayerBufs the layer holds: Wt, Wb, Wb_p, Wh, Wh_f, Wh_p, bias, bias_hs, scale, shift
 };
 struct WireMeta {
     int32_t magic, n_layers;
@@ -106,28 +106,15 @@ struct WBlob {
     size_t bytes;
 };
 
-// every device buffer of a component model that csi_load_weights fills, with the size it allocates (same formulas)
-void model_blobs(const csi_config& cf, int l0_k, Model& m, const WireLayer* wl, const int32_t has_W0p, const int32_t has_W0rm, const int32_t has_conv,
-                 std::vector<WBlob>& v) {
-    const size_t slack = G_SLACK_FLOATS * sizeof(float);
-    for (size_t i = 0; i < m.layers.size(); ++i) {
-        Layer& L = m.layers[i];
-        const WireLayer& w = wl[i];
-        if (w.has_Wt) v.push_back({(void**)&L.Wt, (size_t)L.out * L.ldw * 4 + slack});
-        if (w.has_Wb) v.push_back({(void**)&L.Wb, (size_t)L.out * L.ldwb * 2 + 256});
-        if (w.has_Wb_p) v.push_back({(void**)&L.Wb_p, (size_t)256 * L.ldwb * 2 + 256});
-        if (w.has_Wh) v.push_back({(void**)&L.Wh, (size_t)L.out * L.ldwh * 2 + 4096});
-        if (w.has_Wh_f) v.push_back({(void**)&L.Wh_f, (size_t)L.out * L.ldwh * 2 + 4096});
-        if (w.has_Wh_p) v.push_back({(void**)&L.Wh_p, (size_t)256 * L.ldwh * 2 + 4096});
-        if (w.has_bias) v.push_back({(void**)&L.bias, (size_t)L.out * 4 + slack});
-        if (w.has_bias_hs) v.push_back({(void**)&L.bias_hs, (size_t)L.out * 4 + slack});
-        if (w.has_scale) v.push_back({(void**)&L.scale, (size_t)L.out * 4 + slack});
-        if (w.has_shift) v.push_back({(void**)&L.shift, (size_t)L.out * 4 + slack});
-    }
-    const size_t h1 = m.layers.empty() ? 0 : (size_t)m.layers[0].out;
-    if (has_W0p) v.push_back({(void**)&m.W0p, (size_t)cf.nt * h1 * 4 + slack});
-    if (has_W0rm) v.push_back({(void**)&m.W0rm, (size_t)l0_k * h1 * 4 + slack});
-    if (has_conv) v.push_back({(void**)&m.conv, (size_t)CONV_PRM_FLOATS * 4 + slack});
+static_assert(LAYER_BUFS == 10 && MODEL_BUFS == 3, "a new row of the buffer table changes the record: new WIRE_MAGIC");
+
+// every device buffer of a component model that csi_load_weights fills, sized by the buffer table (csi_context.hpp), in the table's order
+void model_blobs(const csi_config& cf, int l0_k, Model& m, const WireLayer* wl, const int32_t (&has)[MODEL_BUFS], std::vector<WBlob>& v) {
+    for (size_t i = 0; i < m.layers.size(); ++i)
+        for (int k = 0; k < LAYER_BUFS; ++k)
+            if (wl[i].has[k]) v.push_back({kLayerBufs[k].slot(m.layers[i]), kLayerBufs[k].payload(m.layers[i]) + kLayerBufs[k].slack});
+    for (int k = 0; k < MODEL_BUFS; ++k)
+        if (has[k]) v.push_back({kModelBufs[k].slot(m), kModelBufs[k].payload(m, cf.nt, l0_k) + kModelBufs[k].slack});
 }
 
 // ---- the protocol, transport-independent -------------------------------------------------------------------------------------
@@ -154,17 +141,14 @@ void wire_fill(const csi_ctx* c, WireMeta& w) {
         if (!w.loaded[d]) continue;
         w.hs_repr_ok[d] = m.hs_repr_ok;
         w.hs_repr_err[d] = m.hs_repr_err;
-        w.has_W0p[d] = m.W0p != nullptr;
-        w.has_W0rm[d] = m.W0rm != nullptr;
-        w.has_conv[d] = m.conv != nullptr;
+        int32_t* const has[MODEL_BUFS] = {&w.has_W0p[d], &w.has_W0rm[d], &w.has_conv[d]};
+        for (int k = 0; k < MODEL_BUFS; ++k) *has[k] = *kModelBufs[k].slot(m) != nullptr;
         for (int i = 0; i <= cf.n_hidden; ++i) {
             const Layer& L = m.layers[i];
             WireLayer& x = w.layer[d][i];
             x.in = L.in; x.out = L.out; x.ldw = L.ldw; x.ldwb = L.ldwb; x.ldwh = L.ldwh;
             x.wshift = L.wshift; x.wshift_f = L.wshift_f; x.ashift = L.ashift; x.ashift_pre = L.ashift_pre;
-            x.has_Wt = L.Wt != nullptr; x.has_Wb = L.Wb != nullptr; x.has_Wb_p = L.Wb_p != nullptr; x.has_Wh = L.Wh != nullptr; x.has_Wh_f = L.Wh_f != nullptr;
-            x.has_Wh_p = L.Wh_p != nullptr; x.has_bias = L.bias != nullptr; x.has_bias_hs = L.bias_hs != nullptr;
-            x.has_scale = L.scale != nullptr; x.has_shift = L.shift != nullptr;
+            for (int k = 0; k < LAYER_BUFS; ++k) x.has[k] = *kLayerBufs[k].slot(L) != nullptr;
         }
     }
 }
@@ -173,7 +157,7 @@ void wire_fill(const csi_ctx* c, WireMeta& w) {
 void wire_blobs(csi_ctx* c, const WireMeta& w, std::vector<WBlob>& blobs) {
     const csi_config& cf = c->cfg;
     for (int d = 0; d < 2; ++d)
-        if (w.loaded[d]) model_blobs(cf, c->l0_k, c->model[d], w.layer[d], w.has_W0p[d], w.has_W0rm[d], w.has_conv[d], blobs);
+        if (w.loaded[d]) model_blobs(cf, c->l0_k, c->model[d], w.layer[d], {w.has_W0p[d], w.has_W0rm[d], w.has_conv[d]}, blobs);
     if (w.pilot_ok && cf.nt > 0) {
         const size_t ldp = (size_t)(cf.nt + 31) / 32 * 32, slack = G_SLACK_FLOATS * sizeof(float);
         blobs.push_back({(void**)&c->P, (size_t)cf.nt * cf.nt * 4 + slack});

@@ -144,6 +144,27 @@ struct Model {
     bool hs_repr_ok = true;
 };
 
+// The ONE table of the device buffers csi_load_weights fills (prepared on the host by csi_weights.hpp): per row the pointer, the payload bytes as a function of
+// the scalars above, and the zeroed slack allocated behind the payload (256 bytes: bf16 copies, 4096: split-f16 copies, UPLOAD_SLACK: every fp32 array - the K
+// tail of a GEMM's last tile over-reads into finite memory).  The upload, free_layer / free_model, and the blobs and has[] flags of the weight broadcast
+// (csi_comm.hpp) walk it IN THIS ORDER, the order on the wire; a new weight layout is one row here plus the function in csi_weights.hpp that prepares it.
+constexpr size_t UPLOAD_SLACK = G_SLACK_FLOATS * sizeof(float);
+struct LayerBuf { const char* name; void** (*slot)(const Layer&); size_t (*payload)(const Layer&); size_t slack; };
+struct ModelBuf { const char* name; void** (*slot)(const Model&); size_t (*payload)(const Model&, int nt, int l0_k); size_t slack; };
+#define CSI_LAYER_BUF(f, bytes, slack) {#f, [](const Layer& l) { return (void**)&const_cast<Layer&>(l).f; }, [](const Layer& l) { return (size_t)(bytes); }, slack}
+#define CSI_MODEL_BUF(f, bytes) {#f, [](const Model& m) { return (void**)&const_cast<Model&>(m).f; }, \
+                                 [](const Model& m, int nt, int l0_k) { (void)m; (void)nt; (void)l0_k; return (size_t)(bytes); }, UPLOAD_SLACK}
+enum { LB_Wt, LB_Wb, LB_Wb_p, LB_Wh, LB_Wh_f, LB_Wh_p, LB_bias, LB_bias_hs, LB_scale, LB_shift, LAYER_BUFS };
+enum { MB_W0p, MB_W0rm, MB_conv, MODEL_BUFS };
+const LayerBuf kLayerBufs[LAYER_BUFS] = {
+    CSI_LAYER_BUF(Wt, (size_t)l.out * l.ldw * 4, UPLOAD_SLACK),   CSI_LAYER_BUF(Wb, (size_t)l.out * l.ldwb * 2, 256),   CSI_LAYER_BUF(Wb_p, (size_t)256 * l.ldwb * 2, 256),
+    CSI_LAYER_BUF(Wh, (size_t)l.out * l.ldwh * 2, 4096),          CSI_LAYER_BUF(Wh_f, (size_t)l.out * l.ldwh * 2, 4096), CSI_LAYER_BUF(Wh_p, (size_t)256 * l.ldwh * 2, 4096),
+    CSI_LAYER_BUF(bias, (size_t)l.out * 4, UPLOAD_SLACK),         CSI_LAYER_BUF(bias_hs, (size_t)l.out * 4, UPLOAD_SLACK),
+    CSI_LAYER_BUF(scale, (size_t)l.out * 4, UPLOAD_SLACK),        CSI_LAYER_BUF(shift, (size_t)l.out * 4, UPLOAD_SLACK)};
+#define CSI_H1(m) ((m).layers.empty() ? (size_t)0 : (size_t)(m).layers[0].out)
+const ModelBuf kModelBufs[MODEL_BUFS] = {CSI_MODEL_BUF(W0p, (size_t)nt * CSI_H1(m) * 4), CSI_MODEL_BUF(W0rm, (size_t)l0_k * CSI_H1(m) * 4),
+                                         CSI_MODEL_BUF(conv, (size_t)CONV_PRM_FLOATS * 4)};
+
 struct GraphEntry {           // one captured csi_predict_device / csi_estimate_device call
     const void* in_re; const void* in_im; void* out_re; void* out_im;
     void* h_re; void* h_im;   // LS outputs (csi_estimate_device), null for csi_predict_device
@@ -563,39 +584,22 @@ int upload(csi_ctx* c, float** dst, const float* src, size_t n) {
 }
 
 void free_layer(Layer& l) {
-    if (l.Wt) hipFree(l.Wt);
-    if (l.Wb) hipFree(l.Wb);
-    if (l.Wb_p) hipFree(l.Wb_p);
-    if (l.Wh) hipFree(l.Wh);
-    if (l.Wh_f) hipFree(l.Wh_f);
-    if (l.Wh_p) hipFree(l.Wh_p);
-    if (l.bias) hipFree(l.bias);
-    if (l.bias_hs) hipFree(l.bias_hs);
-    if (l.scale) hipFree(l.scale);
-    if (l.shift) hipFree(l.shift);
+    for (const LayerBuf& b : kLayerBufs)
+        if (*b.slot(l)) hipFree(*b.slot(l));
     l = Layer();
 }
 
 void free_model(Model& m) {
     for (auto& l : m.layers) free_layer(l);
     m.layers.clear();
-    if (m.W0p) hipFree(m.W0p);
-    if (m.W0rm) hipFree(m.W0rm);
-    m.W0rm = nullptr;
-    if (m.T) hipFree(m.T);
-    if (m.T_hs) hipFree(m.T_hs);
-    if (m.T_sw) hipFree(m.T_sw);
-    if (m.Wt1) hipFree(m.Wt1);
-    if (m.Wt2) hipFree(m.Wt2);
+    for (const ModelBuf& b : kModelBufs)
+        if (*b.slot(m)) { hipFree(*b.slot(m)); *b.slot(m) = nullptr; }
+    for (void* p : {(void*)m.T, (void*)m.T_hs, (void*)m.T_sw, (void*)m.Wt1, (void*)m.Wt2, (void*)m.l0_rowmax})
+        if (p) hipFree(p);
     m.Wt1 = m.Wt2 = nullptr;
-    m.tiled_ok = false;
-    if (m.l0_rowmax) hipFree(m.l0_rowmax);
-    if (m.conv) hipFree(m.conv);
-    m.conv = nullptr;
-    m.W0p = m.T = m.T_hs = m.T_sw = m.l0_rowmax = nullptr;
-    m.T_sw_ok = false;
+    m.T = m.T_hs = m.T_sw = m.l0_rowmax = nullptr;
     m.T_hs_shift = HS_SHIFT_AUTO;
-    m.loaded = m.table_ok = false;
+    m.loaded = m.table_ok = m.tiled_ok = m.T_sw_ok = false;
     m.hs_repr_err = 0.0;
     m.hs_repr_ok = true;
 }

@@ -11,6 +11,7 @@
 //   csi_predict_samples literal un-shared network      -> gemm_f32_kernel
 //   csi_ls_estimate*    FFT + despread                 -> ls_estimate_kernel
 #include "csi_context.hpp"
+#include "csi_weights.hpp"
 #include "csi_dnn_hs.hpp"
 #include "csi_dnn_f32.hpp"
 #include "csi_ls.hpp"
@@ -367,305 +368,36 @@ int csi_load_weights(csi_ctx* c, int model, const csi_tensor* tensors, int n) {
     if (!c) return CSI_ERR_INVALID_ARG;
     if (model < 0 || model > 1 || !tensors || n <= 0) return fail(c, CSI_ERR_INVALID_ARG, "csi_load_weights: bad argument");
     HIP_TRY(c, hipSetDevice(c->cfg.device));
-    const csi_config& cf = c->cfg;
     Model& m = c->model[model];
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     drop_graphs(c);
-    free_model(m);
-    m.layers.resize(cf.n_hidden + 1);
-    if (c->model_type == CSI_MODEL_CONV1D) {
-        // the front end (conv_frontend.hip.h): cnn1d_1 [7 taps][128 filters] + bias, then its BatchNormalization folded to scale / shift in
-        // double - q = relu(conv) * gamma / sqrt(var + eps) + (beta - mean * gamma / sqrt(var + eps))
-        const char* names[6] = {"cnn1d_1.kernel", "cnn1d_1.bias", "conv_bn.gamma", "conv_bn.beta", "conv_bn.moving_mean", "conv_bn.moving_variance"};
-        const csi_tensor* t[6];
-        for (int i = 0; i < 6; ++i) {
-            t[i] = find_tensor(tensors, n, names[i]);
-            if (!t[i] || !t[i]->data)
-                return fail(c, CSI_ERR_INVALID_ARG, "csi_load_weights: CONV1D model: missing %s (the front end needs cnn1d_1.kernel/.bias and conv_bn.gamma/.beta/.moving_mean/.moving_variance)", names[i]);
-            const int64_t want_rows = i == 0 ? CONV_TAPS : 1;
-            if ((i == 0 && (t[i]->rows != want_rows || t[i]->cols != CONV_FILTERS)) || (i > 0 && t[i]->rows * t[i]->cols != CONV_FILTERS))
-                return fail(c, CSI_ERR_INVALID_ARG, "csi_load_weights: CONV1D model: %s is [%lld,%lld], expected %s", names[i], (long long)t[i]->rows,
-                            (long long)t[i]->cols, i == 0 ? "[7,128] (7 taps x 128 filters)" : "128 values");
-        }
-        std::vector<float> prm(CONV_PRM_FLOATS);
-        for (int i = 0; i < CONV_TAPS * CONV_FILTERS; ++i) prm[i] = t[0]->data[i];
-        for (int ch = 0; ch < CONV_FILTERS; ++ch) {
-            const double sc = (double)t[2]->data[ch] / std::sqrt((double)t[5]->data[ch] + (double)cf.bn_eps);
-            prm[CONV_TAPS * CONV_FILTERS + ch] = t[1]->data[ch];
-            prm[(CONV_TAPS + 1) * CONV_FILTERS + ch] = (float)sc;
-            prm[(CONV_TAPS + 2) * CONV_FILTERS + ch] = (float)((double)t[3]->data[ch] - (double)t[4]->data[ch] * sc);
-        }
-        const int64_t ldw0 = ((int64_t)c->d_in + G_BK - 1) / G_BK * G_BK;
-        if (ldw0 * cf.hidden[0] >= ((int64_t)1 << 31))
-            return fail(c, CSI_ERR_INVALID_ARG, "csi_load_weights: CONV1D model: fc_dense0 holds %lld x %d weights, at or above 2^31 elements (the layer-0 kernels "
-                        "index it with 32-bit element offsets); a narrower hidden[0] or a smaller len_ltf", (long long)ldw0, cf.hidden[0]);
-        int rc = upload(c, &m.conv, prm.data(), prm.size());
-        if (rc) return rc;
+    free_model(m);                          // before the tensors are looked at: a refused load leaves the model unloaded
+    const WeightFacts facts{c->cfg, c->d_in, c->l0_k, c->model_type, c->input_pool}; PreparedModel pm;
+    // upload by the table (csi_context.hpp; T, T_hs, T_sw, Wt1, Wt2, l0_rowmax are derived on the device and not in it): payload + slack allocated and zeroed, the payload copied
+    auto put = [&](void** dst, const HostBuf& b, size_t payload, size_t slack, const char* name) {
+        if (!b.data) return (int)CSI_OK;
+        if (b.bytes != payload) return fail(c, CSI_ERR_INVALID_ARG, "csi_load_weights: internal - %s prepared as %zu bytes, %zu in the buffer table", name, b.bytes, payload);
+        if (hipMalloc(dst, payload + slack) != hipSuccess) { *dst = nullptr; return fail(c, CSI_ERR_NOMEM, "device allocation of %zu bytes failed", payload + slack); }
+        HIP_TRY(c, hipMemset(*dst, 0, payload + slack));
+        HIP_TRY(c, hipMemcpy(*dst, b.data, payload, hipMemcpyHostToDevice));
+        return (int)CSI_OK;
+    };
+    m.layers.resize(c->cfg.n_hidden + 1);
+    for (int li = 0; li <= c->cfg.n_hidden; ++li) {
+        const int bad = prepare_layer(facts, tensors, n, li, pm);
+        m.hs_repr_err = pm.hs_repr_err;         // as measured so far, also when this layer is refused ("hs_weight_err_e12")
+        if (bad) return fail(c, bad, "%s", pm.err.c_str());
+        Layer& L = m.layers[li] = pm.layer;
+        for (int k = 0; k < LAYER_BUFS; ++k)
+            if (int rc = put(kLayerBufs[k].slot(L), pm.lbuf[k], kLayerBufs[k].payload(L), kLayerBufs[k].slack, kLayerBufs[k].name)) return rc;
     }
-    int fan_in = c->d_in;
-    std::vector<float> prev_shift;          // BN shift of the previous layer (split engine: folded into this layer's bias)
-    std::vector<float> prev_scale;          // BN scale of the previous layer (split engine, layer 1 only: folded into the split weights)
-    for (int li = 0; li <= cf.n_hidden; ++li) {
-        const bool reg = li == cf.n_hidden;
-        const std::string base = reg ? std::string("fc_regressor") : "fc_dense" + std::to_string(li);
-        const int out = reg ? cf.n_out : cf.hidden[li];
-        const csi_tensor* k = find_tensor(tensors, n, base + ".kernel");
-        const csi_tensor* b = find_tensor(tensors, n, base + ".bias");
-        if (!k || !b || !k->data || !b->data) return fail(c, CSI_ERR_INVALID_ARG, "csi_load_weights: missing %s.kernel/.bias", base.c_str());
-        if (li == 0 && cf.nt > 0 && k->rows != fan_in && k->cols == out)
-            return fail(c, CSI_ERR_INVALID_ARG, "csi_load_weights: %s.kernel is [%lld,%lld], expected [%d,%d] (%s model, input pooling %s: %d LTF rows + %d pilot rows)%s",
-                        base.c_str(), (long long)k->rows, (long long)k->cols, fan_in, out, model_type_name(c->model_type), input_pool_name(c->input_pool), c->l0_k, cf.nt,
-                        k->rows == (int64_t)64 * cf.len_ltf + cf.nt ? " - a CONV1D model: csi_set_model_type(CONV1D) first" :
-                        k->rows == (int64_t)cf.len_ltf / 2 + cf.nt ? " - a decimated model: csi_set_input_pool(max | avg) first" :
-                        (k->rows == (int64_t)cf.len_ltf + cf.nt ? (c->model_type == CSI_MODEL_CONV1D ? " - an FC model: csi_set_model_type(FC)" : " - a model without pooling: csi_set_input_pool(none)") : ""));
-        if (k->rows != fan_in || k->cols != out || b->rows * b->cols != out)
-            return fail(c, CSI_ERR_INVALID_ARG, "csi_load_weights: %s.kernel is [%lld,%lld], expected [%d,%d]", base.c_str(),
-                        (long long)k->rows, (long long)k->cols, fan_in, out);
-        Layer& L = m.layers[li];
-        L.in = fan_in;
-        L.out = out;
-        // transpose [in][out] -> [out][ldw] (K-major, K zero-padded to a multiple of the k-tile) on
-        // the host, blocked for cache friendliness
-        L.ldw = (fan_in + G_BK - 1) / G_BK * G_BK;
-        std::vector<float> wt((size_t)out * L.ldw, 0.f);
-        const int TB = 32;
-        for (int i0 = 0; i0 < fan_in; i0 += TB)
-            for (int o0 = 0; o0 < out; o0 += TB)
-                for (int i = i0; i < std::min(fan_in, i0 + TB); ++i)
-                    for (int o = o0; o < std::min(out, o0 + TB); ++o) wt[(size_t)o * L.ldw + i] = k->data[(size_t)i * out + o];
-        int rc = CSI_OK;
-        const bool bf16 = cf.dtype == CSI_DTYPE_BF16;
-        auto rne = [](float f) {                       // fp32 -> bf16, round to nearest even
-            uint32_t u;
-            std::memcpy(&u, &f, 4);
-            u += 0x7fffu + ((u >> 16) & 1u);
-            return (uint16_t)(u >> 16);
-        };
-        if (bf16) {
-            L.ldwb = (fan_in + B_BK - 1) / B_BK * B_BK;
-            std::vector<uint16_t> wb((size_t)out * L.ldwb, 0);
-            // bf16 mode: the BatchNormalization of the previous layer lives in THIS layer's operands,
-            //     (relu(z) sc + sh) W + b  =  relu(z) (diag(sc) W) + (b + sh W),
-            // scaled rows rounded once, the shift product kept in fp32 in the bias below - so every hidden activation is
-            // bf16(relu(z)) and the kernels that build or read it carry no per-column affine (the fused first per-pair
-            // layer generated its A operand slower than the matrix cores consumed it)
-            for (int o = 0; o < out; ++o)
-                for (int i = 0; i < fan_in; ++i) {
-                    const float w = wt[(size_t)o * L.ldw + i];
-                    wb[(size_t)o * L.ldwb + i] = rne(prev_scale.empty() ? w : (float)((double)w * (double)prev_scale[i]));
-                }
-            const size_t bytes = wb.size() * 2 + 256;
-            if (hipMalloc((void**)&L.Wb, bytes) != hipSuccess) return fail(c, CSI_ERR_NOMEM, "weight allocation failed");
-            HIP_TRY(c, hipMemset(L.Wb, 0, bytes));
-            HIP_TRY(c, hipMemcpy(L.Wb, wb.data(), wb.size() * 2, hipMemcpyHostToDevice));
-            if (reg && li == 2 && cf.nt > 0 && out <= 256) {
-                // the regressor behind ONE per-pair layer: a copy for the fused band kernel - 256 rows (rows >= out zero), k
-                // permuted inside every group of 16 so that a lane's stage-1 accumulators are its stage-2 operand
-                std::vector<uint16_t> wp((size_t)256 * L.ldwb, 0);
-                for (int o = 0; o < out; ++o)
-                    for (int i = 0; i < L.ldwb; ++i) wp[(size_t)o * L.ldwb + i] = wb[(size_t)o * L.ldwb + (i & ~15) + hs_band_kperm(i & 15)];
-                const size_t pbytes = wp.size() * 2 + 256;
-                if (hipMalloc((void**)&L.Wb_p, pbytes) != hipSuccess) return fail(c, CSI_ERR_NOMEM, "weight allocation failed");
-                HIP_TRY(c, hipMemset(L.Wb_p, 0, pbytes));
-                HIP_TRY(c, hipMemcpy(L.Wb_p, wp.data(), wp.size() * 2, hipMemcpyHostToDevice));
-            }
-        } else {
-            rc = upload(c, &L.Wt, wt.data(), wt.size());
-            if (rc) return rc;
-            // split-f16 copy for gemm_hs.hip.h: W * 2^wshift (largest magnitude in [2^12, 2^13)) as
-            // hi + lo halves in groups of 16 k-columns; layer 0 keeps its LTF columns only (the pilot
-            // rows live in the table T)
-            const int kh = (li == 0 && cf.nt > 0) ? c->l0_k : fan_in;
-            // layer 1 (the first per-pair layer; the regressor when there is one hidden layer) on the shared-layer-0
-            // path: the pair kernel generates A = relu(L0 + T) without bn0, so bn0's scale multiplies the rows of
-            // this copy - (relu(z) sc) W = relu(z) (diag(sc) W) - and bn0's shift sits in bias_hs below
-            const bool fold_scale = li == 1 && cf.nt > 0 && !prev_scale.empty();
-            auto wv = [&](int o, int i) {
-                const float w = wt[(size_t)o * L.ldw + i];
-                return fold_scale ? (float)((double)w * (double)prev_scale[i]) : w;
-            };
-            float wmax = 0.f;
-            for (int o = 0; o < out; ++o)
-                for (int i = 0; i < kh; ++i) wmax = std::max(wmax, std::fabs(wv(o, i)));
-            int e = 0;
-            if (wmax > 0.f && std::isfinite(wmax)) std::frexp(wmax, &e);
-            L.wshift = std::max(-40, std::min(40, 13 - e));
-            const float ws = std::ldexp(1.f, L.wshift);
-            L.ldwh = 2 * ((kh + HS_G - 1) / HS_G * HS_G);
-            std::vector<uint16_t> wh((size_t)out * L.ldwh, 0);
-            // representation error of this split copy: worst OUTPUT ROW, ||x_o - (hi + lo)_o|| / ||x_o|| (a whole-matrix norm would be
-            // carried by the very outlier that causes the damage: the scale follows max |w|, the rows far below it lose their lo halves)
-            double e_worst = 0.0;
-            for (int o = 0; o < out; ++o) {
-                double e_num = 0.0, e_den = 0.0;
-                for (int i = 0; i < kh; ++i) {
-                    const float x = wv(o, i) * ws;
-                    const _Float16 hi = (_Float16)x;
-                    const _Float16 lo = (_Float16)(x - (float)hi);
-                    uint16_t* d = &wh[(size_t)o * L.ldwh + (i >> 4) * 32 + (i & 15)];
-                    std::memcpy(d, &hi, 2);
-                    std::memcpy(d + 16, &lo, 2);
-                    const double r = (double)x - ((double)(float)hi + (double)(float)lo);
-                    e_num += r * r;
-                    e_den += (double)x * (double)x;
-                }
-                if (e_den > 0.0 && std::isfinite(e_den)) e_worst = std::max(e_worst, std::sqrt(e_num / e_den));
-                else if (!std::isfinite(e_den)) e_worst = 1.0;
-            }
-            m.hs_repr_err = std::max(m.hs_repr_err, e_worst);
-            const size_t hbytes = wh.size() * 2 + 4096;
-            if (hipMalloc((void**)&L.Wh, hbytes) != hipSuccess) return fail(c, CSI_ERR_NOMEM, "weight allocation failed");
-            HIP_TRY(c, hipMemset(L.Wh, 0, hbytes));
-            HIP_TRY(c, hipMemcpy(L.Wh, wh.data(), wh.size() * 2, hipMemcpyHostToDevice));
-            if (reg && li == 2 && cf.nt > 0 && !prev_scale.empty()) {
-                // the regressor behind ONE per-pair layer (the shipped 2-hidden-layer network): a second copy with that
-                // layer's BN scale folded into the rows, for the kernel that runs the regressor behind the pair layer
-                // without h2 leaving the CU (gemm_hs.hip.h: hs_fused_regressor); the unfused path keeps Wh
-                float fmax = 0.f;
-                for (int o = 0; o < out; ++o)
-                    for (int i = 0; i < kh; ++i) fmax = std::max(fmax, std::fabs((float)((double)wt[(size_t)o * L.ldw + i] * (double)prev_scale[i])));
-                int ef = 0;
-                if (fmax > 0.f && std::isfinite(fmax)) std::frexp(fmax, &ef);
-                L.wshift_f = std::max(-40, std::min(40, 13 - ef));
-                const float wsf = std::ldexp(1.f, L.wshift_f);
-                std::fill(wh.begin(), wh.end(), 0);
-                double f_worst = 0.0;
-                for (int o = 0; o < out; ++o) {
-                    double f_num = 0.0, f_den = 0.0;
-                    for (int i = 0; i < kh; ++i) {
-                        const float x = (float)((double)wt[(size_t)o * L.ldw + i] * (double)prev_scale[i]) * wsf;
-                        const _Float16 hi = (_Float16)x;
-                        const _Float16 lo = (_Float16)(x - (float)hi);
-                        uint16_t* d = &wh[(size_t)o * L.ldwh + (i >> 4) * 32 + (i & 15)];
-                        std::memcpy(d, &hi, 2);
-                        std::memcpy(d + 16, &lo, 2);
-                        const double r = (double)x - ((double)(float)hi + (double)(float)lo);
-                        f_num += r * r;
-                        f_den += (double)x * (double)x;
-                    }
-                    if (f_den > 0.0 && std::isfinite(f_den)) f_worst = std::max(f_worst, std::sqrt(f_num / f_den));
-                    else if (!std::isfinite(f_den)) f_worst = 1.0;
-                }
-                m.hs_repr_err = std::max(m.hs_repr_err, f_worst);
-                if (hipMalloc((void**)&L.Wh_f, hbytes) != hipSuccess) return fail(c, CSI_ERR_NOMEM, "weight allocation failed");
-                HIP_TRY(c, hipMemset(L.Wh_f, 0, hbytes));
-                HIP_TRY(c, hipMemcpy(L.Wh_f, wh.data(), wh.size() * 2, hipMemcpyHostToDevice));
-                if (out <= 256) {
-                    // ... and the form the fused band kernel reads: 256 rows, k permuted inside every group of 16 so that a
-                    // lane's stage-1 accumulator registers are its stage-2 operand (gemm_hs_band.hip.h)
-                    std::vector<uint16_t> wp((size_t)256 * L.ldwh, 0);
-                    for (int o = 0; o < out; ++o)
-                        for (int g16 = 0; g16 < L.ldwh / 32; ++g16)
-                            for (int pos = 0; pos < 16; ++pos) {
-                                const size_t src = (size_t)o * L.ldwh + (size_t)g16 * 32 + hs_band_kperm(pos);
-                                const size_t dst = (size_t)o * L.ldwh + (size_t)g16 * 32 + pos;
-                                wp[dst] = wh[src];
-                                wp[dst + 16] = wh[src + 16];
-                            }
-                    const size_t pbytes = wp.size() * 2 + 4096;
-                    if (hipMalloc((void**)&L.Wh_p, pbytes) != hipSuccess) return fail(c, CSI_ERR_NOMEM, "weight allocation failed");
-                    HIP_TRY(c, hipMemset(L.Wh_p, 0, pbytes));
-                    HIP_TRY(c, hipMemcpy(L.Wh_p, wp.data(), wp.size() * 2, hipMemcpyHostToDevice));
-                }
-            }
-        }
-        if (bf16 && li >= 1 && !prev_shift.empty()) {
-            std::vector<float> bf(out);
-            for (int o = 0; o < out; ++o) {
-                double acc = b->data[o];
-                for (int i = 0; i < fan_in; ++i) acc += (double)prev_shift[i] * (double)k->data[(size_t)i * out + o];
-                bf[o] = (float)acc;
-            }
-            rc = upload(c, &L.bias, bf.data(), out);
-        } else {
-            rc = upload(c, &L.bias, b->data, out);
-        }
-        if (rc) return rc;
-        if (!bf16 && li >= 1) {
-            // split engine: the previous layer's BatchNormalization shift moves into this layer's bias,
-            //     (relu(z) sc + sh) W + b  =  (relu(z) sc) W + (b + sh W),
-            // so that the A operand keeps the exact zeros of the relu (about half of it) - the f16 matrix
-            // pipe is power-bound and runs ~5 % faster on such operands
-            std::vector<float> bf(out);
-            for (int o = 0; o < out; ++o) {
-                double acc = b->data[o];
-                if (!prev_shift.empty())
-                    for (int i = 0; i < fan_in; ++i) acc += (double)prev_shift[i] * (double)k->data[(size_t)i * out + o];
-                bf[o] = (float)acc;
-            }
-            rc = upload(c, &L.bias_hs, bf.data(), out);
-            if (rc) return rc;
-        }
-        std::vector<float> sc(out, 1.f), sh(out, 0.f);
-        if (!reg && cf.use_bn) {
-            const std::string bn = "bn" + std::to_string(li);
-            const csi_tensor* ga = find_tensor(tensors, n, bn + ".gamma");
-            const csi_tensor* be = find_tensor(tensors, n, bn + ".beta");
-            const csi_tensor* mu = find_tensor(tensors, n, bn + ".moving_mean");
-            const csi_tensor* va = find_tensor(tensors, n, bn + ".moving_variance");
-            if (!ga || !be || !mu || !va) return fail(c, CSI_ERR_INVALID_ARG, "csi_load_weights: missing %s.* (use_bn=1)", bn.c_str());
-            for (const csi_tensor* t : {ga, be, mu, va})
-                if (!t->data || t->rows * t->cols != out)
-                    return fail(c, CSI_ERR_INVALID_ARG, "csi_load_weights: %s.* must have %d elements", bn.c_str(), out);
-            for (int o = 0; o < out; ++o) {
-                // keras non-fused inference: inv = rsqrt(var + eps) * gamma; y = x*inv + (beta - mean*inv)
-                const float inv = (1.0f / std::sqrt(va->data[o] + cf.bn_eps)) * ga->data[o];
-                sc[o] = inv;
-                sh[o] = be->data[o] - mu->data[o] * inv;
-            }
-            // split-f16 engine: scale of the activations this layer hands on.  Where the next kernel reads relu * scale
-            // (BatchNormalization output minus its shift; Layer::ashift): beta + gamma * (standardised relu) is bounded
-            // by |beta| + 6 |gamma| at six moving standard deviations.  Where it reads the bare relu because the scale
-            // sits in the next layer's weights (layer 0 on the shared path, the pair layer in front of the fused
-            // regressor; Layer::ashift_pre): moving_mean + 6 moving standard deviations.  The bound is put at
-            // 2^10..2^11 - 32x of head room for outliers before the range guard takes over, and values down to
-            // 2^-13 of the bound keep a normal lo half
-            float amax = 0.f, amax_pre = 0.f;
-            for (int o = 0; o < out; ++o) {
-                amax = std::max(amax, std::fabs(be->data[o]) + 6.f * std::fabs(ga->data[o]));
-                amax_pre = std::max(amax_pre, std::fabs(mu->data[o]) + 6.f * std::sqrt(std::max(va->data[o], 0.f) + cf.bn_eps));
-            }
-            auto shift_for = [](float bound, int dflt) {
-                int ea = 0;
-                if (!(bound > 0.f) || !std::isfinite(bound)) return dflt;
-                std::frexp(bound, &ea);
-                return std::max(-8, std::min(14, 11 - ea));
-            };
-            L.ashift = shift_for(amax, L.ashift);
-            L.ashift_pre = shift_for(amax_pre, L.ashift_pre);
-        }
-        if (!reg) {
-            // bf16 mode: identity here, the real vectors went into the next layer (above)
-            const std::vector<float> one(out, 1.f), zero(out, 0.f);
-            rc = upload(c, &L.scale, bf16 ? one.data() : sc.data(), out);
-            if (rc) return rc;
-            rc = upload(c, &L.shift, bf16 ? zero.data() : sh.data(), out);
-            if (rc) return rc;
-        }
-        if (li == 0 && cf.nt > 0) {
-            // pilot rows of fc_dense0.kernel, [nt][h1] row-major as stored (bf16 mode: rounded like
-            // every other weight, the table itself is evaluated in fp32)
-            std::vector<float> w0p(k->data + (size_t)c->l0_k * out, k->data + (size_t)(c->l0_k + cf.nt) * out);
-            if (bf16)
-                for (float& v : w0p) { const uint32_t u = (uint32_t)rne(v) << 16; std::memcpy(&v, &u, 4); }
-            rc = upload(c, &m.W0p, w0p.data(), w0p.size());
-            if (rc) return rc;
-            if (!bf16) {
-                rc = upload(c, &m.W0rm, k->data, (size_t)c->l0_k * out);
-                if (rc) return rc;
-            }
-        }
-        prev_shift = sh;
-        prev_scale = sc;
-        fan_in = out;
-    }
-    m.loaded = true;
-    m.table_ok = false;
-    if (cf.dtype == CSI_DTYPE_F32) {
+    for (int k = 0; k < MODEL_BUFS; ++k)
+        if (int rc = put(kModelBufs[k].slot(m), pm.mbuf[k], kModelBufs[k].payload(m, c->cfg.nt, c->l0_k), kModelBufs[k].slack, kModelBufs[k].name)) return rc;
+    m.loaded = true, m.table_ok = false;
+    if (c->cfg.dtype == CSI_DTYPE_F32) {
         m.hs_repr_ok = m.hs_repr_err <= 0x1p-20;
-        // not an error: the fp32 MFMA kernels serve such a model.  It is reported through the counters "hs_weight_pins" /
-        // "hs_weight_err_e12" (include/csi_mamimo.h), never through csi_last_error: a successful call leaves no error text behind
-        // 
+        // not an error: the fp32 MFMA kernels serve such a model.  It is reported through the counters "hs_weight_pins" / "hs_weight_err_e12"
+        // (include/csi_mamimo.h), never through csi_last_error: a successful call leaves no error text behind
         if (!m.hs_repr_ok) ++c->hs_weight_pins;
     }
     return build_pilot_table(c, m);
@@ -1559,7 +1291,7 @@ int csi_train_end(csi_ctx* c, int model, int commit) {
         };
         for (int li = 0; li <= cf.n_hidden; ++li) {
             const auto& l = t->layers[li];
-            const std::string base = li == cf.n_hidden ? std::string("fc_regressor") : "fc_dense" + std::to_string(li);
+            const std::string base = layer_tensor_base(cf, li);
             add(base + ".kernel", l.in, l.out);
             add(base + ".bias", 1, l.out);
             if (li < cf.n_hidden && cf.use_bn)

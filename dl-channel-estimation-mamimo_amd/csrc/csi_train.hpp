@@ -13,6 +13,7 @@
 // kernels of train.hip.h.  csi_train_end(commit) hands the tensors back through csi_load_weights.
 #pragma once
 #include "csi_context.hpp"
+#include "csi_weights.hpp"
 #include "csi_dnn_f32.hpp"
 #include "train.hip.h"
 
@@ -516,7 +517,7 @@ int tr_begin(csi_ctx* c, int model, const csi_train_config* tc, const csi_tensor
     // ---- initial values
     for (int li = 0; li <= nh; ++li) {
         auto& l = t->layers[li];
-        const std::string base = li == nh ? std::string("fc_regressor") : "fc_dense" + std::to_string(li);
+        const std::string base = layer_tensor_base(cf, li);
         if (n > 0) {
             const csi_tensor* k = find_tensor(tensors, n, base + ".kernel");
             const csi_tensor* b = find_tensor(tensors, n, base + ".bias");

@@ -6,7 +6,7 @@
 //   * hipEventRecord marks a position; hipStreamWaitEvent makes a stream wait for the position recorded at call time;
 //     hipEventSynchronize / hipStreamSynchronize / hipDeviceSynchronize block the caller - the happens-before edges HIP guarantees;
 //   * "device" and pinned memory are host memory; hipMalloc fills a buffer with a pattern derived from a global counter, so that two
-//     allocations never look alike by accident;
+//     allocations never look alike by accident; mock::g_live counts the hipMalloc'ed buffers not yet given to hipFree;
 //   * kernel launches go to a hook when it is set (hipLaunchKernel: mock::launch_hook; hipModuleLaunchKernel: mock::module_launch_hook,
 //     which gets the NAME the function was looked up by and the HIP_LAUNCH_PARAM argument record) and are otherwise counted and
 //     dropped - a harness of host logic does not need what the kernels compute; mock::launch_shape_hook sees every hipLaunchKernel with
@@ -96,7 +96,7 @@ struct Event {
 inline std::mutex g_mu;
 inline std::set<Stream*> g_streams;
 inline std::map<const char*, size_t> g_pinned;          // base -> bytes
-inline std::atomic<long> g_copies{0}, g_peer_copies{0}, g_waits{0}, g_launches{0}, g_allocs{0};
+inline std::atomic<long> g_copies{0}, g_peer_copies{0}, g_waits{0}, g_launches{0}, g_allocs{0}, g_live{0};
 inline int n_devices = 8;
 inline thread_local hipError_t last_error = hipSuccess;      // what hipGetLastError returns and clears
 inline thread_local long fail_alloc_in = -1;        // > 0: the n-th hipMalloc of THIS thread from now on fails (out of memory), once
@@ -226,12 +226,14 @@ hipError_t hipMalloc(void** p, size_t n) {
     const size_t bytes = (n + 255) / 256 * 256;
     *p = std::aligned_alloc(256, bytes ? bytes : 256);
     if (!*p) return hipErrorOutOfMemory;
+    ++mock::g_live;
     const unsigned seed = (unsigned)(++mock::g_allocs) * 2654435761u;
     unsigned* w = static_cast<unsigned*>(*p);
     for (size_t i = 0; i < bytes / 4; ++i) w[i] = seed + (unsigned)i * 40503u;
     return hipSuccess;
 }
 hipError_t hipFree(void* p) {
+    if (p) --mock::g_live;
     std::free(p);
     return hipSuccess;
 }

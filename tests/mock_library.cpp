@@ -178,6 +178,26 @@ int64_t csi_mock_pilot_buffer(csi_ctx* c, int which, const void** ptr) {
     *ptr = p[which];
     return (int64_t)bytes[which];
 }
+// what csi_load_weights left on the "device" (tests/test_weight_prep_host.py): the index-th buffer of the loaded models in the order of
+// wire_blobs, the pilot buffers left out; returns its bytes WITH the slack behind the payload (-1: no such buffer) and the address in *ptr
+int64_t csi_mock_weight_blob(csi_ctx* c, int index, const void** ptr) {
+    WireMeta w;
+    wire_fill(c, w);
+    w.pilot_ok = 0;
+    std::vector<WBlob> blobs;
+    wire_blobs(c, w, blobs);
+    if (index < 0 || index >= (int)blobs.size()) return -1;
+    *ptr = *blobs[index].p;
+    return (int64_t)blobs[index].bytes;
+}
+// the record wire_fill makes of the context - every host-side scalar of the loaded models - into buf; returns the bytes it needs
+int64_t csi_mock_wire_meta(csi_ctx* c, void* buf, int64_t cap) {
+    WireMeta w;
+    wire_fill(c, w);
+    if (buf && cap >= (int64_t)sizeof w) std::memcpy(buf, &w, sizeof w);
+    return (int64_t)sizeof w;
+}
+int64_t csi_mock_live_allocs(void) { return mock::g_live; }      // hipMalloc'ed buffers of the process not yet freed
 // the log as text into buf (at most cap bytes incl. the terminator); returns the bytes the whole text needs
 int64_t csi_mock_band_log_read(csi_ctx* c, char* buf, int64_t cap) {
     std::string text;
