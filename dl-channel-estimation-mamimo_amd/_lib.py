@@ -106,6 +106,8 @@ SYMBOLS = {
                                                    ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int] + [_vp] * 13),
     'csi_feedback_compress_device': (ctypes.c_int, [_ctx, _vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [_vp] * 7),
     'csi_feedback_expand_device': (ctypes.c_int, [_ctx] + [_vp] * 5 + [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp]),
+    'csi_rx_combiner_device': (ctypes.c_int, [_ctx, _vp, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, _vp]),
+    'csi_rx_apply_combiner_device': (ctypes.c_int, [_ctx, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp]),
     'csi_capture_begin': (ctypes.c_int, [_ctx]),
     'csi_capture_end': (ctypes.c_int, [_ctx, ctypes.POINTER(ctypes.c_void_p)]),
     'csi_capture_launch': (ctypes.c_int, [_ctx, _vp]),

@@ -32,6 +32,7 @@
 #include "mu_hybrid.hip.h"
 #include "mu_jsdm.hip.h"
 #include "feedback.hip.h"
+#include "rx_combine.hip.h"
 
 using namespace csi;
 
@@ -76,6 +77,8 @@ enum KernelId {
     K_MU_JSDM_BASEBAND,  // multi-user JSDM precoder: zero forcing on the effective channel B Frf per (packet, subcarrier), per group or jointly
     K_FB_COMPRESS,       // quantised CSI feedback (feedback.hip.h): singular vectors, Givens angles and codes per (packet, reported carrier)
     K_FB_EXPAND,         // quantised CSI feedback: the report expanded into precoder or CSI planes per (packet, carrier)
+    K_RX_COMBINER,       // receive combining (rx_combine.hip.h): the U^H combiner of a CSI estimate per (packet, carrier); placed like K_SUBSPACE_SMOOTH
+    K_RX_COMBINE,        // receive combining: E = C H on CSI planes, streaming
     K_BEAM_POWER,        // beam-space smoother (csi_beam_*, beam_smooth.hip.h): beam power E per (packet, rx, beam); placed like K_SUBSPACE_SMOOTH
     K_BEAM_SMOOTH,       // beam-space smoother: y = A diag(w) A^H x across the Tx antennas
     K_SYNTH_SCATTERING,  // known-channel sounding packets of the scattering channel (synth_scattering.hip.h): the power pass and the packet pass of csi_synth_scattering
@@ -89,7 +92,7 @@ const char* const kKernelNames[K_COUNT] = {
     "ls_estimate", "naive_dense0_gemm", "synth_white", "pilot_table", "cast_bf16", "pair_h1_bf16", "lmmse_levinson",
     "train_gemm", "train_elementwise", "nmse_links", "pair_dense_tail", "input_pool", "conv_frontend",
     "hybrid_svd", "hybrid_corr_argmax", "hybrid_solve", "hybrid_finish", "synth_structured", "link_txrx", "link_viterbi",
-    "subspace_smooth", "mu_precoder", "mu_txrx", "mu_beam_score", "mu_beam_select", "mu_hybrid_precoder", "mu_cov", "mu_jsdm_eig", "mu_jsdm_baseband", "fb_compress", "fb_expand", "beam_power", "beam_smooth", "synth_scattering", "lmmse_null_noise", "lmmse_freq_corr", "lmmse_blind"};
+    "subspace_smooth", "mu_precoder", "mu_txrx", "mu_beam_score", "mu_beam_select", "mu_hybrid_precoder", "mu_cov", "mu_jsdm_eig", "mu_jsdm_baseband", "fb_compress", "fb_expand", "rx_combiner", "rx_combine", "beam_power", "beam_smooth", "synth_scattering", "lmmse_null_noise", "lmmse_freq_corr", "lmmse_blind"};
 
 thread_local std::string g_create_error;
 
@@ -290,6 +293,8 @@ struct csi_ctx {
     int fb_tab_bphi = 0, fb_tab_bpsi = 0;
     size_t fb_lds_attr[2] = {};  // dynamic-LDS limit already raised for its compress / expand kernel
     int64_t feedback_launches = 0;   // "feedback_launches": kernels launched by csi_feedback_compress_device / csi_feedback_expand_device
+    size_t rxc_lds_attr = 0;     // receive combining (csi_rx_combine.hpp): dynamic-LDS limit already raised for its combiner kernel
+    int64_t combine_launches = 0;    // "combine_launches": kernels launched by csi_rx_combiner_device / csi_rx_apply_combiner_device
     int64_t link_launches = 0;   // "link_launches": kernels launched by csi_link_sim_device / csi_viterbi_decode_device
     bool user_capture = false;   // between csi_capture_begin and csi_capture_end (csi_hybrid.hpp): device-pointer calls are recorded, not run
     bool user_capture_use_graph = false;

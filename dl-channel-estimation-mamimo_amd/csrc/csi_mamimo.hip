@@ -30,6 +30,7 @@
 #include "csi_mu_hybrid.hpp"
 #include "csi_mu_jsdm.hpp"
 #include "csi_feedback.hpp"
+#include "csi_rx_combine.hpp"
 #include <initializer_list>
 
 namespace {
@@ -853,6 +854,19 @@ int csi_feedback_expand_device(csi_ctx* c, const uint16_t* d_phi_code, const uin
     return feedback_expand_device(c, d_phi_code, d_psi_code, d_phi, d_psi, d_sigma, npkt, nc, b_phi, b_psi, ng, layout, d_out_re, d_out_im);
 }
 
+// ---------------------------------------------------------------- receive combining (csi_rx_combine.hpp, rx_combine.hip.h)
+int csi_rx_combiner_device(csi_ctx* c, const float* d_hest_re, const float* d_hest_im, int64_t npkt, int ns, float* d_c_re, float* d_c_im,
+                           float* d_sigma) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return rx_combiner_device(c, d_hest_re, d_hest_im, npkt, ns, d_c_re, d_c_im, d_sigma);
+}
+
+int csi_rx_apply_combiner_device(csi_ctx* c, const float* d_c_re, const float* d_c_im, const float* d_h_re, const float* d_h_im, int64_t npkt,
+                                 int ns, float* d_e_re, float* d_e_im) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return rx_apply_combiner_device(c, d_c_re, d_c_im, d_h_re, d_h_im, npkt, ns, d_e_re, d_e_im);
+}
+
 // ---------------------------------------------------------------- accuracy metric
 int csi_nmse_device(csi_ctx* c, const float* d_ref_re, const float* d_ref_im, const float* d_est_re, const float* d_est_im,
                     int64_t nlinks, int n_bins, float* d_per_link, double* mean_out) {
@@ -925,6 +939,7 @@ int csi_get_option(csi_ctx* c, const char* name, int64_t* value) {
     else if (n == "beam_launches") *value = c->beam_launches;
     else if (n == "mu_launches") *value = c->mu_launches;
     else if (n == "feedback_launches") *value = c->feedback_launches;
+    else if (n == "combine_launches") *value = c->combine_launches;
     else if (n == "lmmse_blind_fallbacks") {
         // counted on the device behind every launch (lmmse_blind_count_kernel): reading it waits for the stream
         if (c->user_capture) return fail(c, CSI_ERR_INVALID_ARG, "csi_get_option: lmmse_blind_fallbacks cannot be read while a capture is open");

@@ -1173,6 +1173,59 @@ class CsiEngine:
                 if a is not None:
                     a.free()
 
+    # ------------------------------------------------------------------ receive combining (csrc/rx_combine.hip.h)
+    def rx_combiner_device(self, d_hest_re, d_hest_im, npkt, ns, d_c_re, d_c_im, d_sigma=None):
+        """The U^H combiner of the planes d_hest_re / d_hest_im [npkt,nr,nt,234] (csi_rx_combiner_device): d_c_re / d_c_im [npkt, ns, nr,
+        234], row s = exp(i t_s) u_s^H of the s-th largest singular value, (C H)[s][nt-1] real and >= 0; optional d_sigma [npkt, ns, 234].
+        Asynchronous, on the engine's stream."""
+        self._check(self._lib.csi_rx_combiner_device(self._ctx, d_hest_re.ptr, d_hest_im.ptr, int(npkt), int(ns), d_c_re.ptr, d_c_im.ptr,
+                                                     None if d_sigma is None else d_sigma.ptr))
+
+    def rx_apply_combiner_device(self, d_c_re, d_c_im, d_h_re, d_h_im, npkt, ns, d_e_re, d_e_im):
+        """E = C H of the combiner d_c_re / d_c_im [npkt, ns, nr, 234] and the planes d_h_re / d_h_im [npkt,nr,nt,234] into d_e_re / d_e_im
+        [npkt,nr,nt,234] (csi_rx_apply_combiner_device): rows s < ns the combined streams, the other rows zero - what mu_link_sim_device
+        takes as the channel of a combining user, and every estimate consumer as its report.  Asynchronous, on the engine's stream."""
+        self._check(self._lib.csi_rx_apply_combiner_device(self._ctx, d_c_re.ptr, d_c_im.ptr, d_h_re.ptr, d_h_im.ptr, int(npkt), int(ns),
+                                                           d_e_re.ptr, d_e_im.ptr))
+
+    def rx_combiner(self, h, ns, keep_sigma=False):
+        """The same from a complex array h [npkt,nr,nt,234] -> C complex64 [npkt, ns, nr, 234]; with keep_sigma (C, sigma float32 [npkt,
+        ns, 234])."""
+        h = np.asarray(h)
+        if h.ndim != 4 or h.shape[1:] != (self.nr, self.nt, N_DATA):
+            raise CsiError(-1, f'h must be [npkt,{self.nr},{self.nt},{N_DATA}], got {h.shape}')
+        npkt, rows = h.shape[0], max(int(ns), 0)
+        dev = [self.to_device(_f32c(h.real)), self.to_device(_f32c(h.imag))]
+        outs = [self.empty((npkt, rows, self.nr, N_DATA)) for _ in range(2)]
+        sigma = self.empty((npkt, rows, N_DATA)) if keep_sigma else None
+        try:
+            self.rx_combiner_device(dev[0], dev[1], npkt, ns, outs[0], outs[1], sigma)
+            self.synchronize()
+            c = (outs[0].download() + 1j * outs[1].download()).astype(np.complex64)
+            return (c, sigma.download()) if keep_sigma else c
+        finally:
+            for a in dev + outs + [sigma]:
+                if a is not None:
+                    a.free()
+
+    def rx_apply_combiner(self, C, h):
+        """E = C H from complex arrays C [npkt, ns, nr, 234] and h [npkt,nr,nt,234] -> complex64 [npkt,nr,nt,234]."""
+        C, h = np.asarray(C), np.asarray(h)
+        if h.ndim != 4 or h.shape[1:] != (self.nr, self.nt, N_DATA):
+            raise CsiError(-1, f'h must be [npkt,{self.nr},{self.nt},{N_DATA}], got {h.shape}')
+        npkt = h.shape[0]
+        if C.ndim != 4 or C.shape[0] != npkt or C.shape[2:] != (self.nr, N_DATA):
+            raise CsiError(-1, f'C must be [{npkt},ns,{self.nr},{N_DATA}], got {C.shape}')
+        dev = [self.to_device(_f32c(x)) for x in (C.real, C.imag, h.real, h.imag)]
+        outs = [self.empty((npkt, self.nr, self.nt, N_DATA)) for _ in range(2)]
+        try:
+            self.rx_apply_combiner_device(dev[0], dev[1], dev[2], dev[3], npkt, C.shape[1], outs[0], outs[1])
+            self.synchronize()
+            return (outs[0].download() + 1j * outs[1].download()).astype(np.complex64)
+        finally:
+            for a in dev + outs:
+                a.free()
+
     def viterbi_decode(self, llr):
         """Viterbi decoding of terminated codewords of the rate-1/3 K = 7 code (133, 171, 165): llr float [ncw, 3 n_steps], positive = 0
         -> uint8 [ncw, n_steps - 6] (csi_viterbi_decode_device; fp32 metrics, ties to the predecessor with the lower state number)."""

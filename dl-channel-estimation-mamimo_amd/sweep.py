@@ -26,6 +26,10 @@ data phases to a level and nothing else: without an option every output is what 
     --feedback BPHI BPSI --feedbackNg     --ber     bersFB_X, EVM_rmsFB_X, sinrFB_X: one user's data phase behind    4.24
       (feedback)                                    the expanded Givens-angle report of X; with --users also
                                                     bersMUFB_X, EVM_rmsMUFB_X, sinrMUFB_X and mufb_users
+    --rxCombine (rx_combine)              --ber and the families FBC (--feedback), MUC + muc_users (--users), MUFBC +      4.25
+                                          one of    mufbc_users (both): the data phases of FB, MU, MUFB heard through the
+                                          --feedback combiner C_u = U^H of user u's own X planes - the channel handed to
+                                          --users   the data phase is C_u H_u,true; MUC precodes on C_u Hest_u
 
 FAMILIES below states this as data - fields, sources, switches, the per-user record - and MAT_ORDER / JSON_ORDER the two orders
 the rows are written in; metric_fields, format_table and the per-level summary of run_sweep are read off them.
@@ -36,14 +40,14 @@ the rows are written in; metric_fields, format_table and the per-level summary o
                                                             [--blind] [--delayTaps L [--delayPre P]] [--beams]
                                                             [--ber --users U [--muReg zf|rzf] [--userSpacing DEG] [--muHybrid NRF]
                                                              [--muJSDM B [--jsdmRank R] [--jsdmTol T] [--jsdmMode pgp|jgp]]]
-                                                            [--feedback BPHI BPSI [--feedbackNg G]]
+                                                            [--feedback BPHI BPSI [--feedbackNg G]] [--rxCombine]
 
 The module holds no arithmetic of its own: packets come from csi_synth_structured / csi_synth_scattering, labels from
 csi_ls_estimate_device, the fit from trainer.fit, the estimates from csi_estimate_device, csi_lmmse_estimate_device,
 csi_lmmse_blind_device, csi_subspace_smooth_device (basis: subspace.delay_basis) and csi_beam_wiener_device (beams:
 beamspace.dft_basis, error level: csi_null_noise_device), every NMSE from csi_nmse_device, the precoders from
 csi_hybrid_weights_device, csi_mu_precoder_device, csi_mu_hybrid_precoder_device, csi_mu_jsdm_precoder_device and
-csi_feedback_compress_device / csi_feedback_expand_device, bit errors, EVM and gains from csi_link_sim_device,
+csi_feedback_compress_device / csi_feedback_expand_device, the combiners from csi_rx_combiner_device / csi_rx_apply_combiner_device, bit errors, EVM and gains from csi_link_sim_device,
 csi_link_sim_rx_device and csi_mu_link_sim_device, with the noise level of a data symbol from synth.link_noise_var.  Only the
 per-packet mean of the per-link ratios (NMSE_subk, BER_test_maMIMO_LTF.m:675-686), errors / n_info, the mean over the users and the
 confidence interval are taken on the host."""
@@ -68,6 +72,10 @@ RX_FIELDS = ('bersRx_', 'EVM_rmsRx_', 'gNMSE_')     # --rxEstimate: the same dat
 MUH_FIELDS = ('bersMUH_', 'EVM_rmsMUH_', 'sinrMUH_')  # --muHybrid: the same data phase behind the hybrid precoder of n_rf RF chains
 FB_FIELDS = ('bersFB_', 'EVM_rmsFB_', 'sinrFB_')     # --feedback: one user's data phase behind the expanded Givens-angle report of the source's estimate
 MUFB_FIELDS = ('bersMUFB_', 'EVM_rmsMUFB_', 'sinrMUFB_')  # --feedback --users: the multi-user data phase behind the precoder of the users' rebuilt S V^H planes
+# --rxCombine: the data phases of FB, MU and MUFB heard through every user's U^H combiner (the channel of user u is C_u H_u,true)
+FBC_FIELDS = ('bersFBC_', 'EVM_rmsFBC_', 'sinrFBC_')
+MUC_FIELDS = ('bersMUC_', 'EVM_rmsMUC_', 'sinrMUC_')      # ... the precoder on the users' combined estimates C_u Hest_u (ideal feedback)
+MUFBC_FIELDS = ('bersMUFBC_', 'EVM_rmsMUFBC_', 'sinrMUFBC_')
 MUJ_FIELDS = ('bersMUJ_', 'EVM_rmsMUJ_', 'sinrMUJ_')  # --muJSDM: the same data phase behind the JSDM precoder of b RF chains per user
 MU_FIELDS = ('bersMU_', 'EVM_rmsMU_', 'sinrMU_')    # --users: the multi-user data phase, the mean over the users per packet
 DELAY = 'DLY'                            # --delayTaps: the LS rows projected onto a window of delay taps (csi_subspace_smooth_device, w = 1)
@@ -91,7 +99,10 @@ FAMILIES = dict(
     MUH=Family(MUH_FIELDS, MUH_FIELDS, EVERY, ('mu_hybrid',), 'muh_users'),
     MUJ=Family(MUJ_FIELDS, MUJ_FIELDS, EVERY, ('mu_jsdm',), 'muj_users'),
     FB=Family(FB_FIELDS, FB_FIELDS, SINGLE, ('feedback',), None),
-    MUFB=Family(MUFB_FIELDS, MUFB_FIELDS, EVERY, ('feedback', 'mu'), 'mufb_users'))
+    MUFB=Family(MUFB_FIELDS, MUFB_FIELDS, EVERY, ('feedback', 'mu'), 'mufb_users'),
+    FBC=Family(FBC_FIELDS, FBC_FIELDS, SINGLE, ('feedback', 'rx_combine'), None),
+    MUC=Family(MUC_FIELDS, MUC_FIELDS, EVERY, ('mu', 'rx_combine'), 'muc_users'),
+    MUFBC=Family(MUFBC_FIELDS, MUFBC_FIELDS, EVERY, ('feedback', 'mu', 'rx_combine'), 'mufbc_users'))
 # The two orders the rows (family, source) are written in, as blocks (family, sources) - source-major within a block - and
 # (family, USERS) for the per-user record.  Both are contracts with whoever reads the files.  They differ in their heads, which grew
 # option by option; every family behind MU stands whole, in the order of the table, at the end of both.
@@ -208,7 +219,7 @@ def user_estimates(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=Tr
 
 
 def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=True, keep=False, ber=None, channel=None, blind=False,
-                   rx_estimate=False, delay=None, mu=None, beams=False, mu_hybrid=None, mu_jsdm=None, feedback=None):
+                   rx_estimate=False, delay=None, mu=None, beams=False, mu_hybrid=None, mu_jsdm=None, feedback=None, rx_combine=False):
     """One level: the estimates of npkt test packets at `snr_db` (user_estimates: packets first_pkt ... of stream `seed`, keep them
     disjoint from the training packets) and NMSE_subk of each against the true channel, then the data phases the options ask for (the
     table of the module).  Returns {'MSE_X': float64 [npkt], the per-link ratios averaged per packet} for X = LS, MMSE, DNN and every
@@ -216,7 +227,8 @@ def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=Tr
     set_dictionary) with 'MSE_perfect' (zeros), of feedback_level (feedback = {b_phi, b_psi, ng}) and of mu_level (mu = dict(users=U,
     reg='zf' | 'rzf', spacing=degrees), mu_hybrid = n_rf, mu_jsdm = {b, r_star, tol, mode}, feedback) with their per-user records.
     In the multi-user phase user 0 is the user above; user u >= 1 takes its packets from the stream seed + u (scattering channel: at
-    azimuth az_deg + u spacing) and its estimates from the same calls, DLYANG left out.
+    azimuth az_deg + u spacing) and its estimates from the same calls, DLYANG left out.  rx_combine adds, behind every other call, the
+    families of combine_level.
     keep=True adds 'arrays': the DeviceArrays ltf_re, ltf_im, h_re, h_im, ls_re, ls_im (the caller frees them)."""
     nr, nt = engine.nr, engine.nt
     users = [user_estimates(engine, snr_db, npkt, seed, first_pkt, n_taps, amp_scale, channel, blind, delay, beams,
@@ -243,6 +255,10 @@ def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=Tr
             nv = np.stack([synth.link_noise_var(u['noise_std'].download(), amp_scale) for u in users])
             out.update(mu_level(engine, [{x: u['planes'][x] for x in EVERY if x in u['planes']} for u in users], nv, npkt, seed, first_pkt,
                                 ns=ber['ns'], n_sym=ber['n_sym'], bps=ber['bps'], reg=mu.get('reg', 'zf'), n_rf=mu_hybrid, jsdm=mu_jsdm, fb=feedback))
+        if rx_combine:
+            nv = np.stack([synth.link_noise_var(u['noise_std'].download(), amp_scale) for u in users])
+            out.update(combine_level(engine, [{x: u['planes'][x] for x in EVERY if x in u['planes']} for u in users], nv, npkt, seed, first_pkt,
+                                     ns=ber['ns'], n_sym=ber['n_sym'], bps=ber['bps'], reg=(mu or {}).get('reg', 'zf'), fb=feedback, mu=bool(mu)))
     kept = users[0]['ltf'] + planes['perfect'] + planes['LS']
     for a in (a for u in users for a in u['free']):
         if not keep or all(a is not k for k in kept):
@@ -306,6 +322,30 @@ class _Report:
             a.free()
 
 
+class _Combiner:
+    """The device arrays of one user's receive combiner of npkt packets - C [npkt, ns, nr, 234] and the planes E = C H
+    it leaves - and the calls that fill them."""
+
+    def __init__(self, engine, npkt, ns, n_planes=1):
+        self.e, self.npkt, self.ns = engine, npkt, int(ns)
+        self.c = [engine.empty((npkt, self.ns, engine.nr, N_DATA)) for _ in range(2)]
+        self.planes = [[engine.empty((npkt, engine.nr, engine.nt, N_DATA)) for _ in range(2)] for _ in range(n_planes)]
+
+    def derive(self, e_re, e_im):
+        """C from the user's own planes"""
+        self.e.rx_combiner_device(e_re, e_im, self.npkt, self.ns, self.c[0], self.c[1])
+
+    def apply(self, h_re, h_im, slot=0):
+        """C H into the planes of `slot`; returns them"""
+        out = self.planes[slot]
+        self.e.rx_apply_combiner_device(self.c[0], self.c[1], h_re, h_im, self.npkt, self.ns, out[0], out[1])
+        return out
+
+    def free(self):
+        for a in self.c + [x for p in self.planes for x in p]:
+            a.free()
+
+
 def feedback_level(engine, planes, h_re, h_im, noise_var, npkt, seed, first_pkt, ns=1, n_sym=10, bps=2, b_phi=9, b_psi=7, ng=1):
     """The data phase of one user behind the quantised CSI feedback on resident planes: for every source X of `planes`
     the estimate goes through the report of ns columns (feedback_compress_device) and its expansion (feedback_expand_device), and
@@ -323,6 +363,84 @@ def feedback_level(engine, planes, h_re, h_im, noise_var, npkt, seed, first_pkt,
         out.update(zip((f + name for f in FAMILIES['FB'].fields), (v[0] for v in _download_metrics(d_err, d_evm, d_sinr, n_info))))
     for a in w + [d_err, d_evm, d_sinr, d_nv, report]:
         a.free()
+    return out
+
+
+def combine_level(engine, planes, noise_var, npkt, seed, first_pkt, ns=1, n_sym=10, bps=2, reg='zf', fb=None, mu=False):
+    """The data phases of feedback_level and mu_level heard through receive combiners, on resident planes and behind
+    every call of theirs.  planes = one dict {X: (re, im)} per user with the true channel under 'perfect' (one user without mu);
+    noise_var float32 [U, npkt].  For every source X user u derives its combiner C_u from its own X planes (rx_combiner_device; 'perfect':
+    from the true channel) and the data phase runs through E_u = C_u H_u,true (rx_apply_combiner_device) with the seeds and the noise of
+    the family it is paired with:
+      fb        'bersFBC_X', 'EVM_rmsFBC_X', 'sinrFBC_X': user 0 behind the W = sqrt(Nt / ns) Vhat of FB
+      mu        'bersMUC_X', 'EVM_rmsMUC_X', 'sinrMUC_X' and 'muc_users': behind mu_precoder_device on the users' combined estimates
+                C_u X_u (the unquantised report S V^H: ideal feedback), reg as in mu_level
+      fb, mu    'bersMUFBC_X', 'EVM_rmsMUFBC_X', 'sinrMUFBC_X' and 'mufbc_users': behind the precoder of MUFB (the rebuilt planes)
+    in this order; the per-user records stand behind every field."""
+    nu, nt = (len(planes) if mu else 1), engine.nt
+    m = nu * int(ns)
+    if reg not in ('zf', 'rzf'):
+        raise ValueError("reg must be 'zf' or 'rzf', got %r" % (reg,))
+    n_info, _ = engine.link_frame_bits(ns, n_sym, bps)
+    noise_var = np.ascontiguousarray(noise_var, np.float32).reshape(-1, npkt)[:nu]
+    h_re, h_im = [p['perfect'][0] for p in planes[:nu]], [p['perfect'][1] for p in planes[:nu]]
+    comb = [_Combiner(engine, npkt, ns, n_planes=2) for _ in range(nu)]
+    report = _Report(engine, npkt, ns, fb['b_phi'], fb['b_psi'], fb['ng']) if fb else None
+    scratch = comb + ([report] if fb else [])
+
+    def heard_through_the_combiners(e_re, e_im, users):
+        heard = []
+        for u in range(users):
+            comb[u].derive(e_re[u], e_im[u])
+            heard.append(comb[u].apply(h_re[u], h_im[u]))
+        return [x[0] for x in heard], [x[1] for x in heard]
+
+    out, users = {}, {}
+    if fb:
+        d_nv = engine.to_device(noise_var[:1])
+        w = [engine.empty((npkt, int(ns), nt, N_DATA)) for _ in range(2)]
+        d_err, d_evm, d_sinr = (engine.empty((1, npkt)) for _ in range(3))
+        for name in (x for x in FAMILIES['FBC'].sources if x in planes[0]):
+            e_re, e_im = planes[0][name]
+            report.through(e_re, e_im, engine.FB_LAYOUT_W, w[0], w[1])
+            g_re, g_im = heard_through_the_combiners([e_re], [e_im], 1)
+            engine.mu_link_sim_device(g_re, g_im, w[0], w[1], d_nv, seed, first_pkt, npkt, ns, d_err, d_evm, d_sinr, n_sym=n_sym, bps=bps)
+            out.update(zip((f + name for f in FAMILIES['FBC'].fields), (v[0] for v in _download_metrics(d_err, d_evm, d_sinr, n_info))))
+        for a in w + [d_err, d_evm, d_sinr, d_nv]:
+            a.free()
+    if mu:
+        d_nv = engine.to_device(noise_var)
+        d_reg = engine.to_device((m * noise_var.astype(np.float64).mean(0) / nt).astype(np.float32)) if reg == 'rzf' else None
+        w = [engine.empty((npkt, m, nt, N_DATA)) for _ in range(2)]
+        d_err, d_evm, d_sinr = (engine.empty((nu, npkt)) for _ in range(3))
+        scratch += w + [d_err, d_evm, d_sinr, d_nv] + ([d_reg] if d_reg is not None else [])
+
+        def on_the_combined_estimates(e_re, e_im):
+            est = [comb[u].apply(e_re[u], e_im[u], slot=1) for u in range(nu)]
+            engine.mu_precoder_device([x[0] for x in est], [x[1] for x in est], npkt, ns, w[0], w[1], d_reg)
+        variants = [('MUC', on_the_combined_estimates)]
+        if fb:
+            rebuilt = [[engine.empty((npkt, engine.nr, nt, N_DATA)) for _ in range(2)] for _ in range(nu)]
+            scratch += [x for r in rebuilt for x in r]
+
+            def through_the_reports(e_re, e_im):
+                for u in range(nu):
+                    report.through(e_re[u], e_im[u], engine.FB_LAYOUT_CSI, rebuilt[u][0], rebuilt[u][1])
+                engine.mu_precoder_device([r[0] for r in rebuilt], [r[1] for r in rebuilt], npkt, ns, w[0], w[1], d_reg)
+            variants.append(('MUFBC', through_the_reports))
+        for family, precode in variants:
+            fields, per_user = FAMILIES[family].fields, users.setdefault(FAMILIES[family].users, {})
+            for name in (x for x in FAMILIES[family].sources if x in planes[0]):
+                e_re, e_im = [p[name][0] for p in planes], [p[name][1] for p in planes]
+                g_re, g_im = heard_through_the_combiners(e_re, e_im, nu)
+                precode(e_re, e_im)
+                engine.mu_link_sim_device(g_re, g_im, w[0], w[1], d_nv, seed, first_pkt, npkt, ns, d_err, d_evm, d_sinr, n_sym=n_sym, bps=bps)
+                per = _download_metrics(d_err, d_evm, d_sinr, n_info)
+                out.update(zip((f + name for f in fields), (v.mean(axis=0) for v in per)))
+                per_user[name] = dict(zip(('bers', 'EVM_rms', 'sinr'), (v.tolist() for v in per)))
+    for a in scratch:
+        a.free()
+    out.update(users)
     return out
 
 
@@ -543,10 +661,19 @@ def feedback_problem(ns, nr, nt, b_phi, b_psi, ng=1):
     return None
 
 
+def combine_problem(ns, nr):
+    """What the combining entries would refuse of ns combined streams, as text; None when it is served."""
+    if not 1 <= ns <= min(4, nr):
+        return 'numSTS %d streams outside 1 .. min(4, nRX %d)' % (ns, nr)
+    if nr > 16:
+        return 'nRX %d exceeds 16' % nr
+    return None
+
+
 def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500, seed=0, modeldir=None, fit_args=None, n_taps=8,
               amp_scale=True, save_dataset=None, verbose=True, ber=None, channel=None, blind=False, rx_estimate=False,
               delay_taps=None, delay_pre=0, users=None, mu_reg='zf', user_spacing=15.0, beams=False, mu_hybrid=None, mu_jsdm=None,
-              feedback=None):
+              feedback=None, rx_combine=False):
     """Training set -> models (loaded from `modeldir`, else fitted and saved into `out`) -> every level (evaluate_level).  Writes
     <out>/BS<Nt>_SNR<s>/metrics.mat per level and <out>/sweep.json, prints the table, returns the result dict (with the per-packet
     arrays under 'per_packet' = {level: {'MSE_LS', ...}}).  Test packets come from the stream seed + 1, behind the index range of
@@ -555,7 +682,8 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
     with r_star = 4, tol = 0.05, mode = 'pgp' unless given; feedback_problem with ng = 1 unless given) and recorded in sweep.json under
     the key the table's `needs` name ('ber', 'channel': its parameters, 'blind', 'rx_estimate', 'mu': {users, reg, spacing},
     'mu_hybrid': {n_rf}, 'mu_jsdm': {b, r_star, tol, mode}, 'feedback': {b_phi, b_psi, ng, report_bits: the bits of one packet's
-    report}, 'delay': {taps, pre, rank}, 'beams'); a level of sweep.json then holds mean and confidence interval of every field the
+    report}, 'delay': {taps, pre, rank}, 'beams', 'rx_combine': needs ber, one of feedback / users and ns <= min(4, Nr) - combine_problem);
+    a level of sweep.json then holds mean and confidence interval of every field the
     option adds, and the per-user records, in JSON_ORDER."""
     if feedback is not None:
         if ber is None:
@@ -587,6 +715,14 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
         problem = jsdm_problem(mu['users'], int(ber['ns']), engine.nt, **mu_jsdm)
         if problem:
             raise ValueError('mu_jsdm: ' + problem)
+    if rx_combine:
+        if ber is None:
+            raise ValueError('rx_combine needs the data phase (ber)')
+        if feedback is None and mu is None:
+            raise ValueError('rx_combine needs feedback or the multi-user data phase (users >= 2)')
+        problem = combine_problem(int(ber['ns']), engine.nr)
+        if problem:
+            raise ValueError('rx_combine: ' + problem)
     delay = (int(delay_taps), int(delay_pre)) if delay_taps else None
     os.makedirs(out, exist_ok=True)
     result = dict(nt=engine.nt, nr=engine.nr, n_train=int(n_train), n_test=int(n_test), seed=int(seed), n_taps=int(n_taps),
@@ -598,7 +734,8 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
                    channel=channel is not None and dict(scattering_args(channel), model='scattering'), blind=bool(blind),
                    rx_estimate=bool(rx_estimate), mu=mu and dict(mu), mu_hybrid=mu_hybrid and dict(n_rf=mu_hybrid), mu_jsdm=mu_jsdm and dict(mu_jsdm),
                    feedback=feedback and dict(feedback, report_bits=report_bits),
-                   delay=delay and dict(taps=delay[0], pre=delay[1], rank=int(subspace.delay_basis(*delay)[0].shape[1])), beams=bool(beams))
+                   delay=delay and dict(taps=delay[0], pre=delay[1], rank=int(subspace.delay_basis(*delay)[0].shape[1])), beams=bool(beams),
+                   rx_combine=bool(rx_combine))
     result.update((k, v) for k, v in options.items() if v)          # an option that is off leaves no key
     if modeldir:
         load_models(engine, modeldir)
@@ -619,7 +756,7 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
         t0 = time.perf_counter()
         mse = evaluate_level(engine, snr, n_test, seed + 1, n_train + i * n_test, n_taps, amp_scale, ber=ber, channel=channel, blind=blind,
                              rx_estimate=rx_estimate, delay=delay, mu=mu, beams=beams, mu_hybrid=mu_hybrid, mu_jsdm=mu_jsdm,
-                             feedback=feedback)
+                             feedback=feedback, **(dict(rx_combine=True) if rx_combine else {}))
         lv = dict(snr_db=float(snr), seconds=time.perf_counter() - t0)
         write_metrics(os.path.join(out, 'BS%d_SNR%g' % (engine.nt, snr), 'metrics.mat'), mse)
         for key, field, _ in _columns(result):
@@ -680,6 +817,10 @@ def build_parser():
                         '(csi_feedback_compress_device, csi_feedback_expand_device; numSTS <= min(4, nRX, nTX)) - bersFB_ / EVM_rmsFB_ / sinrFB_, '
                         'with --users also bersMUFB_ / EVM_rmsMUFB_ / sinrMUFB_')
     p.add_argument('--feedbackNg', default=1, type=int, metavar='G', help='--feedback: one report per G carriers (1, 2 or 4), held along the group')
+    p.add_argument('--rxCombine', action='store_true',
+                   help='--ber with --feedback and / or --users: also run their data phases heard through every user\'s U^H combiner of its own '
+                        'estimate (csi_rx_combiner_device, csi_rx_apply_combiner_device; numSTS <= min(4, nRX)) - bersFBC_ / EVM_rmsFBC_ / sinrFBC_, '
+                        'bersMUC_ / EVM_rmsMUC_ / sinrMUC_, bersMUFBC_ / EVM_rmsMUFBC_ / sinrMUFBC_')
     p.add_argument('--userSpacing', default=15.0, type=float, metavar='DEG', help='--users with --channel scattering: user u sits at azimuth userAz + u DEG')
     p.add_argument('--channel', default='taps', choices=('taps', 'scattering'),
                    help='taps: i.i.d. impulse responses (csi_synth_structured); scattering: the geometric single-bounce channel (csi_synth_scattering)')
@@ -738,6 +879,14 @@ def parse_args(argv=None):
             parser.error('--feedback: ' + problem)
     elif args.feedbackNg != 1:
         parser.error('--feedbackNg needs --feedback')
+    if args.rxCombine:
+        if not args.ber:
+            parser.error('--rxCombine needs --ber')
+        if args.feedback is None and args.users < 2:
+            parser.error('--rxCombine needs --feedback or --users U (U >= 2)')
+        problem = combine_problem(args.numSTS, args.nRX)
+        if problem:
+            parser.error('--rxCombine: ' + problem)
     if args.delayTaps and not (1 <= args.delayTaps <= subspace.MAX_RANK and 0 <= args.delayPre <= args.delayTaps):
         parser.error('--delayTaps takes 1 .. %d and --delayPre 0 .. L' % subspace.MAX_RANK)
     if args.delayPre and not args.delayTaps:
@@ -765,7 +914,8 @@ def main(argv=None):
               users=args.users if args.users >= 2 else None, mu_reg=args.muReg, user_spacing=args.userSpacing, beams=bool(args.beams),
               mu_hybrid=args.muHybrid or None,
               mu_jsdm=dict(b=args.muJSDM, r_star=args.jsdmRank, tol=args.jsdmTol, mode=args.jsdmMode) if args.muJSDM else None,
-              feedback=dict(b_phi=args.feedback[0], b_psi=args.feedback[1], ng=args.feedbackNg) if args.feedback is not None else None)
+              feedback=dict(b_phi=args.feedback[0], b_psi=args.feedback[1], ng=args.feedbackNg) if args.feedback is not None else None,
+              rx_combine=bool(args.rxCombine))
     return 0
 
 

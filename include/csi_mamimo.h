@@ -43,7 +43,7 @@
  * context's stream and return without waiting; call csi_synchronize before reading results.
  *
  * Device pointers (csi_predict_device, csi_ls_estimate_device, csi_estimate_device, csi_lmmse_estimate_device, csi_lmmse_blind_device, csi_subspace_smooth_device, csi_beam_power_device, csi_beam_smooth_device, csi_beam_wiener_device, csi_null_noise_device, csi_nmse_device,
- * csi_hybrid_weights_device, csi_link_sim_device, csi_link_sim_rx_device, csi_mu_precoder_device, csi_mu_link_sim_device, csi_mu_hybrid_precoder_device, csi_mu_covariance_device, csi_mu_jsdm_precoder_device, csi_feedback_compress_device, csi_feedback_expand_device, csi_viterbi_decode_device, csi_synth_*).  An array of exactly the documented
+ * csi_hybrid_weights_device, csi_link_sim_device, csi_link_sim_rx_device, csi_mu_precoder_device, csi_mu_link_sim_device, csi_mu_hybrid_precoder_device, csi_mu_covariance_device, csi_mu_jsdm_precoder_device, csi_feedback_compress_device, csi_feedback_expand_device, csi_rx_combiner_device, csi_rx_apply_combiner_device, csi_viterbi_decode_device, csi_synth_*).  An array of exactly the documented
  * size suffices: it may be a slice of a larger allocation whose neighbours hold live data of any value (NaN and 1e38 included).
  * Nothing outside the arrays is written, nothing outside them reaches a result, and input arrays are not modified.  Every re / im
  * PLANE (the preambles [npkt][Nr][len_ltf], the CSI planes [npkt][Nr][Nt][234 or n_out], fbb, frf_mean, xeq, gest, the precoder planes W, g) starts on a 16-byte
@@ -569,6 +569,36 @@ int  csi_feedback_compress_device(csi_ctx* ctx, const float* d_h_re, const float
 int  csi_feedback_expand_device(csi_ctx* ctx, const uint16_t* d_phi_code, const uint16_t* d_psi_code, const float* d_phi,
                                 const float* d_psi, const float* d_sigma, int64_t npkt, int nc, int b_phi, int b_psi, int ng, int layout,
                                 float* d_out_re, float* d_out_im);
+
+/* Receive combining: the U^H combiner of a user's CSI estimate and its application to CSI planes (model, plan and traps: DESIGN.md 4.25,
+ * csrc/rx_combine.hip.h).  An addition: the ABI version stays 1.
+ *   combiner   per (packet, carrier), H[i][j] = hest[p][i][j][k] (Nr x Nt): row s < ns of C is exp(i t_s) u_s^H, u_s the left singular
+ *              vector of the s-th largest singular value (fp64 Jacobi on H H^H as csi_hybrid_weights_device runs it: largest first, the
+ *              lowest index on a tie); t_s makes (C H)[s][Nt-1] real and >= 0 (that element 0: no rotation) - the column phase of the
+ *              feedback report, so conj((C H)[s][:]) / sigma_s is the d_v of csi_feedback_compress_device on the same planes and C H is
+ *              what CSI_FB_LAYOUT_CSI expands to at continuous angles.  sigma[s] the singular value in fp32
+ *   rank rule  a row whose eigenvalue is not > 0, not finite or not above 2^-40 of the largest (sigma_s <= 2^-20 sigma_1: the rounding of
+ *              the Jacobi sweeps on a rank-deficient matrix) is all zero and its sigma is 0; the data phase's own singular rule then gives
+ *              x = 0, csi = 0 for the item
+ *   apply      E[s][j] = sum_{i < Nr} C[s][i] H[i][j] for s < ns (i ascending, fmaf chains), rows ns .. Nr-1 exact zeros: the CSI layout
+ *              every estimate consumer reads.  H = the true planes gives the channel csi_mu_link_sim_device sees behind the combiner (its
+ *              rows s < ns are the ns combined streams); H = the estimate gives the unquantised report S V^H
+ *   noise      the rows of C are orthonormal, so C w of white noise w is white with the same variance: the data phase on E draws exactly
+ *              the noise a combining receiver sees.  A combiner whose rows are not orthonormal would colour the noise: not modelled
+ * csi_rx_combiner_device: d_hest_re / d_hest_im [npkt][Nr][Nt][234] IN; d_c_re / d_c_im [npkt][ns][Nr][234] OUT; d_sigma [npkt][ns][234]
+ * OUT, optional (may be NULL).
+ * csi_rx_apply_combiner_device: d_c_re / d_c_im [npkt][ns][Nr][234] IN, d_h_re / d_h_im [npkt][Nr][Nt][234] IN, d_e_re / d_e_im
+ * [npkt][Nr][Nt][234] OUT (no overlap with the inputs).
+ * Both are asynchronous on the context's stream, serve fp32 and bf16 contexts alike (all planes are fp32) and use no workspace: the same
+ * bits whatever the call or the packet's position in it, and nothing to size in front of a capture.  The apply step is one launch.
+ * Refused with text, before anything is launched or counted: ns outside 1 .. min(4, Nr), Nr > 16, a single-input context, null required
+ * pointers, one plane of a pair without the other, re / im planes off a 16-byte boundary, negative npkt, a per-workgroup LDS image beyond
+ * 160 KiB.  npkt == 0 returns 0 and launches nothing; a null context returns -1.  The launches count under "combine_launches"; profile
+ * entries "rx_combiner" and "rx_combine". */
+int  csi_rx_combiner_device(csi_ctx* ctx, const float* d_hest_re, const float* d_hest_im, int64_t npkt, int ns, float* d_c_re,
+                            float* d_c_im, float* d_sigma);
+int  csi_rx_apply_combiner_device(csi_ctx* ctx, const float* d_c_re, const float* d_c_im, const float* d_h_re, const float* d_h_im,
+                                  int64_t npkt, int ns, float* d_e_re, float* d_e_im);
 
 /* Accuracy metric of the reference's evaluation, NMSE_subk (BER_test_maMIMO_LTF.m:675-686): per link
  * ||ref - est||^2 / ||ref||^2 over the n_bins bins, mean over the nlinks links ([link][n_bins] planes, e.g.
