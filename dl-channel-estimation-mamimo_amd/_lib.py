@@ -45,6 +45,11 @@ class CsiScatterConfig(ctypes.Structure):
                 ('el_deg', ctypes.c_float), ('box_frac', ctypes.c_float), ('sample_rate_hz', ctypes.c_float)]
 
 
+class CsiMotionConfig(ctypes.Structure):
+    _fields_ = [('speed_mps', ctypes.c_float), ('heading_az_deg', ctypes.c_float), ('heading_el_deg', ctypes.c_float),
+                ('carrier_hz', ctypes.c_float), ('flags', ctypes.c_uint32)]
+
+
 class CsiTrainConfig(ctypes.Structure):
     _fields_ = [('lr', ctypes.c_float), ('beta1', ctypes.c_float), ('beta2', ctypes.c_float), ('eps', ctypes.c_float),
                 ('bn_momentum', ctypes.c_float), ('dropout', ctypes.c_float), ('seed', ctypes.c_uint64)]
@@ -140,6 +145,8 @@ SYMBOLS = {
                                             _vp, _vp, _vp, _vp, _vp]),
     'csi_synth_scattering': (ctypes.c_int, [_ctx, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, _fp, ctypes.POINTER(CsiScatterConfig),
                                             _vp, _vp, _vp, _vp, _vp, _vp]),
+    'csi_scatter_channel_at_device': (ctypes.c_int, [_ctx, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(CsiScatterConfig),
+                                                     ctypes.POINTER(CsiMotionConfig), ctypes.POINTER(ctypes.c_double), ctypes.c_int, _vp, _vp]),
     'csi_profile_enable': (ctypes.c_int, [_ctx, ctypes.c_int]),
     'csi_profile_reset': (ctypes.c_int, [_ctx]),
     'csi_profile_num_kernels': (ctypes.c_int, []),

@@ -81,6 +81,7 @@ enum KernelId {
     K_RX_COMBINE,        // receive combining: E = C H on CSI planes, streaming
     K_BEAM_POWER,        // beam-space smoother (csi_beam_*, beam_smooth.hip.h): beam power E per (packet, rx, beam); placed like K_SUBSPACE_SMOOTH
     K_BEAM_SMOOTH,       // beam-space smoother: y = A diag(w) A^H x across the Tx antennas
+    K_SCATTER_AGED,      // the scattering channel of a moving user at later times (scatter_aged.hip.h): the one kernel of csi_scatter_channel_at_device; placed like K_SUBSPACE_SMOOTH
     K_SYNTH_SCATTERING,  // known-channel sounding packets of the scattering channel (synth_scattering.hip.h): the power pass and the packet pass of csi_synth_scattering
     K_LMMSE_NULL_NOISE,  // blind LMMSE smoother (csi_lmmse_blind, lmmse.hip.h): noise variance from the null carriers of the sounding symbols
     K_LMMSE_FREQ_CORR,   // blind LMMSE smoother: sample frequency correlation of the LS rows
@@ -92,7 +93,7 @@ const char* const kKernelNames[K_COUNT] = {
     "ls_estimate", "naive_dense0_gemm", "synth_white", "pilot_table", "cast_bf16", "pair_h1_bf16", "lmmse_levinson",
     "train_gemm", "train_elementwise", "nmse_links", "pair_dense_tail", "input_pool", "conv_frontend",
     "hybrid_svd", "hybrid_corr_argmax", "hybrid_solve", "hybrid_finish", "synth_structured", "link_txrx", "link_viterbi",
-    "subspace_smooth", "mu_precoder", "mu_txrx", "mu_beam_score", "mu_beam_select", "mu_hybrid_precoder", "mu_cov", "mu_jsdm_eig", "mu_jsdm_baseband", "fb_compress", "fb_expand", "rx_combiner", "rx_combine", "beam_power", "beam_smooth", "synth_scattering", "lmmse_null_noise", "lmmse_freq_corr", "lmmse_blind"};
+    "subspace_smooth", "mu_precoder", "mu_txrx", "mu_beam_score", "mu_beam_select", "mu_hybrid_precoder", "mu_cov", "mu_jsdm_eig", "mu_jsdm_baseband", "fb_compress", "fb_expand", "rx_combiner", "rx_combine", "beam_power", "beam_smooth", "scatter_aged", "synth_scattering", "lmmse_null_noise", "lmmse_freq_corr", "lmmse_blind"};
 
 thread_local std::string g_create_error;
 
@@ -231,6 +232,8 @@ struct csi_ctx {
     size_t synth_lds_attr = 0;   // dynamic-LDS limit already raised for its kernels
     size_t scatter_lds_attr = 0; // the same for the kernels of csi_synth_scattering (csi_scatter.hpp), which shares synth_ws / synth_host
     int64_t scatter_launches = 0;   // "scatter_launches": kernels launched by csi_synth_scattering
+    size_t scatter_aged_lds_attr = 0;      // csi_scatter_channel_at_device (csi_scatter_aged.hpp): dynamic-LDS limit already raised for its kernel
+    int64_t scatter_aged_launches = 0;     // "scatter_aged_launches": kernels launched by csi_scatter_channel_at_device
     // activation workspace
     char* ws = nullptr;
     size_t ws_bytes = 0;

@@ -31,6 +31,7 @@
 #include "csi_mu_jsdm.hpp"
 #include "csi_feedback.hpp"
 #include "csi_rx_combine.hpp"
+#include "csi_scatter_aged.hpp"      // last: its kernels are emitted behind every other kernel, whose pc-relative addresses stay what they were
 #include <initializer_list>
 
 namespace {
@@ -950,6 +951,7 @@ int csi_get_option(csi_ctx* c, const char* name, int64_t* value) {
         *value = v;
     }
     else if (n == "scatter_launches") *value = c->scatter_launches;
+    else if (n == "scatter_aged_launches") *value = c->scatter_aged_launches;
     else if (n == "small_rows") *value = c->small_rows;
     else if (n == "small_rows_band") *value = c->small_rows_band;
     else if (n == "f32_engine") *value = c->f32_engine;
@@ -1808,6 +1810,12 @@ int csi_synth_scattering(csi_ctx* c, uint64_t seed, int64_t first_pkt, int64_t n
                          float* d_ltf_re, float* d_ltf_im, float* d_h_re, float* d_h_im, float* d_noise_std, float* d_tau) {
     if (!c) return CSI_ERR_INVALID_ARG;
     return synth_scattering(c, seed, first_pkt, npkt, snr_db, cfg, d_ltf_re, d_ltf_im, d_h_re, d_h_im, d_noise_std, d_tau);
+}
+
+int csi_scatter_channel_at_device(csi_ctx* c, uint64_t seed, int64_t first_pkt, int64_t npkt, const csi_scatter_config* cfg,
+                                  const csi_motion_config* motion, const double* t_s, int n_times, float* d_h_re, float* d_h_im) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return scatter_channel_at(c, seed, first_pkt, npkt, cfg, motion, t_s, n_times, d_h_re, d_h_im);
 }
 
 // ---- profiling

@@ -1379,6 +1379,21 @@ class CsiEngine:
                                                    d_std.ptr if want_noise_std else None))
         return d_re, d_im, d_h[0], d_h[1], d_std
 
+    @staticmethod
+    def _scatter_config(who, npkt, n_scat, range_m, az_deg, el_deg, box_frac, random_users, amp_scale, sample_rate_hz):
+        """The csi_scatter_config of the scattering entry points from their keyword arguments; `who` names the entry point in a refusal"""
+        if npkt < 0:
+            raise CsiError(-1, f'{who}: npkt {npkt} must not be negative')
+        if n_scat < 1 or n_scat > 256:
+            raise CsiError(-1, f'{who}: n_scat {n_scat} outside 1 .. 256')
+        for name, val in (('range_m', range_m), ('box_frac', box_frac), ('sample_rate_hz', sample_rate_hz)):
+            if not (np.isfinite(val) and val > 0):      # a zero would select the default of the C configuration
+                raise CsiError(-1, f'{who}: {name} {val} must be finite and positive')
+        az = float(az_deg)
+        return _lib.CsiScatterConfig(n_scat=n_scat, flags=(1 if amp_scale else 0) | (2 if random_users else 0), range_m=float(range_m),
+                                     az_deg=360.0 if az == 0.0 else az, el_deg=float(el_deg), box_frac=float(box_frac),
+                                     sample_rate_hz=float(sample_rate_hz))
+
     def synth_scattering(self, seed, first_pkt, npkt, snr_db=None, n_scat=100, range_m=100.0, az_deg=30.0, el_deg=0.0, box_frac=0.1,
                          random_users=False, amp_scale=True, want_channel=True, want_noise_std=True, want_tau=False,
                          sample_rate_hz=100e6):
@@ -1388,20 +1403,10 @@ class CsiEngine:
         returns plus tau: a DeviceArray [npkt][n_scat] of the absolute path delays in samples (None unless want_tau), the hvec
         rows the reference hands its LMMSE smoother.  Asynchronous."""
         npkt, n_scat = int(npkt), int(n_scat)
-        if npkt < 0:
-            raise CsiError(-1, f'csi_synth_scattering: npkt {npkt} must not be negative')
-        if n_scat < 1 or n_scat > 256:
-            raise CsiError(-1, f'csi_synth_scattering: n_scat {n_scat} outside 1 .. 256')
-        for name, val in (('range_m', range_m), ('box_frac', box_frac), ('sample_rate_hz', sample_rate_hz)):
-            if not (np.isfinite(val) and val > 0):      # a zero would select the default of the C configuration
-                raise CsiError(-1, f'csi_synth_scattering: {name} {val} must be finite and positive')
+        cfg = self._scatter_config('csi_synth_scattering', npkt, n_scat, range_m, az_deg, el_deg, box_frac, random_users, amp_scale, sample_rate_hz)
         snr = None
         if snr_db is not None:
             snr = np.ascontiguousarray(np.broadcast_to(np.asarray(snr_db, dtype=np.float32), (npkt,)))
-        az = float(az_deg)
-        cfg = _lib.CsiScatterConfig(n_scat=n_scat, flags=(1 if amp_scale else 0) | (2 if random_users else 0), range_m=float(range_m),
-                                    az_deg=360.0 if az == 0.0 else az, el_deg=float(el_deg), box_frac=float(box_frac),
-                                    sample_rate_hz=float(sample_rate_hz))
         d_re, d_im = self.empty((npkt, self.nr, SYM_LEN * self.nt)), self.empty((npkt, self.nr, SYM_LEN * self.nt))
         d_h = [self.empty((npkt, self.nr, self.nt, N_DATA)) for _ in range(2)] if want_channel else [None, None]
         d_std = self.empty((npkt,)) if want_noise_std else None
@@ -1411,6 +1416,35 @@ class CsiEngine:
                                                    d_h[0].ptr if want_channel else None, d_h[1].ptr if want_channel else None,
                                                    d_std.ptr if want_noise_std else None, d_tau.ptr if want_tau else None))
         return d_re, d_im, d_h[0], d_h[1], d_std, d_tau
+
+    def scatter_channel_at_device(self, seed, first_pkt, npkt, times_s, d_h_re, d_h_im, speed_mps=0.0, heading_az_deg=0.0, heading_el_deg=0.0,
+                                  carrier_hz=28e9, random_heading=False, amp_scale=True, n_scat=100, range_m=100.0, az_deg=30.0, el_deg=0.0,
+                                  box_frac=0.1, random_users=False, sample_rate_hz=100e6):
+        """Channel aging (csi_scatter_channel_at_device): the true channel of synth_scattering's packets first_pkt ..
+        first_pkt + npkt - 1 of stream `seed` at the times times_s (seconds, 1 .. 16 of them, any sign and order) for a user that
+        moves with speed_mps along (heading_az_deg, heading_el_deg) in the transmitter's frame - or along an azimuth drawn per packet
+        (random_heading).  d_h_re / d_h_im [n_times][npkt][nr][nt][234]: slice t is a plane pair like synth_scattering's h, and IS
+        that h, bit for bit, at t = 0 or speed 0.  The scattering keywords are synth_scattering's.  One launch, asynchronous."""
+        npkt, n_scat = int(npkt), int(n_scat)
+        who = 'csi_scatter_channel_at_device'
+        cfg = self._scatter_config(who, npkt, n_scat, range_m, az_deg, el_deg, box_frac, random_users, amp_scale, sample_rate_hz)
+        if not (np.isfinite(carrier_hz) and carrier_hz > 0):      # a zero would select the default of the C record
+            raise CsiError(-1, f'{who}: carrier_hz {carrier_hz} must be finite and positive')
+        t = np.ascontiguousarray(np.atleast_1d(np.asarray(times_s, dtype=np.float64)))
+        if t.ndim != 1:
+            raise CsiError(-1, f'{who}: times_s must be a scalar or a vector, got shape {t.shape}')
+        motion = _lib.CsiMotionConfig(speed_mps=float(speed_mps), heading_az_deg=float(heading_az_deg), heading_el_deg=float(heading_el_deg),
+                                      carrier_hz=float(carrier_hz), flags=1 if random_heading else 0)
+        self._check(self._lib.csi_scatter_channel_at_device(self._ctx, int(seed), int(first_pkt), npkt, ctypes.byref(cfg), ctypes.byref(motion),
+                                                            t.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(t.size),
+                                                            d_h_re.ptr or None, d_h_im.ptr or None))
+
+    def scatter_channel_at(self, seed, first_pkt, npkt, times_s, **kw):
+        """scatter_channel_at_device into two new DeviceArrays [n_times, npkt, nr, nt, 234], which it returns (h_re, h_im)"""
+        n_times = int(np.atleast_1d(np.asarray(times_s)).size)
+        d_h = [self.empty((n_times, int(npkt), self.nr, self.nt, N_DATA)) for _ in range(2)]
+        self.scatter_channel_at_device(seed, first_pkt, npkt, times_s, d_h[0], d_h[1], **kw)
+        return d_h[0], d_h[1]
 
     def lmmse_estimate_device(self, d_h_re, d_h_im, npkt, d_hvec, L, d_snr_db, d_out_re, d_out_im):
         """LMMSE smoothing of device-resident LS planes (csi_lmmse_estimate_device): d_hvec [npkt][L], d_snr_db [npkt][nr]; asynchronous."""

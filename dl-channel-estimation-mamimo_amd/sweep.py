@@ -30,6 +30,11 @@ data phases to a level and nothing else: without an option every output is what 
                                           one of    mufbc_users (both): the data phases of FB, MU, MUFB heard through the
                                           --feedback combiner C_u = U^H of user u's own X planes - the channel handed to
                                           --users   the data phase is C_u H_u,true; MUC precodes on C_u Hest_u
+    --aging MS --speed --heading          --channel MSEA_X (X also perfect: the floor that ageing alone sets): the NMSE of X            4.26
+      --randomHeading --carrier (aging)   scattering against the channel MS milliseconds behind the sounding instant, for a user that
+                                                    moves; with --ber bersA_X, EVM_rmsA_X, dtSNRA_X and with --users bersMUA_X,
+                                                    EVM_rmsMUA_X, sinrMUA_X, mua_users: the data phases of --ber and --users - the
+                                                    same weights, bits and noise - through that aged channel
 
 FAMILIES below states this as data - fields, sources, switches, the per-user record - and MAT_ORDER / JSON_ORDER the two orders
 the rows are written in; metric_fields, format_table and the per-level summary of run_sweep are read off them.
@@ -41,8 +46,10 @@ the rows are written in; metric_fields, format_table and the per-level summary o
                                                             [--ber --users U [--muReg zf|rzf] [--userSpacing DEG] [--muHybrid NRF]
                                                              [--muJSDM B [--jsdmRank R] [--jsdmTol T] [--jsdmMode pgp|jgp]]]
                                                             [--feedback BPHI BPSI [--feedbackNg G]] [--rxCombine]
+                                                            [--channel scattering --aging MS [--speed MPS] [--heading DEG] [--randomHeading] [--carrier HZ]]
 
-The module holds no arithmetic of its own: packets come from csi_synth_structured / csi_synth_scattering, labels from
+The module holds no arithmetic of its own: packets come from csi_synth_structured / csi_synth_scattering, the aged channel from
+csi_scatter_channel_at_device, labels from
 csi_ls_estimate_device, the fit from trainer.fit, the estimates from csi_estimate_device, csi_lmmse_estimate_device,
 csi_lmmse_blind_device, csi_subspace_smooth_device (basis: subspace.delay_basis) and csi_beam_wiener_device (beams:
 beamspace.dft_basis, error level: csi_null_noise_device), every NMSE from csi_nmse_device, the precoders from
@@ -78,6 +85,10 @@ MUC_FIELDS = ('bersMUC_', 'EVM_rmsMUC_', 'sinrMUC_')      # ... the precoder on 
 MUFBC_FIELDS = ('bersMUFBC_', 'EVM_rmsMUFBC_', 'sinrMUFBC_')
 MUJ_FIELDS = ('bersMUJ_', 'EVM_rmsMUJ_', 'sinrMUJ_')  # --muJSDM: the same data phase behind the JSDM precoder of b RF chains per user
 MU_FIELDS = ('bersMU_', 'EVM_rmsMU_', 'sinrMU_')    # --users: the multi-user data phase, the mean over the users per packet
+# --aging: the NMSE and the data phases of LINK and MU against the channel some milliseconds behind the sounding instant
+MSEA_FIELDS = ('MSEA_',)
+LINKA_FIELDS = ('bersA_', 'EVM_rmsA_', 'dtSNRA_')
+MUA_FIELDS = ('bersMUA_', 'EVM_rmsMUA_', 'sinrMUA_')
 DELAY = 'DLY'                            # --delayTaps: the LS rows projected onto a window of delay taps (csi_subspace_smooth_device, w = 1)
 BEAMS = 'ANG'                            # --beams: the beam-space Wiener smoother across the Tx antennas on the LS planes (csi_beam_wiener_device)
 DELAY_BEAMS = 'DLYANG'                   # --beams with --delayTaps: the same step on the DLY planes
@@ -96,6 +107,10 @@ FAMILIES = dict(
     LINK=Family(LINK_FIELDS, ('BER_', None, None), SINGLE, ('ber',), None),
     RX=Family(RX_FIELDS, RX_FIELDS, SINGLE, ('rx_estimate',), None),
     MU=Family(MU_FIELDS, MU_FIELDS, EVERY, ('mu',), 'mu_users'),
+    # the aged twins of MSE, LINK and MU (--aging): listed beside them, written behind every other family (AGED below)
+    MSEA=Family(MSEA_FIELDS, MSEA_FIELDS, ESTIMATORS + ('perfect', BLIND, DELAY, BEAMS, DELAY_BEAMS), ('aging',), None),
+    LINKA=Family(LINKA_FIELDS, LINKA_FIELDS, SINGLE, ('aging', 'ber'), None),
+    MUA=Family(MUA_FIELDS, MUA_FIELDS, EVERY, ('aging', 'mu'), 'mua_users'),
     MUH=Family(MUH_FIELDS, MUH_FIELDS, EVERY, ('mu_hybrid',), 'muh_users'),
     MUJ=Family(MUJ_FIELDS, MUJ_FIELDS, EVERY, ('mu_jsdm',), 'muj_users'),
     FB=Family(FB_FIELDS, FB_FIELDS, SINGLE, ('feedback',), None),
@@ -105,9 +120,11 @@ FAMILIES = dict(
     MUFBC=Family(MUFBC_FIELDS, MUFBC_FIELDS, EVERY, ('feedback', 'mu', 'rx_combine'), 'mufbc_users'))
 # The two orders the rows (family, source) are written in, as blocks (family, sources) - source-major within a block - and
 # (family, USERS) for the per-user record.  Both are contracts with whoever reads the files.  They differ in their heads, which grew
-# option by option; every family behind MU stands whole, in the order of the table, at the end of both.
+# option by option; every family behind MU stands whole, in the order of the table, at the end of both - the aged families last.
 USERS = ()
-_WHOLE = tuple(b for k in FAMILIES if k not in ('MSE', 'LINK', 'RX', 'MU') for b in ((k, FAMILIES[k].sources), (k, USERS)))
+AGED = ('MSEA', 'LINKA', 'MUA')
+_WHOLE = tuple(b for k in [k for k in FAMILIES if k not in ('MSE', 'LINK', 'RX', 'MU') + AGED] + list(AGED)
+               for b in ((k, FAMILIES[k].sources), (k, USERS)))
 MAT_ORDER = (('MSE', ESTIMATORS), ('LINK', SOURCES), ('MSE', ('perfect',)), ('MSE', (BLIND,)), ('LINK', (BLIND,)), ('RX', SINGLE),
              ('MSE', (DELAY,)), ('MU', SINGLE + (DELAY,)), ('MSE', (BEAMS, DELAY_BEAMS)), ('MU', (BEAMS,))) + _WHOLE      # metrics.mat
 JSON_ORDER = (('MSE', ESTIMATORS + (BLIND, DELAY)), ('LINK', SINGLE), ('RX', SINGLE), ('MU', SINGLE + (DELAY,)), ('MU', USERS),
@@ -149,6 +166,41 @@ def scattering_args(channel):
         raise ValueError('unknown scattering channel parameters: %s' % sorted(unknown))
     out.update(channel)
     return out
+
+
+def aging_args(aging):
+    """`aging` as evaluate_level / run_sweep take it: None = off; a dict with delay_ms (required: the age of the channel in milliseconds)
+    and any of speed_mps (1.0), heading_deg (0.0: the azimuth of the motion in the transmitter's frame), random_heading (False: the
+    azimuth drawn per packet), carrier_hz (28e9).  Returns the dict with every default filled in, or None."""
+    if aging is None:
+        return None
+    out = dict(delay_ms=None, speed_mps=1.0, heading_deg=0.0, random_heading=False, carrier_hz=28e9)
+    unknown = set(aging) - set(out)
+    if unknown:
+        raise ValueError('unknown aging parameters: %s' % sorted(unknown))
+    out.update(aging)
+    if out['delay_ms'] is None or not np.isfinite(out['delay_ms']):
+        raise ValueError('aging needs a finite delay_ms, got %r' % (out['delay_ms'],))
+    if not (np.isfinite(out['speed_mps']) and out['speed_mps'] >= 0):
+        raise ValueError('aging: speed_mps %r must be finite and not negative' % (out['speed_mps'],))
+    if not np.isfinite(out['heading_deg']):
+        raise ValueError('aging: heading_deg %r must be finite' % (out['heading_deg'],))
+    if not (np.isfinite(out['carrier_hz']) and out['carrier_hz'] > 0):
+        raise ValueError('aging: carrier_hz %r must be finite and positive' % (out['carrier_hz'],))
+    return dict(delay_ms=float(out['delay_ms']), speed_mps=float(out['speed_mps']), heading_deg=float(out['heading_deg']),
+                random_heading=bool(out['random_heading']), carrier_hz=float(out['carrier_hz']))
+
+
+def aged_truth(engine, npkt, seed, first_pkt, channel, aging, amp_scale=True, az_offset=0.0):
+    """The true channel of one user's packets (user_estimates with the same seed, first_pkt, channel and az_offset) aging['delay_ms']
+    milliseconds behind the sounding instant (scatter_channel_at_device): new planes (re, im) [npkt, nr, nt, 234]."""
+    ch, ag = scattering_args(channel), aging_args(aging)
+    ch['az_deg'] = ch['az_deg'] + az_offset
+    h = engine.empty((npkt, engine.nr, engine.nt, N_DATA)), engine.empty((npkt, engine.nr, engine.nt, N_DATA))
+    engine.scatter_channel_at_device(seed, first_pkt, npkt, [1e-3 * ag['delay_ms']], h[0], h[1], speed_mps=ag['speed_mps'],
+                                     heading_az_deg=ag['heading_deg'], carrier_hz=ag['carrier_hz'], random_heading=ag['random_heading'],
+                                     amp_scale=amp_scale, **ch)
+    return h
 
 
 def make_dataset(engine, n_train, seed, n_taps=8, amp_scale=True, channel=None):
@@ -219,7 +271,8 @@ def user_estimates(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=Tr
 
 
 def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=True, keep=False, ber=None, channel=None, blind=False,
-                   rx_estimate=False, delay=None, mu=None, beams=False, mu_hybrid=None, mu_jsdm=None, feedback=None, rx_combine=False):
+                   rx_estimate=False, delay=None, mu=None, beams=False, mu_hybrid=None, mu_jsdm=None, feedback=None, rx_combine=False,
+                   aging=None):
     """One level: the estimates of npkt test packets at `snr_db` (user_estimates: packets first_pkt ... of stream `seed`, keep them
     disjoint from the training packets) and NMSE_subk of each against the true channel, then the data phases the options ask for (the
     table of the module).  Returns {'MSE_X': float64 [npkt], the per-link ratios averaged per packet} for X = LS, MMSE, DNN and every
@@ -228,7 +281,11 @@ def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=Tr
     reg='zf' | 'rzf', spacing=degrees), mu_hybrid = n_rf, mu_jsdm = {b, r_star, tol, mode}, feedback) with their per-user records.
     In the multi-user phase user 0 is the user above; user u >= 1 takes its packets from the stream seed + u (scattering channel: at
     azimuth az_deg + u spacing) and its estimates from the same calls, DLYANG left out.  rx_combine adds, behind every other call, the
-    families of combine_level.
+    families of combine_level.  aging (aging_args; scattering channel only) adds, behind all of that, every user's aged
+    true channel h_T (aged_truth) and against it 'MSEA_X' of every estimate and of 'perfect' - the sounding-time truth, the floor that
+    ageing alone sets - and, with ber / mu, the families of link_level ('bersA_X', 'EVM_rmsA_X', 'dtSNRA_X') and of mu_level's zero
+    forcing ('bersMUA_X', 'EVM_rmsMUA_X', 'sinrMUA_X', 'mua_users') with h_T in the place of the true channel: the weights of every
+    source still come from its sounding-time planes, seeds, bits and noise are those of the un-aged families.
     keep=True adds 'arrays': the DeviceArrays ltf_re, ltf_im, h_re, h_im, ls_re, ls_im (the caller frees them)."""
     nr, nt = engine.nr, engine.nt
     users = [user_estimates(engine, snr_db, npkt, seed, first_pkt, n_taps, amp_scale, channel, blind, delay, beams,
@@ -259,6 +316,23 @@ def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=Tr
             nv = np.stack([synth.link_noise_var(u['noise_std'].download(), amp_scale) for u in users])
             out.update(combine_level(engine, [{x: u['planes'][x] for x in EVERY if x in u['planes']} for u in users], nv, npkt, seed, first_pkt,
                                      ns=ber['ns'], n_sym=ber['n_sym'], bps=ber['bps'], reg=(mu or {}).get('reg', 'zf'), fb=feedback, mu=bool(mu)))
+    if aging:
+        spacing = float((mu or {}).get('spacing', 15.0))
+        aged = [aged_truth(engine, npkt, seed + u, first_pkt, channel, aging, amp_scale, az_offset=u * spacing) for u in range(len(users))]
+        d_link = engine.empty((npkt * nr * nt,))
+        for name, (e_re, e_im) in planes.items():
+            engine.nmse_device(aged[0][0], aged[0][1], e_re, e_im, npkt * nr * nt, N_DATA, d_per_link=d_link)
+            out[MSEA_FIELDS[0] + name] = d_link.download().astype(np.float64).reshape(npkt, nr * nt).mean(axis=1)
+        d_link.free()
+        if ber is not None:
+            out.update(link_level(engine, {x: planes[x] for x in SINGLE if x in planes}, aged[0][0], aged[0][1], d_std, npkt, seed, first_pkt,
+                                  amp_scale=amp_scale, fields=LINKA_FIELDS, **ber))
+            if mu:
+                nv = np.stack([synth.link_noise_var(u['noise_std'].download(), amp_scale) for u in users])
+                out.update(mu_level(engine, [{x: u['planes'][x] for x in EVERY if x in u['planes']} for u in users], nv, npkt, seed, first_pkt,
+                                    ns=ber['ns'], n_sym=ber['n_sym'], bps=ber['bps'], reg=mu.get('reg', 'zf'), true=aged, family='MUA'))
+        for a in (a for h in aged for a in h):
+            a.free()
     kept = users[0]['ltf'] + planes['perfect'] + planes['LS']
     for a in (a for u in users for a in u['free']):
         if not keep or all(a is not k for k in kept):
@@ -444,7 +518,8 @@ def combine_level(engine, planes, noise_var, npkt, seed, first_pkt, ns=1, n_sym=
     return out
 
 
-def mu_level(engine, planes, noise_var, npkt, seed, first_pkt, ns=1, n_sym=10, bps=2, reg='zf', n_rf=None, jsdm=None, fb=None):
+def mu_level(engine, planes, noise_var, npkt, seed, first_pkt, ns=1, n_sym=10, bps=2, reg='zf', n_rf=None, jsdm=None, fb=None, true=None,
+             family='MU'):
     """The multi-user data phase of one level on resident planes.  planes = one dict {X: (re, im)} per user, with the
     true channel under 'perfect'; noise_var float32 [U, npkt].  For every source X the precoder of the U users' X planes
     (mu_precoder_device; reg 'zf': none, 'rzf': M noise_var / Nt with the users' mean noise_var of the packet) carries coded QAM through
@@ -459,7 +534,10 @@ def mu_level(engine, planes, noise_var, npkt, seed, first_pkt, ns=1, n_sym=10, b
     'r_g', 'q_g': the mean kept rank and the mean number of nulled directions over packets and users}}.
     fb = {b_phi, b_psi, ng} adds, per source and in the same way, the data phase behind mu_precoder_device on the planes the base station
     rebuilds from every user's own report of ns columns (S V^H in the CSI layout): 'bersMUFB_X', 'EVM_rmsMUFB_X',
-    'sinrMUFB_X' and 'mufb_users': {X: {'bers', 'EVM_rms', 'sinr'}}."""
+    'sinrMUFB_X' and 'mufb_users': {X: {'bers', 'EVM_rms', 'sinr'}}.
+    true = one plane pair (re, im) per user puts these planes in the place of the true channels (the precoders still come from `planes`),
+    and family names the entry of FAMILIES whose fields and per-user record the zero-forcing variant fills: evaluate_level's aged data
+    phase passes the aged planes and 'MUA'."""
     nu, nt = len(planes), engine.nt
     m = nu * int(ns)
     if reg not in ('zf', 'rzf'):
@@ -471,13 +549,15 @@ def mu_level(engine, planes, noise_var, npkt, seed, first_pkt, ns=1, n_sym=10, b
     w = [engine.empty((npkt, m, nt, N_DATA)) for _ in range(2)]
     d_err, d_evm, d_sinr = (engine.empty((nu, npkt)) for _ in range(3))
     h_re, h_im = [p['perfect'][0] for p in planes], [p['perfect'][1] for p in planes]
+    if true is not None:
+        h_re, h_im = [t[0] for t in true], [t[1] for t in true]
     scratch = w + [d_err, d_evm, d_sinr, d_nv] + ([d_reg] if d_reg is not None else [])
 
     # The precoder variants in the order they run: (family, the step that leaves the precoder of the users' planes e_re[u], e_im[u] in
     # w, what the step adds to a source's per-user record - read after the data phase).
     def zero_forcing(e_re, e_im):
         engine.mu_precoder_device(e_re, e_im, npkt, ns, w[0], w[1], d_reg)
-    variants = [('MU', zero_forcing, dict)]
+    variants = [(family, zero_forcing, dict)]
     if n_rf:
         d_idx = engine.empty((npkt, int(n_rf)))
         scratch.append(d_idx)
@@ -521,14 +601,15 @@ def mu_level(engine, planes, noise_var, npkt, seed, first_pkt, ns=1, n_sym=10, b
 
 
 def link_level(engine, planes, h_re, h_im, d_noise_std, npkt, seed, first_pkt, ns=1, ntrf=None, n_sym=10, bps=2, amp_scale=True,
-               rx_estimate=False):
+               rx_estimate=False, fields=LINK_FIELDS):
     """The data phase of one level on resident planes: for every source X of `planes` = {X: (re, im) DeviceArrays [npkt,nr,nt,234]} the
     hybrid weights of X's planes (hybrid_weights_device) precode coded QAM through the TRUE channel h (link_sim_device) - the same
     bits and the same noise for every source, a paired comparison.  The noise level of a data symbol is that of the sounding phase
     (synth.link_noise_var of the packets' noise_std).  Returns {'bers_X': errors / n_info, 'EVM_rms_X', 'dtSNR_X'}: float64 [npkt].
     rx_estimate=True runs every source a second time on the same weights, bits and data noise with the receiver that estimates the
     effective channel from a precoded preamble (link_sim_rx_device) and adds 'bersRx_X', 'EVM_rmsRx_X' and 'gNMSE_X' (|Ghat - G|^2 /
-    |G|^2 per packet), after the fields above."""
+    |G|^2 per packet), after the fields above.  fields: the prefixes of the three metrics - evaluate_level's aged data phase
+    passes the aged planes as h and LINKA_FIELDS."""
     ntrf = int(ns if ntrf is None else ntrf)
     n_info, _ = engine.link_frame_bits(ns, n_sym, bps)
     d_nv = engine.to_device(synth.link_noise_var(d_noise_std.download(), amp_scale))
@@ -542,7 +623,7 @@ def link_level(engine, planes, h_re, h_im, d_noise_std, npkt, seed, first_pkt, n
         engine.hybrid_weights_device(e_re, e_im, npkt, ns, ntrf, fbb[0], fbb[1], d_idx, d_frf_mean_re=frf[0], d_frf_mean_im=frf[1])
         engine.link_sim_device(h_re, h_im, fbb[0], fbb[1], frf[0], frf[1], d_nv, seed, first_pkt, npkt, ns, ntrf, d_err, d_evm, d_gain,
                                n_sym=n_sym, bps=bps)
-        out.update(zip((f + name for f in LINK_FIELDS), _download_metrics(d_err, d_evm, d_gain, n_info)))
+        out.update(zip((f + name for f in fields), _download_metrics(d_err, d_evm, d_gain, n_info)))
         if rx_estimate:
             engine.link_sim_rx_device(h_re, h_im, fbb[0], fbb[1], frf[0], frf[1], d_nv, seed, first_pkt, npkt, ns, ntrf, *d_rx, n_sym=n_sym, bps=bps)
             out_rx.update(zip((f + name for f in RX_FIELDS), _download_metrics(d_rx[0], d_rx[1], d_rx[3], n_info)))
@@ -673,7 +754,7 @@ def combine_problem(ns, nr):
 def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500, seed=0, modeldir=None, fit_args=None, n_taps=8,
               amp_scale=True, save_dataset=None, verbose=True, ber=None, channel=None, blind=False, rx_estimate=False,
               delay_taps=None, delay_pre=0, users=None, mu_reg='zf', user_spacing=15.0, beams=False, mu_hybrid=None, mu_jsdm=None,
-              feedback=None, rx_combine=False):
+              feedback=None, rx_combine=False, aging=None):
     """Training set -> models (loaded from `modeldir`, else fitted and saved into `out`) -> every level (evaluate_level).  Writes
     <out>/BS<Nt>_SNR<s>/metrics.mat per level and <out>/sweep.json, prints the table, returns the result dict (with the per-packet
     arrays under 'per_packet' = {level: {'MSE_LS', ...}}).  Test packets come from the stream seed + 1, behind the index range of
@@ -682,7 +763,8 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
     with r_star = 4, tol = 0.05, mode = 'pgp' unless given; feedback_problem with ng = 1 unless given) and recorded in sweep.json under
     the key the table's `needs` name ('ber', 'channel': its parameters, 'blind', 'rx_estimate', 'mu': {users, reg, spacing},
     'mu_hybrid': {n_rf}, 'mu_jsdm': {b, r_star, tol, mode}, 'feedback': {b_phi, b_psi, ng, report_bits: the bits of one packet's
-    report}, 'delay': {taps, pre, rank}, 'beams', 'rx_combine': needs ber, one of feedback / users and ns <= min(4, Nr) - combine_problem);
+    report}, 'delay': {taps, pre, rank}, 'beams', 'rx_combine': needs ber, one of feedback / users and ns <= min(4, Nr) - combine_problem; 'aging': aging_args, needs the
+    scattering channel);
     a level of sweep.json then holds mean and confidence interval of every field the
     option adds, and the per-user records, in JSON_ORDER."""
     if feedback is not None:
@@ -723,6 +805,9 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
         problem = combine_problem(int(ber['ns']), engine.nr)
         if problem:
             raise ValueError('rx_combine: ' + problem)
+    aging = aging_args(aging)
+    if aging and channel is None:
+        raise ValueError('aging needs the scattering channel (channel): the tap channel has no geometry to move through')
     delay = (int(delay_taps), int(delay_pre)) if delay_taps else None
     os.makedirs(out, exist_ok=True)
     result = dict(nt=engine.nt, nr=engine.nr, n_train=int(n_train), n_test=int(n_test), seed=int(seed), n_taps=int(n_taps),
@@ -735,7 +820,7 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
                    rx_estimate=bool(rx_estimate), mu=mu and dict(mu), mu_hybrid=mu_hybrid and dict(n_rf=mu_hybrid), mu_jsdm=mu_jsdm and dict(mu_jsdm),
                    feedback=feedback and dict(feedback, report_bits=report_bits),
                    delay=delay and dict(taps=delay[0], pre=delay[1], rank=int(subspace.delay_basis(*delay)[0].shape[1])), beams=bool(beams),
-                   rx_combine=bool(rx_combine))
+                   rx_combine=bool(rx_combine), aging=aging and dict(aging))
     result.update((k, v) for k, v in options.items() if v)          # an option that is off leaves no key
     if modeldir:
         load_models(engine, modeldir)
@@ -756,7 +841,7 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
         t0 = time.perf_counter()
         mse = evaluate_level(engine, snr, n_test, seed + 1, n_train + i * n_test, n_taps, amp_scale, ber=ber, channel=channel, blind=blind,
                              rx_estimate=rx_estimate, delay=delay, mu=mu, beams=beams, mu_hybrid=mu_hybrid, mu_jsdm=mu_jsdm,
-                             feedback=feedback, **(dict(rx_combine=True) if rx_combine else {}))
+                             feedback=feedback, **(dict(rx_combine=True) if rx_combine else {}), **(dict(aging=aging) if aging else {}))
         lv = dict(snr_db=float(snr), seconds=time.perf_counter() - t0)
         write_metrics(os.path.join(out, 'BS%d_SNR%g' % (engine.nt, snr), 'metrics.mat'), mse)
         for key, field, _ in _columns(result):
@@ -829,6 +914,14 @@ def build_parser():
     p.add_argument('--userAz', default=30.0, type=float, help='--channel scattering: azimuth of the user in degrees')
     p.add_argument('--userEl', default=0.0, type=float, help='--channel scattering: elevation of the user in degrees')
     p.add_argument('--randomUsers', action='store_true', help='--channel scattering: draw the user position per packet (generate_maMIMO_LTF.m:48-51)')
+    p.add_argument('--aging', default=None, type=float, metavar='MS',
+                   help='--channel scattering: also evaluate against the channel MS milliseconds behind the sounding instant, for a user that moves '
+                        '(csi_scatter_channel_at_device) - MSEA_ (with MSEA_perfect, the floor of ageing alone), with --ber bersA_ / EVM_rmsA_ / dtSNRA_, '
+                        'with --users bersMUA_ / EVM_rmsMUA_ / sinrMUA_')
+    p.add_argument('--speed', default=1.0, type=float, metavar='MPS', help='--aging: speed of the user in metres per second')
+    p.add_argument('--heading', default=0.0, type=float, metavar='DEG', help='--aging: azimuth of the motion in the frame of --userAz, degrees')
+    p.add_argument('--randomHeading', action='store_true', help='--aging: draw the azimuth of the motion per packet')
+    p.add_argument('--carrier', default=28e9, type=float, metavar='HZ', help='--aging: carrier frequency (prm.fc)')
     p.add_argument('--blind', action='store_true',
                    help='add the estimator MMSEb: LMMSE smoothing from the packet\'s own statistics (csi_lmmse_blind_device) - MSE_MMSEb, and with --ber its link metrics')
     p.add_argument('--delayTaps', default=0, type=int, metavar='L',
@@ -845,6 +938,13 @@ def channel_from_args(args):
     if args.channel == 'taps':
         return None
     return dict(n_scat=args.scatterers, range_m=args.range, az_deg=args.userAz, el_deg=args.userEl, random_users=bool(args.randomUsers))
+
+
+def aging_from_args(args):
+    """The `aging` argument of run_sweep that the command line asks for: None without --aging."""
+    if args.aging is None:
+        return None
+    return dict(delay_ms=args.aging, speed_mps=args.speed, heading_deg=args.heading, random_heading=bool(args.randomHeading), carrier_hz=args.carrier)
 
 
 def parse_args(argv=None):
@@ -891,6 +991,13 @@ def parse_args(argv=None):
         parser.error('--delayTaps takes 1 .. %d and --delayPre 0 .. L' % subspace.MAX_RANK)
     if args.delayPre and not args.delayTaps:
         parser.error('--delayPre needs --delayTaps')
+    if args.aging is not None:
+        if args.channel != 'scattering':
+            parser.error('--aging needs --channel scattering: the tap channel has no geometry to move through')
+        try:
+            aging_args(aging_from_args(args))
+        except ValueError as err:
+            parser.error('--aging: ' + str(err))
     if args.beams and args.nTX > beamspace.MAX_NT:
         parser.error('--beams takes nTX up to %d' % beamspace.MAX_NT)
     return args
@@ -915,7 +1022,7 @@ def main(argv=None):
               mu_hybrid=args.muHybrid or None,
               mu_jsdm=dict(b=args.muJSDM, r_star=args.jsdmRank, tol=args.jsdmTol, mode=args.jsdmMode) if args.muJSDM else None,
               feedback=dict(b_phi=args.feedback[0], b_psi=args.feedback[1], ng=args.feedbackNg) if args.feedback is not None else None,
-              rx_combine=bool(args.rxCombine))
+              rx_combine=bool(args.rxCombine), aging=aging_from_args(args))
     return 0
 
 

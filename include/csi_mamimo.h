@@ -30,6 +30,9 @@
  *   NMSE_subk           BER_test_maMIMO_LTF.m:675-686                csi_nmse[_device]
  *   known-channel sounding packets  generate_maMIMO_LTF.m:197-342   csi_synth_structured
  *   phased.ScatteringMIMOChannel    helperApplyMUChannel.m:44-143   csi_synth_scattering
+ *   (an addition, no reference counterpart - the reference sets
+ *        'MaximumDopplerShift',0: that channel at later times for
+ *        a user that moves)                                          csi_scatter_channel_at_device
  *   omphybweights       BER_test_maMIMO_LTF.m:347-376                csi_hybrid_weights[_device]
  *   --execTime profiler loop                       DNN.py:441-475   csi_profile_*
  *   Model.fit step (noise, BN, dropout, Adam)       DNN.py:272-316   csi_train_*
@@ -43,7 +46,7 @@
  * context's stream and return without waiting; call csi_synchronize before reading results.
  *
  * Device pointers (csi_predict_device, csi_ls_estimate_device, csi_estimate_device, csi_lmmse_estimate_device, csi_lmmse_blind_device, csi_subspace_smooth_device, csi_beam_power_device, csi_beam_smooth_device, csi_beam_wiener_device, csi_null_noise_device, csi_nmse_device,
- * csi_hybrid_weights_device, csi_link_sim_device, csi_link_sim_rx_device, csi_mu_precoder_device, csi_mu_link_sim_device, csi_mu_hybrid_precoder_device, csi_mu_covariance_device, csi_mu_jsdm_precoder_device, csi_feedback_compress_device, csi_feedback_expand_device, csi_rx_combiner_device, csi_rx_apply_combiner_device, csi_viterbi_decode_device, csi_synth_*).  An array of exactly the documented
+ * csi_hybrid_weights_device, csi_link_sim_device, csi_link_sim_rx_device, csi_mu_precoder_device, csi_mu_link_sim_device, csi_mu_hybrid_precoder_device, csi_mu_covariance_device, csi_mu_jsdm_precoder_device, csi_feedback_compress_device, csi_feedback_expand_device, csi_rx_combiner_device, csi_rx_apply_combiner_device, csi_viterbi_decode_device, csi_synth_*, csi_scatter_channel_at_device).  An array of exactly the documented
  * size suffices: it may be a slice of a larger allocation whose neighbours hold live data of any value (NaN and 1e38 included).
  * Nothing outside the arrays is written, nothing outside them reaches a result, and input arrays are not modified.  Every re / im
  * PLANE (the preambles [npkt][Nr][len_ltf], the CSI planes [npkt][Nr][Nt][234 or n_out], fbb, frf_mean, xeq, gest, the precoder planes W, g) starts on a 16-byte
@@ -873,6 +876,45 @@ typedef struct {
  * "scatter_launches" (csi_get_option) counts the kernels launched. */
 int  csi_synth_scattering(csi_ctx* ctx, uint64_t seed, int64_t first_pkt, int64_t npkt, const float* snr_db, const csi_scatter_config* cfg,
                           float* d_ltf_re, float* d_ltf_im, float* d_h_re, float* d_h_im, float* d_noise_std, float* d_tau);
+
+/* Channel aging: the true channel of csi_synth_scattering's packets at other times, for a user that moves
+ * (csrc/scatter_aged.hip.h).  No reference counterpart: the reference's channel sets 'MaximumDopplerShift',0. */
+typedef struct {
+    float    speed_mps;                      /* >= 0; 0: a static user, every time returns the planes of csi_synth_scattering */
+    float    heading_az_deg, heading_el_deg; /* literal values, no default substitution; |el| <= 90 */
+    float    carrier_hz;                     /* 0 selects 28e9 (prm.fc) */
+    uint32_t flags;                          /* bit 0: heading azimuth drawn per packet; other bits must be 0 */
+} csi_motion_config;
+/* Packet p = first_pkt + i of stream `seed` has the scatterers, coefficients g_s, delays tau_s and direction cosines v_s, w_s of
+ * csi_synth_scattering: the same draws of kc = key(seed, p, 0), nothing moved.  The transmitter and the scatterers stand still; the user
+ * moves with speed_mps along the unit vector m = (cos el cos az, cos el sin az, sin el) of heading_az_deg / heading_el_deg in the
+ * transmitter's frame, the frame of az_deg / el_deg.  Only the last leg of path s changes: with o_s the scatterer's offset from the
+ * receiver it shortens at speed_mps (m . o_s) / |o_s| metres per second, so
+ *   nu_s = speed_mps carrier_hz / c  (m . o_s) / |o_s|      Hz; 0 for a zero offset; c = 299792458
+ *   H_t[r][j][f] = S^(-1/2) sum_s g_s exp(+2 pi i nu_s t) exp(2 pi i z_r w_s) exp(-2 pi i y_j v_s) exp(-2 pi i f tau_s / 256)
+ *   h_t = amp H_t on the 234 data bins in the LS layout, as in csi_synth_scattering; h_0 IS what that call returns, bit for bit, and
+ *   so is every h_t of a static user.
+ * The model is FIRST ORDER: delays and direction cosines are frozen at their t = 0 values.  That is good while speed_mps |t| is small
+ * against the scatterer box box_frac R - millimetres against metres for walking speed and milliseconds; nothing is refused on it.
+ * Random heading (flag bit 0): the azimuth of m is drawn per packet as 180 (2 uniform(kc, 3) - 1) degrees - index 3 of the channel
+ * stream is otherwise unused (the user takes 0 .. 2, scatterer s starts at 8 (s + 1)), so no existing draw moves - and the elevation
+ * stays as configured.
+ * Precision: nu_s and the product nu_s t are evaluated in fp64 by scatterer s's lane, next to the fp64 geometry; the turn count is
+ * reduced in fp64 (x - rint(x)) and rounded once to fp32 for sincospif; c_s is multiplied by that phasor in fp32; everything behind
+ * it is csi_synth_scattering's fp32 arithmetic in its order.  At t = 0 or speed 0 the phasor is exactly (1, 0).
+ *   cfg          as in csi_synth_scattering, defaults included (sample_rate_hz, n_scat, flag bits 0 and 1 act as there); NULL = all defaults
+ *   motion       NULL = a static user
+ *   t_s          HOST array of n_times seconds, 1 <= n_times <= 16, any sign and any order; it is read before the call returns and
+ *                travels to the kernel as kernel arguments, not as an upload
+ *   d_h_re/im    [n_times][npkt][nr][nt][234], 16-byte aligned: slice t is a plane pair that every consumer of CSI planes takes as it is
+ * No pilot matrix is needed: no LTF is made.  One launch per call, asynchronous on the context's stream; it may be captured between
+ * csi_capture_begin and csi_capture_end.  Serves fp32 and bf16 contexts alike.  Refused with text: everything csi_synth_scattering
+ * refuses about the context, cfg, npkt, first_pkt, alignment and LDS size; n_times outside 1 .. 16, a null t_s, a non-finite time, a
+ * negative or non-finite speed, a non-finite heading azimuth, |heading_el_deg| > 90, a negative or non-finite carrier, unknown motion
+ * flag bits, null planes with npkt > 0, npkt * nr beyond one launch.  npkt == 0 writes nothing.  A null context returns -1.  Profile
+ * entry "scatter_aged"; "scatter_aged_launches" (csi_get_option) counts its kernels ("scatter_launches" does not move). */
+int  csi_scatter_channel_at_device(csi_ctx* ctx, uint64_t seed, int64_t first_pkt, int64_t npkt, const csi_scatter_config* cfg,
+                                   const csi_motion_config* motion, const double* t_s, int n_times, float* d_h_re, float* d_h_im);
 
 /* ---- multi-GPU: packets shard over the GPUs of a node (one process and one context per GPU), the weights are shared and
  * read-only, outputs stay sharded.  The single collective of the path is the load-time broadcast of the
