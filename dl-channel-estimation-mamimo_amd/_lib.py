@@ -147,6 +147,16 @@ SYMBOLS = {
                                             _vp, _vp, _vp, _vp, _vp, _vp]),
     'csi_scatter_channel_at_device': (ctypes.c_int, [_ctx, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(CsiScatterConfig),
                                                      ctypes.POINTER(CsiMotionConfig), ctypes.POINTER(ctypes.c_double), ctypes.c_int, _vp, _vp]),
+    'csi_forecast_gram_device': (ctypes.c_int, [_ctx, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.c_int, ctypes.c_int64, _vp, _vp]),
+    'csi_forecast_gram_blocks_device': (ctypes.c_int, [_ctx, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.c_int, ctypes.c_int64, ctypes.c_int64, _vp, _vp]),
+    'csi_forecast_fit_device': (ctypes.c_int, [_ctx, _vp, _vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                               ctypes.c_uint32, _vp, _vp, _vp, _vp]),
+    'csi_forecast_apply_device': (ctypes.c_int, [_ctx, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.c_int, ctypes.c_int64, ctypes.c_int, _vp, _vp, _vp, _vp]),
+    'csi_forecast_device': (ctypes.c_int, [_ctx, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                           ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'csi_forecast': (ctypes.c_int, [_ctx, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                    ctypes.c_uint32, _fp, _fp, _fp, _fp, _fp, _vp]),
+    'csi_sounding_noise_device': (ctypes.c_int, [_ctx, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp]),
     'csi_profile_enable': (ctypes.c_int, [_ctx, ctypes.c_int]),
     'csi_profile_reset': (ctypes.c_int, [_ctx]),
     'csi_profile_num_kernels': (ctypes.c_int, []),

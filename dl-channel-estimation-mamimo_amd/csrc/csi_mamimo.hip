@@ -32,6 +32,7 @@
 #include "csi_feedback.hpp"
 #include "csi_rx_combine.hpp"
 #include "csi_scatter_aged.hpp"      // last: its kernels are emitted behind every other kernel, whose pc-relative addresses stay what they were
+#include "csi_forecast.hpp"          // ... and these behind them, for the same reason
 #include <initializer_list>
 
 namespace {
@@ -339,6 +340,7 @@ void csi_destroy(csi_ctx* c) {
     if (c->sub_q) hipFree(c->sub_q);
     if (c->beam_a) hipFree(c->beam_a);
     if (c->beam_ws) hipFree(c->beam_ws);
+    if (c->forecast_ws) hipFree(c->forecast_ws);
     if (c->hs_peak) hipFree(c->hs_peak);
     if (c->hs_zero) hipFree(c->hs_zero);
     if (c->fuse_ws) hipFree(c->fuse_ws);
@@ -952,6 +954,7 @@ int csi_get_option(csi_ctx* c, const char* name, int64_t* value) {
     }
     else if (n == "scatter_launches") *value = c->scatter_launches;
     else if (n == "scatter_aged_launches") *value = c->scatter_aged_launches;
+    else if (n == "forecast_launches") *value = c->forecast_launches;
     else if (n == "small_rows") *value = c->small_rows;
     else if (n == "small_rows_band") *value = c->small_rows_band;
     else if (n == "f32_engine") *value = c->f32_engine;
@@ -1816,6 +1819,49 @@ int csi_scatter_channel_at_device(csi_ctx* c, uint64_t seed, int64_t first_pkt, 
                                   const csi_motion_config* motion, const double* t_s, int n_times, float* d_h_re, float* d_h_im) {
     if (!c) return CSI_ERR_INVALID_ARG;
     return scatter_channel_at(c, seed, first_pkt, npkt, cfg, motion, t_s, n_times, d_h_re, d_h_im);
+}
+
+// ---- channel forecast (csi_forecast.hpp, forecast.hip.h)
+int csi_forecast_gram_device(csi_ctx* c, const float* const* d_x_re, const float* const* d_x_im, int n_snd, int64_t npkt, float* d_t_re, float* d_t_im) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return forecast_gram_device(c, d_x_re, d_x_im, n_snd, npkt, d_t_re, d_t_im);
+}
+
+int csi_forecast_gram_blocks_device(csi_ctx* c, const float* const* d_x_re, const float* const* d_x_im, int n_snd, int64_t n_blocks, int64_t block_floats,
+                                    float* d_t_re, float* d_t_im) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return forecast_gram_blocks_device(c, "csi_forecast_gram_blocks_device", d_x_re, d_x_im, n_snd, n_blocks, block_floats, d_t_re, d_t_im);
+}
+
+int csi_forecast_fit_device(csi_ctx* c, const float* d_t_re, const float* d_t_im, int n_snd, int64_t npkt, int order, int steps, double ridge,
+                            uint32_t flags, float* d_c_re, float* d_c_im, float* d_fit_err, int32_t* d_info) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return forecast_fit_device(c, d_t_re, d_t_im, n_snd, npkt, order, steps, ridge, flags, d_c_re, d_c_im, d_fit_err, d_info);
+}
+
+int csi_forecast_apply_device(csi_ctx* c, const float* const* d_x_re, const float* const* d_x_im, int n_snd, int64_t npkt, int order,
+                              const float* d_c_re, const float* d_c_im, float* d_out_re, float* d_out_im) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return forecast_apply_device(c, d_x_re, d_x_im, n_snd, npkt, order, d_c_re, d_c_im, d_out_re, d_out_im);
+}
+
+int csi_forecast_device(csi_ctx* c, const float* const* d_x_re, const float* const* d_x_im, int n_snd, int64_t npkt, int order, int steps, double ridge,
+                        uint32_t flags, float* d_out_re, float* d_out_im, float* d_c_re, float* d_c_im, float* d_fit_err, int32_t* d_info) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return forecast_device(c, "csi_forecast_device", d_x_re, d_x_im, n_snd, npkt, order, steps, ridge, flags, d_out_re, d_out_im, d_c_re, d_c_im,
+                           d_fit_err, d_info);
+}
+
+int csi_forecast(csi_ctx* c, const float* const* x_re, const float* const* x_im, int n_snd, int64_t npkt, int order, int steps, double ridge, uint32_t flags,
+                 float* out_re, float* out_im, float* c_re, float* c_im, float* fit_err, int32_t* info) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return forecast_host(c, x_re, x_im, n_snd, npkt, order, steps, ridge, flags, out_re, out_im, c_re, c_im, fit_err, info);
+}
+
+int csi_sounding_noise_device(csi_ctx* c, uint64_t seed, int64_t first_pkt, int64_t npkt, const float* d_err_var, const float* d_x_re, const float* d_x_im,
+                              float* d_out_re, float* d_out_im) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return sounding_noise_device(c, seed, first_pkt, npkt, d_err_var, d_x_re, d_x_im, d_out_re, d_out_im);
 }
 
 // ---- profiling

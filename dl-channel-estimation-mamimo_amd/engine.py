@@ -65,6 +65,24 @@ class DeviceArray:
             pass
 
 
+class DeviceView(DeviceArray):
+    """Row `index` along axis 0 of a DeviceArray as an array of its own (shape parent.shape[1:]) that owns no memory: one time slice
+    of scatter_channel_at's planes as a sounding of the forecast entries (CsiEngine.view makes it).  It keeps its parent alive; freeing
+    the parent by hand, or closing the engine, ends the view: free() only forgets the address."""
+
+    def __init__(self, parent, index):
+        if not 0 <= index < parent.shape[0]:
+            raise IndexError(f'view: index {index} outside 0 .. {parent.shape[0] - 1}')
+        self.engine, self.parent = parent.engine, parent
+        self.shape = parent.shape[1:]
+        self.nbytes = parent.nbytes // parent.shape[0]
+        self.ptr = parent.ptr + index * self.nbytes
+        self.engine._arrays.add(self)          # close() forgets the address with the parent's memory
+
+    def free(self):
+        self.ptr = 0
+
+
 HybridWeights = collections.namedtuple('HybridWeights', 'fbb idx n_atoms gain frf_mean')
 LinkResult = collections.namedtuple('LinkResult', 'bit_errors evm_rms dt_snr_db n_info xeq csi llr bits')
 LinkRxResult = collections.namedtuple('LinkRxResult', LinkResult._fields + ('g_nmse', 'gest'))
@@ -281,6 +299,10 @@ class CsiEngine:
 
     def empty(self, shape):
         return DeviceArray(self, shape)
+
+    def view(self, array, index):
+        """Row `index` along axis 0 of `array` as a DeviceView: no copy, no memory of its own."""
+        return DeviceView(array, int(index))
 
     def to_device(self, host):
         host = _f32c(host)
@@ -1445,6 +1467,69 @@ class CsiEngine:
         d_h = [self.empty((n_times, int(npkt), self.nr, self.nt, N_DATA)) for _ in range(2)]
         self.scatter_channel_at_device(seed, first_pkt, npkt, times_s, d_h[0], d_h[1], **kw)
         return d_h[0], d_h[1]
+
+    # ------------------------------------------------------------------ channel forecast (csrc/forecast.hip.h)
+    def forecast_gram_device(self, d_x_re, d_x_im, npkt, d_t_re, d_t_im):
+        """Gram matrix of P = len(d_x_re) soundings per (packet, rx) (csi_forecast_gram_device): d_x_re / d_x_im lists of DeviceArrays
+        [npkt,nr,nt,234], oldest first; T[i][q] = sum conj(x_i) x_q into d_t_re / d_t_im [npkt,nr,P,P].  Asynchronous."""
+        self._check(self._lib.csi_forecast_gram_device(self._ctx, self._ptr_array(d_x_re), self._ptr_array(d_x_im), len(d_x_re), int(npkt),
+                                                       d_t_re.ptr or None, d_t_im.ptr or None))
+
+    def forecast_gram_blocks_device(self, d_x_re, d_x_im, n_blocks, block_floats, d_t_re, d_t_im):
+        """The same kernel on n_blocks blocks of block_floats contiguous floats per plane (csi_forecast_gram_blocks_device): T
+        [n_blocks,P,P].  forecast_gram_device is the case (npkt nr, 234 nt)."""
+        self._check(self._lib.csi_forecast_gram_blocks_device(self._ctx, self._ptr_array(d_x_re), self._ptr_array(d_x_im), len(d_x_re), int(n_blocks),
+                                                              int(block_floats), d_t_re.ptr or None, d_t_im.ptr or None))
+
+    def forecast_fit_device(self, d_t_re, d_t_im, n_snd, npkt, order, steps, d_c_re, d_c_im, ridge=1e-5, pool_rx=False, d_fit_err=None, d_info=None):
+        """The predictor of every (packet, rx) from its Gram matrix (csi_forecast_fit_device): normal equations of order `order` for a
+        horizon of `steps` sounding intervals, ridge * trace / order on the diagonal, fp64 Cholesky; c into d_c_re / d_c_im
+        [npkt,nr,order].  pool_rx: one fit per packet from the summed systems of its rx antennas.  d_fit_err float [npkt,nr], d_info
+        [npkt,nr] int32 bits in a DeviceArray (1 = the fallback c = (1, 0, ..) was taken), both optional.  Asynchronous."""
+        self._check(self._lib.csi_forecast_fit_device(self._ctx, d_t_re.ptr or None, d_t_im.ptr or None, int(n_snd), int(npkt), int(order), int(steps),
+                                                      float(ridge), 1 if pool_rx else 0, d_c_re.ptr or None, d_c_im.ptr or None,
+                                                      d_fit_err.ptr if d_fit_err is not None else None, d_info.ptr if d_info is not None else None))
+
+    def forecast_apply_device(self, d_x_re, d_x_im, npkt, order, d_c_re, d_c_im, d_out_re, d_out_im):
+        """y = sum_m c_m x_{P-1-m} per (packet, rx) (csi_forecast_apply_device).  Asynchronous."""
+        self._check(self._lib.csi_forecast_apply_device(self._ctx, self._ptr_array(d_x_re), self._ptr_array(d_x_im), len(d_x_re), int(npkt), int(order),
+                                                        d_c_re.ptr or None, d_c_im.ptr or None, d_out_re.ptr or None, d_out_im.ptr or None))
+
+    def forecast_device(self, d_x_re, d_x_im, npkt, order, steps, d_out_re, d_out_im, ridge=1e-5, pool_rx=False, d_c_re=None, d_c_im=None,
+                        d_fit_err=None, d_info=None):
+        """Gram, fit and apply in sequence (csi_forecast_device), the same bits as the three calls; T and, without d_c_re / d_c_im, c
+        live in the engine's workspace (inside a capture an eager call of the same shape must have sized it).  Asynchronous."""
+        opt = [a.ptr if a is not None else None for a in (d_c_re, d_c_im, d_fit_err, d_info)]
+        self._check(self._lib.csi_forecast_device(self._ctx, self._ptr_array(d_x_re), self._ptr_array(d_x_im), len(d_x_re), int(npkt), int(order), int(steps),
+                                                  float(ridge), 1 if pool_rx else 0, d_out_re.ptr or None, d_out_im.ptr or None, *opt))
+
+    def sounding_noise_device(self, seed, first_pkt, npkt, d_err_var, d_x_re, d_x_im, d_out_re=None, d_out_im=None):
+        """White estimation error on a CSI plane pair (csi_sounding_noise_device): out = x + sqrt(v / 2) (n_re + i n_im) with v =
+        d_err_var [npkt,nr] and the normals of the noise stream of packets first_pkt .. of `seed`; in place without out planes.
+        Asynchronous."""
+        d_out_re = d_x_re if d_out_re is None else d_out_re
+        d_out_im = d_x_im if d_out_im is None else d_out_im
+        self._check(self._lib.csi_sounding_noise_device(self._ctx, int(seed), int(first_pkt), int(npkt), d_err_var.ptr or None, d_x_re.ptr or None,
+                                                        d_x_im.ptr or None, d_out_re.ptr or None, d_out_im.ptr or None))
+
+    def forecast(self, x, order, steps, ridge=1e-5, pool_rx=False, details=False):
+        """Channel forecast from host arrays (csi_forecast): x complex [P,npkt,nr,nt,234], the soundings oldest first and equally
+        spaced; returns the forecast of the channel `steps` intervals behind the newest one, complex64 [npkt,nr,nt,234].  With
+        ``details`` also (c complex64 [npkt,nr,order], fit_err float32 [npkt,nr], info int32 [npkt,nr])."""
+        x = np.asarray(x)
+        if x.ndim != 5 or x.shape[2:] != (self.nr, self.nt, N_DATA):
+            raise CsiError(-1, f'x must be [P,npkt,{self.nr},{self.nt},{N_DATA}], got {x.shape}')
+        P, npkt = x.shape[:2]
+        re, im = [_f32c(x[i].real) for i in range(P)], [_f32c(x[i].imag) for i in range(P)]
+        host = lambda planes: (ctypes.c_void_p * max(P, 1))(*[a.ctypes.data for a in planes])      # noqa: E731
+        o_re, o_im = np.empty((npkt, self.nr, self.nt, N_DATA), np.float32), np.empty((npkt, self.nr, self.nt, N_DATA), np.float32)
+        m = max(int(order), 0)
+        c_re, c_im = np.empty((npkt, self.nr, m), np.float32), np.empty((npkt, self.nr, m), np.float32)
+        fit_err, info = np.empty((npkt, self.nr), np.float32), np.empty((npkt, self.nr), np.int32)
+        self._check(self._lib.csi_forecast(self._ctx, host(re), host(im), P, npkt, int(order), int(steps), float(ridge), 1 if pool_rx else 0,
+                                           _fp(o_re), _fp(o_im), _fp(c_re), _fp(c_im), _fp(fit_err), info.ctypes.data))
+        out = self._c64(o_re, o_im)
+        return (out, self._c64(c_re, c_im), fit_err, info) if details else out
 
     def lmmse_estimate_device(self, d_h_re, d_h_im, npkt, d_hvec, L, d_snr_db, d_out_re, d_out_im):
         """LMMSE smoothing of device-resident LS planes (csi_lmmse_estimate_device): d_hvec [npkt][L], d_snr_db [npkt][nr]; asynchronous."""

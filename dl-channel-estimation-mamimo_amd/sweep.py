@@ -35,6 +35,10 @@ data phases to a level and nothing else: without an option every output is what 
                                                     moves; with --ber bersA_X, EVM_rmsA_X, dtSNRA_X and with --users bersMUA_X,
                                                     EVM_rmsMUA_X, sinrMUA_X, mua_users: the data phases of --ber and --users - the
                                                     same weights, bits and noise - through that aged channel
+    --forecast P M --forecastSteps D      --aging   MSEF_X for X = LS, perfect: the NMSE, against that aged channel, of the forecast           4.27
+      (forecast)                                    of order M from P soundings MS / D apart (the newest: X's own plane); with --users
+                                                    bersMUF_X, EVM_rmsMUF_X, sinrMUF_X, muf_users: the data phase of MUA with the
+                                                    forecast planes as estimates, same bits and noise
 
 FAMILIES below states this as data - fields, sources, switches, the per-user record - and MAT_ORDER / JSON_ORDER the two orders
 the rows are written in; metric_fields, format_table and the per-level summary of run_sweep are read off them.
@@ -46,10 +50,12 @@ the rows are written in; metric_fields, format_table and the per-level summary o
                                                             [--ber --users U [--muReg zf|rzf] [--userSpacing DEG] [--muHybrid NRF]
                                                              [--muJSDM B [--jsdmRank R] [--jsdmTol T] [--jsdmMode pgp|jgp]]]
                                                             [--feedback BPHI BPSI [--feedbackNg G]] [--rxCombine]
-                                                            [--channel scattering --aging MS [--speed MPS] [--heading DEG] [--randomHeading] [--carrier HZ]]
+                                                            [--channel scattering --aging MS [--speed MPS] [--heading DEG] [--randomHeading] [--carrier HZ]
+                                                             [--forecast P M [--forecastSteps D]]]
 
 The module holds no arithmetic of its own: packets come from csi_synth_structured / csi_synth_scattering, the aged channel from
-csi_scatter_channel_at_device, labels from
+csi_scatter_channel_at_device, its forecast from csi_forecast_device on soundings made of that call and
+csi_sounding_noise_device, labels from
 csi_ls_estimate_device, the fit from trainer.fit, the estimates from csi_estimate_device, csi_lmmse_estimate_device,
 csi_lmmse_blind_device, csi_subspace_smooth_device (basis: subspace.delay_basis) and csi_beam_wiener_device (beams:
 beamspace.dft_basis, error level: csi_null_noise_device), every NMSE from csi_nmse_device, the precoders from
@@ -89,6 +95,10 @@ MU_FIELDS = ('bersMU_', 'EVM_rmsMU_', 'sinrMU_')    # --users: the multi-user da
 MSEA_FIELDS = ('MSEA_',)
 LINKA_FIELDS = ('bersA_', 'EVM_rmsA_', 'dtSNRA_')
 MUA_FIELDS = ('bersMUA_', 'EVM_rmsMUA_', 'sinrMUA_')
+# --forecast: the NMSE and the zero-forcing data phase of MUA with the forecast of the aged channel in the place of the estimate
+MSEF_FIELDS = ('MSEF_',)
+MUF_FIELDS = ('bersMUF_', 'EVM_rmsMUF_', 'sinrMUF_')
+FORECAST_SOURCES = ('LS', 'perfect')      # the sources whose history can be simulated: the truth, and LS, whose error is white
 DELAY = 'DLY'                            # --delayTaps: the LS rows projected onto a window of delay taps (csi_subspace_smooth_device, w = 1)
 BEAMS = 'ANG'                            # --beams: the beam-space Wiener smoother across the Tx antennas on the LS planes (csi_beam_wiener_device)
 DELAY_BEAMS = 'DLYANG'                   # --beams with --delayTaps: the same step on the DLY planes
@@ -111,6 +121,9 @@ FAMILIES = dict(
     MSEA=Family(MSEA_FIELDS, MSEA_FIELDS, ESTIMATORS + ('perfect', BLIND, DELAY, BEAMS, DELAY_BEAMS), ('aging',), None),
     LINKA=Family(LINKA_FIELDS, LINKA_FIELDS, SINGLE, ('aging', 'ber'), None),
     MUA=Family(MUA_FIELDS, MUA_FIELDS, EVERY, ('aging', 'mu'), 'mua_users'),
+    # the forecast twins of MSEA and MUA (--forecast): written behind the aged families (FORECAST below)
+    MSEF=Family(MSEF_FIELDS, MSEF_FIELDS, FORECAST_SOURCES, ('aging', 'forecast'), None),
+    MUF=Family(MUF_FIELDS, MUF_FIELDS, FORECAST_SOURCES, ('aging', 'forecast', 'mu'), 'muf_users'),
     MUH=Family(MUH_FIELDS, MUH_FIELDS, EVERY, ('mu_hybrid',), 'muh_users'),
     MUJ=Family(MUJ_FIELDS, MUJ_FIELDS, EVERY, ('mu_jsdm',), 'muj_users'),
     FB=Family(FB_FIELDS, FB_FIELDS, SINGLE, ('feedback',), None),
@@ -120,10 +133,12 @@ FAMILIES = dict(
     MUFBC=Family(MUFBC_FIELDS, MUFBC_FIELDS, EVERY, ('feedback', 'mu', 'rx_combine'), 'mufbc_users'))
 # The two orders the rows (family, source) are written in, as blocks (family, sources) - source-major within a block - and
 # (family, USERS) for the per-user record.  Both are contracts with whoever reads the files.  They differ in their heads, which grew
-# option by option; every family behind MU stands whole, in the order of the table, at the end of both - the aged families last.
+# option by option; every family behind MU stands whole, in the order of the table, at the end of both - the aged families behind the
+# others, the forecast families last.
 USERS = ()
 AGED = ('MSEA', 'LINKA', 'MUA')
-_WHOLE = tuple(b for k in [k for k in FAMILIES if k not in ('MSE', 'LINK', 'RX', 'MU') + AGED] + list(AGED)
+FORECAST = ('MSEF', 'MUF')
+_WHOLE = tuple(b for k in [k for k in FAMILIES if k not in ('MSE', 'LINK', 'RX', 'MU') + AGED + FORECAST] + list(AGED + FORECAST)
                for b in ((k, FAMILIES[k].sources), (k, USERS)))
 MAT_ORDER = (('MSE', ESTIMATORS), ('LINK', SOURCES), ('MSE', ('perfect',)), ('MSE', (BLIND,)), ('LINK', (BLIND,)), ('RX', SINGLE),
              ('MSE', (DELAY,)), ('MU', SINGLE + (DELAY,)), ('MSE', (BEAMS, DELAY_BEAMS)), ('MU', (BEAMS,))) + _WHOLE      # metrics.mat
@@ -203,6 +218,65 @@ def aged_truth(engine, npkt, seed, first_pkt, channel, aging, amp_scale=True, az
     return h
 
 
+def forecast_args(forecast):
+    """`forecast` as evaluate_level / run_sweep take it: None = off; a dict with soundings (P, 2 .. 16) and order (M, 1 .. 8), both
+    required, and any of steps (4: D, the horizon in sounding intervals, M + D <= P) and ridge (1e-5).  Returns the dict with every
+    default filled in, or None."""
+    if forecast is None:
+        return None
+    out = dict(soundings=None, order=None, steps=4, ridge=1e-5)
+    unknown = set(forecast) - set(out)
+    if unknown:
+        raise ValueError('unknown forecast parameters: %s' % sorted(unknown))
+    out.update(forecast)
+    if out['soundings'] is None or out['order'] is None:
+        raise ValueError('forecast needs soundings and order, got %r' % (forecast,))
+    P, M, D = int(out['soundings']), int(out['order']), int(out['steps'])
+    if not 2 <= P <= 16:
+        raise ValueError('forecast: soundings %d outside 2 .. 16' % P)
+    if not 1 <= M <= 8:
+        raise ValueError('forecast: order %d outside 1 .. 8' % M)
+    if D < 1 or M + D > P:
+        raise ValueError('forecast: steps %d must be at least 1 and order %d + steps %d at most soundings %d' % (D, M, D, P))
+    if not (np.isfinite(out['ridge']) and out['ridge'] >= 0):
+        raise ValueError('forecast: ridge %r must be finite and not negative' % (out['ridge'],))
+    return dict(soundings=P, order=M, steps=D, ridge=float(out['ridge']))
+
+
+def forecast_planes(engine, user, npkt, seed, first_pkt, channel, aging, forecast, amp_scale=True, az_offset=0.0):
+    """The forecast of one user's channel aging['delay_ms'] milliseconds ahead for the sources FORECAST_SOURCES of
+    `user` (user_estimates with the same seed, first_pkt, channel and az_offset): P = forecast['soundings'] soundings delay_ms / steps
+    apart, t_i = -(P - 1 - i) delay_ms / steps.  One scatter_channel_at_device call gives the P - 1 earlier slices; the newest sounding
+    is the source's own sounding-time plane, untouched.  'perfect' takes the slices as they are; 'LS' adds sounding_noise_device to
+    slice i with v = null_noise / Nt of the user's packets and the seed `seed ^ ((i + 1) << 32)`.  Returns {X: (re, im)} of new
+    DeviceArrays [npkt, nr, nt, 234] (forecast_device)."""
+    ch, ag, fc = scattering_args(channel), aging_args(aging), forecast_args(forecast)
+    ch['az_deg'] = ch['az_deg'] + az_offset
+    nr, nt, P = engine.nr, engine.nt, fc['soundings']
+    times = [-1e-3 * (P - 1 - i) * ag['delay_ms'] / fc['steps'] for i in range(P - 1)]
+    d_nv = engine.empty((npkt, nr, 2))
+    engine.null_noise_device(user['ltf'][0], user['ltf'][1], npkt, d_nv)
+    d_v = engine.to_device((d_nv.download().view(np.float64)[..., 0] / nt).astype(np.float32))
+    d_nv.free()
+    out = {}
+    for name in FORECAST_SOURCES:
+        past = engine.empty((P - 1, npkt, nr, nt, N_DATA)), engine.empty((P - 1, npkt, nr, nt, N_DATA))
+        engine.scatter_channel_at_device(seed, first_pkt, npkt, times, past[0], past[1], speed_mps=ag['speed_mps'], heading_az_deg=ag['heading_deg'],
+                                         carrier_hz=ag['carrier_hz'], random_heading=ag['random_heading'], amp_scale=amp_scale, **ch)
+        x_re = [engine.view(past[0], i) for i in range(P - 1)] + [user['planes'][name][0]]
+        x_im = [engine.view(past[1], i) for i in range(P - 1)] + [user['planes'][name][1]]
+        if name == 'LS':
+            for i in range(P - 1):
+                engine.sounding_noise_device(seed ^ ((i + 1) << 32), first_pkt, npkt, d_v, x_re[i], x_im[i])
+        out[name] = engine.empty((npkt, nr, nt, N_DATA)), engine.empty((npkt, nr, nt, N_DATA))
+        engine.forecast_device(x_re, x_im, npkt, fc['order'], fc['steps'], out[name][0], out[name][1], ridge=fc['ridge'])
+        engine.synchronize()
+        for a in past:
+            a.free()
+    d_v.free()
+    return out
+
+
 def make_dataset(engine, n_train, seed, n_taps=8, amp_scale=True, channel=None):
     """Noise-free training packets generated on the device (the pipeline trains on "SNR 120 ... NOISELESS" packets,
     full_pipeline_maMIMO_DNNEst.sh:21,33) with the LS estimate of the same signal as labels, as the dataset's y is
@@ -272,7 +346,7 @@ def user_estimates(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=Tr
 
 def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=True, keep=False, ber=None, channel=None, blind=False,
                    rx_estimate=False, delay=None, mu=None, beams=False, mu_hybrid=None, mu_jsdm=None, feedback=None, rx_combine=False,
-                   aging=None):
+                   aging=None, forecast=None):
     """One level: the estimates of npkt test packets at `snr_db` (user_estimates: packets first_pkt ... of stream `seed`, keep them
     disjoint from the training packets) and NMSE_subk of each against the true channel, then the data phases the options ask for (the
     table of the module).  Returns {'MSE_X': float64 [npkt], the per-link ratios averaged per packet} for X = LS, MMSE, DNN and every
@@ -286,6 +360,9 @@ def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=Tr
     ageing alone sets - and, with ber / mu, the families of link_level ('bersA_X', 'EVM_rmsA_X', 'dtSNRA_X') and of mu_level's zero
     forcing ('bersMUA_X', 'EVM_rmsMUA_X', 'sinrMUA_X', 'mua_users') with h_T in the place of the true channel: the weights of every
     source still come from its sounding-time planes, seeds, bits and noise are those of the un-aged families.
+    forecast (forecast_args; needs aging) adds, behind the aged families, every user's forecast planes (forecast_planes) and against h_T
+    'MSEF_X' for X = LS, perfect and, with mu, the zero-forcing data phase of MUA with the forecast planes as estimates ('bersMUF_X',
+    'EVM_rmsMUF_X', 'sinrMUF_X', 'muf_users').
     keep=True adds 'arrays': the DeviceArrays ltf_re, ltf_im, h_re, h_im, ls_re, ls_im (the caller frees them)."""
     nr, nt = engine.nr, engine.nt
     users = [user_estimates(engine, snr_db, npkt, seed, first_pkt, n_taps, amp_scale, channel, blind, delay, beams,
@@ -331,6 +408,19 @@ def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=Tr
                 nv = np.stack([synth.link_noise_var(u['noise_std'].download(), amp_scale) for u in users])
                 out.update(mu_level(engine, [{x: u['planes'][x] for x in EVERY if x in u['planes']} for u in users], nv, npkt, seed, first_pkt,
                                     ns=ber['ns'], n_sym=ber['n_sym'], bps=ber['bps'], reg=mu.get('reg', 'zf'), true=aged, family='MUA'))
+        if forecast:
+            ahead = [forecast_planes(engine, users[u], npkt, seed + u, first_pkt, channel, aging, forecast, amp_scale, az_offset=u * spacing)
+                     for u in range(len(users))]
+            d_link = engine.empty((npkt * nr * nt,))
+            for name, (e_re, e_im) in ahead[0].items():
+                engine.nmse_device(aged[0][0], aged[0][1], e_re, e_im, npkt * nr * nt, N_DATA, d_per_link=d_link)
+                out[MSEF_FIELDS[0] + name] = d_link.download().astype(np.float64).reshape(npkt, nr * nt).mean(axis=1)
+            d_link.free()
+            if ber is not None and mu:
+                out.update(mu_level(engine, ahead, nv, npkt, seed, first_pkt, ns=ber['ns'], n_sym=ber['n_sym'], bps=ber['bps'],
+                                    reg=mu.get('reg', 'zf'), true=aged, family='MUF'))
+            for a in (a for f in ahead for p in f.values() for a in p):
+                a.free()
         for a in (a for h in aged for a in h):
             a.free()
     kept = users[0]['ltf'] + planes['perfect'] + planes['LS']
@@ -754,7 +844,7 @@ def combine_problem(ns, nr):
 def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500, seed=0, modeldir=None, fit_args=None, n_taps=8,
               amp_scale=True, save_dataset=None, verbose=True, ber=None, channel=None, blind=False, rx_estimate=False,
               delay_taps=None, delay_pre=0, users=None, mu_reg='zf', user_spacing=15.0, beams=False, mu_hybrid=None, mu_jsdm=None,
-              feedback=None, rx_combine=False, aging=None):
+              feedback=None, rx_combine=False, aging=None, forecast=None):
     """Training set -> models (loaded from `modeldir`, else fitted and saved into `out`) -> every level (evaluate_level).  Writes
     <out>/BS<Nt>_SNR<s>/metrics.mat per level and <out>/sweep.json, prints the table, returns the result dict (with the per-packet
     arrays under 'per_packet' = {level: {'MSE_LS', ...}}).  Test packets come from the stream seed + 1, behind the index range of
@@ -764,7 +854,7 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
     the key the table's `needs` name ('ber', 'channel': its parameters, 'blind', 'rx_estimate', 'mu': {users, reg, spacing},
     'mu_hybrid': {n_rf}, 'mu_jsdm': {b, r_star, tol, mode}, 'feedback': {b_phi, b_psi, ng, report_bits: the bits of one packet's
     report}, 'delay': {taps, pre, rank}, 'beams', 'rx_combine': needs ber, one of feedback / users and ns <= min(4, Nr) - combine_problem; 'aging': aging_args, needs the
-    scattering channel);
+    scattering channel; 'forecast': forecast_args, needs aging);
     a level of sweep.json then holds mean and confidence interval of every field the
     option adds, and the per-user records, in JSON_ORDER."""
     if feedback is not None:
@@ -808,6 +898,9 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
     aging = aging_args(aging)
     if aging and channel is None:
         raise ValueError('aging needs the scattering channel (channel): the tap channel has no geometry to move through')
+    forecast = forecast_args(forecast)
+    if forecast and not aging:
+        raise ValueError('forecast needs aging (and with it the scattering channel): it forecasts the aged channel')
     delay = (int(delay_taps), int(delay_pre)) if delay_taps else None
     os.makedirs(out, exist_ok=True)
     result = dict(nt=engine.nt, nr=engine.nr, n_train=int(n_train), n_test=int(n_test), seed=int(seed), n_taps=int(n_taps),
@@ -820,7 +913,7 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
                    rx_estimate=bool(rx_estimate), mu=mu and dict(mu), mu_hybrid=mu_hybrid and dict(n_rf=mu_hybrid), mu_jsdm=mu_jsdm and dict(mu_jsdm),
                    feedback=feedback and dict(feedback, report_bits=report_bits),
                    delay=delay and dict(taps=delay[0], pre=delay[1], rank=int(subspace.delay_basis(*delay)[0].shape[1])), beams=bool(beams),
-                   rx_combine=bool(rx_combine), aging=aging and dict(aging))
+                   rx_combine=bool(rx_combine), aging=aging and dict(aging), forecast=forecast and dict(forecast))
     result.update((k, v) for k, v in options.items() if v)          # an option that is off leaves no key
     if modeldir:
         load_models(engine, modeldir)
@@ -841,7 +934,8 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
         t0 = time.perf_counter()
         mse = evaluate_level(engine, snr, n_test, seed + 1, n_train + i * n_test, n_taps, amp_scale, ber=ber, channel=channel, blind=blind,
                              rx_estimate=rx_estimate, delay=delay, mu=mu, beams=beams, mu_hybrid=mu_hybrid, mu_jsdm=mu_jsdm,
-                             feedback=feedback, **(dict(rx_combine=True) if rx_combine else {}), **(dict(aging=aging) if aging else {}))
+                             feedback=feedback, **(dict(rx_combine=True) if rx_combine else {}), **(dict(aging=aging) if aging else {}),
+                             **(dict(forecast=forecast) if forecast else {}))
         lv = dict(snr_db=float(snr), seconds=time.perf_counter() - t0)
         write_metrics(os.path.join(out, 'BS%d_SNR%g' % (engine.nt, snr), 'metrics.mat'), mse)
         for key, field, _ in _columns(result):
@@ -922,6 +1016,10 @@ def build_parser():
     p.add_argument('--heading', default=0.0, type=float, metavar='DEG', help='--aging: azimuth of the motion in the frame of --userAz, degrees')
     p.add_argument('--randomHeading', action='store_true', help='--aging: draw the azimuth of the motion per packet')
     p.add_argument('--carrier', default=28e9, type=float, metavar='HZ', help='--aging: carrier frequency (prm.fc)')
+    p.add_argument('--forecast', default=None, type=int, nargs=2, metavar=('P', 'M'),
+                   help='--aging: also forecast the aged channel with a linear predictor of order M over P soundings MS / D apart '
+                        '(csi_forecast_device; sources LS and perfect) - MSEF_, with --users bersMUF_ / EVM_rmsMUF_ / sinrMUF_')
+    p.add_argument('--forecastSteps', default=4, type=int, metavar='D', help='--forecast: the horizon MS in sounding intervals')
     p.add_argument('--blind', action='store_true',
                    help='add the estimator MMSEb: LMMSE smoothing from the packet\'s own statistics (csi_lmmse_blind_device) - MSE_MMSEb, and with --ber its link metrics')
     p.add_argument('--delayTaps', default=0, type=int, metavar='L',
@@ -938,6 +1036,13 @@ def channel_from_args(args):
     if args.channel == 'taps':
         return None
     return dict(n_scat=args.scatterers, range_m=args.range, az_deg=args.userAz, el_deg=args.userEl, random_users=bool(args.randomUsers))
+
+
+def forecast_from_args(args):
+    """The `forecast` argument of run_sweep that the command line asks for: None without --forecast."""
+    if args.forecast is None:
+        return None
+    return dict(soundings=args.forecast[0], order=args.forecast[1], steps=args.forecastSteps)
 
 
 def aging_from_args(args):
@@ -998,6 +1103,15 @@ def parse_args(argv=None):
             aging_args(aging_from_args(args))
         except ValueError as err:
             parser.error('--aging: ' + str(err))
+    if args.forecast is not None:
+        if args.channel != 'scattering' or args.aging is None:
+            parser.error('--forecast needs --channel scattering --aging MS: it forecasts the aged channel')
+        try:
+            forecast_args(forecast_from_args(args))
+        except ValueError as err:
+            parser.error('--forecast: ' + str(err))
+    elif args.forecastSteps != 4:
+        parser.error('--forecastSteps needs --forecast')
     if args.beams and args.nTX > beamspace.MAX_NT:
         parser.error('--beams takes nTX up to %d' % beamspace.MAX_NT)
     return args
@@ -1022,7 +1136,7 @@ def main(argv=None):
               mu_hybrid=args.muHybrid or None,
               mu_jsdm=dict(b=args.muJSDM, r_star=args.jsdmRank, tol=args.jsdmTol, mode=args.jsdmMode) if args.muJSDM else None,
               feedback=dict(b_phi=args.feedback[0], b_psi=args.feedback[1], ng=args.feedbackNg) if args.feedback is not None else None,
-              rx_combine=bool(args.rxCombine), aging=aging_from_args(args))
+              rx_combine=bool(args.rxCombine), aging=aging_from_args(args), forecast=forecast_from_args(args))
     return 0
 
 

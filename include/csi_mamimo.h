@@ -33,6 +33,8 @@
  *   (an addition, no reference counterpart - the reference sets
  *        'MaximumDopplerShift',0: that channel at later times for
  *        a user that moves)                                          csi_scatter_channel_at_device
+ *   (an addition: a linear predictor over several soundings of
+ *        that channel, fitted on the soundings themselves)          csi_forecast[_device], csi_forecast_gram/fit/apply_device, csi_sounding_noise_device
  *   omphybweights       BER_test_maMIMO_LTF.m:347-376                csi_hybrid_weights[_device]
  *   --execTime profiler loop                       DNN.py:441-475   csi_profile_*
  *   Model.fit step (noise, BN, dropout, Adam)       DNN.py:272-316   csi_train_*
@@ -46,7 +48,7 @@
  * context's stream and return without waiting; call csi_synchronize before reading results.
  *
  * Device pointers (csi_predict_device, csi_ls_estimate_device, csi_estimate_device, csi_lmmse_estimate_device, csi_lmmse_blind_device, csi_subspace_smooth_device, csi_beam_power_device, csi_beam_smooth_device, csi_beam_wiener_device, csi_null_noise_device, csi_nmse_device,
- * csi_hybrid_weights_device, csi_link_sim_device, csi_link_sim_rx_device, csi_mu_precoder_device, csi_mu_link_sim_device, csi_mu_hybrid_precoder_device, csi_mu_covariance_device, csi_mu_jsdm_precoder_device, csi_feedback_compress_device, csi_feedback_expand_device, csi_rx_combiner_device, csi_rx_apply_combiner_device, csi_viterbi_decode_device, csi_synth_*, csi_scatter_channel_at_device).  An array of exactly the documented
+ * csi_hybrid_weights_device, csi_link_sim_device, csi_link_sim_rx_device, csi_mu_precoder_device, csi_mu_link_sim_device, csi_mu_hybrid_precoder_device, csi_mu_covariance_device, csi_mu_jsdm_precoder_device, csi_feedback_compress_device, csi_feedback_expand_device, csi_rx_combiner_device, csi_rx_apply_combiner_device, csi_viterbi_decode_device, csi_synth_*, csi_scatter_channel_at_device, csi_forecast_*_device, csi_sounding_noise_device).  An array of exactly the documented
  * size suffices: it may be a slice of a larger allocation whose neighbours hold live data of any value (NaN and 1e38 included).
  * Nothing outside the arrays is written, nothing outside them reaches a result, and input arrays are not modified.  Every re / im
  * PLANE (the preambles [npkt][Nr][len_ltf], the CSI planes [npkt][Nr][Nt][234 or n_out], fbb, frf_mean, xeq, gest, the precoder planes W, g) starts on a 16-byte
@@ -915,6 +917,61 @@ typedef struct {
  * entry "scatter_aged"; "scatter_aged_launches" (csi_get_option) counts its kernels ("scatter_launches" does not move). */
 int  csi_scatter_channel_at_device(csi_ctx* ctx, uint64_t seed, int64_t first_pkt, int64_t npkt, const csi_scatter_config* cfg,
                                    const csi_motion_config* motion, const double* t_s, int n_times, float* d_h_re, float* d_h_im);
+
+/* Channel forecasting: a linear predictor over several soundings (csrc/forecast.hip.h).  No reference counterpart (the
+ * reference's channel does not move); it is what a transmitter does about the ageing csi_scatter_channel_at_device shows.
+ * The soundings x_0 .. x_{n_snd-1} run oldest to newest and are equally spaced; each is a CSI plane pair [npkt][nr][nt][234].  They
+ * arrive as HOST arrays of n_snd device pointers (the convention of csi_mu_precoder_device).  With P = n_snd, order M, horizon
+ * d = steps (in sounding intervals), 2 <= P <= 16, 1 <= M <= 8, d >= 1, M + d <= P, per (packet, rx):
+ *   T[i][q]  = sum_j sum_k conj(x_i[j][k]) x_q[j][k]                 P x P, Hermitian to the bit       csi_forecast_gram_device
+ *   G[a][b]  = sum_{p = M+d-1}^{P-1} T[p-d-a][p-d-b]                 M x M
+ *   rhs[a]   = sum_{p = M+d-1}^{P-1} T[p-d-a][p]
+ *   (G + ridge trace(G) / M I) c = rhs                               fp64 Cholesky, c rounded to fp32  csi_forecast_fit_device
+ *   y[j][k]  = sum_{m < M} c_m x_{P-1-m}[j][k]                       the forecast of x at index P-1+d  csi_forecast_apply_device
+ * flags bit 0 (pooling): G, rhs and the target energy of a packet's receive antennas are added in ascending rx order before the solve;
+ * every rx of the packet gets the same c, fit_err and info.  Other bits must be 0.
+ * Fallback: a pivot <= 0 or not finite (all-zero planes included) gives c = (1, 0, .., 0) - the newest sounding is held - and info 1
+ * (0 otherwise).  fit_err = max(0, 1 - Re(c^H rhs) / sum_{p = M+d-1}^{P-1} T[p][p]) with the fp64 c, the in-sample relative residual
+ * (0 where that energy is not positive).  ridge is taken literally (0 is 0; the Python default is 1e-5): without it the noise-free
+ * system of a smooth channel has a condition number near 1e7.
+ * Arithmetic: T on the fp32 matrix cores (three v_mfma_f32_16x16x4_f32 products per four floats, re = RR + II, im = RI - RI^T), the
+ * order of every sum fixed by (nt, P) alone, no atomics: a (packet, rx) has the same bits whatever the call size or its position.
+ * The fit in fp64 from the fp32 T.  The apply pass in fp32, complex FMAs in the order m = 0 .. M-1.
+ *   d_t_re/im    [npkt][nr][P][P], 16-byte aligned
+ *   d_c_re/im    [npkt][nr][M]
+ *   d_fit_err    float [npkt][nr] or NULL;  d_info  int32 [npkt][nr] or NULL
+ *   d_out_re/im  a plane pair like a sounding, 16-byte aligned
+ * csi_forecast_gram_blocks_device is the Gram kernel on its own terms: n_blocks blocks of block_floats contiguous floats per plane
+ * (even, >= 2: a block starts on an 8-byte boundary; the kernel assumes nothing wider), T [n_blocks][P][P]; csi_forecast_gram_device
+ * is the case (npkt nr, 234 nt) of it.
+ * csi_forecast_device runs the three in sequence - the same bits as the three calls made by hand; T and, when d_c_re / d_c_im are
+ * NULL, c live in a context workspace sized by eager calls: inside a capture (csi_capture_begin) the workspace must already hold the
+ * call, so an eager call of the same shape goes first.  csi_forecast: the same on host buffers (x_re / x_im: host arrays of n_snd host
+ * pointers), in packet chunks of 256 MiB of staging (the context's workspace_bytes when that is smaller); same bits as the device entry; its host arrays obey the overlap rule of
+ * the device entries (no output array may share a byte with a sounding or with another output).
+ * csi_sounding_noise_device gives a simulated history its estimation error: out = x + s (n_re + i n_im), s = sqrtf(0.5f v[p][r]),
+ * n_re / n_im = normal(kn, 2 e) / normal(kn, 2 e + 1), kn the noise key of packet first_pkt + p of stream `seed` (kind 1 of
+ * csi_synth_structured), e = (r nt + j) 234 + k; one fused multiply-add per component.  d_err_var float [npkt][nr].  out may be x
+ * itself (re with re, im with im); a zero v returns the input bits.
+ * Every entry is asynchronous on the context's stream and may be captured.  Refused with text, before any launch: n_snd, order, steps
+ * outside the ranges above, a negative npkt (or first_pkt), npkt * nr beyond one launch, a non-finite or negative ridge, unknown flag
+ * bits, null required pointers, planes off a 16-byte boundary, an output that overlaps an input or another output (the noise entry's
+ * in-place case excepted), a single-input context.  npkt == 0 launches nothing.  A null context returns -1.  Profile entries
+ * "forecast_gram" (1536 flop per float of a block; 8 P K + 8 P^2 bytes per block, K = 234 nt), "forecast_fit", "forecast_apply"
+ * (8 M flop and 8 (M + 1) bytes per float) and "sounding_noise"; read-only option "forecast_launches" counts their kernels. */
+int  csi_forecast_gram_device(csi_ctx* ctx, const float* const* d_x_re, const float* const* d_x_im, int n_snd, int64_t npkt, float* d_t_re, float* d_t_im);
+int  csi_forecast_gram_blocks_device(csi_ctx* ctx, const float* const* d_x_re, const float* const* d_x_im, int n_snd, int64_t n_blocks,
+                                     int64_t block_floats, float* d_t_re, float* d_t_im);
+int  csi_forecast_fit_device(csi_ctx* ctx, const float* d_t_re, const float* d_t_im, int n_snd, int64_t npkt, int order, int steps, double ridge,
+                             uint32_t flags, float* d_c_re, float* d_c_im, float* d_fit_err, int32_t* d_info);
+int  csi_forecast_apply_device(csi_ctx* ctx, const float* const* d_x_re, const float* const* d_x_im, int n_snd, int64_t npkt, int order,
+                               const float* d_c_re, const float* d_c_im, float* d_out_re, float* d_out_im);
+int  csi_forecast_device(csi_ctx* ctx, const float* const* d_x_re, const float* const* d_x_im, int n_snd, int64_t npkt, int order, int steps,
+                         double ridge, uint32_t flags, float* d_out_re, float* d_out_im, float* d_c_re, float* d_c_im, float* d_fit_err, int32_t* d_info);
+int  csi_forecast(csi_ctx* ctx, const float* const* x_re, const float* const* x_im, int n_snd, int64_t npkt, int order, int steps, double ridge,
+                  uint32_t flags, float* out_re, float* out_im, float* c_re, float* c_im, float* fit_err, int32_t* info);
+int  csi_sounding_noise_device(csi_ctx* ctx, uint64_t seed, int64_t first_pkt, int64_t npkt, const float* d_err_var, const float* d_x_re,
+                               const float* d_x_im, float* d_out_re, float* d_out_im);
 
 /* ---- multi-GPU: packets shard over the GPUs of a node (one process and one context per GPU), the weights are shared and
  * read-only, outputs stay sharded.  The single collective of the path is the load-time broadcast of the
