@@ -32,7 +32,7 @@ import sys
 import os
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from band_kernel_gen import (Block, Wait, simulate, sreg, vreg, areg, DESCRIPTOR, S_AS2, S_INSC, S_AS1OS, S_OUTSC, META_KERNEL, KARG_BYTES, KARG_BYTES_CS, S_PART,     # noqa: E402
+from band_kernel_gen import (Block, Wait, LdsWait, simulate, sreg, vreg, areg, DESCRIPTOR, S_AS2, S_INSC, S_AS1OS, S_OUTSC, META_KERNEL, KARG_BYTES, KARG_BYTES_CS, S_PART,     # noqa: E402
                              S_L0, S_TS, S_W1, S_B1, S_W2, S_B2, S_OUT, S_PEAK, S_STAMPS, S_LDL, S_NT, S_LDB1, S_M, S_K1, S_N1, S_LDB2, S_N2,
                              S_LDO, S_MAGIC, S_WAVE, S_H, S_M0, S_W1P, S_W2P, S_L0P, S_TSP, S_TRIP, S_COL, S_NCOL, S_NSUB1, S_DMA, S_T,
                              S_ROWMASK, S_SAVE, S_COLBYTES, S_BIAS2OFF, S_TSLABB)
@@ -468,7 +468,8 @@ class RoleH(Role4):
     def u_read_w(self, plane, slot):
         if 'noread' in self.dbg:
             return []
-        return [['  ds_read_b128 %s, %s offset:%d' % (self.wh(plane, jj), vreg(V_RD1 if plane else V_RD0), slot * RING_SLOT + jj * 2048)] for jj in range(4)]
+        return [['  ds_read_b128 %s, %s offset:%d' % (self.wh(plane, jj), vreg(V_RD1 if plane else V_RD0), slot * RING_SLOT + jj * 2048), ('lds', 'WL' if plane else 'WH')]
+                for jj in range(4)]
 
     def u_stage_issue(self, slot, reset=False):
         units = []
@@ -492,10 +493,10 @@ class RoleH(Role4):
         """this lane's 8 T and 8 L0 values (k = 8 hi .. + 7 of the sub-step's 16) of ITS row of row group r = h"""
         if 'noreq' in self.dbg:
             return []
-        return [['  ds_read_b128 %s, %s offset:%d' % (vreg(H_SLT, 4), vreg(V_TL0), slot * TSLAB)],
-                ['  ds_read_b128 %s, %s offset:%d' % (vreg(H_SLT + 4, 4), vreg(V_TL1), slot * TSLAB)],
-                ['  ds_read_b128 %s, %s offset:%d' % (vreg(H_SLL, 4), vreg(V_LL), slot * 1024)],
-                ['  ds_read_b128 %s, %s offset:%d' % (vreg(H_SLL + 4, 4), vreg(V_LL), slot * 1024 + 16)]]
+        return [['  ds_read_b128 %s, %s offset:%d' % (vreg(H_SLT, 4), vreg(V_TL0), slot * TSLAB), ('lds', 'SL')],
+                ['  ds_read_b128 %s, %s offset:%d' % (vreg(H_SLT + 4, 4), vreg(V_TL1), slot * TSLAB), ('lds', 'SL')],
+                ['  ds_read_b128 %s, %s offset:%d' % (vreg(H_SLL, 4), vreg(V_LL), slot * 1024), ('lds', 'SL')],
+                ['  ds_read_b128 %s, %s offset:%d' % (vreg(H_SLL + 4, 4), vreg(V_LL), slot * 1024 + 16), ('lds', 'SL')]]
 
     def split_units(self, hi, lo, pk):
         """GV (8 fp32, relu applied) -> hi halves, lo = f16(x - hi) through v_fma_mix (gemm_hs.hip.h hs_lo_pair), packed maximum of the hi halves"""
@@ -515,19 +516,24 @@ class RoleH(Role4):
         if 'noconv' not in self.dbg:
             for e in range(8):
                 units.append(['  v_fma_f32 %s, %s, %s, %s' % (vreg(H_GV + e), vreg(H_SLL + e), sreg(S_INSC), vreg(H_SLT + e))])
+            if self.lw and 'noreq' not in self.dbg:          # counted waits: the slab values, in front of the first instruction that reads them
+                units[-8].insert(0, LdsWait({'SL'}))
             for e in range(8):
                 units.append(['  v_max_f32_e32 %s, 0, %s' % (vreg(H_GV + e), vreg(H_GV + e))])
             units += self.split_units(hi, lo, V_PK1)
-        units.append(['  ds_write_b128 %s, %s offset:%d' % (vreg(V_AX1), vreg(hi, 4), par_next * 4096 + self.h * 2048)])
-        units.append(['  ds_write_b128 %s, %s offset:%d' % (vreg(V_AX1), vreg(lo, 4), par_next * 4096 + self.h * 2048 + 1024)])
+        units.append(['  ds_write_b128 %s, %s offset:%d' % (vreg(V_AX1), vreg(hi, 4), par_next * 4096 + self.h * 2048), ('lds', 'XW')])
+        units.append(['  ds_write_b128 %s, %s offset:%d' % (vreg(V_AX1), vreg(lo, 4), par_next * 4096 + self.h * 2048 + 1024), ('lds', 'XW')])
         return units
 
     def u_read_f1(self, par_next):
         o = 1 - self.h
-        return [['  ds_read_b128 %s, %s offset:%d' % (vreg(H_AF + 8 * par_next + 4 * pl, 4), vreg(V_AX1), par_next * 4096 + o * 2048 + pl * 1024)] for pl in range(2)]
+        return [['  ds_read_b128 %s, %s offset:%d' % (vreg(H_AF + 8 * par_next + 4 * pl, 4), vreg(V_AX1), par_next * 4096 + o * 2048 + pl * 1024), ('lds', 'AL' if pl else 'AH')]
+                for pl in range(2)]
 
     def u_read_f2(self, par_next):
-        return [['  ds_read_b128 %s, %s offset:%d' % (self.a2(par_next, r, pl), vreg(V_AX2), par_next * 4096 + r * 2048 + pl * 1024)] for r in range(2) for pl in range(2)]
+        # counted waits: the hi planes of both row groups first (P0 of the next sub-step reads them), then the lo planes (P2 does)
+        order = [(r, pl) for pl in range(2) for r in range(2)] if self.lw else [(r, pl) for r in range(2) for pl in range(2)]
+        return [['  ds_read_b128 %s, %s offset:%d' % (self.a2(par_next, r, pl), vreg(V_AX2), par_next * 4096 + r * 2048 + pl * 1024), ('lds', 'AL' if pl else 'AH')] for r, pl in order]
 
     @staticmethod
     def frag(q):
@@ -537,10 +543,10 @@ class RoleH(Role4):
     def u_bias(self, q):
         jt, g = self.frag(q)
         imm = (128 * self.h + 32 * jt + 16 * g) * 4
-        return [['  ds_read_b128 %s, %s offset:%d' % (vreg(H_BQ, 4), vreg(V_BADDR), imm)],
-                ['  ds_read_b128 %s, %s offset:%d' % (vreg(H_BQ + 4, 4), vreg(V_BADDR), imm + 32)]]
+        return [['  ds_read_b128 %s, %s offset:%d' % (vreg(H_BQ, 4), vreg(V_BADDR), imm), ('lds', 'BQ')],
+                ['  ds_read_b128 %s, %s offset:%d' % (vreg(H_BQ + 4, 4), vreg(V_BADDR), imm + 32), ('lds', 'BQ')]]
 
-    def u_unit(self, q, r, cset):
+    def u_unit(self, q, r, cset, wait_bias=False):
         """h2 unit (fragment q, row group r): accumulator registers 8 g .. of tile jt -> (hi, lo) in CV set cset"""
         if 'noconv' in self.dbg:
             return []
@@ -551,26 +557,76 @@ class RoleH(Role4):
             u.append(['  v_accvgpr_read_b32 %s, %s' % (vreg(H_GV + e), areg(acc + e))])
         for e in range(8):
             u.append(['  v_fma_f32 %s, %s, %s, %s' % (vreg(H_GV + e), vreg(H_GV + e), sreg(S_AS1OS), vreg(H_BQ + e))])
+        if self.lw and wait_bias:                            # counted waits: the bias quads of the fragment (read one sub-step earlier), in front of their first use
+            u[-8].insert(0, LdsWait({'BQ'}))
         for e in range(8):
             u.append(['  v_max_f32_e32 %s, 0, %s' % (vreg(H_GV + e), vreg(H_GV + e))])
         return u + self.split_units(H_CV + 8 * cset, H_CV + 8 * cset + 4, V_PK2)
 
     def u_write_unit(self, q, r, cset):
-        return [['  ds_write_b128 %s, %s offset:%d' % (vreg(V_AX2), vreg(H_CV + 8 * cset + 4 * pl, 4), (q & 1) * 4096 + r * 2048 + pl * 1024)] for pl in range(2)]
+        return [['  ds_write_b128 %s, %s offset:%d' % (vreg(V_AX2), vreg(H_CV + 8 * cset + 4 * pl, 4), (q & 1) * 4096 + r * 2048 + pl * 1024), ('lds', 'XW')] for pl in range(2)]
 
-    def substep(self, b, kind, slot, par, pre, post, needs, first=False):
-        """P0 = w_lo x a_hi (w_lo was read behind the previous barrier), P1 = w_hi x a_hi, barrier, P2 = w_hi x a_lo"""
-        b.e('s_waitcnt lgkmcnt(0)')
+    # Schedule flags of the split-f16 form (each can be timed alone, tools/band4_waits_ab.py; none = the first form's schedule, kept as csi_band4_oldwaits):
+    #   'lw'  counted LDS waits.  The first form drained the LDS queue three times per sub-step (top, in front of P1, in front of the barrier); each drain also
+    #         waited for reads that are used much later.  Here every wait names what the next instructions need (tags of the ('lds', tag) items) and the
+    #         path simulation turns it into s_waitcnt lgkmcnt(N):
+    #           top            w_lo fragments + the hi planes of the fragments read from the exchange      (P0)
+    #           in unit        the slab values / the bias quads, in front of the first conversion instruction that reads them
+    #           front of P1    the four w_hi reads
+    #           front of the barrier   this wave's exchange writes since the last barrier, the lo planes read from the exchange (P2), w_hi;
+    #                          one s_waitcnt together with the vmcnt of the landed pieces
+    #         post orders its reads by first use: w_lo jj 0 .. 3, exchange hi, exchange lo, slab values, bias quads, then the exchange writes.
+    #   'ex'  early exchange.  The conversion unit with its two exchange writes is dealt over P0 and the FIRST four MFMAs of P1, the slab LDS-DMA and the
+    #         pointer steps over the last four: the writes have four MFMAs to land before the wait in front of the barrier instead of none.
+    # Property the counted waits rely on (checked by reading every address operand of the main loop): NO address depends on a value a counted wait protects.
+    # LDS addresses (V_RD0 / V_RD1, V_AX1 / V_AX2, V_TL0 / V_TL1 / V_LL, V_BADDR), the LDS-DMA offsets (V_VO, V_TOFF, V_LOFF), m0 and the stream pointers
+    # come from the prologue or from SGPR arithmetic (V_BADDR advances by a constant per column step); what the ds_reads return is only ever an MFMA or VALU
+    # data operand.  A miscounted wait therefore shows as wrong numbers (tests/test_gpu_band4_waits.py: run-to-run and against recorded bits), never as a fault.
+    @property
+    def lw(self):
+        return 'lw' in self.dbg
+
+    @staticmethod
+    def has_tag(unit, tag):
+        return any(isinstance(it, tuple) and it == ('lds', tag) for it in unit)
+
+    def substep(self, b, kind, slot, par, pre, post, needs, first=False, late=()):
+        """P0 = w_lo x a_hi (w_lo was read behind the previous barrier), P1 = w_hi x a_hi, barrier, P2 = w_hi x a_lo.
+        late = the units of `pre` that nothing in front of the barrier waits for (slab LDS-DMA, pointer steps): they follow pre"""
+        late = list(late)
+        if self.lw:
+            b.wait_lds({'WL', 'AH'})
+        else:
+            b.e('s_waitcnt lgkmcnt(0)')
         order = [(jj, r) for jj in range(4) for r in range(2)]
         p0 = [self.mf(kind, r, jj, 1, 0, par, zero_c=first) for jj, r in order]
         p1 = [self.mf(kind, r, jj, 0, 0, par) for jj, r in order]
         p2 = [self.mf(kind, r, jj, 0, 1, par) for jj, r in order]
-        # the plane-0 (hi) weight reads lead the list: they go out among P0's first MFMAs and are waited for in front of P1
-        cut = min(len(pre), max(4, (len(pre) + 1) // 2))
-        self.deal(b, p0, pre[:cut])
-        b.e('s_waitcnt lgkmcnt(0)')
-        self.deal(b, p1, pre[cut:])
-        b.e('s_waitcnt lgkmcnt(0)')
+        writes = [i for i, u in enumerate(pre) if self.has_tag(u, 'XW')]
+        if 'ex' in self.dbg and writes:
+            early, rest = pre[:writes[-1] + 1], pre[writes[-1] + 1:] + late
+            cut = min(len(early), max(4, (2 * len(early) + 2) // 3))           # 8 of the 12 gaps in front of the exchange writes belong to P0
+            self.deal(b, p0, early[:cut])
+            if self.lw:
+                b.wait_lds({'WH'})
+            else:
+                b.e('s_waitcnt lgkmcnt(0)')
+            self.deal(b, p1[:4], early[cut:])
+            self.deal(b, p1[4:], rest)
+        else:
+            # the plane-0 (hi) weight reads lead the list: they go out among P0's first MFMAs and are waited for in front of P1
+            pre = pre + late
+            cut = min(len(pre), max(4, (len(pre) + 1) // 2))
+            self.deal(b, p0, pre[:cut])
+            if self.lw:
+                b.wait_lds({'WH'})
+            else:
+                b.e('s_waitcnt lgkmcnt(0)')
+            self.deal(b, p1, pre[cut:])
+        if self.lw:
+            b.wait_lds({'XW', 'AL', 'WH'})
+        else:
+            b.e('s_waitcnt lgkmcnt(0)')
         b.wait_vm(needs)
         self.barrier(b)
         self.deal(b, p2, post)
@@ -616,9 +672,8 @@ class RoleH(Role4):
             pre = self.u_read_w(0, slot)
             if produce_ok:
                 pre += self.u_convert1(par ^ 1)
-            if issue_ok:
-                pre += self.u_stage_issue(i & 3)
-            post = self.u_read_w(1, nslot)
+            late = self.u_stage_issue(i & 3) if issue_ok else []
+            post = self.u_read_w(1, nslot)                   # (in the order of first use: w_lo, exchange hi, exchange lo, slab values)
             if produce_ok:
                 post += self.u_read_f1(par ^ 1)
             if stage_ok:
@@ -627,7 +682,7 @@ class RoleH(Role4):
             needs = {'P%d' % nslot}
             if stage_ok:
                 needs |= {'T%d' % ((i + 2) & 3), 'L%d' % ((i + 2) & 3)}
-            self.substep(b, 1, slot, par, pre, post, needs, first=first)
+            self.substep(b, 1, slot, par, pre, post, needs, first=first, late=late)
 
         head.label(L('col'))
         for i in range(4):
@@ -675,16 +730,20 @@ class RoleH(Role4):
             if q < NQ - 1:
                 post += self.u_read_f2(par ^ 1)
             fa, fb = q + 2, q + 1                            # fragments whose unit r 0 / r 1 this half may own in this sub-step
+            post_w, post_b, late = [], [], []
             if fa < NQ and (fa & 1) == h and fa >= 2:
-                pre += self.u_unit(fa, 0, 0)
-                post += self.u_write_unit(fa, 0, 0)
+                pre += self.u_unit(fa, 0, 0, wait_bias=True)
+                post_w = self.u_write_unit(fa, 0, 0)
             if fb < NQ and (fb & 1) == h and fb >= 2:
                 pre += self.u_unit(fb, 1, 1) + self.u_write_unit(fb, 1, 1)
             fn = q + 3                                       # bias quads of the fragment whose first unit comes in the next sub-step
             if fn < NQ and (fn & 1) == h and 'noconv' not in self.dbg:
-                post += self.u_bias(fn)
+                post_b = self.u_bias(fn)
             if NQ - 5 <= q <= NQ - 2:
-                pre += self.u_stage_issue(q - (NQ - 5), reset=(q == NQ - 5))
+                late = self.u_stage_issue(q - (NQ - 5), reset=(q == NQ - 5))
+            if not self.lw:                                  # the first form's order
+                post += post_w + post_b
+                pre, late = pre + late, []
             if q == NQ - 2:
                 post += self.u_stage_read(0)
                 needs |= {'T0', 'L0'}
@@ -692,12 +751,16 @@ class RoleH(Role4):
                 pre += self.u_convert1(0)
                 post += self.u_read_f1(0) + self.u_stage_read(1)
                 needs |= {'T1', 'L1'}
+            if self.lw:                                      # by first use: (w_lo, exchange hi, exchange lo, slab values,) bias quads, then the exchange writes
+                post += post_b + post_w
             post += self.u_pieces('s2' if q < NQ - 4 else 's1', slot)
-            self.substep(st2, 2, slot, par, pre, post, needs)
+            self.substep(st2, 2, slot, par, pre, post, needs, late=late)
         tail.e('v_add_u32_e32 %s, 1024, %s' % (vreg(V_BADDR), vreg(V_BADDR)))
         tail.e('s_add_u32 %s, %s, 1' % (sreg(S_COL), sreg(S_COL)))
         tail.e('s_cmp_lt_u32 %s, %s' % (sreg(S_COL), sreg(S_NCOL)))
         tail.e('s_cbranch_scc1 %s' % L('col'))
+        if self.lw:                                          # the epilogue's scratch registers alias the slab values: the last slab reads have returned
+            tail.e('s_waitcnt lgkmcnt(0)')
         tail.e('s_branch L_epilogue_%d' % h)
 
         col0 = [head, last, bub, st2, tail]
@@ -1155,10 +1218,17 @@ def kernel(name, dbg=()):
     end.e('s_endpgm')
     blocks.append(end)
     for b in blocks:
-        for it in b.items:
-            if isinstance(it, tuple):
+        items = [it for it in b.items if not isinstance(it, tuple)]
+        k = 0
+        while k < len(items):
+            it = items[k]
+            if isinstance(it, LdsWait) and k + 1 < len(items) and isinstance(items[k + 1], Wait):      # a wait_lds and a wait_vm that stand together: one s_waitcnt
+                out.append(items[k + 1].text() + (' lgkmcnt(%d)' % it.count() if it.n is not None else ''))
+                k += 2
                 continue
-            out.append(it.text() if isinstance(it, Wait) else it)
+            if not (isinstance(it, LdsWait) and it.n is None):           # (a counted wait for something that is in flight on no path: nothing to emit)
+                out.append(it.text() if isinstance(it, (Wait, LdsWait)) else it)
+            k += 1
     text = '\n'.join(out)
     return re.sub(r'\bL_\w+', lambda m: name + '_' + m.group(0), text)      # labels are per kernel
 
@@ -1166,7 +1236,14 @@ def kernel(name, dbg=()):
 DESCRIPTOR4 = DESCRIPTOR.replace('.amdhsa_next_free_vgpr 256', '.amdhsa_next_free_vgpr 512').replace('.amdhsa_accum_offset 128', '.amdhsa_accum_offset 256')
 META4 = META_KERNEL.replace('.vgpr_count: 256', '.vgpr_count: 512').replace('.agpr_count: 128', '.agpr_count: 256').replace('.max_flat_workgroup_size: 512', '.max_flat_workgroup_size: 256')
 
-VARIANTS = [('csi_band4', ('hs',)), ('csi_band4_cs', ('hs', 'colsplit')), ('csi_band4_bf16_cs', ('colsplit',)), ('csi_band4_rowstores', ('hs', 'rowstores')), ('csi_band4_roleslabs', ('hs', 'roleslabs')), ('csi_band4_bf16_roleslabs', ('roleslabs',)), ('csi_band4_skeleton', ('hs', 'noconv', 'noreq', 'nodma', 'noread')), ('csi_band4_skeleton_nobarrier', ('hs', 'noconv', 'noreq', 'nodma', 'noread', 'nobarrier')), ('csi_band4_noaside', ('hs', 'noconv', 'noreq')),
+# schedule flags of the product's split-f16 kernels (RoleH.substep); csi_band4_oldwaits = none of them = the first form's schedule (A arm of tools/band4_waits_ab.py).
+# Measured at the headline shape against that schedule (profiles/band4_waits_ab.txt; kept = at least 5 x the A / A' spread on the launch AND on the step):
+#   'ex' alone -1.9 ... -2.9 % per launch / -1.8 ... -2.3 % per step (four runs; three of them beyond the margin on both): kept.   'lw' alone -0.13 % / -0.20 % (3.4 x / 4.7 x): not in the product form.
+#   'lw' + 'ex' -2.5 % / -1.9 % (10.9 x / 10.2 x): no step gain over 'ex' alone that the runs can tell from box drift; stays a tools variant (csi_band4_lw_ex).
+HS_SCHEDULE = ('ex',)
+
+VARIANTS = [('csi_band4', ('hs',) + HS_SCHEDULE), ('csi_band4_cs', ('hs', 'colsplit') + HS_SCHEDULE), ('csi_band4_oldwaits', ('hs',)), ('csi_band4_cs_oldwaits', ('hs', 'colsplit')),
+            ('csi_band4_lw', ('hs', 'lw')), ('csi_band4_ex', ('hs', 'ex')), ('csi_band4_lw_ex', ('hs', 'lw', 'ex')), ('csi_band4_bf16_cs', ('colsplit',)), ('csi_band4_rowstores', ('hs', 'rowstores')), ('csi_band4_roleslabs', ('hs', 'roleslabs')), ('csi_band4_bf16_roleslabs', ('roleslabs',)), ('csi_band4_skeleton', ('hs', 'noconv', 'noreq', 'nodma', 'noread')), ('csi_band4_skeleton_nobarrier', ('hs', 'noconv', 'noreq', 'nodma', 'noread', 'nobarrier')), ('csi_band4_noaside', ('hs', 'noconv', 'noreq')),
             ('csi_band4_nodma', ('hs', 'nodma')), ('csi_band4_nostore', ('hs', 'nostore')), ('csi_band4_noconv', ('hs', 'noconv')),
             ('csi_band4_bf16', ()), ('csi_band4_bf16_noconv', ('noconv',)), ('csi_band4_bf16_noaside', ('noconv', 'noreq')),
             ('csi_band4_bf16_skeleton', ('noconv', 'noreq', 'nodma', 'noread')), ('csi_band4_bf16_nodma', ('nodma',)), ('csi_band4_bf16_noread', ('noread',)),

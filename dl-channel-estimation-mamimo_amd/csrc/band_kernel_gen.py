@@ -106,10 +106,32 @@ class Wait:
         return '  s_waitcnt vmcnt(%d)' % min(self.n if self.n is not None else 0, 63)
 
 
+LGKM_MAX = 15                      # what the lgkmcnt field of s_waitcnt holds on gfx950 (4 bits)
+
+
+class LdsWait:
+    """placeholder of a counted LDS wait (s_waitcnt lgkmcnt(N)); `needs` = tags whose last issued LDS operation must have completed.  LDS operations
+    retire in order among themselves, so N = the operations younger than the newest needed one.  Scalar memory shares the counter and does NOT retire
+    in order: simulate() refuses a counted wait with a scalar load outstanding (blocks that issue one keep lgkmcnt(0))."""
+
+    def __init__(self, needs):
+        self.needs = set(needs)
+        self.n = None              # min over the simulated paths; None = nothing of it in flight on any path
+
+    def count(self):
+        return min(self.n if self.n is not None else LGKM_MAX, LGKM_MAX)
+
+    def text(self):
+        return '  s_waitcnt lgkmcnt(%d)' % self.count()
+
+
+SMEM_RE = re.compile(r'^\s*s_(load|memtime|memrealtime)')
+
+
 class Block:
     def __init__(self, name):
         self.name = name
-        self.items = []            # str | Wait | ('vm', tag)
+        self.items = []            # str | Wait | LdsWait | ('vm', tag) | ('lds', tag)
 
     def e(self, s):
         self.items.append('  ' + s)
@@ -131,16 +153,45 @@ class Block:
         self.items.append(w)
         return w
 
+    def lds(self, s, tag):
+        self.items.append('  ' + s)
+        self.items.append(('lds', tag))
+
+    def wait_lds(self, needs):
+        w = LdsWait(needs)
+        self.items.append(w)
+        return w
+
 
 def simulate(blocks_in_order, queue=None, with_opt=True):
-    """walk the blocks in execution order; every Wait gets n = min(n, operations younger than its newest needed one)"""
+    """walk the blocks in execution order; every Wait gets n = min(n, operations younger than its newest needed one).  The LDS queue (('lds', tag) items,
+    LdsWait) is counted the same way beside the vector-memory one; a literal lgkmcnt(0) in the text empties it."""
     q = list(queue or [])
+    lq, smem = [], False
     for b in blocks_in_order:
         for it in b.items:
             if isinstance(it, tuple):
                 if it[0] == 'unit' or (it[0] == 'vmopt' and not with_opt):
                     continue
+                if it[0] == 'lds':
+                    lq.append(it[1])
+                    continue
                 q.append(it[1])
+            elif isinstance(it, str):
+                if 'lgkmcnt(0)' in it:
+                    lq, smem = [], False
+                elif SMEM_RE.match(it):
+                    smem = True
+            elif isinstance(it, LdsWait):
+                assert not smem, 'block %s: a counted LDS wait with a scalar load outstanding (scalar memory shares lgkmcnt and returns out of order)' % b.name
+                pos = -1
+                for i, t in enumerate(lq):
+                    if t in it.needs:
+                        pos = i
+                if pos >= 0:
+                    n = len(lq) - 1 - pos
+                    it.n = n if it.n is None else min(it.n, n)
+                    lq = lq[pos + 1:]
             elif isinstance(it, Wait):
                 pos = -1
                 for i, t in enumerate(q):

@@ -173,6 +173,7 @@ BandPlan band_plan(const csi_ctx* c, const BandArgs& ba, bool bf16, bool staged,
 
 int band_launch(csi_ctx* c, const BandKernel& k, const BandArgs& ba, double flops, double bytes) {
     ++c->band_launches;
+    c->band4_launches += band_tiled(k);      // a csi_band4* function (band_load: 256 threads <=> that name)
     ProfScope ps(c, K_PAIR_DENSE, flops, bytes);
     Band8Args a8 = band8_args(ba);
     size_t sz = sizeof(a8);
@@ -185,6 +186,7 @@ int band_launch(csi_ctx* c, const BandKernel& k, const BandArgs& ba, double flop
 // the WHOLE layer, split y starts at its own column steps); partial outputs of splits 1 .. in `part`, added to split 0's output in split order
 int band_launch_split(csi_ctx* c, const BandKernel& k, const BandArgs& ba, int S, float* part, double flops, double bytes, int kid) {
     ++c->band_launches;
+    c->band4_launches += band_tiled(k);
     ++c->band_split_launches;
     BandArgs one = ba;
     one.N1 = ba.N1 / S;

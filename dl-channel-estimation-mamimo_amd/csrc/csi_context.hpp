@@ -363,6 +363,7 @@ struct csi_ctx {
                                              // 4 waves x 512 registers) in fp32 and bf16 contexts alike; 0 = the 8-wave forms csi_band8* everywhere (A/B)
     bool band_failed = false;                // the code object could not be loaded: separate kernels from then on
     int64_t band_launches = 0;
+    int64_t band4_launches = 0;              // "band4_launches" (read-only): those of band_launches that launched a register-blocked csi_band4* function
     int band_split = -1;         // "band_split": calls with fewer bands than CUs split every band's hidden features over 2 / 4 workgroups (the
                                  // regressor sums of the splits are added in split order by band_split_sum_kernel); -1 = automatic (as many
                                  // splits as keep the workgroups of the models in flight within the 256 CUs), 0 / 1 = never, 2 / 4 = always

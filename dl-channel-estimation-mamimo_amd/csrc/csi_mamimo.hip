@@ -962,6 +962,7 @@ int csi_get_option(csi_ctx* c, const char* name, int64_t* value) {
     else if (n == "band4") *value = c->band4;
     else if (n == "band4_available") *value = c->band_kernel[c->cfg.dtype == CSI_DTYPE_BF16][BAND_FOUR].fn != nullptr;
     else if (n == "band_launches") *value = c->band_launches;
+    else if (n == "band4_launches") *value = c->band4_launches;              // read-only: launches of a csi_band4* function (band_run)
     else if (n == "band_split") *value = c->band_split;
     else if (n == "aux_fork_early") *value = c->aux_fork_early;
     else if (n == "l0_stream") *value = c->l0_stream;

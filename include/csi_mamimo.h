@@ -760,7 +760,11 @@ int  csi_synchronize(csi_ctx* ctx);
  *                         (csrc/band4_kernel_gen.py "csi_band4" / "csi_band4_bf16" and their "_cs" launches: 4 waves x 512 registers,
  *                         every weight fragment against two row groups, weights pre-tiled at first use); 4 column splits stay on the
  *                         8-wave form; 0: the 8-wave forms "csi_band8*" everywhere (A/B runs; same operand roundings, fp32 sums in
- *                         another order).  Read-only: "band4_available".
+ *                         another order).  Read-only: "band4_available"; "band4_launches" counts the launches of a "csi_band4*" function
+ *                         (a subset of "band_launches": which form served a call).
+ *                         Routing of fp32 contexts: the split engine's band kernel takes the register-blocked form at 16 <= nt <= 128
+ *                         when the call runs in ONE launch ("csi_band4") or in at most TWO column splits ("csi_band4_cs", also the tail
+ *                         launch of "band_tail_split" when that is 2 splits); 4 splits and nt outside that range take "csi_band8*".
  *   "band_split"       -1 (default): a call with fewer bands of 128 pair rows than the part has CUs (24 ... 64 packets of the shipped
  *                         shape) splits every band's hidden features over 2 or 4 workgroups ("csi_band8_cs") and adds their regressor
  *                         sums in split order - same arithmetic, the final fp32 sums associate differently (1 ulp class);
