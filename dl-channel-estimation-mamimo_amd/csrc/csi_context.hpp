@@ -86,6 +86,8 @@ enum KernelId {
     K_FORECAST_FIT,      // channel forecast: normal equations, ridge and fp64 Cholesky per (packet, rx) or per packet
     K_FORECAST_APPLY,    // channel forecast: y = sum_m c_m x_{P-1-m}, streaming
     K_SOUNDING_NOISE,    // white estimation error on a CSI plane pair (csi_sounding_noise_device)
+    K_CFO_CORR,          // carrier frequency offset (csi_cfo_*, cfo.hip.h): cyclic-prefix correlation, eps_hat and quality per packet; placed like K_SUBSPACE_SMOOTH
+    K_CFO_ROTATE,        // carrier frequency offset: y = x exp(2 pi i scale eps n / 256), streaming
     K_SYNTH_SCATTERING,  // known-channel sounding packets of the scattering channel (synth_scattering.hip.h): the power pass and the packet pass of csi_synth_scattering
     K_LMMSE_NULL_NOISE,  // blind LMMSE smoother (csi_lmmse_blind, lmmse.hip.h): noise variance from the null carriers of the sounding symbols
     K_LMMSE_FREQ_CORR,   // blind LMMSE smoother: sample frequency correlation of the LS rows
@@ -97,7 +99,7 @@ const char* const kKernelNames[K_COUNT] = {
     "ls_estimate", "naive_dense0_gemm", "synth_white", "pilot_table", "cast_bf16", "pair_h1_bf16", "lmmse_levinson",
     "train_gemm", "train_elementwise", "nmse_links", "pair_dense_tail", "input_pool", "conv_frontend",
     "hybrid_svd", "hybrid_corr_argmax", "hybrid_solve", "hybrid_finish", "synth_structured", "link_txrx", "link_viterbi",
-    "subspace_smooth", "mu_precoder", "mu_txrx", "mu_beam_score", "mu_beam_select", "mu_hybrid_precoder", "mu_cov", "mu_jsdm_eig", "mu_jsdm_baseband", "fb_compress", "fb_expand", "rx_combiner", "rx_combine", "beam_power", "beam_smooth", "scatter_aged", "forecast_gram", "forecast_fit", "forecast_apply", "sounding_noise", "synth_scattering", "lmmse_null_noise", "lmmse_freq_corr", "lmmse_blind"};
+    "subspace_smooth", "mu_precoder", "mu_txrx", "mu_beam_score", "mu_beam_select", "mu_hybrid_precoder", "mu_cov", "mu_jsdm_eig", "mu_jsdm_baseband", "fb_compress", "fb_expand", "rx_combiner", "rx_combine", "beam_power", "beam_smooth", "scatter_aged", "forecast_gram", "forecast_fit", "forecast_apply", "sounding_noise", "cfo_corr", "cfo_rotate", "synth_scattering", "lmmse_null_noise", "lmmse_freq_corr", "lmmse_blind"};
 
 thread_local std::string g_create_error;
 
@@ -240,6 +242,9 @@ struct csi_ctx {
     int64_t scatter_aged_launches = 0;     // "scatter_aged_launches": kernels launched by csi_scatter_channel_at_device
     char* forecast_ws = nullptr;           // channel forecast (csi_forecast.hpp): T and, when the caller keeps none, c of a csi_forecast_device call (sized by eager calls)
     size_t forecast_ws_bytes = 0;
+    char* cfo_ws = nullptr;                // carrier frequency offset (csi_cfo.hpp): eps of a csi_cfo_correct_device call whose caller keeps none (sized by eager calls)
+    size_t cfo_ws_bytes = 0;
+    int64_t cfo_launches = 0;              // "cfo_launches": kernels launched by the csi_cfo_* entry points
     int64_t forecast_launches = 0;         // "forecast_launches": kernels launched by the csi_forecast_* entry points and csi_sounding_noise_device
     // activation workspace
     char* ws = nullptr;

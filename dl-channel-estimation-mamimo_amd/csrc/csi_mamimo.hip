@@ -33,6 +33,7 @@
 #include "csi_rx_combine.hpp"
 #include "csi_scatter_aged.hpp"      // last: its kernels are emitted behind every other kernel, whose pc-relative addresses stay what they were
 #include "csi_forecast.hpp"          // ... and these behind them, for the same reason
+#include "csi_cfo.hpp"               // ... and these
 #include <initializer_list>
 
 namespace {
@@ -341,6 +342,7 @@ void csi_destroy(csi_ctx* c) {
     if (c->beam_a) hipFree(c->beam_a);
     if (c->beam_ws) hipFree(c->beam_ws);
     if (c->forecast_ws) hipFree(c->forecast_ws);
+    if (c->cfo_ws) hipFree(c->cfo_ws);
     if (c->hs_peak) hipFree(c->hs_peak);
     if (c->hs_zero) hipFree(c->hs_zero);
     if (c->fuse_ws) hipFree(c->fuse_ws);
@@ -955,6 +957,7 @@ int csi_get_option(csi_ctx* c, const char* name, int64_t* value) {
     else if (n == "scatter_launches") *value = c->scatter_launches;
     else if (n == "scatter_aged_launches") *value = c->scatter_aged_launches;
     else if (n == "forecast_launches") *value = c->forecast_launches;
+    else if (n == "cfo_launches") *value = c->cfo_launches;
     else if (n == "small_rows") *value = c->small_rows;
     else if (n == "small_rows_band") *value = c->small_rows_band;
     else if (n == "f32_engine") *value = c->f32_engine;
@@ -1863,6 +1866,30 @@ int csi_sounding_noise_device(csi_ctx* c, uint64_t seed, int64_t first_pkt, int6
                               float* d_out_re, float* d_out_im) {
     if (!c) return CSI_ERR_INVALID_ARG;
     return sounding_noise_device(c, seed, first_pkt, npkt, d_err_var, d_x_re, d_x_im, d_out_re, d_out_im);
+}
+
+// ---- carrier frequency offset (csi_cfo.hpp, cfo.hip.h)
+int csi_cfo_estimate_device(csi_ctx* c, const float* d_ltf_re, const float* d_ltf_im, int64_t npkt, int cp_skip, double* d_eps, float* d_quality) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return cfo_estimate_device(c, d_ltf_re, d_ltf_im, npkt, cp_skip, d_eps, d_quality);
+}
+
+int csi_cfo_rotate_device(csi_ctx* c, const float* d_in_re, const float* d_in_im, int64_t npkt, const double* d_eps, double scale, float* d_out_re,
+                          float* d_out_im) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return cfo_rotate_device(c, d_in_re, d_in_im, npkt, d_eps, scale, d_out_re, d_out_im);
+}
+
+int csi_cfo_correct_device(csi_ctx* c, const float* d_ltf_re, const float* d_ltf_im, int64_t npkt, int cp_skip, float* d_out_re, float* d_out_im,
+                           double* d_eps, float* d_quality) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return cfo_correct_device(c, "csi_cfo_correct_device", d_ltf_re, d_ltf_im, npkt, cp_skip, d_out_re, d_out_im, d_eps, d_quality);
+}
+
+int csi_cfo_correct(csi_ctx* c, const float* ltf_re, const float* ltf_im, int64_t npkt, int cp_skip, float* out_re, float* out_im, double* eps,
+                    float* quality) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return cfo_correct_host(c, ltf_re, ltf_im, npkt, cp_skip, out_re, out_im, eps, quality);
 }
 
 // ---- profiling

@@ -1531,6 +1531,42 @@ class CsiEngine:
         out = self._c64(o_re, o_im)
         return (out, self._c64(c_re, c_im), fit_err, info) if details else out
 
+    # ------------------------------------------------------------------ carrier frequency offset (csrc/cfo.hip.h)
+    def cfo_estimate_device(self, d_ltf_re, d_ltf_im, npkt, d_eps, cp_skip=0, d_quality=None):
+        """The carrier frequency offset of every packet from the cyclic prefixes of its sounding symbols (csi_cfo_estimate_device):
+        d_eps [npkt] as float64 in subcarrier spacings (an array of 2 float32 words per packet, as null_noise_device's), optional
+        d_quality [npkt] = |gamma| / E, about snr / (1 + snr); cp_skip 0 .. 63 leaves out the head of every prefix.  Asynchronous."""
+        self._check(self._lib.csi_cfo_estimate_device(self._ctx, d_ltf_re.ptr or None, d_ltf_im.ptr or None, int(npkt), int(cp_skip), d_eps.ptr or None,
+                                                      d_quality.ptr if d_quality is not None else None))
+
+    def cfo_rotate_device(self, d_in_re, d_in_im, npkt, d_eps, scale, d_out_re=None, d_out_im=None):
+        """y[p,r,n] = x[p,r,n] exp(2 pi i scale eps[p] n / 256) on device-resident preambles (csi_cfo_rotate_device): d_eps [npkt] as
+        float64 (2 float32 words per packet); scale +1 impairs, -1 corrects; in place without out planes.  Asynchronous."""
+        d_out_re = d_in_re if d_out_re is None else d_out_re
+        d_out_im = d_in_im if d_out_im is None else d_out_im
+        self._check(self._lib.csi_cfo_rotate_device(self._ctx, d_in_re.ptr or None, d_in_im.ptr or None, int(npkt), d_eps.ptr or None, float(scale),
+                                                    d_out_re.ptr or None, d_out_im.ptr or None))
+
+    def cfo_correct_device(self, d_ltf_re, d_ltf_im, npkt, d_out_re=None, d_out_im=None, cp_skip=0, d_eps=None, d_quality=None):
+        """Estimate, then rotate by -eps_hat (csi_cfo_correct_device): two launches, the bits of the two calls; in place without out
+        planes; optional d_eps [npkt] as float64 and d_quality [npkt] receive the estimate.  Asynchronous."""
+        d_out_re = d_ltf_re if d_out_re is None else d_out_re
+        d_out_im = d_ltf_im if d_out_im is None else d_out_im
+        self._check(self._lib.csi_cfo_correct_device(self._ctx, d_ltf_re.ptr or None, d_ltf_im.ptr or None, int(npkt), int(cp_skip), d_out_re.ptr or None,
+                                                     d_out_im.ptr or None, d_eps.ptr if d_eps is not None else None,
+                                                     d_quality.ptr if d_quality is not None else None))
+
+    def cfo_correct(self, ltf, cp_skip=0, details=False):
+        """Carrier-frequency-offset correction from host arrays (csi_cfo_correct): ltf complex [npkt,nr,len_ltf]; returns the corrected
+        preambles, complex64 of the same shape.  With ``details`` also (eps_hat float64 [npkt], quality float32 [npkt])."""
+        re, im = self._split(ltf, None)
+        npkt = re.shape[0]
+        o_re, o_im = np.empty_like(re), np.empty_like(im)
+        eps, quality = np.empty(npkt, np.float64), np.empty(npkt, np.float32)
+        self._check(self._lib.csi_cfo_correct(self._ctx, _fp(re), _fp(im), npkt, int(cp_skip), _fp(o_re), _fp(o_im), eps.ctypes.data, _fp(quality)))
+        out = self._c64(o_re, o_im)
+        return (out, eps, quality) if details else out
+
     def lmmse_estimate_device(self, d_h_re, d_h_im, npkt, d_hvec, L, d_snr_db, d_out_re, d_out_im):
         """LMMSE smoothing of device-resident LS planes (csi_lmmse_estimate_device): d_hvec [npkt][L], d_snr_db [npkt][nr]; asynchronous."""
         self._check(self._lib.csi_lmmse_estimate_device(self._ctx, d_h_re.ptr, d_h_im.ptr, int(npkt), d_hvec.ptr, int(L), d_snr_db.ptr,

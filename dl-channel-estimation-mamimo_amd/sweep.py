@@ -39,6 +39,9 @@ data phases to a level and nothing else: without an option every output is what 
       (forecast)                                    of order M from P soundings MS / D apart (the newest: X's own plane); with --users
                                                     bersMUF_X, EVM_rmsMUF_X, sinrMUF_X, muf_users: the data phase of MUA with the
                                                     forecast planes as estimates, same bits and noise
+    --cfo EPS --cfoSkip M (cfo)           -         MSEO_X and MSEOC_X for X = LS, MMSE, DNN, cfo_rmse, cfo_quality: the level's packets      4.28
+                                                    under a carrier frequency offset uniform in +-EPS subcarrier spacings per packet,
+                                                    estimated as they are and after the cyclic-prefix correction (cp_skip = M)
 
 FAMILIES below states this as data - fields, sources, switches, the per-user record - and MAT_ORDER / JSON_ORDER the two orders
 the rows are written in; metric_fields, format_table and the per-level summary of run_sweep are read off them.
@@ -52,10 +55,12 @@ the rows are written in; metric_fields, format_table and the per-level summary o
                                                             [--feedback BPHI BPSI [--feedbackNg G]] [--rxCombine]
                                                             [--channel scattering --aging MS [--speed MPS] [--heading DEG] [--randomHeading] [--carrier HZ]
                                                              [--forecast P M [--forecastSteps D]]]
+                                                            [--cfo EPS [--cfoSkip M]]
 
 The module holds no arithmetic of its own: packets come from csi_synth_structured / csi_synth_scattering, the aged channel from
 csi_scatter_channel_at_device, its forecast from csi_forecast_device on soundings made of that call and
-csi_sounding_noise_device, labels from
+csi_sounding_noise_device, the offset packets from csi_cfo_rotate_device (offsets: synth.cfo_offsets) and their correction from
+csi_cfo_correct_device, labels from
 csi_ls_estimate_device, the fit from trainer.fit, the estimates from csi_estimate_device, csi_lmmse_estimate_device,
 csi_lmmse_blind_device, csi_subspace_smooth_device (basis: subspace.delay_basis) and csi_beam_wiener_device (beams:
 beamspace.dft_basis, error level: csi_null_noise_device), every NMSE from csi_nmse_device, the precoders from
@@ -98,6 +103,9 @@ MUA_FIELDS = ('bersMUA_', 'EVM_rmsMUA_', 'sinrMUA_')
 # --forecast: the NMSE and the zero-forcing data phase of MUA with the forecast of the aged channel in the place of the estimate
 MSEF_FIELDS = ('MSEF_',)
 MUF_FIELDS = ('bersMUF_', 'EVM_rmsMUF_', 'sinrMUF_')
+# --cfo: the NMSE of the estimators on the level's packets under a carrier frequency offset, as they are and after the correction
+MSEO_FIELDS = ('MSEO_',)
+MSEOC_FIELDS = ('MSEOC_',)
 FORECAST_SOURCES = ('LS', 'perfect')      # the sources whose history can be simulated: the truth, and LS, whose error is white
 DELAY = 'DLY'                            # --delayTaps: the LS rows projected onto a window of delay taps (csi_subspace_smooth_device, w = 1)
 BEAMS = 'ANG'                            # --beams: the beam-space Wiener smoother across the Tx antennas on the LS planes (csi_beam_wiener_device)
@@ -128,17 +136,21 @@ FAMILIES = dict(
     MUJ=Family(MUJ_FIELDS, MUJ_FIELDS, EVERY, ('mu_jsdm',), 'muj_users'),
     FB=Family(FB_FIELDS, FB_FIELDS, SINGLE, ('feedback',), None),
     MUFB=Family(MUFB_FIELDS, MUFB_FIELDS, EVERY, ('feedback', 'mu'), 'mufb_users'),
+    # the offset twins of MSE (--cfo): written behind every other whole family, in front of the aged ones (CFO below)
+    MSEO=Family(MSEO_FIELDS, MSEO_FIELDS, ESTIMATORS, ('cfo',), None),
+    MSEOC=Family(MSEOC_FIELDS, MSEOC_FIELDS, ESTIMATORS, ('cfo',), None),
     FBC=Family(FBC_FIELDS, FBC_FIELDS, SINGLE, ('feedback', 'rx_combine'), None),
     MUC=Family(MUC_FIELDS, MUC_FIELDS, EVERY, ('mu', 'rx_combine'), 'muc_users'),
     MUFBC=Family(MUFBC_FIELDS, MUFBC_FIELDS, EVERY, ('feedback', 'mu', 'rx_combine'), 'mufbc_users'))
 # The two orders the rows (family, source) are written in, as blocks (family, sources) - source-major within a block - and
 # (family, USERS) for the per-user record.  Both are contracts with whoever reads the files.  They differ in their heads, which grew
-# option by option; every family behind MU stands whole, in the order of the table, at the end of both - the aged families behind the
-# others, the forecast families last.
+# option by option; every family behind MU stands whole, in the order of the table, at the end of both - the offset families behind the
+# others, the aged families behind them, the forecast families last.
 USERS = ()
 AGED = ('MSEA', 'LINKA', 'MUA')
 FORECAST = ('MSEF', 'MUF')
-_WHOLE = tuple(b for k in [k for k in FAMILIES if k not in ('MSE', 'LINK', 'RX', 'MU') + AGED + FORECAST] + list(AGED + FORECAST)
+CFO = ('MSEO', 'MSEOC')
+_WHOLE = tuple(b for k in [k for k in FAMILIES if k not in ('MSE', 'LINK', 'RX', 'MU') + CFO + AGED + FORECAST] + list(CFO + AGED + FORECAST)
                for b in ((k, FAMILIES[k].sources), (k, USERS)))
 MAT_ORDER = (('MSE', ESTIMATORS), ('LINK', SOURCES), ('MSE', ('perfect',)), ('MSE', (BLIND,)), ('LINK', (BLIND,)), ('RX', SINGLE),
              ('MSE', (DELAY,)), ('MU', SINGLE + (DELAY,)), ('MSE', (BEAMS, DELAY_BEAMS)), ('MU', (BEAMS,))) + _WHOLE      # metrics.mat
@@ -277,6 +289,57 @@ def forecast_planes(engine, user, npkt, seed, first_pkt, channel, aging, forecas
     return out
 
 
+def cfo_args(cfo):
+    """`cfo` as evaluate_level / run_sweep take it: None = off; a dict with max_eps (required: the offsets are uniform in +-max_eps
+    subcarrier spacings, 0 < max_eps < 0.5, the range the cyclic-prefix estimate is unambiguous in) and cp_skip (0: the samples left
+    out at the head of every prefix, 0 .. 63).  Returns the dict with every default filled in, or None."""
+    if cfo is None:
+        return None
+    out = dict(max_eps=None, cp_skip=0)
+    unknown = set(cfo) - set(out)
+    if unknown:
+        raise ValueError('unknown cfo parameters: %s' % sorted(unknown))
+    out.update(cfo)
+    if out['max_eps'] is None or not 0.0 < float(out['max_eps']) < 0.5:
+        raise ValueError('cfo: max_eps %r outside (0, 0.5) subcarrier spacings' % (out['max_eps'],))
+    if int(out['cp_skip']) != out['cp_skip'] or not 0 <= int(out['cp_skip']) <= 63:
+        raise ValueError('cfo: cp_skip %r outside 0 .. 63' % (out['cp_skip'],))
+    return dict(max_eps=float(out['max_eps']), cp_skip=int(out['cp_skip']))
+
+
+def cfo_level(engine, user, npkt, seed, first_pkt, cfo):
+    """The level's packets under a carrier frequency offset.  `user`: user_estimates of the level (same seed and
+    first_pkt).  The preambles rotated by synth.cfo_offsets(seed, first_pkt, npkt, max_eps) (cfo_rotate_device, scale +1) into planes
+    of their own, the estimators of ESTIMATORS on them as they are (plane_estimates with the level's own LMMSE inputs) -> 'MSEO_X',
+    their correction (cfo_correct_device) and the estimators again -> 'MSEOC_X', both against the unchanged true planes.  Also
+    'cfo_err' float64 [npkt] = eps_hat - eps, wrapped into [-1/2, 1/2), and 'cfo_quality' float32 [npkt]."""
+    cfo = cfo_args(cfo)
+    nr, nt = engine.nr, engine.nt
+    h_re, h_im = user['planes']['perfect']
+    eps = synth.cfo_offsets(seed, first_pkt, npkt, cfo['max_eps'])
+    d_eps = engine.to_device(eps.view(np.float32).reshape(npkt, 2))          # float64 as 2 float32 words per packet
+    shape = user['ltf'][0].shape
+    off, fixed = (engine.empty(shape), engine.empty(shape)), (engine.empty(shape), engine.empty(shape))
+    d_hat, d_q, d_link = engine.empty((npkt, 2)), engine.empty((npkt,)), engine.empty((npkt * nr * nt,))
+    out = {}
+    engine.cfo_rotate_device(user['ltf'][0], user['ltf'][1], npkt, d_eps, 1.0, off[0], off[1])
+    for field, ltf in ((MSEO_FIELDS[0], off), (MSEOC_FIELDS[0], fixed)):
+        if ltf is fixed:
+            engine.cfo_correct_device(off[0], off[1], npkt, fixed[0], fixed[1], cp_skip=cfo['cp_skip'], d_eps=d_hat, d_quality=d_q)
+        est = plane_estimates(engine, ltf[0], ltf[1], npkt, user['lmmse'])
+        for name in ESTIMATORS:
+            engine.nmse_device(h_re, h_im, est[name][0], est[name][1], npkt * nr * nt, N_DATA, d_per_link=d_link)
+            out[field + name] = d_link.download().astype(np.float64).reshape(npkt, nr * nt).mean(axis=1)
+        for a in (a for p in est.values() for a in p):
+            a.free()
+    err = d_hat.download().view(np.float64)[..., 0] - eps
+    out['cfo_err'] = err - np.rint(err)
+    out['cfo_quality'] = d_q.download()
+    for a in (d_eps, d_hat, d_q, d_link) + off + fixed:
+        a.free()
+    return out
+
+
 def make_dataset(engine, n_train, seed, n_taps=8, amp_scale=True, channel=None):
     """Noise-free training packets generated on the device (the pipeline trains on "SNR 120 ... NOISELESS" packets,
     full_pipeline_maMIMO_DNNEst.sh:21,33) with the LS estimate of the same signal as labels, as the dataset's y is
@@ -298,6 +361,18 @@ def make_dataset(engine, n_train, seed, n_taps=8, amp_scale=True, channel=None):
     return ds.dataset_from_packets(ltf, labels, engine.pilot)
 
 
+def plane_estimates(engine, d_re, d_im, npkt, lmmse):
+    """The estimators of ESTIMATORS from given preamble planes: LS + DNN (estimate_device) and the LMMSE smoother on the LS planes
+    (lmmse_estimate_device).  lmmse: its inputs (d_hvec, L, d_snr_db), or a function without arguments that returns them - called
+    behind estimate_device, where user_estimates has always uploaded them.  Returns {X: (re, im)} of new DeviceArrays."""
+    shape = (npkt, engine.nr, engine.nt, N_DATA)
+    o_re, o_im, ls_re, ls_im, m_re, m_im = (engine.empty(shape) for _ in range(6))
+    engine.estimate_device(d_re, d_im, npkt, o_re, o_im, ls_re, ls_im, checked=True)
+    d_hvec, L, d_snr = lmmse() if callable(lmmse) else lmmse
+    engine.lmmse_estimate_device(ls_re, ls_im, npkt, d_hvec, L, d_snr, m_re, m_im)
+    return dict(LS=(ls_re, ls_im), MMSE=(m_re, m_im), DNN=(o_re, o_im))
+
+
 def user_estimates(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=True, channel=None, blind=False, delay=None, beams=False,
                    az_offset=0.0, want_noise_std=True, delay_beams=False):
     """npkt test packets of one user at `snr_db` (packets first_pkt ... of stream `seed`) and every estimate of their channel: LS + DNN
@@ -310,7 +385,8 @@ def user_estimates(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=Tr
     (L = n_scat), the input the reference gives LMMSE_ce (h_tau, generate_maMIMO_LTF.m:342); snr_db[p][r] is the level.
 
     Returns {'planes': {X: (re, im)} with the true channel under 'perfect', 'ltf': (re, im), 'noise_std' (None unless wanted),
-    'free': every DeviceArray allocated here, for the caller to free}."""
+    'lmmse': the LMMSE inputs (d_hvec, L, d_snr_db) as plane_estimates takes them, 'free': every DeviceArray allocated here, for the
+    caller to free}."""
     nr, nt = engine.nr, engine.nt
     ch = scattering_args(channel)
     if ch is None:
@@ -321,16 +397,19 @@ def user_estimates(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=Tr
         d_re, d_im, h_re, h_im, d_std, d_tau = engine.synth_scattering(seed, first_pkt, npkt, snr_db=float(snr_db), amp_scale=amp_scale,
                                                                        want_noise_std=want_noise_std, want_tau=True, **ch)
     shape = (npkt, nr, nt, N_DATA)
-    o_re, o_im, ls_re, ls_im, m_re, m_im = (engine.empty(shape) for _ in range(6))
-    engine.estimate_device(d_re, d_im, npkt, o_re, o_im, ls_re, ls_im, checked=True)
-    if ch is None:
-        prof = tap_profile(n_taps)
-        d_hvec, L = engine.to_device(np.tile(prof, (npkt, 1))), prof.size
-    else:
-        d_hvec, L = d_tau, ch['n_scat']
-    d_snr = engine.to_device(np.full((npkt, nr), float(snr_db), np.float32))
-    engine.lmmse_estimate_device(ls_re, ls_im, npkt, d_hvec, L, d_snr, m_re, m_im)
-    planes = dict(LS=(ls_re, ls_im), MMSE=(m_re, m_im), DNN=(o_re, o_im), perfect=(h_re, h_im))
+    lmmse = []
+
+    def lmmse_inputs():
+        if ch is None:
+            prof = tap_profile(n_taps)
+            d_hvec, L = engine.to_device(np.tile(prof, (npkt, 1))), prof.size
+        else:
+            d_hvec, L = d_tau, ch['n_scat']
+        lmmse.append((d_hvec, L, engine.to_device(np.full((npkt, nr), float(snr_db), np.float32))))
+        return lmmse[0]
+
+    planes = dict(plane_estimates(engine, d_re, d_im, npkt, lmmse_inputs), perfect=(h_re, h_im))
+    (ls_re, ls_im), (d_hvec, _, d_snr) = planes['LS'], lmmse[0]
     if blind:
         planes[BLIND] = (engine.empty(shape), engine.empty(shape))
         engine.lmmse_blind_device(d_re, d_im, ls_re, ls_im, npkt, *planes[BLIND])
@@ -341,12 +420,12 @@ def user_estimates(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=Tr
     if beams:
         planes.update(beam_planes(engine, d_re, d_im, planes['LS'], planes[DELAY] if delay_beams and delay is not None else None, npkt, delay))
     free = [d_re, d_im, d_hvec, d_snr] + [a for p in planes.values() for a in p] + ([d_std] if d_std is not None else [])
-    return dict(planes=planes, ltf=(d_re, d_im), noise_std=d_std, free=free)
+    return dict(planes=planes, ltf=(d_re, d_im), noise_std=d_std, lmmse=lmmse[0], free=free)
 
 
 def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=True, keep=False, ber=None, channel=None, blind=False,
                    rx_estimate=False, delay=None, mu=None, beams=False, mu_hybrid=None, mu_jsdm=None, feedback=None, rx_combine=False,
-                   aging=None, forecast=None):
+                   aging=None, forecast=None, cfo=None):
     """One level: the estimates of npkt test packets at `snr_db` (user_estimates: packets first_pkt ... of stream `seed`, keep them
     disjoint from the training packets) and NMSE_subk of each against the true channel, then the data phases the options ask for (the
     table of the module).  Returns {'MSE_X': float64 [npkt], the per-link ratios averaged per packet} for X = LS, MMSE, DNN and every
@@ -363,6 +442,8 @@ def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=Tr
     forecast (forecast_args; needs aging) adds, behind the aged families, every user's forecast planes (forecast_planes) and against h_T
     'MSEF_X' for X = LS, perfect and, with mu, the zero-forcing data phase of MUA with the forecast planes as estimates ('bersMUF_X',
     'EVM_rmsMUF_X', 'sinrMUF_X', 'muf_users').
+    cfo (cfo_args) adds, behind the calls of every option above and in front of the aged block, the families of cfo_level ('MSEO_X',
+    'MSEOC_X', 'cfo_err', 'cfo_quality').
     keep=True adds 'arrays': the DeviceArrays ltf_re, ltf_im, h_re, h_im, ls_re, ls_im (the caller frees them)."""
     nr, nt = engine.nr, engine.nt
     users = [user_estimates(engine, snr_db, npkt, seed, first_pkt, n_taps, amp_scale, channel, blind, delay, beams,
@@ -393,6 +474,8 @@ def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=Tr
             nv = np.stack([synth.link_noise_var(u['noise_std'].download(), amp_scale) for u in users])
             out.update(combine_level(engine, [{x: u['planes'][x] for x in EVERY if x in u['planes']} for u in users], nv, npkt, seed, first_pkt,
                                      ns=ber['ns'], n_sym=ber['n_sym'], bps=ber['bps'], reg=(mu or {}).get('reg', 'zf'), fb=feedback, mu=bool(mu)))
+    if cfo:
+        out.update(cfo_level(engine, users[0], npkt, seed, first_pkt, cfo))
     if aging:
         spacing = float((mu or {}).get('spacing', 15.0))
         aged = [aged_truth(engine, npkt, seed + u, first_pkt, channel, aging, amp_scale, az_offset=u * spacing) for u in range(len(users))]
@@ -844,7 +927,7 @@ def combine_problem(ns, nr):
 def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500, seed=0, modeldir=None, fit_args=None, n_taps=8,
               amp_scale=True, save_dataset=None, verbose=True, ber=None, channel=None, blind=False, rx_estimate=False,
               delay_taps=None, delay_pre=0, users=None, mu_reg='zf', user_spacing=15.0, beams=False, mu_hybrid=None, mu_jsdm=None,
-              feedback=None, rx_combine=False, aging=None, forecast=None):
+              feedback=None, rx_combine=False, aging=None, forecast=None, cfo=None):
     """Training set -> models (loaded from `modeldir`, else fitted and saved into `out`) -> every level (evaluate_level).  Writes
     <out>/BS<Nt>_SNR<s>/metrics.mat per level and <out>/sweep.json, prints the table, returns the result dict (with the per-packet
     arrays under 'per_packet' = {level: {'MSE_LS', ...}}).  Test packets come from the stream seed + 1, behind the index range of
@@ -854,7 +937,8 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
     the key the table's `needs` name ('ber', 'channel': its parameters, 'blind', 'rx_estimate', 'mu': {users, reg, spacing},
     'mu_hybrid': {n_rf}, 'mu_jsdm': {b, r_star, tol, mode}, 'feedback': {b_phi, b_psi, ng, report_bits: the bits of one packet's
     report}, 'delay': {taps, pre, rank}, 'beams', 'rx_combine': needs ber, one of feedback / users and ns <= min(4, Nr) - combine_problem; 'aging': aging_args, needs the
-    scattering channel; 'forecast': forecast_args, needs aging);
+    scattering channel; 'forecast': forecast_args, needs aging; 'cfo': cfo_args - a level then also holds cfo_rmse, the rms of the
+    wrapped error of the offset estimate in subcarrier spacings, and cfo_quality, the mean);
     a level of sweep.json then holds mean and confidence interval of every field the
     option adds, and the per-user records, in JSON_ORDER."""
     if feedback is not None:
@@ -901,6 +985,7 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
     forecast = forecast_args(forecast)
     if forecast and not aging:
         raise ValueError('forecast needs aging (and with it the scattering channel): it forecasts the aged channel')
+    cfo = cfo_args(cfo)
     delay = (int(delay_taps), int(delay_pre)) if delay_taps else None
     os.makedirs(out, exist_ok=True)
     result = dict(nt=engine.nt, nr=engine.nr, n_train=int(n_train), n_test=int(n_test), seed=int(seed), n_taps=int(n_taps),
@@ -913,7 +998,8 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
                    rx_estimate=bool(rx_estimate), mu=mu and dict(mu), mu_hybrid=mu_hybrid and dict(n_rf=mu_hybrid), mu_jsdm=mu_jsdm and dict(mu_jsdm),
                    feedback=feedback and dict(feedback, report_bits=report_bits),
                    delay=delay and dict(taps=delay[0], pre=delay[1], rank=int(subspace.delay_basis(*delay)[0].shape[1])), beams=bool(beams),
-                   rx_combine=bool(rx_combine), aging=aging and dict(aging), forecast=forecast and dict(forecast))
+                   rx_combine=bool(rx_combine), aging=aging and dict(aging), forecast=forecast and dict(forecast),
+                   cfo=cfo and dict(cfo))
     result.update((k, v) for k, v in options.items() if v)          # an option that is off leaves no key
     if modeldir:
         load_models(engine, modeldir)
@@ -935,11 +1021,14 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
         mse = evaluate_level(engine, snr, n_test, seed + 1, n_train + i * n_test, n_taps, amp_scale, ber=ber, channel=channel, blind=blind,
                              rx_estimate=rx_estimate, delay=delay, mu=mu, beams=beams, mu_hybrid=mu_hybrid, mu_jsdm=mu_jsdm,
                              feedback=feedback, **(dict(rx_combine=True) if rx_combine else {}), **(dict(aging=aging) if aging else {}),
-                             **(dict(forecast=forecast) if forecast else {}))
+                             **(dict(forecast=forecast) if forecast else {}), **(dict(cfo=cfo) if cfo else {}))
         lv = dict(snr_db=float(snr), seconds=time.perf_counter() - t0)
         write_metrics(os.path.join(out, 'BS%d_SNR%g' % (engine.nt, snr), 'metrics.mat'), mse)
         for key, field, _ in _columns(result):
             lv[key] = mse[key] if field is None else _interval(mse[field])
+        if cfo:
+            lv['cfo_rmse'] = float(np.sqrt(np.mean(np.asarray(mse['cfo_err'], np.float64) ** 2)))
+            lv['cfo_quality'] = float(np.mean(mse['cfo_quality']))
         result['levels'].append(lv)
         per_packet[float(snr)] = mse
     with open(os.path.join(out, 'sweep.json'), 'w') as f:
@@ -1020,6 +1109,11 @@ def build_parser():
                    help='--aging: also forecast the aged channel with a linear predictor of order M over P soundings MS / D apart '
                         '(csi_forecast_device; sources LS and perfect) - MSEF_, with --users bersMUF_ / EVM_rmsMUF_ / sinrMUF_')
     p.add_argument('--forecastSteps', default=4, type=int, metavar='D', help='--forecast: the horizon MS in sounding intervals')
+    p.add_argument('--cfo', default=None, type=float, metavar='EPS',
+                   help='also evaluate LS / MMSE / DNN on the level\'s packets under a carrier frequency offset uniform in +-EPS subcarrier spacings '
+                        'per packet (0 < EPS < 0.5; csi_cfo_rotate_device), as they are - MSEO_ - and after the cyclic-prefix correction '
+                        '(csi_cfo_correct_device) - MSEOC_, with cfo_rmse and cfo_quality per level')
+    p.add_argument('--cfoSkip', default=0, type=int, metavar='M', help='--cfo: samples left out at the head of every cyclic prefix (0 .. 63)')
     p.add_argument('--blind', action='store_true',
                    help='add the estimator MMSEb: LMMSE smoothing from the packet\'s own statistics (csi_lmmse_blind_device) - MSE_MMSEb, and with --ber its link metrics')
     p.add_argument('--delayTaps', default=0, type=int, metavar='L',
@@ -1043,6 +1137,13 @@ def forecast_from_args(args):
     if args.forecast is None:
         return None
     return dict(soundings=args.forecast[0], order=args.forecast[1], steps=args.forecastSteps)
+
+
+def cfo_from_args(args):
+    """The `cfo` argument of run_sweep that the command line asks for: None without --cfo."""
+    if args.cfo is None:
+        return None
+    return dict(max_eps=args.cfo, cp_skip=args.cfoSkip)
 
 
 def aging_from_args(args):
@@ -1112,6 +1213,13 @@ def parse_args(argv=None):
             parser.error('--forecast: ' + str(err))
     elif args.forecastSteps != 4:
         parser.error('--forecastSteps needs --forecast')
+    if args.cfo is not None:
+        try:
+            cfo_args(cfo_from_args(args))
+        except ValueError as err:
+            parser.error('--cfo: ' + str(err))
+    elif args.cfoSkip != 0:
+        parser.error('--cfoSkip needs --cfo')
     if args.beams and args.nTX > beamspace.MAX_NT:
         parser.error('--beams takes nTX up to %d' % beamspace.MAX_NT)
     return args
@@ -1136,7 +1244,8 @@ def main(argv=None):
               mu_hybrid=args.muHybrid or None,
               mu_jsdm=dict(b=args.muJSDM, r_star=args.jsdmRank, tol=args.jsdmTol, mode=args.jsdmMode) if args.muJSDM else None,
               feedback=dict(b_phi=args.feedback[0], b_psi=args.feedback[1], ng=args.feedbackNg) if args.feedback is not None else None,
-              rx_combine=bool(args.rxCombine), aging=aging_from_args(args), forecast=forecast_from_args(args))
+              rx_combine=bool(args.rxCombine), aging=aging_from_args(args), forecast=forecast_from_args(args),
+              cfo=cfo_from_args(args))
     return 0
 
 

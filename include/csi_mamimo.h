@@ -35,6 +35,9 @@
  *        a user that moves)                                          csi_scatter_channel_at_device
  *   (an addition: a linear predictor over several soundings of
  *        that channel, fitted on the soundings themselves)          csi_forecast[_device], csi_forecast_gram/fit/apply_device, csi_sounding_noise_device
+ *   (an addition: the synchronisation stage in front of the
+ *        estimators - carrier frequency offset of the preamble
+ *        from its cyclic prefixes, and the rotation that removes it) csi_cfo_estimate_device, csi_cfo_rotate_device, csi_cfo_correct[_device]
  *   omphybweights       BER_test_maMIMO_LTF.m:347-376                csi_hybrid_weights[_device]
  *   --execTime profiler loop                       DNN.py:441-475   csi_profile_*
  *   Model.fit step (noise, BN, dropout, Adam)       DNN.py:272-316   csi_train_*
@@ -48,7 +51,7 @@
  * context's stream and return without waiting; call csi_synchronize before reading results.
  *
  * Device pointers (csi_predict_device, csi_ls_estimate_device, csi_estimate_device, csi_lmmse_estimate_device, csi_lmmse_blind_device, csi_subspace_smooth_device, csi_beam_power_device, csi_beam_smooth_device, csi_beam_wiener_device, csi_null_noise_device, csi_nmse_device,
- * csi_hybrid_weights_device, csi_link_sim_device, csi_link_sim_rx_device, csi_mu_precoder_device, csi_mu_link_sim_device, csi_mu_hybrid_precoder_device, csi_mu_covariance_device, csi_mu_jsdm_precoder_device, csi_feedback_compress_device, csi_feedback_expand_device, csi_rx_combiner_device, csi_rx_apply_combiner_device, csi_viterbi_decode_device, csi_synth_*, csi_scatter_channel_at_device, csi_forecast_*_device, csi_sounding_noise_device).  An array of exactly the documented
+ * csi_hybrid_weights_device, csi_link_sim_device, csi_link_sim_rx_device, csi_mu_precoder_device, csi_mu_link_sim_device, csi_mu_hybrid_precoder_device, csi_mu_covariance_device, csi_mu_jsdm_precoder_device, csi_feedback_compress_device, csi_feedback_expand_device, csi_rx_combiner_device, csi_rx_apply_combiner_device, csi_viterbi_decode_device, csi_synth_*, csi_scatter_channel_at_device, csi_forecast_*_device, csi_sounding_noise_device, csi_cfo_*_device).  An array of exactly the documented
  * size suffices: it may be a slice of a larger allocation whose neighbours hold live data of any value (NaN and 1e38 included).
  * Nothing outside the arrays is written, nothing outside them reaches a result, and input arrays are not modified.  Every re / im
  * PLANE (the preambles [npkt][Nr][len_ltf], the CSI planes [npkt][Nr][Nt][234 or n_out], fbb, frf_mean, xeq, gest, the precoder planes W, g) starts on a 16-byte
@@ -976,6 +979,40 @@ int  csi_forecast(csi_ctx* ctx, const float* const* x_re, const float* const* x_
                   uint32_t flags, float* out_re, float* out_im, float* c_re, float* c_im, float* fit_err, int32_t* info);
 int  csi_sounding_noise_device(csi_ctx* ctx, uint64_t seed, int64_t first_pkt, int64_t npkt, const float* d_err_var, const float* d_x_re,
                                const float* d_x_im, float* d_out_re, float* d_out_im);
+
+/* Carrier frequency offset of the sounding preamble: cyclic-prefix estimator and corrector (csrc/cfo.hip.h).  No
+ * reference counterpart (the reference's receiver sits exactly on the transmitter's carrier); it is the synchronisation stage in front of
+ * csi_ls_estimate_device / csi_estimate_device / csi_lmmse_blind_device, and the impairment that tests it.
+ * x[p][r][n] are the preamble planes [npkt][Nr][320 Nt], n = 320 s + m (64 samples of cyclic prefix, 256 of body per symbol); eps is in
+ * subcarrier spacings (cycles per 256 samples), one per packet, shared by its Nr antennas.
+ *   y[p][r][n] = x[p][r][n] exp(2 pi i scale eps[p] n / 256)              scale +1 impairs, -1 corrects    csi_cfo_rotate_device
+ *   gamma[p]   = sum_r sum_s sum_{m = cp_skip}^{63} conj(x[p][r][320 s + m]) x[p][r][320 s + m + 256]
+ *   E[p]       = 1/2 sum (|x[.. m]|^2 + |x[.. m + 256]|^2) over the same samples
+ *   eps_hat[p] = atan2(Im gamma, Re gamma) / 2 pi,  quality[p] = |gamma| / E  (about snr / (1 + snr));
+ *   E == 0 gives eps_hat = 0 and quality = 0                                                               csi_cfo_estimate_device
+ * cp_skip (0 .. 63) leaves out the head of every prefix, which a real capture loses to the previous symbol's echo.  The phase counts
+ * from sample 0 of the packet: a corrected packet carries no residual common phase.  The estimate is unambiguous for |eps| < 0.5.
+ * Arithmetic: the estimator reads only [cp_skip, 64) and [256 + cp_skip, 320) of every symbol; products in fp32, every sum in fp64 in an
+ * order fixed by (Nt, Nr, cp_skip) alone, no atomics, one fp64 atan2 per packet: a packet has the same bits whatever the call size or
+ * its position.  The rotation forms the turn count scale eps n / 256 in fp64, reduces it to [-1/2, 1/2] in fp64 and only then takes an
+ * fp32 sine and cosine; scale eps[p] == 0 returns the input bits.  out may be in itself (re with re, im with im).
+ *   d_eps      double [npkt], 8-byte aligned;  d_quality  float [npkt] or NULL
+ * csi_cfo_correct_device is the estimate followed by the rotation with scale -1, two launches, the bits of the two calls made by hand;
+ * d_eps may be NULL, then eps lives in a context workspace sized by eager calls (inside a capture an eager call of the same shape goes
+ * first).  csi_cfo_correct: the same on host buffers in packet chunks of 256 MiB of staging (the context's workspace_bytes when that is
+ * smaller), eps and quality optional; same bits as the device entry.
+ * Every device entry is asynchronous on the context's stream and may be captured.  Refused with text, before any launch: null planes,
+ * npkt < 1, cp_skip outside 0 .. 63, planes off a 16-byte boundary, planes that overlap partially (an output plane that is not its own
+ * input plane but shares a byte with a plane), d_eps / d_quality that share a byte with a plane, a non-finite scale, a single-input
+ * context.  A null context returns -1.  Profile entries "cfo_corr" (16 bytes per correlated pair of samples) and "cfo_rotate" (16 bytes
+ * per sample); read-only option "cfo_launches" counts their kernels. */
+int  csi_cfo_estimate_device(csi_ctx* ctx, const float* d_ltf_re, const float* d_ltf_im, int64_t npkt, int cp_skip, double* d_eps, float* d_quality);
+int  csi_cfo_rotate_device(csi_ctx* ctx, const float* d_in_re, const float* d_in_im, int64_t npkt, const double* d_eps, double scale,
+                           float* d_out_re, float* d_out_im);
+int  csi_cfo_correct_device(csi_ctx* ctx, const float* d_ltf_re, const float* d_ltf_im, int64_t npkt, int cp_skip, float* d_out_re, float* d_out_im,
+                            double* d_eps, float* d_quality);
+int  csi_cfo_correct(csi_ctx* ctx, const float* ltf_re, const float* ltf_im, int64_t npkt, int cp_skip, float* out_re, float* out_im, double* eps,
+                     float* quality);
 
 /* ---- multi-GPU: packets shard over the GPUs of a node (one process and one context per GPU), the weights are shared and
  * read-only, outputs stay sharded.  The single collective of the path is the load-time broadcast of the
