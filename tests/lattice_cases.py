@@ -17,6 +17,9 @@ and every route must then EQUAL the fp64 oracle; a mismatch is an indexing fact 
   * "dense" (fp32 contexts only - h2 would need more than 8 bits): +-1 everywhere.
   * biases: integers in [-3, 3].
 
+  * CONV1D models (conv_lattice_case): the same FC stack behind the front end's 64 len_ltf features, which integer samples, taps of +-1 and
+    a conv BatchNormalization of the kind above keep on multiples of 1/2 - see the section "CONV1D models" below.
+
 Everything is generated from seeds derived from the shape; there are no golden files.  TEST INFRASTRUCTURE ONLY."""
 import functools
 import math
@@ -176,10 +179,212 @@ def lattice_case(nt, nr, npkt, hidden, n_out=234, pm1_pilot=False, dense=False, 
     ltf_in = pool_ltf(ltf, pool) if pool else ltf            # what layer 0 reads: the oracle's input (the engine pools `ltf` itself)
     revive_dead_units(w_re, ltf_in.real.astype(np.float64).reshape(npkt * nr, -1), P)
     revive_dead_units(w_im, ltf_in.imag.astype(np.float64).reshape(npkt * nr, -1), P)
-    c =types.SimpleNamespace(nt=nt, nr=nr, npkt=npkt, hidden=hidden, n_out=n_out, dense=dense, bn_eps=BN_EPS, pool=pool,
+    c = types.SimpleNamespace(nt=nt, nr=nr, npkt=npkt, hidden=hidden, n_out=n_out, dense=dense, bn_eps=BN_EPS, pool=pool, conv=None,
                               w_re=w_re, w_im=w_im, P=np.asarray(P, dtype=np.float64), ltf=ltf, ltf_in=ltf_in)
     c.trace = functools.lru_cache(maxsize=None)(lambda d: trace(c, d))
     c.cover = lambda: (min(c.trace(d).k_cover for d in ('real', 'imag')), min(c.trace(d).nonzero_out for d in ('real', 'imag')))
+    return c
+
+
+# ---------------------------------------------------------------------------------------------------------------- CONV1D models
+# The front end (csrc/conv_frontend.hip.h) turns a preamble part x[L] into 64 L features; layer 0 then has K0 = 64 L + nt rows.
+#   * cnn1d_1: two taps of +-1 per channel (channel c holds tap c mod 7 and one other, so every tap index is used by ~36 channels), the
+#     rest 0; conv_bn: variance 1 - 2^-10 (scale = gamma exactly), gamma in {+-1, +-2}, integer mean.  With integer samples every
+#     relu(conv) * scale + shift is an integer and every pooled feature a multiple of 1/2.
+#   * 'zero_rest' (both context types): bias in {0, -1}, beta = mean gamma - the folded shift is exactly 0 (the fold is still computed from
+#     non-zero statistics), so a feature is non-zero only around a non-zero sample and layer 0's sum stays inside bf16's 8 bits.
+#   * 'full' (fp32 contexts): bias in [-2, 2], free beta in [-2, 2] - every one of the 64 L features of every preamble is non-zero.
+#   * 'tie' (bf16 contexts, compared with the bf16 emulation): 'zero_rest' with the walked samples raised to +-257 / +-259, whose pooled
+#     features 128.5 / 129.5 lie half way between two bf16 numbers - nearest-even, truncation and half-up store three different arrays.
+#   * samples: `nnz` integers of {+-1, +-2} per part at walked positions, and pinned ones (CONV_TILE = 128 samples per front-end tile):
+#     t in {0, 1, 2, L-3, L-2, L-1} in preambles 0 AND 1 (a halo that reads the neighbouring row meets data where zeros belong), and
+#     e-3 ... e+2 around the first and the last interior tile edge e, value +-2, dealt over the preambles with free slots (they reach the
+#     neighbouring tile only through its halo; both parities of t, hence both members of a pooled pair, for every tap).
+# (nt, nr, npkt, hidden, variant, nnz): shared with test_lattice_host.py, which proves every one of them
+CONV_TILE = 128
+CONV_F32_SMALL_CASES = [(4, 2, 1, (64,), v, 16) for v in ('zero_rest', 'full')] + [(4, 2, 2, (64,), v, 16) for v in ('zero_rest', 'full')]
+CONV_F32_MID_CASES = [(4, 2, 37, (64,), 'zero_rest', 16), (4, 2, 37, (64,), 'full', 16)]          # 74 preambles: 9 ... 256
+CONV_F32_STRIDE_CASES = [(4, 2, 110, (64,), 'full', 16)]           # 2200 front-end tiles: more than the 2048 workgroups of a launch
+CONV_RANGES_CASES = [(16, 3, 3, (64,), 'zero_rest', 8)]            # K0 = 327680: 256 k ranges of layer 0 (fp32 and bf16 contexts)
+CONV_BF16_CASES = [(4, 4, 1, (64,), 'zero_rest', 8), (4, 2, 37, (64,), 'zero_rest', 9), (4, 2, 140, (64,), 'zero_rest', 8)]
+CONV_TIE_CASES = [(4, 2, 3, (64,), 'tie', 8)]
+CONV_F32_CASES = CONV_F32_SMALL_CASES + CONV_F32_MID_CASES + CONV_F32_STRIDE_CASES + CONV_RANGES_CASES
+CONV_CASES = CONV_F32_CASES + [c for c in CONV_BF16_CASES if c not in CONV_F32_CASES]
+
+
+def conv_id(c):
+    return 'conv-nt%d-nr%d-p%d-h%s-%s-nnz%d' % (c[0], c[1], c[2], 'x'.join(map(str, c[3])), c[4], c[5])
+
+
+def make_conv_front(rng, variant):
+    """cnn1d_1.kernel [7, 1, 128] / .bias and conv_bn.* of one component model"""
+    ch = np.arange(128)
+    j1 = ch % 7
+    j2 = (j1 + 1 + (ch // 7) % 6) % 7
+    taps = np.zeros((7, 1, 128), dtype=np.float32)
+    taps[j1, 0, ch] = rng.choice(np.array([-1.0, 1.0], dtype=np.float32), 128)
+    taps[j2, 0, ch] = rng.choice(np.array([-1.0, 1.0], dtype=np.float32), 128)
+    gamma = rng.choice(np.array([-2.0, -1.0, 1.0, 2.0], dtype=np.float32), 128)
+    mean = rng.integers(0, 4, 128).astype(np.float32)
+    if variant == 'full':
+        bias, beta = rng.integers(-2, 3, 128).astype(np.float32), rng.integers(-2, 3, 128).astype(np.float32)
+    else:
+        bias, beta = -(ch % 8 == 7).astype(np.float32), mean * gamma
+    return {'cnn1d_1.kernel': taps, 'cnn1d_1.bias': bias, 'conv_bn.gamma': gamma, 'conv_bn.beta': beta, 'conv_bn.moving_mean': mean,
+            'conv_bn.moving_variance': np.full(128, 1.0 - BN_EPS, dtype=np.float32)}
+
+
+def conv_edges(nt):
+    """the interior tile edges the pins surround: the first and the last"""
+    return (CONV_TILE, 320 * nt - CONV_TILE)
+
+
+def conv_positions(nt, m1, part, nnz):
+    """(pos [m1, nnz] sample indices of the non-zeros of preamble part `part`, pins): pins is a list of (preamble, slot, t, edge) with
+    edge = None for the row-end pins; every slot that is not pinned walks the sample axis on a stride coprime to it."""
+    L = 320 * nt
+    assert m1 >= 2 and nnz >= 6 and m1 * nnz >= 24, 'no room for the pinned samples'
+    i = np.arange(m1 * nnz, dtype=np.int64).reshape(m1, nnz)
+    pos = (i * coprime_stride(L) + part * (L // 2 + 7)) % L
+    pins = []
+    for m in (0, 1):
+        for s, t in enumerate((0, 1, 2, L - 3, L - 2, L - 1)):
+            pos[m, s] = t
+            pins.append((m, s, t, None))
+    free = [6, 6] + [0] * (m1 - 2)
+    order = list(range(2, m1)) + [0, 1]
+    at = 0
+    for off in range(-3, 3):
+        for e in conv_edges(nt):
+            while free[order[at % len(order)]] >= nnz:
+                at += 1
+            m = order[at % len(order)]
+            pos[m, free[m]] = e + off
+            pins.append((m, free[m], e + off, e))
+            free[m] += 1
+            at += 1
+    return pos, pins
+
+
+def make_conv_packets(rng, nt, nr, npkt, nnz, tie):
+    m1, L = npkt * nr, 320 * nt
+    planes = []
+    for part in (0, 1):
+        pos, pins = conv_positions(nt, m1, part, nnz)
+        v = rng.choice(np.array([-2.0, -1.0, -1.0, -1.0, 1.0, 1.0, 1.0, 2.0], dtype=np.float32), pos.shape)      # three +-1 for every +-2
+        pinned = np.zeros(pos.shape, dtype=bool)
+        for m, s, _, e in pins:
+            pinned[m, s] = True
+            if e is not None:
+                v[m, s] = np.sign(v[m, s]) * 2              # also a channel of bias -1 answers a +-2
+        if tie:
+            v = np.where(pinned, v, np.sign(v) * np.where(np.abs(v) == 1, 257.0, 259.0)).astype(np.float32)
+        x = np.zeros((m1, L), dtype=np.float32)
+        x[np.arange(m1)[:, None], pos] = v
+        for m, s, t, _ in pins:                                 # (a walked slot of the same preamble may fall on a pinned sample)
+            x[m, t] = v[m, s]
+        planes.append(x.reshape(npkt, nr, L))
+    return (planes[0] + 1j * planes[1]).astype(np.complex64)
+
+
+def conv_fold(w):
+    """(scale, shift) of conv_bn in fp64, as csi_load_weights folds it"""
+    sc = w['conv_bn.gamma'].astype(np.float64) / np.sqrt(w['conv_bn.moving_variance'].astype(np.float64) + float(w['bn_eps']))
+    return sc, w['conv_bn.beta'].astype(np.float64) - w['conv_bn.moving_mean'].astype(np.float64) * sc
+
+
+def conv_features(x, w, rows_per_pass=32):
+    """fp64 statement of the front end: x [rows, L] -> [rows, 64 L].  conv[t, c] = b[c] + sum_j K[j, c] x[t + j - 3] (zeros outside the row),
+    q = relu(conv) scale + shift, f[u 128 + c] = (q[2u, c] + q[2u + 1, c]) / 2."""
+    x = np.asarray(x, dtype=np.float64)
+    rows, L = x.shape
+    k = w['cnn1d_1.kernel'].astype(np.float64).reshape(7, 128)
+    b = w['cnn1d_1.bias'].astype(np.float64)
+    sc, sh = conv_fold(w)
+    out = np.empty((rows, 64 * L))
+    for r0 in range(0, rows, rows_per_pass):
+        xp = np.pad(x[r0:r0 + rows_per_pass], ((0, 0), (3, 3)))
+        win = np.lib.stride_tricks.sliding_window_view(xp, 7, axis=1)              # [rows, L, 7]: x[t - 3 .. t + 3]
+        q = np.maximum(win @ k + b, 0.0) * sc + sh
+        out[r0:r0 + rows_per_pass] = (0.5 * (q[:, 0::2] + q[:, 1::2])).reshape(len(xp), 64 * L)
+    return out
+
+
+def conv_rest(w):
+    """[128] the feature of channel c where no sample is in reach: relu(b) scale + shift"""
+    sc, sh = conv_fold(w)
+    return np.maximum(w['cnn1d_1.bias'].astype(np.float64), 0.0) * sc + sh
+
+
+def conv_feat_want(c, d):
+    """The feature columns the samples of the batch move, derived from the sample list alone (no dense forward): every (sample, channel,
+    tap) term is summed into its conv output by key, the change of relu(conv) scale against the rest value is summed into its pooled
+    position, and a column counts where that sum is non-zero in some preamble and layer 0 holds a non-zero weight for it."""
+    w = c.w_re if d == 'real' else c.w_im
+    L, m1 = 320 * c.nt, c.npkt * c.nr
+    x = (c.ltf.real if d == 'real' else c.ltf.imag).reshape(m1, L)
+    m, t = np.nonzero(x)
+    v = x[m, t].astype(np.float64)
+    k = w['cnn1d_1.kernel'].astype(np.float64).reshape(7, 128)
+    j, ch = np.nonzero(k)
+    to = t[:, None] + 3 - j[None, :]                                              # the output sample tap j of a sample at t lands in
+    ok = (to >= 0) & (to < L)
+    key = ((m[:, None] * L + to) * 128 + ch[None, :])[ok]
+    term = (v[:, None] * k[j, ch][None, :])[ok]
+    key, inv = np.unique(key, return_inverse=True)
+    s = np.zeros(len(key))
+    np.add.at(s, inv.ravel(), term)
+    chk = key % 128
+    b, (sc, _) = w['cnn1d_1.bias'].astype(np.float64), conv_fold(w)
+    dq = (np.maximum(b[chk] + s, 0.0) - np.maximum(b[chk], 0.0)) * sc[chk]
+    mt = key // 128                                                                # m L + t
+    key2 = ((mt // L) * (L // 2) + (mt % L) // 2) * 128 + chk
+    key2, inv2 = np.unique(key2, return_inverse=True)
+    s2 = np.zeros(len(key2))
+    np.add.at(s2, inv2.ravel(), dq)
+    col = np.unique(key2[s2 != 0] % (64 * L))
+    used = np.abs(w['fc_dense0.kernel'][:64 * L]).sum(1) > 0
+    return float(np.count_nonzero(used[col])) / (64 * L)
+
+
+def conv_feat_cover(c, d):
+    """measured on the features layer 0 reads: share of columns that differ from their channel's rest value in some preamble and meet a weight"""
+    w = c.w_re if d == 'real' else c.w_im
+    f = (c.ltf_in.real if d == 'real' else c.ltf_in.imag).reshape(c.npkt * c.nr, -1)
+    moved = (f != np.tile(conv_rest(w), f.shape[1] // 128).astype(np.float32)).any(0)
+    return float(np.mean(moved & (np.abs(w['fc_dense0.kernel'][:f.shape[1]]).sum(1) > 0)))
+
+
+@functools.lru_cache(maxsize=2)
+def conv_lattice_case(nt, nr, npkt, hidden, variant='zero_rest', nnz=16, n_out=234):
+    """The fixture of one CONV1D shape: the namespace of lattice_case, with w_re / w_im carrying cnn1d_1.* and conv_bn.* as well, ltf the raw
+    preambles the engine gets, ltf_in complex64 [npkt, nr, 64 * 320 nt] the features layer 0 reads (conv_features of each part through its
+    own model: the oracle's input), conv = the variant, pins[part] = the pinned samples, feat_cover() = the minimum over both models."""
+    hidden = tuple(hidden)
+    vi = ('zero_rest', 'full', 'tie').index(variant)
+    rng = np.random.default_rng([nt, n_out, len(hidden)] + list(hidden) + [7, vi])
+    L = 320 * nt
+    ws = []
+    for _ in range(2):
+        w = make_model(rng, nt, hidden, n_out, False, 64 * L)
+        w.update(make_conv_front(rng, variant))
+        ws.append(w)
+    w_re, w_im = ws
+    P = np.asarray(o.hadamard(nt), dtype=np.float64)
+    ltf = make_conv_packets(np.random.default_rng([nt, nr, npkt, nnz, 11]), nt, nr, npkt, nnz, variant == 'tie')
+    f_re = conv_features(ltf.real.reshape(npkt * nr, L), w_re)
+    f_im = conv_features(ltf.imag.reshape(npkt * nr, L), w_im)
+    revive_dead_units(w_re, f_re, P)
+    revive_dead_units(w_im, f_im, P)
+    ltf_in = np.empty((npkt, nr, 64 * L), dtype=np.complex64)
+    ltf_in.real, ltf_in.imag = f_re.reshape(ltf_in.shape), f_im.reshape(ltf_in.shape)
+    assert np.array_equal(ltf_in.real.reshape(f_re.shape), f_re) and np.array_equal(ltf_in.imag.reshape(f_im.shape), f_im)     # exact as float32
+    c = types.SimpleNamespace(nt=nt, nr=nr, npkt=npkt, hidden=hidden, n_out=n_out, dense=False, bn_eps=BN_EPS, pool=None, conv=variant, nnz=nnz,
+                              w_re=w_re, w_im=w_im, P=P, ltf=ltf, ltf_in=ltf_in,
+                              pins=[conv_positions(nt, npkt * nr, part, nnz)[1] for part in (0, 1)])
+    c.trace = functools.lru_cache(maxsize=None)(lambda d: trace(c, d))
+    c.cover = lambda: (min(c.trace(d).k_cover for d in ('real', 'imag')), min(c.trace(d).nonzero_out for d in ('real', 'imag')))
+    c.feat_cover = lambda: min(conv_feat_cover(c, d) for d in ('real', 'imag'))
     return c
 
 
@@ -202,7 +407,8 @@ def trace(c, d):
     t = types.SimpleNamespace()
     row_used = np.abs(k0).sum(1) > 0
     t.l0_cover = float(np.mean((np.abs(x).sum(0) > 0) & row_used[:len_ltf]))
-    t.l0_want = min(1.0, np.unique(l0_positions(c.nt, c.npkt * c.nr, 0 if d == 'real' else 1)).size / len_ltf) if not c.pool else None
+    plain = not c.pool and not getattr(c, 'conv', None)          # (pooled and CONV1D models: layer 0 reads features, not the walked samples)
+    t.l0_want = min(1.0, np.unique(l0_positions(c.nt, c.npkt * c.nr, 0 if d == 'real' else 1)).size / len_ltf) if plain else None
     covers = [float(np.mean((np.abs(c.P).sum(0) > 0) & row_used[len_ltf:]))]
     abs_sum = [float((np.abs(x) @ np.abs(k0[:len_ltf])).max() + (np.abs(c.P) @ np.abs(k0[len_ltf:])).max())]
     z = (x @ k0[:len_ltf])[:, None, :] + (c.P @ k0[len_ltf:] + w['fc_dense0.bias'].astype(np.float64))[None, :, :]
@@ -261,3 +467,78 @@ def forward_bf16_hooked(x, w, h1_hook=None, round_h1=o.bf16_round):
         if i == 0 and h1_hook is not None:
             h = h1_hook(h)
         i += 1
+
+
+def bf16_half_up(x):
+    """round half away from zero on the magnitude bits: what `u + 0x8000` in place of the nearest-even increment stores"""
+    a = np.ascontiguousarray(x, dtype=np.float32)
+    return ((a.view(np.uint32).astype(np.uint64) + 0x8000) & 0xFFFF0000).astype(np.uint32).view(np.float32).reshape(a.shape)
+
+
+CONV_MUTANTS = ('halo_from_neighbouring_row', 'halo_zero_at_tile_edges', 'taps_reversed', 'pool_pairs_shifted', 'channels_first',
+                'bn_before_relu', 'other_model', 'lane_groups_of_4_swapped', 'lane_groups_of_8_swapped', 'position_dropped_at_tile_end')
+
+
+def frontend_f32(x, w, mutant=None, other=None):
+    """The front end in float32 in the operation order of conv_frontend_kernel: x [rows, L] -> [rows, 64 L] float32.  e / o start at the bias
+    and take the taps j = 0 .. 6 in turn (fma: exact products here), q = fma(relu, scale, shift) with the constants folded in double and
+    stored as float32, f = 0.5 (qe + qo).  `mutant` (one of CONV_MUTANTS) breaks it the way a kernel port would; `other` = the weights of
+    the other component model, which 'other_model' takes its constants from.  Tiles of CONV_TILE samples as the kernel cuts them."""
+    f32 = np.float32
+    x = np.ascontiguousarray(x, dtype=f32)
+    rows, L = x.shape
+    src = other if mutant == 'other_model' else w
+    k = src['cnn1d_1.kernel'].astype(f32).reshape(7, 128)
+    if mutant == 'taps_reversed':
+        k = k[::-1]
+    b = src['cnn1d_1.bias'].astype(f32)
+    sc, sh = (v.astype(f32) for v in conv_fold(src))
+    if mutant == 'halo_from_neighbouring_row':                     # x[r L + t] for t outside [0, L): the neighbouring rows, zeros only around the plane
+        flat = np.concatenate([np.zeros(3, f32), x.ravel(), np.zeros(3, f32)])
+        xp = np.lib.stride_tricks.sliding_window_view(flat, L + 6)[::L]
+    elif mutant == 'halo_zero_at_tile_edges':                      # every tile sees zeros beyond its own samples
+        xp = np.pad(x.reshape(rows * (L // CONV_TILE), CONV_TILE), ((0, 0), (3, 3)))
+    else:
+        xp = np.pad(x, ((0, 0), (3, 3)))
+    n, T = xp.shape[0], xp.shape[1] - 6
+    acc = np.broadcast_to(b, (n, T, 128)).astype(f32)
+    for j in range(7):
+        acc = xp[:, j:j + T, None] * k[j] + acc
+    acc = acc.reshape(rows, L, 128)
+    if mutant == 'bn_before_relu':
+        q = np.maximum(acc * sc + sh, f32(0))
+    else:
+        q = np.maximum(acc, f32(0)) * sc + sh
+    if mutant == 'pool_pairs_shifted':                             # (q[2u - 1], q[2u])
+        q = np.roll(q, 1, axis=1)
+    f = f32(0.5) * (q[:, 0::2] + q[:, 1::2])                       # [rows, L / 2, 128]
+    if mutant == 'lane_groups_of_4_swapped':
+        f = f.copy()
+        f[..., 0:4], f[..., 4:8] = f[..., 4:8].copy(), f[..., 0:4].copy()
+    if mutant == 'lane_groups_of_8_swapped':
+        f = f.copy()
+        f[..., 0:8], f[..., 8:16] = f[..., 8:16].copy(), f[..., 0:8].copy()
+    if mutant == 'position_dropped_at_tile_end':                   # the last pooled position of the first tile is never written
+        f = f.copy()
+        f[:, CONV_TILE // 2 - 1] = 0
+    if mutant == 'channels_first':
+        f = f.transpose(0, 2, 1)
+    return np.ascontiguousarray(f).reshape(rows, 64 * L)
+
+
+def forward_shared(x, P, w):
+    """fp64 forward of one component model from its layer-0 inputs x [M1, K0] (layer 0 shared across the Nt pairs): [M1 nt, n_out]"""
+    k0 = w['fc_dense0.kernel'].astype(np.float64)
+    K0 = x.shape[1]
+    z = (np.asarray(x, np.float64) @ k0[:K0])[:, None, :] + (P @ k0[K0:] + w['fc_dense0.bias'].astype(np.float64))[None, :, :]
+    h = np.maximum(z, 0.0).reshape(-1, k0.shape[1])
+    i = 0
+    while True:
+        sc, sh = bn_fold(w, i)
+        a = h * sc + sh
+        i += 1
+        name = f'fc_dense{i}' if f'fc_dense{i}.kernel' in w else 'fc_regressor'
+        z = a @ w[name + '.kernel'].astype(np.float64) + w[name + '.bias'].astype(np.float64)
+        if name == 'fc_regressor':
+            return z
+        h = np.maximum(z, 0.0)

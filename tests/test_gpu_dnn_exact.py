@@ -8,8 +8,14 @@ test_gpu_dnn_f32.py, test_gpu_l0_mfma16.py, test_gpu_small_calls.py); a case tha
 predicts twice and the two runs must be equal as well.  The reference is oracle.predict_packets_shared for every shape: the host module
 shows it equal to the literal oracle.predict_packets on these fixtures, and the literal form of the large batches would take minutes.
 
-Routes that are not bit-exact: none.  Left out: the CONV1D front end (its BatchNormalization sits between the convolution and an average
-pooling of 4 taps, and its 64 len_ltf layer-0 inputs need their own builder)."""
+The CONV1D models (conv_frontend_kernel and a layer 0 of K0 = 64 len_ltf) run on the fixtures of lc.conv_lattice_case: integer samples, taps of
++-1, a conv BatchNormalization whose scale is gamma exactly, so every feature is a multiple of 1/2 that bf16 holds.  'zero_rest' (shift folded
+to 0, bias <= 0: features only around the samples, so layer 0's sum stays inside bf16's 8 bits; both context types), 'full' (every feature
+non-zero; fp32 contexts) and 'tie' (features half way between two bf16 numbers, against the bf16 emulation - still equality) cover the
+one-packet gemv, the skinny gemv + range sum, l0_hs_stream, the split-f16 and the fp32 MFMA GEMM, the bf16 GEMM, 256 k ranges, the
+grid-stride loop of the front end, several chunks, the rows form and graph replay.
+
+Routes that are not bit-exact: none."""
 import numpy as np
 import pytest
 
@@ -33,8 +39,9 @@ def _case(case, dense=False, pool=None):
     return c, _REF[key]
 
 
-def _engine(pkg, c, dtype='f32'):
-    e = pkg.CsiEngine(c.nt, c.nr, hidden=c.hidden, n_out=c.n_out, bn_eps=c.bn_eps, dtype=dtype, input_pool=c.pool)
+def _engine(pkg, c, dtype='f32', **kw):
+    e = pkg.CsiEngine(c.nt, c.nr, hidden=c.hidden, n_out=c.n_out, bn_eps=c.bn_eps, dtype=dtype, input_pool=c.pool,
+                      model='CONV1D' if getattr(c, 'conv', None) else 'FC', **kw)
     e.load_weights('real', c.w_re)
     e.load_weights('imag', c.w_im)
     e.set_pilot(c.P)
@@ -388,3 +395,160 @@ def test_pooled_input_models(pkg, oracle, case, mode):
             if engine == 1:
                 _split_engine_served(e, h0, g0, what)
         e.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------- CONV1D models
+def _conv_case(case):
+    """the fixture and its reference: the fp64 oracle on the features layer 0 reads ('tie': the bf16 emulation, which rounds them to nearest even)"""
+    c = lc.conv_lattice_case(*case)
+    key = (case, 'conv')
+    if key not in _REF:
+        if len(_REF) > 3:
+            _REF.clear()
+        from oracle import csi_oracle
+        if c.conv == 'tie':
+            _REF[key] = csi_oracle.predict_packets_bf16(c.ltf_in, c.P, c.w_re, c.w_im)
+            assert _REF[key][0].dtype == np.float32
+        else:
+            r_re, r_im = csi_oracle.predict_packets_shared(c.ltf_in, c.P, c.w_re, c.w_im)
+            _REF[key] = (r_re.astype(np.float32), r_im.astype(np.float32))
+            assert np.array_equal(_REF[key][0], r_re) and np.array_equal(_REF[key][1], r_im)
+    return c, _REF[key]
+
+
+def _conv_engine(pkg, c, dtype='f32', **kw):
+    e = _engine(pkg, c, dtype, **kw)
+    assert e.get_option('model_type') == 1
+    if c.conv == 'full':
+        e.set_option('hs_act_shift', 4)          # |h1 scale + shift| reaches 3200: the automatic scale of a small model (up to 2^7) leaves f16
+    return e
+
+
+@pytest.mark.parametrize('case', lc.CONV_F32_SMALL_CASES, ids=lc.conv_id)
+def test_conv_f32_one_packet_route(pkg, oracle, case):
+    """at most 8 preambles: ONE front-end launch for both planes (each with its own model's constants) + small_l0_gemv_kernel; with
+    "small_fused" = 0 one launch per model + layer0_skinny_kernel + splitk_reduce"""
+    c, ref = _conv_case(case)
+    e = _conv_engine(pkg, c)
+    n0, v0 = _counters(e, 'small_calls', 'conv_launches')
+    _predict_exact(e, c, ref, 'conv one-packet route %s' % c.conv)
+    assert _counters(e, 'small_calls', 'conv_launches') == (n0 + 2, v0 + 2), 'the one-packet path (one two-plane front-end launch per call) did not take the calls'
+    e.set_option('small_fused', 0)
+    _predict_exact(e, c, ref, 'conv small_fused 0 %s' % c.conv)
+    assert _counters(e, 'small_calls', 'conv_launches', 'l0_stream_launches') == (n0 + 2, v0 + 6, 0), 'the general path with the skinny layer 0 was asked for'
+    e.close()
+
+
+@pytest.mark.parametrize('case', lc.CONV_F32_MID_CASES, ids=lc.conv_id)
+def test_conv_f32_layer0_routes(pkg, oracle, case):
+    """74 preambles: l0_hs_stream, the split-f16 GEMM ("l0_stream" 0, "f32_engine" 1) and the fp32 MFMA GEMM ("f32_engine" 0) over the feature slab"""
+    c, ref = _conv_case(case)
+    e = _conv_engine(pkg, c)
+    v0, s0, g0 = e.get_option('conv_launches'), e.get_option('l0_stream_launches'), _counters(e, *HS_GUARDS)
+    _predict_exact(e, c, ref, 'conv l0_hs_stream %s' % c.conv)
+    assert _counters(e, 'conv_launches', 'l0_stream_launches') == (v0 + 4, s0 + 4), 'the streaming kernel did not serve both models of both calls'
+    e.set_option('l0_stream', 0)
+    e.set_option('f32_engine', 1)
+    h0 = e.get_option('hs_launches')
+    _predict_exact(e, c, ref, 'conv split-f16 GEMM %s' % c.conv)
+    _split_engine_served(e, h0, g0, 'conv split-f16 GEMM %s' % c.conv)
+    e.set_option('f32_engine', 0)
+    h0 = e.get_option('hs_launches')
+    _predict_exact(e, c, ref, 'conv fp32 MFMA GEMM %s' % c.conv)
+    assert _counters(e, 'hs_launches', 'l0_stream_launches', 'conv_launches') == (h0, s0 + 4, v0 + 12)
+    assert _counters(e, *HS_GUARDS) == g0
+    e.close()
+
+
+@pytest.mark.parametrize('case', lc.CONV_F32_STRIDE_CASES, ids=lc.conv_id)
+def test_conv_front_end_grid_stride_and_chunks(pkg, oracle, case):
+    """220 preambles x 10 tiles: more tiles than the n_cu x 8 workgroups of a launch, so workgroups loop and their prefetched window crosses
+    rows; a small workspace cuts the same batch into several chunks (feature slab behind each chunk's buffers), which must change nothing"""
+    c, ref = _conv_case(case)
+    assert c.npkt * c.nr * (320 * c.nt // lc.CONV_TILE) > 256 * 8
+    one = _conv_engine(pkg, c)
+    v0 = one.get_option('conv_launches')
+    _predict_exact(one, c, ref, 'conv one chunk %s' % c.conv)
+    assert one.get_option('conv_launches') == v0 + 4, 'one front-end launch per model and call expected'
+    one.close()
+    many = _conv_engine(pkg, c, workspace_bytes=32 << 20)
+    v0 = many.get_option('conv_launches')
+    _predict_exact(many, c, ref, 'conv several chunks %s' % c.conv)
+    assert many.get_option('conv_launches') >= v0 + 2 * 4, 'expected several chunks per call'
+    many.close()
+
+
+@pytest.mark.parametrize('case', lc.CONV_RANGES_CASES, ids=lc.conv_id)
+def test_conv_layer0_many_k_ranges(pkg, oracle, case):
+    """Nt = 16, 9 preambles: K0 = 327680 over one output tile - the fp32 MFMA GEMM and the bf16 GEMM cut it into L0_CONV_MAX_SPLITS = 256
+    ranges (slabs beyond BF16_L0_MAX_SPLITS in the split-K scratch), the split-f16 GEMM into 32"""
+    c, ref = _conv_case(case)
+    assert c.npkt * c.nr > 8 and 64 * 320 * c.nt // 1024 >= 256
+    e = _conv_engine(pkg, c)
+    e.set_option('l0_stream', 0)
+    for engine in (0, 1):
+        e.set_option('f32_engine', engine)
+        h0, g0 = e.get_option('hs_launches'), _counters(e, *HS_GUARDS)
+        _predict_exact(e, c, ref, 'conv k ranges f32_engine %d' % engine)
+        if engine:
+            _split_engine_served(e, h0, g0, 'conv k ranges split f16')
+        else:
+            assert e.get_option('hs_launches') == h0
+        assert e.get_option('l0_stream_launches') == 0
+    e.close()
+    e = _conv_engine(pkg, c, 'bf16')
+    v0 = e.get_option('conv_launches')
+    _predict_exact(e, c, ref, 'conv k ranges bf16')
+    assert e.get_option('conv_launches') == v0 + 4
+    e.close()
+
+
+@pytest.mark.parametrize('case', lc.CONV_BF16_CASES, ids=lc.conv_id)
+def test_conv_bf16_contexts(pkg, oracle, case):
+    """bf16 features (16-byte stores of 8 channels) into xb, then gemm_bf16 over k ranges"""
+    c, ref = _conv_case(case)
+    e = _conv_engine(pkg, c, 'bf16')
+    v0 = e.get_option('conv_launches')
+    _predict_exact(e, c, ref, 'conv bf16')
+    assert e.get_option('conv_launches') == v0 + 4
+    e.close()
+
+
+@pytest.mark.parametrize('case', lc.CONV_TIE_CASES, ids=lc.conv_id)
+def test_conv_bf16_store_rounds_ties_to_even(pkg, oracle, case):
+    """features of 128.5 / 129.5: a truncating or a half-up store gives other outputs (host module); the reference is the bf16 emulation, all of whose sums are exact"""
+    c, ref = _conv_case(case)
+    e = _conv_engine(pkg, c, 'bf16')
+    _predict_exact(e, c, ref, 'conv bf16 tie fixture')
+    e.close()
+
+
+@pytest.mark.parametrize('dtype,case', [('f32', lc.CONV_F32_MID_CASES[0]), ('f32', lc.CONV_F32_MID_CASES[1]), ('bf16', lc.CONV_BF16_CASES[1])],
+                         ids=lambda v: v if isinstance(v, str) else lc.conv_id(v))
+def test_conv_rows_form(pkg, oracle, dtype, case):
+    """csi_predict_samples on raw rows [B, 320 nt + nt]: feature rows of pitch K0 + nt, the pilot columns copied behind the features"""
+    c, ref = _conv_case(case)
+    e = _conv_engine(pkg, c, dtype)
+    v0 = e.get_option('conv_launches')
+    _samples_exact(oracle, e, c, ref, 'conv rows form %s %s' % (dtype, c.conv))
+    assert e.get_option('conv_launches') == v0 + 2
+    e.close()
+
+
+def test_conv_f32_under_graph_replay(pkg, oracle):
+    c, ref = _conv_case(lc.CONV_F32_MID_CASES[0])
+    e = _conv_engine(pkg, c)
+    d_re, d_im = e.to_device(np.ascontiguousarray(c.ltf.real)), e.to_device(np.ascontiguousarray(c.ltf.imag))
+    outs = [e.empty((c.npkt, c.nr, c.nt, c.n_out)) for _ in range(2)]
+    v0, g0 = e.get_option('conv_launches'), _counters(e, *HS_GUARDS)
+    for use_graph, runs in ((0, 1), (1, 4)):
+        e.set_option('use_graph', use_graph)
+        for it in range(runs):
+            e.predict_device(d_re, d_im, c.npkt, *outs)
+            e.synchronize()
+            what = 'conv use_graph %d run %d' % (use_graph, it)
+            assert_exact(outs[0].download(), ref[0], what + ', real model')
+            assert_exact(outs[1].download(), ref[1], what + ', imag model')
+    assert e.get_option('graph_replays') >= 1 and e.get_option('conv_launches') > v0
+    assert _counters(e, *HS_GUARDS) == g0
+    e.close()

@@ -1,7 +1,8 @@
 """Host tests (no GPU) of the integer-lattice fixtures of tests/lattice_cases.py, for every shape tests/test_gpu_dnn_exact.py runs:
 the fixture stays on the lattice (every emulation of a device arithmetic EQUALS the fp64 oracle), it reaches what it claims to reach
 (conditions, not measurements), and it is sensitive: mutants of the emulation - each one an indexing or rounding-mode error of the kind a
-kernel port makes - change the output, while the norm-relative tolerance of the bf16 tests lets some of them through."""
+kernel port makes - change the output, while the norm-relative tolerance of the bf16 tests lets some of them through.  The CONV1D fixtures
+(last section) get the same three proofs for the front end in front of layer 0, and a tie fixture for its bf16 store."""
 import numpy as np
 import pytest
 
@@ -235,3 +236,157 @@ def test_assert_exact_reports_where_the_arrays_differ():
     assert 'row % 128 in [11, 15]' in msg and 'column % 32 in [1, 17]' in msg and 'column % 16 in [1]' in msg
     with pytest.raises(AssertionError):
         assert_exact(ref.astype(np.float64), ref, 'dtype')
+
+
+# ---------------------------------------------------------------------------------------------------------------- CONV1D models
+CONV_FIXTURES = [(c, c in lc.CONV_BF16_CASES or c in lc.CONV_RANGES_CASES) for c in lc.CONV_CASES]        # (case, a bf16 context runs it)
+CONV_IDS = [lc.conv_id(c) for c, _ in CONV_FIXTURES]
+
+
+def _conv_parts(c):
+    """(component, weights, other model's weights, raw rows [M1, L], feature rows [M1, 64 L]) of both models"""
+    m1 = c.npkt * c.nr
+    yield 'real', c.w_re, c.w_im, c.ltf.real.reshape(m1, -1), c.ltf_in.real.reshape(m1, -1)
+    yield 'imag', c.w_im, c.w_re, c.ltf.imag.reshape(m1, -1), c.ltf_in.imag.reshape(m1, -1)
+
+
+def _pin_rows(c, part):
+    """the preambles that hold pinned samples, at most the first 16"""
+    return sorted({m for m, _, _, _ in c.pins[part]})[:16]
+
+
+@pytest.mark.parametrize('case,bf16', CONV_FIXTURES, ids=CONV_IDS, scope='module')      # (module scope: the tests of one fixture run in a row and share its build)
+def test_conv_fixture_is_on_the_lattice(oracle, monkeypatch, case, bf16):
+    """the front end: the builder's fp64 statement is the one tests/test_gpu_conv1d.py states (with the lattice's eps) and the float32
+    restatement in the kernel's operation order; every feature is a multiple of 1/2 that bf16 holds; behind it every forward form is ONE array"""
+    import test_gpu_conv1d as tc
+    monkeypatch.setattr(tc, 'BN_EPS', lc.BN_EPS)
+    c = lc.conv_lattice_case(*case)
+    assert c.ltf.shape == (c.npkt, c.nr, 320 * c.nt) and c.ltf_in.shape == (c.npkt, c.nr, 64 * 320 * c.nt)
+    for d, w, _, x, f in _conv_parts(c):
+        some = sorted(set(_pin_rows(c, d == 'imag')) | set(range(len(x) - 2, len(x))))       # (the dense fp64 statement: the pinned preambles and the last two)
+        assert np.array_equal(tc.features(x[some], w), f[some]), 'the builder\'s front end is not the one the CONV1D tests state'
+        for r0 in range(0, len(x), 32):
+            assert np.array_equal(lc.frontend_f32(x[r0:r0 + 32], w), f[r0:r0 + 32]), 'the float32 front end leaves the lattice'
+        assert np.array_equal(2 * f, np.rint(2 * f))
+        assert np.array_equal(oracle.bf16_round(f), f), 'a feature needs more than 8 significand bits'
+        sc, sh = lc.conv_fold(w)
+        assert np.array_equal(sc, w['conv_bn.gamma']) and np.array_equal(sh, np.rint(sh))
+        if c.conv == 'zero_rest':
+            assert not sh.any() and w['conv_bn.moving_mean'].any() and (w['cnn1d_1.bias'] <= 0).all() and not lc.conv_rest(w).any()
+        else:
+            assert (sh != 0).sum() > 64 and (w['cnn1d_1.bias'] > 0).any() and (w['cnn1d_1.bias'] < 0).any() and (f != 0).mean() > 0.8
+        k = w['cnn1d_1.kernel'].reshape(7, 128)
+        assert set(np.unique(k)) == {-1.0, 0.0, 1.0} and ((k != 0).sum(1) >= 8).all() and ((k != 0).sum(0) >= 1).all()
+    s_re, s_im = oracle.predict_packets_shared(c.ltf_in, c.P, c.w_re, c.w_im)
+    assert np.array_equal(s_re, c.trace('real').out) and np.array_equal(s_im, c.trace('imag').out)
+    sel = _subset(c, 1) if c.nt <= 4 else [0]          # (K0 = 327680 at Nt = 16: the rows of the first packet, first rx antenna)
+    nr = c.nr if c.nt <= 4 else 1
+    l_re, l_im = oracle.predict_packets(c.ltf_in[sel][:, :nr], c.P, c.w_re, c.w_im, np.float64, pkt_batch=len(sel))
+    assert np.array_equal(l_re, s_re[sel][:, :nr]) and np.array_equal(l_im, s_im[sel][:, :nr]), 'shared form != literal form'
+    for d, w, ref in (('real', c.w_re, s_re), ('imag', c.w_im, s_im)):
+        t = c.trace(d)
+        x = oracle.samples_from_packets(c.ltf_in[sel][:, :nr], c.P.astype(np.float32), d)
+        want = ref[sel][:, :nr].reshape(x.shape[0], -1)
+        assert np.array_equal(lc.forward_shared(x[::c.nt, :-c.nt], c.P, w), want)
+        assert np.array_equal(oracle.fc_forward(x, w, np.float32), want), 'fp32 arithmetic leaves the lattice'
+        step = 1 if c.nt <= 4 else 2                                   # the two ends and the middle of the accepted range (Nt = 16: the ends)
+        for s_in in _shifts(t.max_in, False)[::step]:
+            assert np.array_equal(oracle.fc_forward_split_f16(x, w, in_shift=s_in, act_shift=0), want), ('hs_in_shift', s_in)
+        for s_act in _shifts(t.max_act, False)[::step]:
+            assert np.array_equal(oracle.fc_forward_split_f16(x, w, in_shift=4, act_shift=s_act), want), ('hs_act_shift', s_act)
+        if bf16:
+            assert np.array_equal(oracle.fc_forward_bf16(x, w), want), 'bf16 operands leave the lattice'
+            assert np.array_equal(lc.forward_bf16_hooked(x, w), want)
+
+
+@pytest.mark.parametrize('case,bf16', CONV_FIXTURES, ids=CONV_IDS, scope='module')      # (module scope: the tests of one fixture run in a row and share its build)
+def test_conv_fixture_reaches_what_it_claims(case, bf16):
+    c = lc.conv_lattice_case(*case)
+    k_cover, nonzero = c.cover()
+    assert k_cover == 1.0, 'a k index behind layer 0 never meets a non-zero activation and a non-zero weight'
+    assert nonzero >= 0.90
+    L, m1 = 320 * c.nt, c.npkt * c.nr
+    for part, (d, w, _, x, f) in enumerate(_conv_parts(c)):
+        t = c.trace(d)
+        assert 2 * t.max_abs_sum < lc.SUM_LIMIT                       # (the features are multiples of 1/2)
+        if bf16:
+            assert c.conv == 'zero_rest' and t.act_bf16_exact, 'a hidden activation needs more than 8 significand bits'
+        # the cover is what the sample list reaches, derived without the dense forward
+        cover = lc.conv_feat_cover(c, d)
+        assert cover == lc.conv_feat_want(c, d)
+        if m1 >= 64:
+            assert cover >= 0.5
+        # the pinned samples are where the builder says, and each one moves a feature that layer 0 weighs: the row-end pins the first /
+        # last pooled position, an edge pin a position of the NEIGHBOURING tile (reached through that tile's halo only)
+        pins = c.pins[part]
+        assert {(m, tt) for m, _, tt, e in pins if e is None} == {(m, tt) for m in (0, 1) for tt in (0, 1, 2, L - 3, L - 2, L - 1)}
+        assert {(tt - e, e) for _, _, tt, e in pins if e is not None} == {(off, e) for off in range(-3, 3) for e in lc.conv_edges(c.nt)}
+        assert len(lc.conv_edges(c.nt)) >= 2 and all(e % lc.CONV_TILE == 0 and 0 < e < L for e in lc.conv_edges(c.nt))
+        rest = lc.conv_rest(w)
+        used = (np.abs(w['fc_dense0.kernel'][:64 * L]).sum(1) > 0).reshape(L // 2, 128)
+        k = w['cnn1d_1.kernel'].reshape(7, 128)
+        b = w['cnn1d_1.bias']
+        for m, _, tt, e in pins:
+            v = x[m, tt]
+            assert v != 0 and (e is None or abs(v) == 2)
+            if e is None:
+                us = [0] if tt < 3 else [L // 2 - 1]
+            else:
+                us = [e // 2 - 1] if tt >= e else [e // 2]
+            # derived for the sample alone: tap j of channel ch carries it to output sample tt + 3 - j
+            alone = [(u, ch) for u in us for j in range(7) for ch in np.flatnonzero(k[j]) if (tt + 3 - j) // 2 == u
+                     and max(b[ch] + k[j, ch] * v, 0) != max(b[ch], 0)]
+            assert alone, ('no channel answers the pinned sample', m, tt)
+            moved = (f[m].reshape(L // 2, 128)[us] != rest) & used[us]
+            assert moved.any(), ('the pinned sample moves no weighed feature', m, tt)
+        # both parities of the output sample for every tap: both members of a pooled pair see every tap
+        mm, ts = np.nonzero(x)
+        for j in range(7):
+            to = ts + 3 - j
+            to = to[(to >= 0) & (to < L)]
+            assert (to % 2 == 0).any() and (to % 2 == 1).any(), j
+
+
+@pytest.mark.parametrize('case,bf16', CONV_FIXTURES, ids=CONV_IDS, scope='module')      # (module scope: the tests of one fixture run in a row and share its build)
+def test_mutants_of_the_front_end_change_the_output(oracle, case, bf16):
+    """every mutant of the front-end emulation moves at least one OUTPUT element of the preambles that hold the pinned samples"""
+    c = lc.conv_lattice_case(*case)
+    for part, (d, w, other, x, f) in enumerate(_conv_parts(c)):
+        rows = _pin_rows(c, part)
+        rows = list(range(min(rows), max(rows) + 1))                  # consecutive: the neighbouring-row mutant needs the neighbours
+        ref = lc.forward_shared(lc.frontend_f32(x[rows], w), c.P, w)
+        assert np.array_equal(ref, c.trace(d).out.reshape(c.npkt * c.nr, c.nt, -1)[rows].reshape(ref.shape))
+        for mutant in lc.CONV_MUTANTS:
+            got = lc.forward_shared(lc.frontend_f32(x[rows], w, mutant, other), c.P, w)
+            assert not np.array_equal(got, ref), (d, mutant)
+        if part == 0 and bf16:
+            break                                                     # (the imag model of the bf16 shapes: nothing the real one does not show)
+
+
+@pytest.mark.parametrize('case', lc.CONV_TIE_CASES, ids=lc.conv_id)
+def test_conv_tie_fixture_tells_the_rounding_modes_apart(oracle, case):
+    """the bf16 store of the front end: pooled features of 128.5 / 129.5 (and 257 / 259 behind gamma = +-2) lie half way between two bf16
+    numbers.  Nearest-even, truncation and half-up give three feature arrays and three outputs; the emulation's sums are exact, so the
+    device must EQUAL oracle.predict_packets_bf16 on the unrounded features (it rounds them to nearest even itself)."""
+    c = lc.conv_lattice_case(*case)
+    assert len(c.hidden) == 1
+    for d, w, _, x, f in _conv_parts(c):
+        assert np.array_equal(lc.frontend_f32(x, w), f)
+        stores = [oracle.bf16_round(f), lc.bf16_truncate(f), lc.bf16_half_up(f)]
+        ties = stores[1] != stores[2]
+        assert ties.sum() >= 64 and {128.5, 129.5} <= set(np.abs(f[ties]).tolist())
+        assert (stores[0] != stores[1]).any() and (stores[0] != stores[2]).any()
+        P32 = c.P.astype(np.float32)
+        rows = lambda feat: np.concatenate([np.repeat(feat, c.nt, 0), np.tile(P32, (len(feat), 1))], axis=1)
+        outs = [oracle.fc_forward_bf16(rows(s), w) for s in stores]
+        assert np.array_equal(outs[0], oracle.fc_forward_bf16(rows(f), w)), 'the emulation rounds the features to nearest even itself'
+        assert not np.array_equal(outs[1], outs[0]), 'truncating store'
+        assert not np.array_equal(outs[2], outs[0]), 'half-up store'
+        assert not np.array_equal(outs[1], outs[2])
+        # every fp32 sum of the emulation is exact whatever its order: operands are multiples of 1/2 (features, h1 after rounding ...)
+        k0 = np.abs(w['fc_dense0.kernel'].astype(np.float64))
+        h_max = (np.abs(stores[0].astype(np.float64)) @ k0[:f.shape[1]]).max() + np.abs(c.P).sum(1).max() + 3
+        assert 2 * h_max < lc.SUM_LIMIT
+        sc, sh = lc.bn_fold(w, 0)
+        assert 2 * (h_max * np.abs(sc).max() + np.abs(sh).max()) * np.abs(w['fc_regressor.kernel']).sum(0).max() < lc.SUM_LIMIT
