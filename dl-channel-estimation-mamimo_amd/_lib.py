@@ -161,6 +161,11 @@ SYMBOLS = {
     'csi_cfo_rotate_device': (ctypes.c_int, [_ctx, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_double, _vp, _vp]),
     'csi_cfo_correct_device': (ctypes.c_int, [_ctx, _vp, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, _vp, _vp]),
     'csi_cfo_correct': (ctypes.c_int, [_ctx, _fp, _fp, ctypes.c_int64, ctypes.c_int, _fp, _fp, _vp, _fp]),
+    'csi_sync_embed_device': (ctypes.c_int, [_ctx, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'csi_sync_estimate_device': (ctypes.c_int, [_ctx, _vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_double, _vp, _vp, _vp, _vp]),
+    'csi_sync_extract_device': (ctypes.c_int, [_ctx, _vp, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, _vp, _vp]),
+    'csi_sync_correct_device': (ctypes.c_int, [_ctx, _vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp]),
+    'csi_sync_correct': (ctypes.c_int, [_ctx, _fp, _fp, ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_uint32, _fp, _fp, _vp, _vp, _fp]),
     'csi_profile_enable': (ctypes.c_int, [_ctx, ctypes.c_int]),
     'csi_profile_reset': (ctypes.c_int, [_ctx]),
     'csi_profile_num_kernels': (ctypes.c_int, []),

@@ -85,6 +85,9 @@ enum KernelId {
     K_FORECAST_GRAM,     // channel forecast (csi_forecast_*, forecast.hip.h): Gram matrix of the soundings per (packet, rx) (fp32 MFMA); placed like K_SUBSPACE_SMOOTH
     K_FORECAST_FIT,      // channel forecast: normal equations, ridge and fp64 Cholesky per (packet, rx) or per packet
     K_FORECAST_APPLY,    // channel forecast: y = sum_m c_m x_{P-1-m}, streaming
+    K_SYNC_METRIC,       // symbol timing (csi_sync_*, sync.hip.h): cyclic-prefix timing metric, theta_hat / eps_hat / quality per packet; placed like K_SUBSPACE_SMOOTH
+    K_SYNC_EXTRACT,      // symbol timing: y[n] = c[theta + n] exp(-2 pi i eps n / 256), streaming
+    K_SYNC_EMBED,        // symbol timing: the packet at theta inside a capture with noise margins, streaming
     K_SOUNDING_NOISE,    // white estimation error on a CSI plane pair (csi_sounding_noise_device)
     K_CFO_CORR,          // carrier frequency offset (csi_cfo_*, cfo.hip.h): cyclic-prefix correlation, eps_hat and quality per packet; placed like K_SUBSPACE_SMOOTH
     K_CFO_ROTATE,        // carrier frequency offset: y = x exp(2 pi i scale eps n / 256), streaming
@@ -99,7 +102,7 @@ const char* const kKernelNames[K_COUNT] = {
     "ls_estimate", "naive_dense0_gemm", "synth_white", "pilot_table", "cast_bf16", "pair_h1_bf16", "lmmse_levinson",
     "train_gemm", "train_elementwise", "nmse_links", "pair_dense_tail", "input_pool", "conv_frontend",
     "hybrid_svd", "hybrid_corr_argmax", "hybrid_solve", "hybrid_finish", "synth_structured", "link_txrx", "link_viterbi",
-    "subspace_smooth", "mu_precoder", "mu_txrx", "mu_beam_score", "mu_beam_select", "mu_hybrid_precoder", "mu_cov", "mu_jsdm_eig", "mu_jsdm_baseband", "fb_compress", "fb_expand", "rx_combiner", "rx_combine", "beam_power", "beam_smooth", "scatter_aged", "forecast_gram", "forecast_fit", "forecast_apply", "sounding_noise", "cfo_corr", "cfo_rotate", "synth_scattering", "lmmse_null_noise", "lmmse_freq_corr", "lmmse_blind"};
+    "subspace_smooth", "mu_precoder", "mu_txrx", "mu_beam_score", "mu_beam_select", "mu_hybrid_precoder", "mu_cov", "mu_jsdm_eig", "mu_jsdm_baseband", "fb_compress", "fb_expand", "rx_combiner", "rx_combine", "beam_power", "beam_smooth", "scatter_aged", "forecast_gram", "forecast_fit", "forecast_apply", "sync_metric", "sync_extract", "sync_embed", "sounding_noise", "cfo_corr", "cfo_rotate", "synth_scattering", "lmmse_null_noise", "lmmse_freq_corr", "lmmse_blind"};
 
 thread_local std::string g_create_error;
 
@@ -245,6 +248,9 @@ struct csi_ctx {
     char* cfo_ws = nullptr;                // carrier frequency offset (csi_cfo.hpp): eps of a csi_cfo_correct_device call whose caller keeps none (sized by eager calls)
     size_t cfo_ws_bytes = 0;
     int64_t cfo_launches = 0;              // "cfo_launches": kernels launched by the csi_cfo_* entry points
+    char* sync_ws = nullptr;               // symbol timing (csi_sync.hpp): eps and theta of a csi_sync_correct_device call whose caller keeps none (sized by eager calls)
+    size_t sync_ws_bytes = 0;
+    int64_t sync_launches = 0;             // "sync_launches": kernels launched by the csi_sync_* entry points
     int64_t forecast_launches = 0;         // "forecast_launches": kernels launched by the csi_forecast_* entry points and csi_sounding_noise_device
     // activation workspace
     char* ws = nullptr;

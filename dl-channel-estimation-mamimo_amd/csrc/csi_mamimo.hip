@@ -34,6 +34,7 @@
 #include "csi_scatter_aged.hpp"      // last: its kernels are emitted behind every other kernel, whose pc-relative addresses stay what they were
 #include "csi_forecast.hpp"          // ... and these behind them, for the same reason
 #include "csi_cfo.hpp"               // ... and these
+#include "csi_sync.hpp"              // ... and these
 #include <initializer_list>
 
 namespace {
@@ -343,6 +344,7 @@ void csi_destroy(csi_ctx* c) {
     if (c->beam_ws) hipFree(c->beam_ws);
     if (c->forecast_ws) hipFree(c->forecast_ws);
     if (c->cfo_ws) hipFree(c->cfo_ws);
+    if (c->sync_ws) hipFree(c->sync_ws);
     if (c->hs_peak) hipFree(c->hs_peak);
     if (c->hs_zero) hipFree(c->hs_zero);
     if (c->fuse_ws) hipFree(c->fuse_ws);
@@ -958,6 +960,7 @@ int csi_get_option(csi_ctx* c, const char* name, int64_t* value) {
     else if (n == "scatter_aged_launches") *value = c->scatter_aged_launches;
     else if (n == "forecast_launches") *value = c->forecast_launches;
     else if (n == "cfo_launches") *value = c->cfo_launches;
+    else if (n == "sync_launches") *value = c->sync_launches;
     else if (n == "small_rows") *value = c->small_rows;
     else if (n == "small_rows_band") *value = c->small_rows_band;
     else if (n == "f32_engine") *value = c->f32_engine;
@@ -1890,6 +1893,37 @@ int csi_cfo_correct(csi_ctx* c, const float* ltf_re, const float* ltf_im, int64_
                     float* quality) {
     if (!c) return CSI_ERR_INVALID_ARG;
     return cfo_correct_host(c, ltf_re, ltf_im, npkt, cp_skip, out_re, out_im, eps, quality);
+}
+
+// ---- symbol timing (csi_sync.hpp, sync.hip.h)
+int csi_sync_embed_device(csi_ctx* c, uint64_t seed, int64_t first_pkt, int64_t npkt, int span, const int32_t* d_theta, const float* d_margin_std,
+                          const float* d_x_re, const float* d_x_im, float* d_cap_re, float* d_cap_im) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return sync_embed_device(c, seed, first_pkt, npkt, span, d_theta, d_margin_std, d_x_re, d_x_im, d_cap_re, d_cap_im);
+}
+
+int csi_sync_estimate_device(csi_ctx* c, const float* d_cap_re, const float* d_cap_im, int64_t npkt, int span, double rho, int32_t* d_theta, double* d_eps,
+                             float* d_quality, double* d_metric) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return sync_estimate_device(c, d_cap_re, d_cap_im, npkt, span, rho, d_theta, d_eps, d_quality, d_metric);
+}
+
+int csi_sync_extract_device(csi_ctx* c, const float* d_cap_re, const float* d_cap_im, int64_t npkt, int span, const int32_t* d_theta, const double* d_eps,
+                            float* d_out_re, float* d_out_im) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return sync_extract_device(c, d_cap_re, d_cap_im, npkt, span, d_theta, d_eps, d_out_re, d_out_im);
+}
+
+int csi_sync_correct_device(csi_ctx* c, const float* d_cap_re, const float* d_cap_im, int64_t npkt, int span, double rho, uint32_t flags, float* d_out_re,
+                            float* d_out_im, int32_t* d_theta, double* d_eps, float* d_quality) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return sync_correct_device(c, "csi_sync_correct_device", d_cap_re, d_cap_im, npkt, span, rho, flags, d_out_re, d_out_im, d_theta, d_eps, d_quality);
+}
+
+int csi_sync_correct(csi_ctx* c, const float* cap_re, const float* cap_im, int64_t npkt, int span, double rho, uint32_t flags, float* out_re, float* out_im,
+                     int32_t* theta, double* eps, float* quality) {
+    if (!c) return CSI_ERR_INVALID_ARG;
+    return sync_correct_host(c, cap_re, cap_im, npkt, span, rho, flags, out_re, out_im, theta, eps, quality);
 }
 
 // ---- profiling

@@ -1567,6 +1567,53 @@ class CsiEngine:
         out = self._c64(o_re, o_im)
         return (out, eps, quality) if details else out
 
+    # ------------------------------------------------------------------ symbol timing (csrc/sync.hip.h)
+    def sync_embed_device(self, seed, first_pkt, npkt, span, d_theta, d_x_re, d_x_im, d_cap_re, d_cap_im, d_margin_std=None):
+        """Packets [npkt][nr][len_ltf] placed at d_theta [npkt] (int32 words in a float32 DeviceArray; 0 .. span, clamped) inside capture
+        planes [npkt][nr][len_ltf + span] (csi_sync_embed_device); the margins are noise of deviation d_margin_std [npkt] per real
+        component from the stream (seed, first_pkt + p), zero without it.  Asynchronous."""
+        self._check(self._lib.csi_sync_embed_device(self._ctx, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_pkt), int(npkt), int(span), d_theta.ptr or None,
+                                                    d_margin_std.ptr if d_margin_std is not None else None, d_x_re.ptr or None, d_x_im.ptr or None,
+                                                    d_cap_re.ptr or None, d_cap_im.ptr or None))
+
+    def sync_estimate_device(self, d_cap_re, d_cap_im, npkt, span, d_theta, rho=1.0, d_eps=None, d_quality=None, d_metric=None):
+        """Where every packet starts inside its capture, and its carrier frequency offset, from the cyclic prefixes
+        (csi_sync_estimate_device): d_theta [npkt] int32 words = the lowest argmax of |gamma| - rho Phi over 0 .. span; optional d_eps
+        [npkt] as float64 (2 float32 words per packet), d_quality [npkt], d_metric [npkt][span + 1] as float64.  Asynchronous."""
+        opt = lambda d: d.ptr if d is not None else None      # noqa: E731
+        self._check(self._lib.csi_sync_estimate_device(self._ctx, d_cap_re.ptr or None, d_cap_im.ptr or None, int(npkt), int(span), float(rho),
+                                                       d_theta.ptr or None, opt(d_eps), opt(d_quality), opt(d_metric)))
+
+    def sync_extract_device(self, d_cap_re, d_cap_im, npkt, span, d_theta, d_out_re, d_out_im, d_eps=None):
+        """y[p,r,n] = c[p,r,theta[p] + n] exp(-2 pi i eps[p] n / 256) (csi_sync_extract_device): the packet cut out of its capture at
+        d_theta (clamped into 0 .. span), a copy of the bits without d_eps.  Asynchronous."""
+        self._check(self._lib.csi_sync_extract_device(self._ctx, d_cap_re.ptr or None, d_cap_im.ptr or None, int(npkt), int(span), d_theta.ptr or None,
+                                                      d_eps.ptr if d_eps is not None else None, d_out_re.ptr or None, d_out_im.ptr or None))
+
+    def sync_correct_device(self, d_cap_re, d_cap_im, npkt, span, d_out_re, d_out_im, rho=1.0, remove_cfo=True, d_theta=None, d_eps=None, d_quality=None):
+        """Estimate, then cut out at theta_hat, with ``remove_cfo`` also removing eps_hat (csi_sync_correct_device): two launches, the
+        bits of the two calls; optional d_theta / d_eps / d_quality receive the estimate.  Asynchronous."""
+        opt = lambda d: d.ptr if d is not None else None      # noqa: E731
+        self._check(self._lib.csi_sync_correct_device(self._ctx, d_cap_re.ptr or None, d_cap_im.ptr or None, int(npkt), int(span), float(rho),
+                                                      1 if remove_cfo else 0, d_out_re.ptr or None, d_out_im.ptr or None, opt(d_theta), opt(d_eps),
+                                                      opt(d_quality)))
+
+    def sync_correct(self, capture, span, rho=1.0, remove_cfo=True, details=False):
+        """Timing (and carrier-frequency-offset) correction from host arrays (csi_sync_correct): capture complex
+        [npkt,nr,len_ltf + span]; returns the packets cut out at theta_hat, complex64 [npkt,nr,len_ltf].  With ``details`` also
+        (theta_hat int32 [npkt], eps_hat float64 [npkt], quality float32 [npkt])."""
+        capture = np.asarray(capture)
+        re, im = _f32c(capture.real), _f32c(capture.imag)
+        if re.ndim != 3 or re.shape[1:] != (self.nr, self.len_ltf + int(span)):
+            raise CsiError(-1, f'captures must be [npkt,{self.nr},{self.len_ltf + int(span)}], got {re.shape}')
+        npkt = re.shape[0]
+        o_re, o_im = (np.empty((npkt, self.nr, self.len_ltf), np.float32) for _ in range(2))
+        theta, eps, quality = np.empty(npkt, np.int32), np.empty(npkt, np.float64), np.empty(npkt, np.float32)
+        self._check(self._lib.csi_sync_correct(self._ctx, _fp(re), _fp(im), npkt, int(span), float(rho), 1 if remove_cfo else 0, _fp(o_re), _fp(o_im),
+                                               theta.ctypes.data, eps.ctypes.data, _fp(quality)))
+        out = self._c64(o_re, o_im)
+        return (out, theta, eps, quality) if details else out
+
     def lmmse_estimate_device(self, d_h_re, d_h_im, npkt, d_hvec, L, d_snr_db, d_out_re, d_out_im):
         """LMMSE smoothing of device-resident LS planes (csi_lmmse_estimate_device): d_hvec [npkt][L], d_snr_db [npkt][nr]; asynchronous."""
         self._check(self._lib.csi_lmmse_estimate_device(self._ctx, d_h_re.ptr, d_h_im.ptr, int(npkt), d_hvec.ptr, int(L), d_snr_db.ptr,

@@ -42,6 +42,10 @@ data phases to a level and nothing else: without an option every output is what 
     --cfo EPS --cfoSkip M (cfo)           -         MSEO_X and MSEOC_X for X = LS, MMSE, DNN, cfo_rmse, cfo_quality: the level's packets      4.28
                                                     under a carrier frequency offset uniform in +-EPS subcarrier spacings per packet,
                                                     estimated as they are and after the cyclic-prefix correction (cp_skip = M)
+    --timing SPAN --timingRho RHO         -         MSET_X and MSETC_X for X = LS, MMSE, DNN, timing_exact, timing_rmse,                      4.29
+      (timing)                                      timing_quality: the level's packets (with --cfo the offset ones) at a start uniform
+                                                    in 0 .. SPAN inside captures with noise margins, cut out at the fixed start SPAN / 2
+                                                    and at the cyclic-prefix estimate of the start (with --cfo also removing eps_hat)
 
 FAMILIES below states this as data - fields, sources, switches, the per-user record - and MAT_ORDER / JSON_ORDER the two orders
 the rows are written in; metric_fields, format_table and the per-level summary of run_sweep are read off them.
@@ -55,12 +59,13 @@ the rows are written in; metric_fields, format_table and the per-level summary o
                                                             [--feedback BPHI BPSI [--feedbackNg G]] [--rxCombine]
                                                             [--channel scattering --aging MS [--speed MPS] [--heading DEG] [--randomHeading] [--carrier HZ]
                                                              [--forecast P M [--forecastSteps D]]]
-                                                            [--cfo EPS [--cfoSkip M]]
+                                                            [--cfo EPS [--cfoSkip M]] [--timing SPAN [--timingRho RHO]]
 
 The module holds no arithmetic of its own: packets come from csi_synth_structured / csi_synth_scattering, the aged channel from
 csi_scatter_channel_at_device, its forecast from csi_forecast_device on soundings made of that call and
 csi_sounding_noise_device, the offset packets from csi_cfo_rotate_device (offsets: synth.cfo_offsets) and their correction from
-csi_cfo_correct_device, labels from
+csi_cfo_correct_device, the captures from csi_sync_embed_device (starts: synth.timing_offsets), their cut-outs from
+csi_sync_extract_device and csi_sync_correct_device, labels from
 csi_ls_estimate_device, the fit from trainer.fit, the estimates from csi_estimate_device, csi_lmmse_estimate_device,
 csi_lmmse_blind_device, csi_subspace_smooth_device (basis: subspace.delay_basis) and csi_beam_wiener_device (beams:
 beamspace.dft_basis, error level: csi_null_noise_device), every NMSE from csi_nmse_device, the precoders from
@@ -106,6 +111,9 @@ MUF_FIELDS = ('bersMUF_', 'EVM_rmsMUF_', 'sinrMUF_')
 # --cfo: the NMSE of the estimators on the level's packets under a carrier frequency offset, as they are and after the correction
 MSEO_FIELDS = ('MSEO_',)
 MSEOC_FIELDS = ('MSEOC_',)
+# --timing: the NMSE of the estimators on the level's packets cut out of a capture at a fixed start, and at the estimated start
+MSET_FIELDS = ('MSET_',)
+MSETC_FIELDS = ('MSETC_',)
 FORECAST_SOURCES = ('LS', 'perfect')      # the sources whose history can be simulated: the truth, and LS, whose error is white
 DELAY = 'DLY'                            # --delayTaps: the LS rows projected onto a window of delay taps (csi_subspace_smooth_device, w = 1)
 BEAMS = 'ANG'                            # --beams: the beam-space Wiener smoother across the Tx antennas on the LS planes (csi_beam_wiener_device)
@@ -136,6 +144,9 @@ FAMILIES = dict(
     MUJ=Family(MUJ_FIELDS, MUJ_FIELDS, EVERY, ('mu_jsdm',), 'muj_users'),
     FB=Family(FB_FIELDS, FB_FIELDS, SINGLE, ('feedback',), None),
     MUFB=Family(MUFB_FIELDS, MUFB_FIELDS, EVERY, ('feedback', 'mu'), 'mufb_users'),
+    # the timing twins of MSE (--timing): written in front of the receive-combining families (TIMING below)
+    MSET=Family(MSET_FIELDS, MSET_FIELDS, ESTIMATORS, ('timing',), None),
+    MSETC=Family(MSETC_FIELDS, MSETC_FIELDS, ESTIMATORS, ('timing',), None),
     # the offset twins of MSE (--cfo): written behind every other whole family, in front of the aged ones (CFO below)
     MSEO=Family(MSEO_FIELDS, MSEO_FIELDS, ESTIMATORS, ('cfo',), None),
     MSEOC=Family(MSEOC_FIELDS, MSEOC_FIELDS, ESTIMATORS, ('cfo',), None),
@@ -145,12 +156,16 @@ FAMILIES = dict(
 # The two orders the rows (family, source) are written in, as blocks (family, sources) - source-major within a block - and
 # (family, USERS) for the per-user record.  Both are contracts with whoever reads the files.  They differ in their heads, which grew
 # option by option; every family behind MU stands whole, in the order of the table, at the end of both - the offset families behind the
-# others, the aged families behind them, the forecast families last.
+# others, the aged families behind them, the forecast families last.  The offset families keep the receive-combining families
+# directly in front of them and the aged ones directly behind, so the timing families, whose calls run behind the offset block, stand in
+# front of the receive-combining families.
 USERS = ()
 AGED = ('MSEA', 'LINKA', 'MUA')
 FORECAST = ('MSEF', 'MUF')
 CFO = ('MSEO', 'MSEOC')
-_WHOLE = tuple(b for k in [k for k in FAMILIES if k not in ('MSE', 'LINK', 'RX', 'MU') + CFO + AGED + FORECAST] + list(CFO + AGED + FORECAST)
+TIMING = ('MSET', 'MSETC')
+_OTHERS = [k for k in FAMILIES if k not in ('MSE', 'LINK', 'RX', 'MU') + TIMING + CFO + AGED + FORECAST]
+_WHOLE = tuple(b for k in _OTHERS[:_OTHERS.index('FBC')] + list(TIMING) + _OTHERS[_OTHERS.index('FBC'):] + list(CFO + AGED + FORECAST)
                for b in ((k, FAMILIES[k].sources), (k, USERS)))
 MAT_ORDER = (('MSE', ESTIMATORS), ('LINK', SOURCES), ('MSE', ('perfect',)), ('MSE', (BLIND,)), ('LINK', (BLIND,)), ('RX', SINGLE),
              ('MSE', (DELAY,)), ('MU', SINGLE + (DELAY,)), ('MSE', (BEAMS, DELAY_BEAMS)), ('MU', (BEAMS,))) + _WHOLE      # metrics.mat
@@ -340,6 +355,71 @@ def cfo_level(engine, user, npkt, seed, first_pkt, cfo):
     return out
 
 
+def timing_args(timing):
+    """`timing` as evaluate_level / run_sweep take it: None = off; a dict with span (required: the starts are uniform in 0 .. span
+    samples, span a multiple of 4 in 4 .. 256, what csi_sync_* serve) and rho (1.0: the weight of the energy term of the metric, in
+    [0, 1]).  Returns the dict with every default filled in, or None."""
+    if timing is None:
+        return None
+    out = dict(span=None, rho=1.0)
+    unknown = set(timing) - set(out)
+    if unknown:
+        raise ValueError('unknown timing parameters: %s' % sorted(unknown))
+    out.update(timing)
+    if out['span'] is None or int(out['span']) != out['span'] or not 4 <= int(out['span']) <= 256 or int(out['span']) % 4:
+        raise ValueError('timing: span %r is no multiple of 4 in 4 .. 256' % (out['span'],))
+    if not 0.0 <= float(out['rho']) <= 1.0:
+        raise ValueError('timing: rho %r outside [0, 1]' % (out['rho'],))
+    return dict(span=int(out['span']), rho=float(out['rho']))
+
+
+def timing_level(engine, user, npkt, seed, first_pkt, timing, cfo=None, amp_scale=True):
+    """The level's packets at an unknown start inside a capture.  `user`: user_estimates of the level (same seed and
+    first_pkt, with its noise_std).  The preambles - with cfo (cfo_args) rotated by synth.cfo_offsets as in cfo_level - embedded at
+    synth.timing_offsets(seed, first_pkt, npkt, span) (sync_embed_device) with margins at the level's own noise deviation as applied
+    (noise_std times the amplitude scale), cut out at the fixed start span / 2 (sync_extract_device) and the estimators of ESTIMATORS on
+    that (plane_estimates with the level's own LMMSE inputs) -> 'MSET_X', cut out at the estimated start (sync_correct_device, with cfo
+    also removing eps_hat) and the estimators again -> 'MSETC_X', both against the unchanged true planes.  Also 'timing_err' int64
+    [npkt] = theta_hat - theta and 'timing_quality' float32 [npkt]."""
+    timing, cfo = timing_args(timing), cfo_args(cfo)
+    nr, nt, span = engine.nr, engine.nt, timing['span']
+    h_re, h_im = user['planes']['perfect']
+    theta = synth.timing_offsets(seed, first_pkt, npkt, span)
+    d_theta = engine.to_device(theta.view(np.float32))                       # int32 words
+    d_half = engine.to_device(np.full(npkt, span // 2, np.int32).view(np.float32))
+    amp = float(np.float32(synth.AMP_SCALE)) if amp_scale else 1.0
+    d_margin = engine.to_device((user['noise_std'].download() * np.float32(amp)).astype(np.float32))
+    shape = user['ltf'][0].shape
+    source, scratch = user['ltf'], [d_theta, d_half, d_margin]
+    if cfo:
+        d_eps = engine.to_device(synth.cfo_offsets(seed, first_pkt, npkt, cfo['max_eps']).view(np.float32).reshape(npkt, 2))
+        source = (engine.empty(shape), engine.empty(shape))
+        engine.cfo_rotate_device(user['ltf'][0], user['ltf'][1], npkt, d_eps, 1.0, source[0], source[1])
+        scratch += [d_eps] + list(source)
+    cap = (engine.empty(shape[:2] + (shape[2] + span,)), engine.empty(shape[:2] + (shape[2] + span,)))
+    cut, fixed = (engine.empty(shape), engine.empty(shape)), (engine.empty(shape), engine.empty(shape))
+    d_hat, d_q, d_link = engine.empty((npkt,)), engine.empty((npkt,)), engine.empty((npkt * nr * nt,))
+    out = {}
+    engine.sync_embed_device(seed, first_pkt, npkt, span, d_theta, source[0], source[1], cap[0], cap[1], d_margin_std=d_margin)
+    for field, ltf in ((MSET_FIELDS[0], cut), (MSETC_FIELDS[0], fixed)):
+        if ltf is cut:
+            engine.sync_extract_device(cap[0], cap[1], npkt, span, d_half, cut[0], cut[1])
+        else:
+            engine.sync_correct_device(cap[0], cap[1], npkt, span, fixed[0], fixed[1], rho=timing['rho'], remove_cfo=bool(cfo), d_theta=d_hat,
+                                       d_quality=d_q)
+        est = plane_estimates(engine, ltf[0], ltf[1], npkt, user['lmmse'])
+        for name in ESTIMATORS:
+            engine.nmse_device(h_re, h_im, est[name][0], est[name][1], npkt * nr * nt, N_DATA, d_per_link=d_link)
+            out[field + name] = d_link.download().astype(np.float64).reshape(npkt, nr * nt).mean(axis=1)
+        for a in (a for p in est.values() for a in p):
+            a.free()
+    out['timing_err'] = d_hat.download().view(np.int32).astype(np.int64) - theta
+    out['timing_quality'] = d_q.download()
+    for a in tuple(scratch) + (d_hat, d_q, d_link) + cap + cut + fixed:
+        a.free()
+    return out
+
+
 def make_dataset(engine, n_train, seed, n_taps=8, amp_scale=True, channel=None):
     """Noise-free training packets generated on the device (the pipeline trains on "SNR 120 ... NOISELESS" packets,
     full_pipeline_maMIMO_DNNEst.sh:21,33) with the LS estimate of the same signal as labels, as the dataset's y is
@@ -425,7 +505,7 @@ def user_estimates(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=Tr
 
 def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=True, keep=False, ber=None, channel=None, blind=False,
                    rx_estimate=False, delay=None, mu=None, beams=False, mu_hybrid=None, mu_jsdm=None, feedback=None, rx_combine=False,
-                   aging=None, forecast=None, cfo=None):
+                   aging=None, forecast=None, cfo=None, timing=None):
     """One level: the estimates of npkt test packets at `snr_db` (user_estimates: packets first_pkt ... of stream `seed`, keep them
     disjoint from the training packets) and NMSE_subk of each against the true channel, then the data phases the options ask for (the
     table of the module).  Returns {'MSE_X': float64 [npkt], the per-link ratios averaged per packet} for X = LS, MMSE, DNN and every
@@ -444,10 +524,12 @@ def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=Tr
     'EVM_rmsMUF_X', 'sinrMUF_X', 'muf_users').
     cfo (cfo_args) adds, behind the calls of every option above and in front of the aged block, the families of cfo_level ('MSEO_X',
     'MSEOC_X', 'cfo_err', 'cfo_quality').
+    timing (timing_args) adds, behind the offset block and in front of the aged block, the families of timing_level ('MSET_X', 'MSETC_X',
+    'timing_err', 'timing_quality'); the level then asks the generator for its noise deviation whether or not ber is set.
     keep=True adds 'arrays': the DeviceArrays ltf_re, ltf_im, h_re, h_im, ls_re, ls_im (the caller frees them)."""
     nr, nt = engine.nr, engine.nt
     users = [user_estimates(engine, snr_db, npkt, seed, first_pkt, n_taps, amp_scale, channel, blind, delay, beams,
-                            want_noise_std=ber is not None, delay_beams=True)]
+                            want_noise_std=ber is not None or bool(timing), delay_beams=True)]
     planes, d_std = users[0]['planes'], users[0]['noise_std']
     h_re, h_im = planes['perfect']
     d_link = engine.empty((npkt * nr * nt,))
@@ -476,6 +558,8 @@ def evaluate_level(engine, snr_db, npkt, seed, first_pkt, n_taps=8, amp_scale=Tr
                                      ns=ber['ns'], n_sym=ber['n_sym'], bps=ber['bps'], reg=(mu or {}).get('reg', 'zf'), fb=feedback, mu=bool(mu)))
     if cfo:
         out.update(cfo_level(engine, users[0], npkt, seed, first_pkt, cfo))
+    if timing:
+        out.update(timing_level(engine, users[0], npkt, seed, first_pkt, timing, cfo, amp_scale))
     if aging:
         spacing = float((mu or {}).get('spacing', 15.0))
         aged = [aged_truth(engine, npkt, seed + u, first_pkt, channel, aging, amp_scale, az_offset=u * spacing) for u in range(len(users))]
@@ -927,7 +1011,7 @@ def combine_problem(ns, nr):
 def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500, seed=0, modeldir=None, fit_args=None, n_taps=8,
               amp_scale=True, save_dataset=None, verbose=True, ber=None, channel=None, blind=False, rx_estimate=False,
               delay_taps=None, delay_pre=0, users=None, mu_reg='zf', user_spacing=15.0, beams=False, mu_hybrid=None, mu_jsdm=None,
-              feedback=None, rx_combine=False, aging=None, forecast=None, cfo=None):
+              feedback=None, rx_combine=False, aging=None, forecast=None, cfo=None, timing=None):
     """Training set -> models (loaded from `modeldir`, else fitted and saved into `out`) -> every level (evaluate_level).  Writes
     <out>/BS<Nt>_SNR<s>/metrics.mat per level and <out>/sweep.json, prints the table, returns the result dict (with the per-packet
     arrays under 'per_packet' = {level: {'MSE_LS', ...}}).  Test packets come from the stream seed + 1, behind the index range of
@@ -938,7 +1022,9 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
     'mu_hybrid': {n_rf}, 'mu_jsdm': {b, r_star, tol, mode}, 'feedback': {b_phi, b_psi, ng, report_bits: the bits of one packet's
     report}, 'delay': {taps, pre, rank}, 'beams', 'rx_combine': needs ber, one of feedback / users and ns <= min(4, Nr) - combine_problem; 'aging': aging_args, needs the
     scattering channel; 'forecast': forecast_args, needs aging; 'cfo': cfo_args - a level then also holds cfo_rmse, the rms of the
-    wrapped error of the offset estimate in subcarrier spacings, and cfo_quality, the mean);
+    wrapped error of the offset estimate in subcarrier spacings, and cfo_quality, the mean; 'timing': timing_args - a level then also
+    holds timing_exact, the share of packets with theta_hat == theta, timing_rmse, the rms of theta_hat - theta in samples, and
+    timing_quality, the mean);
     a level of sweep.json then holds mean and confidence interval of every field the
     option adds, and the per-user records, in JSON_ORDER."""
     if feedback is not None:
@@ -986,6 +1072,7 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
     if forecast and not aging:
         raise ValueError('forecast needs aging (and with it the scattering channel): it forecasts the aged channel')
     cfo = cfo_args(cfo)
+    timing = timing_args(timing)
     delay = (int(delay_taps), int(delay_pre)) if delay_taps else None
     os.makedirs(out, exist_ok=True)
     result = dict(nt=engine.nt, nr=engine.nr, n_train=int(n_train), n_test=int(n_test), seed=int(seed), n_taps=int(n_taps),
@@ -999,7 +1086,7 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
                    feedback=feedback and dict(feedback, report_bits=report_bits),
                    delay=delay and dict(taps=delay[0], pre=delay[1], rank=int(subspace.delay_basis(*delay)[0].shape[1])), beams=bool(beams),
                    rx_combine=bool(rx_combine), aging=aging and dict(aging), forecast=forecast and dict(forecast),
-                   cfo=cfo and dict(cfo))
+                   cfo=cfo and dict(cfo), timing=timing and dict(timing))
     result.update((k, v) for k, v in options.items() if v)          # an option that is off leaves no key
     if modeldir:
         load_models(engine, modeldir)
@@ -1021,7 +1108,8 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
         mse = evaluate_level(engine, snr, n_test, seed + 1, n_train + i * n_test, n_taps, amp_scale, ber=ber, channel=channel, blind=blind,
                              rx_estimate=rx_estimate, delay=delay, mu=mu, beams=beams, mu_hybrid=mu_hybrid, mu_jsdm=mu_jsdm,
                              feedback=feedback, **(dict(rx_combine=True) if rx_combine else {}), **(dict(aging=aging) if aging else {}),
-                             **(dict(forecast=forecast) if forecast else {}), **(dict(cfo=cfo) if cfo else {}))
+                             **(dict(forecast=forecast) if forecast else {}), **(dict(cfo=cfo) if cfo else {}),
+                             **(dict(timing=timing) if timing else {}))
         lv = dict(snr_db=float(snr), seconds=time.perf_counter() - t0)
         write_metrics(os.path.join(out, 'BS%d_SNR%g' % (engine.nt, snr), 'metrics.mat'), mse)
         for key, field, _ in _columns(result):
@@ -1029,6 +1117,10 @@ def run_sweep(engine, out, levels=synth.SNR_LEVELS_DB, n_train=3000, n_test=500,
         if cfo:
             lv['cfo_rmse'] = float(np.sqrt(np.mean(np.asarray(mse['cfo_err'], np.float64) ** 2)))
             lv['cfo_quality'] = float(np.mean(mse['cfo_quality']))
+        if timing:
+            lv['timing_exact'] = float(np.mean(np.asarray(mse['timing_err']) == 0))
+            lv['timing_rmse'] = float(np.sqrt(np.mean(np.asarray(mse['timing_err'], np.float64) ** 2)))
+            lv['timing_quality'] = float(np.mean(mse['timing_quality']))
         result['levels'].append(lv)
         per_packet[float(snr)] = mse
     with open(os.path.join(out, 'sweep.json'), 'w') as f:
@@ -1114,6 +1206,12 @@ def build_parser():
                         'per packet (0 < EPS < 0.5; csi_cfo_rotate_device), as they are - MSEO_ - and after the cyclic-prefix correction '
                         '(csi_cfo_correct_device) - MSEOC_, with cfo_rmse and cfo_quality per level')
     p.add_argument('--cfoSkip', default=0, type=int, metavar='M', help='--cfo: samples left out at the head of every cyclic prefix (0 .. 63)')
+    p.add_argument('--timing', default=None, type=int, metavar='SPAN',
+                   help='also evaluate LS / MMSE / DNN on the level\'s packets (with --cfo the offset ones) placed at a start uniform in 0 .. SPAN '
+                        'samples inside captures with noise margins (SPAN a multiple of 4 in 4 .. 256; csi_sync_embed_device), cut out at the fixed '
+                        'start SPAN / 2 - MSET_ - and at the cyclic-prefix estimate of the start (csi_sync_correct_device) - MSETC_, with '
+                        'timing_exact, timing_rmse and timing_quality per level')
+    p.add_argument('--timingRho', default=1.0, type=float, metavar='RHO', help='--timing: weight of the energy term of the timing metric, 0 .. 1')
     p.add_argument('--blind', action='store_true',
                    help='add the estimator MMSEb: LMMSE smoothing from the packet\'s own statistics (csi_lmmse_blind_device) - MSE_MMSEb, and with --ber its link metrics')
     p.add_argument('--delayTaps', default=0, type=int, metavar='L',
@@ -1144,6 +1242,13 @@ def cfo_from_args(args):
     if args.cfo is None:
         return None
     return dict(max_eps=args.cfo, cp_skip=args.cfoSkip)
+
+
+def timing_from_args(args):
+    """The `timing` argument of run_sweep that the command line asks for: None without --timing."""
+    if args.timing is None:
+        return None
+    return dict(span=args.timing, rho=args.timingRho)
 
 
 def aging_from_args(args):
@@ -1220,6 +1325,13 @@ def parse_args(argv=None):
             parser.error('--cfo: ' + str(err))
     elif args.cfoSkip != 0:
         parser.error('--cfoSkip needs --cfo')
+    if args.timing is not None:
+        try:
+            timing_args(timing_from_args(args))
+        except ValueError as err:
+            parser.error('--timing: ' + str(err))
+    elif args.timingRho != 1.0:
+        parser.error('--timingRho needs --timing')
     if args.beams and args.nTX > beamspace.MAX_NT:
         parser.error('--beams takes nTX up to %d' % beamspace.MAX_NT)
     return args
@@ -1245,7 +1357,7 @@ def main(argv=None):
               mu_jsdm=dict(b=args.muJSDM, r_star=args.jsdmRank, tol=args.jsdmTol, mode=args.jsdmMode) if args.muJSDM else None,
               feedback=dict(b_phi=args.feedback[0], b_psi=args.feedback[1], ng=args.feedbackNg) if args.feedback is not None else None,
               rx_combine=bool(args.rxCombine), aging=aging_from_args(args), forecast=forecast_from_args(args),
-              cfo=cfo_from_args(args))
+              cfo=cfo_from_args(args), timing=timing_from_args(args))
     return 0
 
 

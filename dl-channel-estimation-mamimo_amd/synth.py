@@ -190,6 +190,22 @@ def cfo_offsets(seed, first_pkt, npkt, max_eps):
     return float(max_eps) * (2.0 * u - 1.0)
 
 
+def timing_offsets(seed, first_pkt, npkt, span):
+    """Packet starts of packets first_pkt .. first_pkt + npkt - 1 inside captures of len_ltf + span samples (the theta of
+    CsiEngine.sync_embed_device): int32 [npkt], uniform in 0 .. span.  Packet i's draw is a hash of (seed, i) alone, the hash of
+    cfo_offsets under its own tag, so the levels of a sweep, its chunks and any sub-range of a longer call see the same start for the
+    same packet, and a packet's start is independent of its frequency offset."""
+    def mix(z):
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return z ^ (z >> np.uint64(31))
+    with np.errstate(over='ignore'):
+        i = np.arange(int(first_pkt), int(first_pkt) + int(npkt), dtype=np.uint64)
+        z = mix(mix((np.uint64(int(seed) & 0xFFFFFFFFFFFFFFFF) ^ np.uint64(0x53594E43)) + np.uint64(0x9E3779B97F4A7C15)) + (i + np.uint64(1)) * np.uint64(0x9E3779B97F4A7C15))
+    u = (z >> np.uint64(11)).astype(np.float64) * 2.0 ** -53          # [0, 1)
+    return np.minimum(np.floor(u * (int(span) + 1)), int(span)).astype(np.int32)
+
+
 def link_noise_var(noise_std, amp_scale=True):
     """Noise variance per complex frequency-domain sample, in the units of the channel planes h, that goes with a sounding packet
     of csi_synth_structured: the time samples carry amp * noise_std per real component (2 amp^2 noise_std^2 per complex sample), and

@@ -38,6 +38,9 @@
  *   (an addition: the synchronisation stage in front of the
  *        estimators - carrier frequency offset of the preamble
  *        from its cyclic prefixes, and the rotation that removes it) csi_cfo_estimate_device, csi_cfo_rotate_device, csi_cfo_correct[_device]
+ *   (an addition, the stage in front of that one: where the packet
+ *        starts inside a capture, from the same cyclic prefixes,
+ *        the cut-out that applies it and the embedding that tests it) csi_sync_embed_device, csi_sync_estimate_device, csi_sync_extract_device, csi_sync_correct[_device]
  *   omphybweights       BER_test_maMIMO_LTF.m:347-376                csi_hybrid_weights[_device]
  *   --execTime profiler loop                       DNN.py:441-475   csi_profile_*
  *   Model.fit step (noise, BN, dropout, Adam)       DNN.py:272-316   csi_train_*
@@ -51,7 +54,7 @@
  * context's stream and return without waiting; call csi_synchronize before reading results.
  *
  * Device pointers (csi_predict_device, csi_ls_estimate_device, csi_estimate_device, csi_lmmse_estimate_device, csi_lmmse_blind_device, csi_subspace_smooth_device, csi_beam_power_device, csi_beam_smooth_device, csi_beam_wiener_device, csi_null_noise_device, csi_nmse_device,
- * csi_hybrid_weights_device, csi_link_sim_device, csi_link_sim_rx_device, csi_mu_precoder_device, csi_mu_link_sim_device, csi_mu_hybrid_precoder_device, csi_mu_covariance_device, csi_mu_jsdm_precoder_device, csi_feedback_compress_device, csi_feedback_expand_device, csi_rx_combiner_device, csi_rx_apply_combiner_device, csi_viterbi_decode_device, csi_synth_*, csi_scatter_channel_at_device, csi_forecast_*_device, csi_sounding_noise_device, csi_cfo_*_device).  An array of exactly the documented
+ * csi_hybrid_weights_device, csi_link_sim_device, csi_link_sim_rx_device, csi_mu_precoder_device, csi_mu_link_sim_device, csi_mu_hybrid_precoder_device, csi_mu_covariance_device, csi_mu_jsdm_precoder_device, csi_feedback_compress_device, csi_feedback_expand_device, csi_rx_combiner_device, csi_rx_apply_combiner_device, csi_viterbi_decode_device, csi_synth_*, csi_scatter_channel_at_device, csi_forecast_*_device, csi_sounding_noise_device, csi_cfo_*_device, csi_sync_*_device).  An array of exactly the documented
  * size suffices: it may be a slice of a larger allocation whose neighbours hold live data of any value (NaN and 1e38 included).
  * Nothing outside the arrays is written, nothing outside them reaches a result, and input arrays are not modified.  Every re / im
  * PLANE (the preambles [npkt][Nr][len_ltf], the CSI planes [npkt][Nr][Nt][234 or n_out], fbb, frf_mean, xeq, gest, the precoder planes W, g) starts on a 16-byte
@@ -1013,6 +1016,54 @@ int  csi_cfo_correct_device(csi_ctx* ctx, const float* d_ltf_re, const float* d_
                             double* d_eps, float* d_quality);
 int  csi_cfo_correct(csi_ctx* ctx, const float* ltf_re, const float* ltf_im, int64_t npkt, int cp_skip, float* out_re, float* out_im, double* eps,
                      float* quality);
+
+/* Symbol timing of the sounding preamble: cyclic-prefix timing estimator, joint with the carrier frequency offset (csrc/sync.hip.h,
+ * DESIGN.md 4.29).  No reference counterpart (the reference's receiver is handed the packet from its first sample); it is the stage in
+ * front of csi_cfo_* and of every estimator, and the impairment that tests it.
+ * c[p][r][n] are CAPTURE planes [npkt][Nr][L], L = 320 Nt + span; span is a multiple of 4 in 4 .. 256, so every row starts on a 16-byte
+ * boundary.  The packet of len = 320 Nt samples starts at theta[p] in 0 .. span, one per packet, shared by its Nr antennas.  A span of
+ * 320 would be ambiguous by a whole symbol; the metric takes no cp_skip, which would make every start in [theta - cp_skip, theta] an
+ * exact tie (a caller who wants one runs csi_cfo_estimate_device on the cut-out planes).  For theta = 0 .. span:
+ *   gamma(theta)  = sum_r sum_s sum_{m<64} conj(c[p][r][theta + 320 s + m]) c[p][r][theta + 320 s + m + 256]
+ *   Phi(theta)    = 1/2 sum (|c[.. m]|^2 + |c[.. m + 256]|^2) over the same samples
+ *   Lambda(theta) = |gamma(theta)| - rho Phi(theta)        rho in [0, 1]; 1 is the high-SNR form (van de Beek's rho = snr / (1 + snr))
+ *   theta_hat = the lowest theta of the largest Lambda,  eps_hat = atan2(Im, Re of gamma(theta_hat)) / 2 pi,
+ *   quality = |gamma(theta_hat)| / Phi(theta_hat);  Phi == 0 there gives eps_hat = 0 and quality = 0; an all-zero capture (0, 0, 0)
+ *                                                                                                          csi_sync_estimate_device
+ *   y[p][r][n] = c[p][r][theta[p] + n] exp(-2 pi i eps[p] n / 256), n < len; without d_eps, or with eps[p] == 0, a copy of the bits;
+ *   the phase counts from the packet's own sample 0 and the bits are those of a plain cut-out followed by
+ *   csi_cfo_rotate_device(scale = -1)                                                                      csi_sync_extract_device
+ *   c[p][r][theta[p] + n] = x[p][r][n] (the packet's bits); every other sample is the margin
+ *   std[p] (normal(km, 2 e) + i normal(km, 2 e + 1)), e = r L + n, km = splitmix64(kn ^ 0x53594E43), kn the noise key of packet
+ *   first_pkt + p of csi_synth_structured's streams; d_margin_std NULL or std[p] == 0 gives zero margins.  std is the deviation per
+ *   real component as applied (csi_synth_*'s noise_std times the amplitude scale where flag bit 0 was set)   csi_sync_embed_device
+ * A theta outside 0 .. span in a device array cannot be refused before the launch: embed and extract clamp it into the range, so
+ * nothing outside the arrays is ever touched.
+ * Arithmetic of the estimator: products in fp32 as in csi_cfo_estimate_device, every sum in fp64 in an order fixed by (Nt, Nr, span)
+ * alone, no atomics: a packet has the same bits whatever the call size or its position.
+ *   d_theta    int32 [npkt];  d_eps  double [npkt], 8-byte aligned;  d_quality  float [npkt];  d_metric  double [npkt][span + 1], the
+ *   values of Lambda the argmax compared.  d_eps, d_quality and d_metric of the estimate are optional (NULL).
+ * csi_sync_correct_device is the estimate followed by the cut-out at theta_hat - with bit 0 of flags also removing eps_hat - two
+ * launches, the bits of the two calls made by hand; d_theta / d_eps / d_quality are optional, theta and eps then live in a context
+ * workspace sized by eager calls (inside a capture an eager call of the same shape goes first).  csi_sync_correct: the same on host
+ * buffers in packet chunks of 256 MiB of staging (the context's workspace_bytes when that is smaller), theta, eps and quality optional;
+ * same bits as the device entry.
+ * Every device entry is asynchronous on the context's stream and may be captured.  Refused with text, before any launch: null planes,
+ * npkt < 1, a span that is no multiple of 4 in 4 .. 256, rho non-finite or outside [0, 1], unknown flag bits, planes off a 16-byte
+ * boundary, an output that shares a byte with an input or with another output (the cut-out is never in place), per-packet arrays off
+ * their word size, a single-input context.  A null context returns -1.  Profile entries "sync_metric" (16 bytes per folded pair of
+ * samples), "sync_extract" (16 bytes per sample of the packet) and "sync_embed" (8 bytes per sample in and out); read-only option
+ * "sync_launches" counts their kernels. */
+int  csi_sync_embed_device(csi_ctx* ctx, uint64_t seed, int64_t first_pkt, int64_t npkt, int span, const int32_t* d_theta, const float* d_margin_std,
+                           const float* d_x_re, const float* d_x_im, float* d_cap_re, float* d_cap_im);
+int  csi_sync_estimate_device(csi_ctx* ctx, const float* d_cap_re, const float* d_cap_im, int64_t npkt, int span, double rho, int32_t* d_theta,
+                              double* d_eps, float* d_quality, double* d_metric);
+int  csi_sync_extract_device(csi_ctx* ctx, const float* d_cap_re, const float* d_cap_im, int64_t npkt, int span, const int32_t* d_theta,
+                             const double* d_eps, float* d_out_re, float* d_out_im);
+int  csi_sync_correct_device(csi_ctx* ctx, const float* d_cap_re, const float* d_cap_im, int64_t npkt, int span, double rho, uint32_t flags,
+                             float* d_out_re, float* d_out_im, int32_t* d_theta, double* d_eps, float* d_quality);
+int  csi_sync_correct(csi_ctx* ctx, const float* cap_re, const float* cap_im, int64_t npkt, int span, double rho, uint32_t flags, float* out_re,
+                      float* out_im, int32_t* theta, double* eps, float* quality);
 
 /* ---- multi-GPU: packets shard over the GPUs of a node (one process and one context per GPU), the weights are shared and
  * read-only, outputs stay sharded.  The single collective of the path is the load-time broadcast of the
